@@ -6,8 +6,15 @@ BASELINE.json configs[1] per GPU: 12-layer/512-dim AR decoder, 32 rows, 1024-tok
 random-init weights, inputs resident in HBM before the timed region.  value = new tokens of all
 ranks / wall time (prefill + 511 graph-replayed decode steps included).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall milliseconds of one timed step, plus the run's configuration).  Everything else below (the phase
+split, roofline, PMC traffic, beams, default generate, perf mode, rows64, config5, NAR, training, CPU baseline) runs
+only with `--full`; the `--no-*` options then leave single legs out.  `--dump-outputs DIR` writes, after the timed
+steps, the token matrix the last timed `generate_batch` returned (float32, ids are exact) as DIR/tokens.npy
+(DIR/tokens_rank<r>.npy per rank when N > 1); weights and utterances are seeded, so the inputs are the same every run.
 
 Multi-GPU: the utterance batch shards across ranks (32 rows per GPU, weights replicated, no
 data-path collective: SURVEY.md §8e "inference: replicas only"); ranks meet at a barrier before and
@@ -17,7 +24,7 @@ after the timed region and the slowest rank's time is used (RCCL all-reduce MAX)
 process per GPU, RCCL rendezvous on 127.0.0.1) BEFORE this process touches the GPU — the parent never
 initialises HIP and never execs; under `torch.distributed.run` the environment's ranks are used as is.
 
-Extra objects on the same JSON line: `roofline` (decode-attention kernel, HIP-event timed, HBM
+Extra objects on the same JSON line (`--full` only): `roofline` (decode-attention kernel, HIP-event timed, HBM
 bound), `prefill` (event-timed prompt pass against the fp32 MFMA peak), `decode_step` (one replayed
 decode step against the HBM peak, all algorithmic bytes of the step), `train` (configs[3] forward +
 backward + gradient all-reduce + clip/AdamW step time, AR and NAR, on every rank: the RCCL leg),
@@ -67,6 +74,11 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary leg (phase split, roofline, traffic, beams, default generate, perf mode, '
+                         'rows64, config5, NAR, training, CPU baseline); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-nar', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
@@ -83,7 +95,16 @@ def parse():
     ap.add_argument('--small', action='store_true', help='tiny shapes for a functional check')
     ap.add_argument('--allow-partial-group', action='store_true',
                     help='N > 1: print the line even if RCCL did not carry all N ranks through an all-reduce (default: exit 3)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:                      # a plain run: the headline and nothing else
+        for leg in ('cpu_baseline', 'nar', 'roofline', 'train', 'beams', 'config5', 'perf_mode', 'rows64',
+                    'default_generate', 'traffic'):
+            setattr(args, f'no_{leg}', True)
+    if args.dump_outputs:                  # main() works in a scratch CWD: a relative DIR means the caller's
+        args.dump_outputs = str(Path(args.dump_outputs).resolve())
+    return args
 
 
 def log(msg):
@@ -651,6 +672,14 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     log(f'{ms_per_step:.1f} ms per generate')
     value = world * rows * new * args.steps / elapsed
+    if args.dump_outputs:
+        # what generate_batch handed its caller in the last timed step: per row the prompt codes, BOS and the new tokens
+        import numpy as np
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        name = 'tokens' if world == 1 else f'tokens_rank{rank}'
+        np.save(dump / f'{name}.npy', out.cpu().numpy().astype(np.float32))
+        log(f'outputs of the last timed step written to {dump}')
 
     result = {
         'metric': 'acoustic tokens/sec (AR decode)', 'value': value, 'unit': 'tokens/s',
@@ -694,7 +723,7 @@ def main():
 
     l_pl = 4 * cfg.d_model ** 2 + 2 * cfg.d_model * cfg.dim_feedforward   # matmul weights per layer
     st = model.last_generate_stats
-    if rank == 0 and 'prefill_ms' in st:
+    if rank == 0 and args.full and 'prefill_ms' in st:
         # phase split of the LAST timed generate (HIP events on the launch stream, recorded inside generate_batch)
         x, y = text, frames + 1
         pairs = x * x + y * x + y * (y + 1) // 2                            # unmasked (query, key) pairs per row

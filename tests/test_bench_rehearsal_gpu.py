@@ -23,7 +23,7 @@ def test_bench_small_four_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(VALLE2_DIST_BACKEND='gloo', VALLE2_FORCE_DEVICE='0', HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--small', '--gpus', '4', '--steps', '2', '--warmup', '1',
-                          '--no-cpu-baseline', '--no-roofline'], env=env, capture_output=True, text=True, timeout=600)
+                          '--full', '--no-cpu-baseline', '--no-roofline'], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(line) for line in out.stdout.splitlines() if line.startswith('{')]
     assert len(lines) == 1, out.stdout                       # rank 0 prints the ONE line

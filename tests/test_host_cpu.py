@@ -176,6 +176,29 @@ def test_bench_byte_accounting():
     assert b == 4.0 * (2 * 32 * 1280 * 512 + 2 * 32 * 512)
 
 
+def test_bench_plain_run_leaves_the_secondary_legs_to_full(monkeypatch, tmp_path):
+    """A plain `bench.py` run times the headline only; `--full` runs every secondary leg unless a --no-* option drops it;
+    `--steps` is the number of timed steps; a relative --dump-outputs DIR is the caller's, not the bench's scratch CWD."""
+    import sys
+
+    import bench
+    legs = ('cpu_baseline', 'nar', 'roofline', 'train', 'beams', 'config5', 'perf_mode', 'rows64', 'default_generate',
+            'traffic')
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '3', '--dump-outputs', 'o'])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full) == (7, 3, False)
+    assert all(getattr(a, f'no_{leg}') for leg in legs)
+    assert a.dump_outputs == str(tmp_path / 'o')                 # the autouse fixture's CWD
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-train'])
+    a = bench.parse()
+    assert a.full and a.no_train and a.dump_outputs is None
+    assert not any(getattr(a, f'no_{leg}') for leg in legs if leg != 'train')
+    for bad in (['--steps', '0'], ['--warmup', '-1']):
+        monkeypatch.setattr(sys, 'argv', ['bench.py'] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
 def test_collate_matches_reference_golden():
     """valle/collate.py:19-44 wire format (BOS-prepend / EOS-append / zero pad / lens), pinned by a
     fixture produced by the reference's own ValleARCollate; NAR layout fixed per defect D7."""

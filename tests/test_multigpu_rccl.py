@@ -23,7 +23,7 @@ def _clean_env():
 
 def test_bench_small_two_gpus_spawns_its_own_ranks():
     out = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--small', '--gpus', '2', '--steps', '2',
-                          '--warmup', '1'], env=_clean_env(), capture_output=True, text=True, timeout=600)
+                          '--warmup', '1', '--full'], env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [json.loads(line) for line in out.stdout.splitlines() if line.startswith('{')]
     assert len(lines) == 1, 'exactly one JSON line (rank 0)'

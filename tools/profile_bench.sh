@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end evidence run (on the GPU box through gpurun): the default bench line as the driver runs it, the same command
+# Round-end evidence run (on the GPU box): the full bench line (bench.py --full), the same command
 # under rocprofv3 --kernel-trace --stats, the two PMC passes for the dominant kernel's HBM traffic (separate passes, no
 # tracing domain beside --kernel-trace; bench.py also measures the traffic itself through child processes), and the
 # training step's kernel statistics and launch trace.  Summaries land in gpurun_out/prof_bench/ — copy them to profiles/.
@@ -12,9 +12,9 @@ trap 'rm -rf $OUT/stats $OUT/fetch $OUT/write $OUT/mfma $OUT/train $OUT/tt $OUT/
 cd $R
 PART=${1:-all}          # "1": the bench line + its kernel statistics + the PMC passes; "2": the beams / perf-mode / training passes
 if [ "$PART" != "2" ]; then
-timeout -k 10 700 python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 700 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
-P="--no-cpu-baseline --no-traffic --no-config5 --no-beams --no-perf-mode --no-rows64"
+P="--full --no-cpu-baseline --no-traffic --no-config5 --no-beams --no-perf-mode --no-rows64"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- python3 $R/bench.py $P > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 python3 $R/tools/summarize_prof.py $OUT/stats $OUT/kernel_stats.md "rocprofv3 --kernel-trace --stats -- python3 bench.py $P"
 Q="--steps 1 --warmup 0 --no-nar --no-roofline --no-train $P"
@@ -29,9 +29,9 @@ python3 $R/tools/summarize_prof.py $OUT/mfma $OUT/pmc_mfma_busy.md "rocprofv3 --
 fi
 if [ "$PART" = "1" ]; then exit 0; fi
 cd /tmp && export TMPDIR=/tmp
-P="--no-cpu-baseline --no-traffic --no-config5 --no-beams --no-perf-mode --no-rows64"
+P="--full --no-cpu-baseline --no-traffic --no-config5 --no-beams --no-perf-mode --no-rows64"
 # round 5: the shared-prompt decode (the `beams` leg: generate() of one utterance with 32 beams) under the kernel trace ...
-W="--steps 1 --warmup 0 --no-nar --no-roofline --no-train --no-cpu-baseline --no-traffic --no-config5 --no-perf-mode --no-rows64 --no-default-generate"
+W="--full --steps 1 --warmup 0 --no-nar --no-roofline --no-train --no-cpu-baseline --no-traffic --no-config5 --no-perf-mode --no-rows64 --no-default-generate"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/beams -o stats --output-format csv -- python3 $R/bench.py $W > $OUT/beams.json 2> $OUT/beams.err
 python3 $R/tools/summarize_prof.py $OUT/beams $OUT/beams_kernel_stats.md "rocprofv3 --kernel-trace --stats -- python3 bench.py $W"
 # ... and the perf-mode (bf16 MFMA) kernels: kernel statistics, MFMA-busy and LDS bank-conflict counters (separate passes)
