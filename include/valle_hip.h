@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 127            /* 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 128            /* 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 8           /* EnCodec @6 kbps: 8 codebooks (valle/config.py:15-17) */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
 
@@ -212,6 +212,25 @@ int vh_linear_qkv_folded(const float* A, int lda, const float* Wf, const float* 
                          float* q_out, int ldq, float* kcache, float* vcache, const int32_t* cache_len, int B,
                          int T, int d_model, int n_heads, int S_max, float ln_eps, void* stream);
 
+/* ---- the same two for a head width other than 64 (the decode step of such a model) --------------------------------
+ * vh_linear_qkv / vh_linear_qkv_folded with the K and V rows appended to caches (B, h, S_max, head_dim), head_dim =
+ * d_model / n_heads a multiple of 4 (a 4-column group never crosses a head).  The decode step's form only: T == 1 and
+ * B <= 64 (anything else is refused with VH_EUNSUPPORTED); the folded form takes the K of vh_linear_qkv_folded. */
+int vh_linear_qkv_hd(const float* A, int lda, const float* Wqkv, float* q_out, int ldq, float* kcache, float* vcache,
+                     const int32_t* cache_len, int B, int T, int d_model, int n_heads, int S_max, const float* ln_gamma,
+                     const float* ln_beta, const float* ada_scale, const float* ada_shift, float ln_eps, int head_dim,
+                     void* stream);
+int vh_linear_qkv_folded_hd(const float* A, int lda, const float* Wf, const float* c1, const float* c2, float* q_out, int ldq,
+                            float* kcache, float* vcache, const int32_t* cache_len, int B, int T, int d_model, int n_heads,
+                            int S_max, float ln_eps, int head_dim, void* stream);
+
+/* ---- prompt pass at a head width other than 64: K / V of the QKV projection into the cache --------------------------
+ * qkv (B*T, ld) holds [Q | K | V] column blocks of d = n_heads * head_dim columns (the projection the prompt's attention
+ * used); K and V of row (b, t) go to kcache / vcache[(b*h + head)*S_max + t][0 .. head_dim-1], t < T <= S_max.  16-byte
+ * loads and stores (head_dim % 4 == 0, ld % 4 == 0, 16-byte aligned pointers); a bit-exact copy. */
+int vh_kv_store(const float* qkv, int ld, float* kcache, float* vcache, int B, int T, int n_heads, int head_dim, int S_max,
+                void* stream);
+
 /* ---- FeedForward + residual of the decode step as one launch split over dim_feedforward --------
  * replaces FeedForward.forward + the residual add of EncoderLayer.forward (valle/models/modules.py:215-221,
  * :278-279) for M <= 64 rows:   out = x + b2 + GELU(LN2(x) W1^T + b1) W2^T
@@ -314,6 +333,18 @@ int vh_attn_decode_shared(const float* q, int ldq, const float* kprefix, const f
                           int prefix_S, const float* ksuffix, const float* vsuffix, float* out, int ldo,
                           const int32_t* suffix_len, int len_bias, int B, int n_heads, int S_suf, int n_split_suffix,
                           void* partial, size_t partial_bytes, void* stream);
+/* ---- decode attention at a head width other than 64 ------------------------------------------------------------------
+ * vh_attn_decode's contract over fp32 caches (B, h, S_max, head_dim): keys 0 .. cache_len[b] + len_bias - 1 of row b,
+ * out (B, ldo) at columns head * head_dim.  scale is the softmax scale (callers pass (float)(1 / sqrt((double)head_dim)),
+ * the reference's head_dim ** -0.5).  head_dim: a multiple of 4 from 16 to 256 (64 included, for comparisons; anything
+ * else is refused with VH_EUNSUPPORTED).  n_split > 1 splits the key range of a (b, head) over n_split workgroups whose
+ * records (round_up(head_dim + 2, 4) floats each) a second launch adds in split order: partial must hold
+ * vh_attn_decode_hd_ws_bytes(B, n_heads, head_dim, n_split) bytes (partial_bytes says how many it holds), no
+ * initialisation needed.  Deterministic. */
+size_t vh_attn_decode_hd_ws_bytes(int B, int n_heads, int head_dim, int n_split);
+int vh_attn_decode_hd(const float* q, int ldq, const float* kcache, const float* vcache, float* out, int ldo,
+                      const int32_t* cache_len, int len_bias, int B, int n_heads, int head_dim, int S_max, float scale,
+                      int n_split, void* partial, size_t partial_bytes, void* stream);
 
 /* ---- perf mode of the decode step: bf16 K/V cache (opt-in; never the parity path) ---------------
  * SURVEY.md section 7's "perf mode": the K/V cache — 93 % of the bytes a decode step reads at configs[1] — stored
@@ -379,7 +410,7 @@ int vh_sample_step(const float* logits, int ldl, int V, int eos, int top_k, floa
  * (valle/models/valle_ar.py:141-171 with modules.py:336-352).  */
 typedef struct {
     const float *ln1_g, *ln1_b, *wqkv, *wo, *bo, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2;
-    float *kcache, *vcache;           /* this layer's (B,h,S_max,64) caches */
+    float *kcache, *vcache;           /* this layer's (B,h,S_max,head_dim) caches, head_dim = d_model / n_heads */
     /* optional vh_ln_fold outputs for (ln1, wqkv) and (ln2, w1, b1); all NULL → LayerNorm applied in
      * the operand load from ln*_g / ln*_b.  Used by the decode step only. */
     const float *wqkv_f, *qkv_c1, *qkv_c2, *w1_f, *w1_c1, *w1_c2;

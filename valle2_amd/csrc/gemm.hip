@@ -46,6 +46,7 @@ struct GemmArgs {
     int rg_rows;  // rows per row group when gridDim.z > 1 (16, or 8: half of the MFMA's 16 rows idle)
     int w16;      // decode GEMMs of perf mode: W points at an h16 (N,K) matrix (vh_common.h vh_h16), read as 8 bytes per fragment
     DropArgs drop;  // training forward (EPI_PLAIN, LDS-DMA tile kernel): out = dropout(act(acc + bias)) + residual
+    int head_dim;   // EPI_QKV_HD: the cache's row width d_model / n_heads (a multiple of 4: a column group never crosses a head)
 #ifdef VH_STAMPS
     long long* dbg;  // diagnostic build only (tools/probe_skinny.hip): per-wave phase stamps
 #endif
@@ -63,8 +64,9 @@ struct GemmArgs {
 
 enum { EPI_PLAIN = 0, EPI_QKV = 1, EPI_PARTIAL = 2,
        EPI_QKV16 = 3 /* EPI_QKV with the K / V rows appended as bf16 (perf mode of the decode step; skinny kernels only) */,
-       EPI_HEAD = 4  /* the AR head with the greedy step in the same launch (vh_head_greedy; gemm_skinny_fast, MT = 1 only) */ };
-#define IS_QKV(E) ((E) == EPI_QKV || (E) == EPI_QKV16)
+       EPI_HEAD = 4  /* the AR head with the greedy step in the same launch (vh_head_greedy; gemm_skinny_fast, MT = 1 only) */,
+       EPI_QKV_HD = 5 /* EPI_QKV into a cache (B, h, S_max, head_dim) of a runtime head width (vh_linear_qkv_hd; skinny kernels) */ };
+#define IS_QKV(E) ((E) == EPI_QKV || (E) == EPI_QKV16 || (E) == EPI_QKV_HD)
 
 // What the greedy step needs beside the head product (vh_head_greedy): the operands of greedy_step_kernel
 // (elementwise.hip) + the hand-over area of the launch — one (logit, column) candidate per (row, 16-column block)
@@ -112,6 +114,19 @@ __device__ __forceinline__ void store4(const GemmArgs& a, int m, int n, f32x4 v)
         }
         return;
     }
+    if (EPI == EPI_QKV_HD) {
+        const int which = n / a.d_model, c = n - which * a.d_model;
+        if (which == 0) {
+            st4(a.out + (int64_t)m * a.ldo + c, v);
+        } else {
+            const int head = c / a.head_dim, e = c - head * a.head_dim;
+            const int b = m / a.T, t = m - b * a.T;
+            const int pos = (a.cache_len ? a.cache_len[b] : 0) + t;
+            float* base = which == 1 ? a.kc : a.vc;
+            st4(base + (((int64_t)b * a.n_heads + head) * a.S_max + pos) * a.head_dim + e, v);
+        }
+        return;
+    }
     const bool full = n + 3 < a.N;
     if (full) {
         if (a.bias) v += ld4(a.bias + n);
@@ -144,6 +159,19 @@ __device__ __forceinline__ void store1(const GemmArgs& a, int m, int n, float s)
             const int pos = (a.cache_len ? a.cache_len[b] : 0) + t;
             float* base = which == 1 ? a.kc : a.vc;
             base[(((int64_t)b * a.n_heads + head) * a.S_max + pos) * VH_HEAD_DIM + e] = s;
+        }
+        return;
+    }
+    if (EPI == EPI_QKV_HD) {
+        const int which = n / a.d_model, c = n - which * a.d_model;
+        if (which == 0) {
+            a.out[(int64_t)m * a.ldo + c] = s;
+        } else {
+            const int head = c / a.head_dim, e = c - head * a.head_dim;
+            const int b = m / a.T, t = m - b * a.T;
+            const int pos = (a.cache_len ? a.cache_len[b] : 0) + t;
+            float* base = which == 1 ? a.kc : a.vc;
+            base[(((int64_t)b * a.n_heads + head) * a.S_max + pos) * a.head_dim + e] = s;
         }
         return;
     }
@@ -914,7 +942,8 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
         if (a.res) a.res += (int64_t)r0 * a.ldr;
         a.out += (int64_t)r0 * a.ldo;
         if (IS_QKV(EPI)) {                 // T == 1 (host check): row = batch index
-            const int64_t off = (int64_t)r0 * a.n_heads * a.S_max * VH_HEAD_DIM / (EPI == EPI_QKV16 ? 2 : 1);   // bf16: half
+            const int64_t off = EPI == EPI_QKV_HD ? (int64_t)r0 * a.S_max * a.d_model       // any width: S_max d_model per row
+                                                  : (int64_t)r0 * a.n_heads * a.S_max * VH_HEAD_DIM / (EPI == EPI_QKV16 ? 2 : 1);   // bf16: half
             a.kc += off;
             a.vc += off;
             if (a.cache_len) a.cache_len += r0;
@@ -1132,10 +1161,11 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
             if (which == 0) {
                 st4(a.out + (int64_t)em * a.ldo + c, sacc);
             } else {
-                const int head = c / VH_HEAD_DIM, e = c - head * VH_HEAD_DIM;
+                const int hdim = EPI == EPI_QKV_HD ? a.head_dim : VH_HEAD_DIM;
+                const int head = c / hdim, e = c - head * hdim;
                 const int b = em / a.T, t = em - b * a.T;
                 float* base = which == 1 ? a.kc : a.vc;
-                const int64_t at = (((int64_t)b * a.n_heads + head) * a.S_max + e_pos + t) * VH_HEAD_DIM + e;
+                const int64_t at = (((int64_t)b * a.n_heads + head) * a.S_max + e_pos + t) * hdim + e;
                 if (EPI == EPI_QKV16) {           // four bf16 = one 8-byte store
                     const uint64_t lo = vh_pack_h16(sacc.x, sacc.y);
                     const uint64_t hi = vh_pack_h16(sacc.z, sacc.w);
@@ -1481,6 +1511,9 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
     } else if constexpr (EPI == EPI_QKV16) {
         vh_set_error("%s: bf16 K/V append is the decode path (M <= 64)", name);
         return VH_EUNSUPPORTED;
+    } else if constexpr (EPI == EPI_QKV_HD) {
+        vh_set_error("%s: the K/V append at a runtime head width is the decode path (M <= 64)", name);
+        return VH_EUNSUPPORTED;
     } else {
         if (a.w16) { vh_set_error("%s: 16-bit weights are the decode step's form (M <= 64)", name); return VH_EUNSUPPORTED; }
         const int tm = (a.M + TM - 1) / TM, tn = (a.N + TN - 1) / TN;
@@ -1697,6 +1730,51 @@ extern "C" int vh_linear_qkv_folded(const float* A, int lda, const float* Wf, co
     if (int rc = check_gemm("vh_linear_qkv_folded", a, ln)) return rc;
     if (int rc = check_folded("vh_linear_qkv_folded", a, ln)) return rc;
     return launch_gemm<EPI_QKV>("vh_linear_qkv_folded", a, ln, (hipStream_t)stream);
+}
+
+// ---- the decode step at a head width other than 64: vh_linear_qkv / vh_linear_qkv_folded for one new row per sequence
+// with the K / V rows appended to a cache (B, h, S_max, head_dim) ----
+static int qkv_hd_args(const char* name, GemmArgs& a, const float* A, int lda, const float* W, float* q_out, int ldq,
+                       float* kcache, float* vcache, const int32_t* cache_len, int B, int T, int d_model, int n_heads,
+                       int head_dim, int S_max) {
+    VH_REQUIRE(kcache && vcache, VH_EINVAL, "%s: null cache", name);
+    VH_REQUIRE(T == 1 && B >= 0 && B <= 64, VH_EUNSUPPORTED, "%s: the decode step's form: T == 1, B <= 64 (T=%d B=%d)", name,
+               T, B);
+    VH_REQUIRE(n_heads > 0 && head_dim > 0 && head_dim % 4 == 0 && d_model == n_heads * head_dim, VH_EUNSUPPORTED,
+               "%s: d_model=%d must equal n_heads=%d x head_dim=%d, head_dim a multiple of 4", name, d_model, n_heads, head_dim);
+    VH_REQUIRE(S_max >= 1 && ldq >= d_model, VH_EINVAL, "%s: S_max=%d / ldq=%d", name, S_max, ldq);
+    VH_REQUIRE(vh_aligned16(kcache) && vh_aligned16(vcache), VH_EALIGN, "%s: cache alignment", name);
+    a = GemmArgs{};
+    a.A = A; a.lda = lda; a.W = W; a.out = q_out; a.ldo = ldq; a.M = B; a.N = 3 * d_model;
+    a.K = d_model; a.k_len = d_model; a.act = VH_ACT_NONE; a.kc = kcache; a.vc = vcache; a.cache_len = cache_len;
+    a.T = 1; a.S_max = S_max; a.d_model = d_model; a.n_heads = n_heads; a.head_dim = head_dim;
+    return VH_OK;
+}
+
+extern "C" int vh_linear_qkv_hd(const float* A, int lda, const float* Wqkv, float* q_out, int ldq, float* kcache,
+                                float* vcache, const int32_t* cache_len, int B, int T, int d_model, int n_heads, int S_max,
+                                const float* ln_gamma, const float* ln_beta, const float* ada_scale, const float* ada_shift,
+                                float ln_eps, int head_dim, void* stream) {
+    GemmArgs a;
+    if (int rc = qkv_hd_args("vh_linear_qkv_hd", a, A, lda, Wqkv, q_out, ldq, kcache, vcache, cache_len, B, T, d_model, n_heads,
+                             head_dim, S_max))
+        return rc;
+    LnFuse ln{ln_gamma, ln_beta, ada_scale, ada_shift, ln_eps};
+    if (int rc = check_gemm("vh_linear_qkv_hd", a, ln)) return rc;
+    return launch_gemm<EPI_QKV_HD>("vh_linear_qkv_hd", a, ln, (hipStream_t)stream);
+}
+
+extern "C" int vh_linear_qkv_folded_hd(const float* A, int lda, const float* Wf, const float* c1, const float* c2, float* q_out,
+                                       int ldq, float* kcache, float* vcache, const int32_t* cache_len, int B, int T,
+                                       int d_model, int n_heads, int S_max, float ln_eps, int head_dim, void* stream) {
+    GemmArgs a;
+    if (int rc = qkv_hd_args("vh_linear_qkv_folded_hd", a, A, lda, Wf, q_out, ldq, kcache, vcache, cache_len, B, T, d_model,
+                             n_heads, head_dim, S_max))
+        return rc;
+    LnFuse ln{nullptr, nullptr, nullptr, nullptr, ln_eps, c1, c2};
+    if (int rc = check_gemm("vh_linear_qkv_folded_hd", a, ln)) return rc;
+    if (int rc = check_folded("vh_linear_qkv_folded_hd", a, ln)) return rc;
+    return launch_gemm<EPI_QKV_HD>("vh_linear_qkv_folded_hd", a, ln, (hipStream_t)stream);
 }
 
 // perf mode of the decode step: the same launch with the K / V rows appended to a bf16 cache (B,h,S_max,64)

@@ -58,8 +58,25 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
     VH_REQUIRE(d->B > 0 && d->B <= 64, VH_EUNSUPPORTED,
                "vh_ar_decoder: B=%d (decode rows per GPU must be 1..64)", d->B);
     VH_REQUIRE(d->n_layers > 0 && d->layers, VH_EINVAL, "vh_ar_decoder: no layers");
-    VH_REQUIRE(d->d_model == d->n_heads * VH_HEAD_DIM, VH_EUNSUPPORTED,
-               "vh_ar_decoder: d_model=%d != n_heads=%d x 64", d->d_model, d->n_heads);
+    VH_REQUIRE(d->n_heads > 0 && d->d_model > 0 && d->d_model % d->n_heads == 0, VH_EUNSUPPORTED,
+               "vh_ar_decoder: d_model=%d is not a multiple of n_heads=%d", d->d_model, d->n_heads);
+    const int hd = d->d_model / d->n_heads;
+    if (hd != VH_HEAD_DIM) {          // a head width other than 64: vh_linear_qkv[_folded]_hd + vh_attn_decode_hd
+        VH_REQUIRE(hd % 4 == 0 && hd >= 16 && hd <= 256, VH_EUNSUPPORTED,
+                   "vh_ar_decoder: head width %d (d_model=%d / n_heads=%d): the cached decoder serves 64 and multiples of 4 "
+                   "from 16 to 256", hd, d->d_model, d->n_heads);
+        VH_REQUIRE(d->d_model % 16 == 0 && d->d_model <= 1024, VH_EUNSUPPORTED,
+                   "vh_ar_decoder: head width %d needs d_model %% 16 == 0 and d_model <= 1024 (got %d)", hd, d->d_model);
+        VH_REQUIRE(!d->kv_bf16, VH_EUNSUPPORTED, "vh_ar_decoder: the bf16 K/V cache (perf mode) is width 64 only (head width %d)",
+                   hd);
+        VH_REQUIRE(d->prefix_len == 0, VH_EUNSUPPORTED,
+                   "vh_ar_decoder: the shared prompt (prefix_len=%d) is width 64 only (head width %d)", d->prefix_len, hd);
+        VH_REQUIRE(d->n_split == 1 ||
+                       (d->attn_partial && d->attn_partial_bytes >= vh_attn_decode_hd_ws_bytes(d->B, d->n_heads, hd, d->n_split)),
+                   VH_EINVAL, "vh_ar_decoder: head width %d with n_split=%d needs attn_partial of vh_attn_decode_hd_ws_bytes() = %zu "
+                   "bytes (got %zu)", hd, d->n_split, vh_attn_decode_hd_ws_bytes(d->B, d->n_heads, hd, d->n_split),
+                   d->attn_partial_bytes);
+    }
     VH_REQUIRE(d->dff % 16 == 0 && d->V > 0 && d->S_max > 0 && d->n_split >= 1, VH_EINVAL,
                "vh_ar_decoder: bad dff/V/S_max/n_split");
     VH_REQUIRE(d->proj_w && d->audio_emb && d->audio_pe && d->x && d->q && d->attn && d->hidden &&
@@ -130,6 +147,7 @@ extern "C" void vh_ar_decoder_destroy(vh_ar_decoder* dec) {
 // One decode step for every row: x (B,d) holds the new token's embedding on entry and the NEXT
 // token's embedding on exit.  `ev` (optional) brackets each decode-attention launch.
 void vh_internal_attn_decode_events(hipEvent_t start, hipEvent_t stop);   // attention.hip
+void vh_internal_attn_decode_hd_events(hipEvent_t start, hipEvent_t stop);   // attention_hd.hip
 int vh_internal_linear_w16(const float* A, int lda, const uint16_t* W16, const float* bias, const float* residual, int ldr,
                            float* out, int ldo, int M, int N, int K, void* stream);                                   // gemm.hip
 int vh_internal_linear_qkv_folded_kv16_w16(const float* A, int lda, const uint16_t* Wf16, const float* c1, const float* c2,
@@ -147,6 +165,7 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
                            std::vector<hipEvent_t>* kev = nullptr) {
     const vh_ar_decoder_desc& d = dec->d;
     const int B = d.B, D = d.d_model;
+    const int hd = D / d.n_heads;       // 64: the kernels below as always; otherwise the _hd forms (decoder_check)
     // FeedForward as one launch split over dim_feedforward + the slab reduce (vh_ffn_decode) when the caller gave
     // the workspace and the folded weights; else linear_1 and linear_2 (split-K + reduce) as separate launches
     // measured: +1.6 us per step at 12L/512d x 32 rows, but 1.2 us per LAYER slower at 24L/1024d x 8 rows (256 slices of
@@ -155,6 +174,9 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
     const bool ffn_fused = d.ffn_ws && ffn_knob != 1 && (d.d_model <= 512 || ffn_knob == 2);
     // decode attention of one layer, optionally bracketed by events (vh_ar_decoder_profile_attn)
     auto attention = [&](const vh_layer& L) -> int {
+        if (hd != VH_HEAD_DIM)
+            return vh_attn_decode_hd(d.q, D, L.kcache, L.vcache, d.attn, D, d.cache_len, 1, B, d.n_heads, hd, d.S_max,
+                                     (float)(1.0 / sqrt((double)hd)), d.n_split, d.attn_partial, d.attn_partial_bytes, s);
         if (d.kv_bf16)
             return vh_attn_decode_kv16(d.q, D, (const uint16_t*)L.kcache, (const uint16_t*)L.vcache, d.attn, D, d.cache_len,
                                        1, B, d.n_heads, d.S_max, s);
@@ -175,6 +197,7 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         hipEvent_t k0 = nullptr, k1 = nullptr;
         if (kev && hipEventCreate(&k0) == hipSuccess && hipEventCreate(&k1) == hipSuccess) {
             vh_internal_attn_decode_events(k0, k1);
+            vh_internal_attn_decode_hd_events(k0, k1);
             kev->push_back(k0);
             kev->push_back(k1);
         }
@@ -182,6 +205,7 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         const int arc = attention(L);
         (void)hipEventRecord(e1, s);
         vh_internal_attn_decode_events(nullptr, nullptr);
+        vh_internal_attn_decode_hd_events(nullptr, nullptr);
         ev->push_back(e0);
         ev->push_back(e1);
         return arc;
@@ -191,7 +215,13 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         // LN1 fused into the QKV GEMM; K/V rows appended at cache_len[b]  (modules.py:146-157,271)
         // (perf mode with h16 copies of the step's four matrices: the same launches over half the weight bytes)
         const bool w16 = d.kv_bf16 && L.wqkv_f16 && L.wo16 && L.w1_f16 && L.w2_16 && D <= 1024;
-        if (w16)
+        if (hd != VH_HEAD_DIM && L.wqkv_f)
+            TRY(vh_linear_qkv_folded_hd(d.x, D, L.wqkv_f, L.qkv_c1, L.qkv_c2, d.q, D, L.kcache, L.vcache, d.cache_len, B, 1, D,
+                                        d.n_heads, d.S_max, d.ln_eps, hd, s));
+        else if (hd != VH_HEAD_DIM)
+            TRY(vh_linear_qkv_hd(d.x, D, L.wqkv, d.q, D, L.kcache, L.vcache, d.cache_len, B, 1, D, d.n_heads, d.S_max, L.ln1_g,
+                                 L.ln1_b, nullptr, nullptr, d.ln_eps, hd, s));
+        else if (w16)
             TRY(vh_internal_linear_qkv_folded_kv16_w16(d.x, D, L.wqkv_f16, L.qkv_c1, L.qkv_c2, d.q, D, (uint16_t*)L.kcache,
                                                        (uint16_t*)L.vcache, d.cache_len, B, D, d.n_heads, d.S_max, d.ln_eps, s));
         else if (d.kv_bf16)

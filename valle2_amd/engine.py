@@ -4,7 +4,7 @@ libvalle_hip.so (`_lib.lib()` raises without a HIP device — there is no CPU fa
 
 Data layout in HBM (all fp32):
   residual stream x        (B*T, d) row-major, updated in place by the GEMM epilogues
-  KV cache per layer       K (B, h, S_max, 64), V (B, h, S_max, 64): one (b,head) stream is
+  KV cache per layer       K (B, h, S_max, hd), V (B, h, S_max, hd), hd = d_model / n_heads: one (b,head) stream is
                            contiguous, so decode attention reads it as pure 16-B-per-lane bursts
                            and a new token's K/V row is appended in place (no torch.cat regrow,
                            valle/models/modules.py:151-157)
@@ -27,12 +27,13 @@ HEAD_DIM = kernels.HEAD_DIM
 
 
 class KVCache:
-    """(L, 2, B, h, S_max, 64) in one allocation; `length` rows are valid for every batch row
+    """(L, 2, B, h, S_max, head_dim) in one allocation; `length` rows are valid for every batch row
     unless a per-row `cache_len` tensor says otherwise."""
 
-    def __init__(self, n_layers, batch, n_heads, s_max, device, dtype=torch.float32):
-        self.buf = torch.empty(n_layers, 2, batch, n_heads, s_max, HEAD_DIM, device=device, dtype=dtype)
+    def __init__(self, n_layers, batch, n_heads, s_max, device, dtype=torch.float32, head_dim=HEAD_DIM):
+        self.buf = torch.empty(n_layers, 2, batch, n_heads, s_max, head_dim, device=device, dtype=dtype)
         self.n_layers, self.batch, self.n_heads, self.s_max = n_layers, batch, n_heads, s_max
+        self.head_dim = head_dim
 
     @property
     def bf16(self):
@@ -43,6 +44,8 @@ class KVCache:
         nearest even, vh_kv_to_bf16): the decode steps of perf mode read half the bytes."""
         if self.bf16 or s_max < self.s_max:
             raise _lib.VhError('KVCache.narrowed: an fp32 cache and s_max >= its length')
+        if self.head_dim != HEAD_DIM:
+            raise _lib.VhError(f'KVCache.narrowed: the bf16 cache is width 64 only (head width {self.head_dim})')
         out = KVCache(self.n_layers, self.batch, self.n_heads, s_max, self.buf.device, dtype=kernels.H16)
         check(_lib.lib().vh_kv_to_bf16(ptr(self.buf), ptr(out.buf), self.n_layers * 2 * self.batch * self.n_heads,
                                        self.s_max, self.s_max, s_max, stream()), 'vh_kv_to_bf16')
@@ -316,8 +319,10 @@ def transformer_forward(transformer, x, cache: KVCache, *, mode, x_len=0, x_len_
     if x_in is not None and (tuple(x_in.shape) != tuple(x.shape) or x_in.dtype != torch.float32):
         raise _lib.VhError('x_in must match x')
     if d != cfg.n_heads * HEAD_DIM:                          # a head width the native composite is not built for
+        # (a cache of this width is filled from the projections; any other cache argument is not this path's)
+        kv = cache if cache is not None and getattr(cache, 'head_dim', HEAD_DIM) == d // cfg.n_heads else None
         return _transformer_forward_generic(transformer, x, mode=mode, x_len=x_len, x_len_dev=x_len_dev, kv_len=kv_len,
-                                            mask=mask, pad=pad, embedding=embedding, x_in=x_in)
+                                            mask=mask, pad=pad, embedding=embedding, x_in=x_in, cache=kv)
     if cache is None or cache.batch != B or cache.s_max < T or cache.n_layers != cfg.num_layers:
         raise _lib.VhError('KV cache does not fit this forward')
     scratch = scratch or ForwardScratch(B * T, d, cfg.dim_feedforward, x.device)
@@ -337,18 +342,22 @@ def transformer_forward(transformer, x, cache: KVCache, *, mode, x_len=0, x_len_
     return x
 
 
-def _transformer_forward_generic(transformer, x, *, mode, x_len, x_len_dev, kv_len, mask, pad, embedding, x_in):
+def _transformer_forward_generic(transformer, x, *, mode, x_len, x_len_dev, kv_len, mask, pad, embedding, x_in, cache=None):
     """`transformer_forward` for a head width other than 64 (valle/models/modules.py:109-111 allows any divisor of d_model;
     every configuration of the path and of the reference's tests has 64, which is what the flash kernels and the native
     composite are built for).  The same pre-norm stack layer by layer on the general kernels — LayerNorm, the tile / skinny
-    GEMMs, materialised attention (`kernels.attn_generic`) — correct, not tuned, and without a KV cache: a caller that
-    decodes recomputes (ValleAR.generate_batch does)."""
+    GEMMs, materialised attention (`kernels.attn_generic`) — correct, not tuned.  With `cache` (a KVCache of this head
+    width) every layer's K / V columns of the projection the attention used are copied into cache rows 0..T-1
+    (`vh_kv_store`): the prompt pass of the cached decoder at these widths.  Without it nothing is cached."""
     cfg = transformer.hparams
     B, T, d = x.shape
     h = cfg.n_heads
     hd = d // h
     if hd % 4:
         raise _lib.VhError(f'head_dim {hd}: the general attention path needs a multiple of 4')
+    if cache is not None and (cache.bf16 or cache.head_dim != hd or cache.batch != B or cache.s_max < T
+                              or cache.n_layers != cfg.num_layers or cache.n_heads != h):
+        raise _lib.VhError('KV cache does not fit this forward')
     ada = None
     if cfg.norm != 'LayerNorm':
         if embedding is None:
@@ -362,6 +371,8 @@ def _transformer_forward_generic(transformer, x, *, mode, x_len, x_len_dev, kv_l
         sc1, sh1, sc2, sh2 = (ada[i, 0, 0], ada[i, 0, 1], ada[i, 1, 0], ada[i, 1, 1]) if ada is not None else (None,) * 4
         xn = kernels.layernorm(cur, g1, b1, ada_scale=sc1, ada_shift=sh1, eps=layer.norm1.eps)
         qkv = kernels.linear(xn, wqkv, out=torch.empty(B * T, 3 * d, **f32))
+        if cache is not None:
+            kernels.kv_store(qkv, cache.k(i), cache.v(i), B, T)
         q, k, v = (qkv.view(B, T, 3, h, hd)[:, :, j].permute(0, 2, 1, 3) for j in range(3))
         attn = torch.empty(B * T, d, **f32)
         kernels.attn_generic(q, k, v, attn.view(B, T, h, hd).permute(0, 2, 1, 3), hd ** -0.5, **spec)
@@ -386,6 +397,22 @@ def shared_prompt_fits(batch: int, n_heads: int, prefix_len: int) -> bool:
     """Whether vh_attn_decode_shared takes a prompt of prefix_len keys for `batch` beams (its merge serves at most 256
     records per (row, head): ceil(prefix_len / 32) prefix blocks + the suffix splits) — 4 beams x 8 heads: up to 7680 keys."""
     return (prefix_len + 31) // 32 + shared_n_split(batch, n_heads) <= SHARED_MAX_RECORDS
+
+
+def cached_decode_supported(cfg) -> bool:
+    """Whether ValleAR.generate_batch decodes `cfg` on the native K/V cache and the hipGraph decoder (pure Python: the
+    rule of plan.hip's decoder_check).  Width 64: config.use_kv_cache, as always.  Other head widths d_model / n_heads:
+    a multiple of 4 from 16 to 256 with d_model % 16 == 0 and d_model <= 1024 (the LayerNorm-fused decode GEMMs);
+    anything else recomputes every step."""
+    if not cfg.use_kv_cache:
+        return False
+    d, h = int(cfg.d_model), int(cfg.n_heads)
+    if h > 0 and d == h * HEAD_DIM:
+        return True
+    if h <= 0 or d % h:
+        return False
+    hd = d // h
+    return hd % 4 == 0 and 16 <= hd <= 256 and d % 16 == 0 and d <= 1024
 
 
 def pick_n_split(rows_x_heads: int) -> int:
@@ -475,7 +502,15 @@ class ArDecoder:
         self.hidden = torch.empty(batch, dff, **f32)
         self.logits = torch.zeros(batch, self.ldl, **f32)
         self.prefix, self.prefix_len = prefix, int(prefix_len)
-        if prefix is not None:
+        self.head_dim = hd = d // cfg.n_heads
+        if hd != HEAD_DIM:
+            # a head width other than 64: vh_attn_decode_hd over an fp32 cache of that width; no shared prompt, no bf16 cache
+            if prefix is not None or cache.bf16 or cache.head_dim != hd:
+                raise _lib.VhError(f'head width {hd}: the cached decoder takes an fp32 cache of that width, no shared prompt '
+                                   'and no bf16 (perf-mode) cache')
+            n = _lib.lib().vh_attn_decode_hd_ws_bytes(batch, cfg.n_heads, hd, self.n_split)
+            self.partial = torch.empty(max(n, 16) // 4, **f32) if n else None
+        elif prefix is not None:
             if prefix.bf16 or cache.bf16 or prefix.batch != 1 or prefix.n_layers != cfg.num_layers or not 0 < prefix_len <= prefix.s_max:
                 raise _lib.VhError('shared-prompt decoding: a one-row fp32 prefix cache holding prefix_len rows')
             self.partial = kernels.attn_decode_shared_ws(batch, cfg.n_heads, self.prefix_len, self.n_split, dev)

@@ -368,7 +368,9 @@ def attn_decode_ws(B, n_heads, n_split, device):
 
 def attn_decode(q, kcache, vcache, out, cache_len, len_bias, n_split=1, partial=None):
     B, n_heads, S_max, hd = kcache.shape
-    if hd != HEAD_DIM or q.shape[0] != B or out.shape[0] != B:
+    if hd != HEAD_DIM:                                   # another head width: the _hd kernel (width 64 is unchanged below)
+        return attn_decode_hd(q, kcache, vcache, out, cache_len, len_bias, n_split, partial)
+    if q.shape[0] != B or out.shape[0] != B:
         raise _lib.VhError('attn_decode: shapes')
     if cache_len.dtype != torch.int32 or cache_len.numel() != B:
         raise _lib.VhError('attn_decode: cache_len must be int32 (B)')
@@ -377,6 +379,75 @@ def attn_decode(q, kcache, vcache, out, cache_len, len_bias, n_split=1, partial=
         ptr(cache_len), len_bias, B, n_heads, S_max, n_split, ptr(partial), stream()),
         'vh_attn_decode')
     return out
+
+
+def attn_decode_hd_ws(B, n_heads, head_dim, n_split, device):
+    """Record workspace of `attn_decode_hd` (vh_attn_decode_hd_ws_bytes), as a float32 tensor; None without key splits."""
+    n = _lib.lib().vh_attn_decode_hd_ws_bytes(B, n_heads, head_dim, n_split)
+    return torch.empty(max(n, 16) // 4, device=device, dtype=torch.float32) if n else None
+
+
+def attn_decode_hd(q, kcache, vcache, out, cache_len, len_bias, n_split=1, partial=None, scale=None):
+    """One-query attention of B rows over fp32 caches (B, h, S_max, head_dim) at any served head width (multiples of 4
+    from 16 to 256; vh_attn_decode_hd): keys 0 .. cache_len[b] + len_bias - 1; scale defaults to head_dim ** -0.5."""
+    B, n_heads, S_max, hd = kcache.shape
+    if tuple(vcache.shape) != tuple(kcache.shape) or q.shape[0] != B or out.shape[0] != B or \
+            q.shape[1] < n_heads * hd or out.shape[1] < n_heads * hd:
+        raise _lib.VhError(f'attn_decode_hd: q {tuple(q.shape)} cache {tuple(kcache.shape)} out {tuple(out.shape)}')
+    if not (kcache.is_contiguous() and vcache.is_contiguous()) or kcache.dtype != torch.float32 or vcache.dtype != torch.float32:
+        raise _lib.VhError('attn_decode_hd: contiguous fp32 caches')
+    if cache_len.dtype != torch.int32 or cache_len.numel() != B:
+        raise _lib.VhError('attn_decode_hd: cache_len must be int32 (B)')
+    if partial is None and n_split > 1:
+        partial = attn_decode_hd_ws(B, n_heads, hd, n_split, q.device)
+    scale = float(hd ** -0.5) if scale is None else float(scale)
+    check(_lib.lib().vh_attn_decode_hd(
+        _dev_f32(q, 'q'), q.stride(0), ptr(kcache), ptr(vcache), _dev_f32(out, 'out'), out.stride(0), ptr(cache_len),
+        len_bias, B, n_heads, hd, S_max, scale, n_split, ptr(partial), partial.numel() * 4 if partial is not None else 0,
+        stream()), 'vh_attn_decode_hd')
+    return out
+
+
+def linear_qkv_hd(a, wqkv, q_out, kcache, vcache, n_heads, cache_len, ln=None, folded=None, eps=1e-5):
+    """The decode step's QKV projection at any head width (vh_linear_qkv_hd / vh_linear_qkv_folded_hd): one new row per
+    sequence (T = 1, B <= 64); Q -> q_out (B, d), the K / V rows appended at cache_len[b] of the caches
+    (B, h, S_max, d / h).  LayerNorm fused from ln = (gamma, beta, ada_scale, ada_shift, eps) as in `linear`, or from the
+    folded triple of ln_fold."""
+    B, d = a.shape
+    S_max = kcache.shape[2]
+    hd = d // n_heads if n_heads else 0
+    w = folded[0] if folded is not None else wqkv
+    if tuple(w.shape) != (3 * d, d) or d != n_heads * hd or tuple(kcache.shape) != (B, n_heads, S_max, hd) or \
+            kcache.shape != vcache.shape or tuple(q_out.shape[:1]) != (B,):
+        raise _lib.VhError(f'linear_qkv_hd: shapes a={tuple(a.shape)} w={tuple(w.shape)} cache={tuple(kcache.shape)}')
+    if cache_len is None or cache_len.dtype != torch.int32 or cache_len.numel() != B:
+        raise _lib.VhError('linear_qkv_hd: cache_len must be int32 (B)')
+    if folded is not None:
+        wf, c1, c2 = folded
+        check(_lib.lib().vh_linear_qkv_folded_hd(
+            _dev_f32(a, 'a'), a.stride(0), ptr(wf), ptr(c1), ptr(c2), _dev_f32(q_out, 'q_out'), q_out.stride(0), ptr(kcache),
+            ptr(vcache), ptr(cache_len), B, 1, d, n_heads, S_max, eps, hd, stream()), 'vh_linear_qkv_folded_hd')
+        return q_out
+    g, b, sc, sh, ln_eps = _ln_args(ln)
+    check(_lib.lib().vh_linear_qkv_hd(
+        _dev_f32(a, 'a'), a.stride(0), ptr(wqkv), _dev_f32(q_out, 'q_out'), q_out.stride(0), ptr(kcache), ptr(vcache),
+        ptr(cache_len), B, 1, d, n_heads, S_max, g, b, sc, sh, ln_eps, hd, stream()), 'vh_linear_qkv_hd')
+    return q_out
+
+
+def kv_store(qkv, kcache, vcache, B, T):
+    """K / V column blocks of a (B*T, 3 d) QKV projection into cache rows 0..T-1 of (B, h, S_max, d / h) caches
+    (vh_kv_store; a bit-exact copy)."""
+    _, n_heads, S_max, hd = kcache.shape
+    d = n_heads * hd
+    if qkv.dim() != 2 or qkv.shape[0] != B * T or qkv.shape[1] < 3 * d or qkv.stride(1) != 1 or \
+            tuple(kcache.shape[:2]) != (B, n_heads) or kcache.shape != vcache.shape or T > S_max:
+        raise _lib.VhError(f'kv_store: qkv {tuple(qkv.shape)} cache {tuple(kcache.shape)} B={B} T={T}')
+    if not (kcache.is_contiguous() and vcache.is_contiguous()) or kcache.dtype != torch.float32:
+        raise _lib.VhError('kv_store: contiguous fp32 caches')
+    check(_lib.lib().vh_kv_store(_dev_f32(qkv, 'qkv'), qkv.stride(0), ptr(kcache), ptr(vcache), B, T, n_heads, hd, S_max,
+                                 stream()), 'vh_kv_store')
+    return kcache, vcache
 
 
 def attn_decode_shared_ws(B, n_heads, prefix_len, n_split, device):

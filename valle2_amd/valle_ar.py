@@ -18,7 +18,8 @@ import torch.nn as nn
 from torch import optim
 
 from . import _lib, dropout, kernels
-from .engine import (ArDecoder, ForwardScratch, ForwardScratch16, KVCache, StepSampler, perf_forward_supported,
+from .engine import (ArDecoder, ForwardScratch, ForwardScratch16, KVCache, StepSampler, cached_decode_supported,
+                     perf_forward_supported,
                      shared_prompt_fits,
                      transformer_forward, transformer_forward_bf16)
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device, device_mirror
@@ -287,6 +288,8 @@ class ValleAR(_Base):
             cache, prefix = slot.cache, slot.prefix          # the buffers this shape's captured graphs point at
         elif run.any_head_dim:
             cache = None
+        elif run.hd_cached:                               # another head width: an fp32 cache of that width (no shared / perf form)
+            cache = KVCache(cfg.num_layers, B, cfg.n_heads, s_max, dev, head_dim=cfg.d_model // cfg.n_heads)
         elif run.shared:
             # ONE row through the prompt pass: its K/V are the prefix every beam reads; the beams' cache holds generated rows only
             prefix = KVCache(cfg.num_layers, 1, cfg.n_heads, (s0 + 31) // 32 * 32, dev)
@@ -313,7 +316,7 @@ class ValleAR(_Base):
             transformer_forward_bf16(self.transformer, x, cache, mode=kernels.MASK_PREFIX,
                                      scratch=ForwardScratch16(B * s0, d, cfg.dim_feedforward, dev), **run.fwd)
         else:
-            scratch = None if run.any_head_dim else ForwardScratch(rows * s0, d, cfg.dim_feedforward, dev)
+            scratch = None if run.any_head_dim or run.hd_cached else ForwardScratch(rows * s0, d, cfg.dim_feedforward, dev)
             transformer_forward(self.transformer, x, prefix if run.shared else cache, mode=kernels.MASK_PREFIX,
                                 scratch=scratch, **run.fwd)
         if run.ragged:
@@ -419,13 +422,20 @@ class ValleAR(_Base):
             raise ValueError('generate_batch: texts and first_codes must be non-empty lists of equal length')
         run = _Run()
         run.B, run.max_new = B, cfg.max_audio_len if max_new is None else max_new
-        # a head width other than 64 (modules.py:109-111 allows it; no configuration of the path has it): the native
-        # decoder and its KV-cache kernels are built for 64, so such a model decodes by recomputation on the general kernels
-        run.any_head_dim = cfg.d_model != cfg.n_heads * kernels.HEAD_DIM
+        # a head width other than 64 (modules.py:109-111 allows it): a multiple of 4 from 16 to 256 at d_model <= 1024 decodes on
+        # the cached decoder with the _hd kernels (hd_cached; the prompt pass runs on the general kernels and fills the cache);
+        # any other width recomputes every step on the general kernels (any_head_dim)
+        other_width = cfg.d_model != cfg.n_heads * kernels.HEAD_DIM
+        run.hd_cached = other_width and cached_decode_supported(cfg)
+        run.any_head_dim = other_width and not run.hd_cached
+        hd = cfg.d_model // cfg.n_heads if cfg.n_heads else 0
         no_cache = not cfg.use_kv_cache or run.any_head_dim
         if no_cache and (perf_mode or profile_attn or forced is not None or shared_prompt):
-            raise ValueError('use_kv_cache=False (or a head width other than 64) recomputes every step from scratch: '
-                             'perf_mode / profile_attn / forced / shared_prompt belong to the cached decoder')
+            raise ValueError('use_kv_cache=False (or a head width the cached decoder does not serve) recomputes every step '
+                             'from scratch: perf_mode / profile_attn / forced / shared_prompt belong to the cached decoder')
+        if run.hd_cached and (perf_mode or shared_prompt):
+            raise ValueError(f'head width {hd}: perf_mode and shared_prompt are width-64 forms of the cached decoder '
+                             '(this width decodes fp32 rows, each with its own prompt K/V)')
         if B > MAX_DECODE_ROWS:
             if shared_prompt or forced is not None:
                 raise ValueError(f'shared_prompt / forced serve at most {MAX_DECODE_ROWS} rows')
@@ -549,7 +559,8 @@ class ValleAR(_Base):
                                         # (nothing on a reused slot) + the tail after the last step has finished
                                         'decoder_reused': bool(reuse), 'slot_uses': slot.uses if slot is not None else 0,
                                         'host_setup_ms': (t_host1 - t_host0) * 1e3,
-                                        'host_decoder_ms': (t_host3 - t_host2) * 1e3}
+                                        'host_decoder_ms': (t_host3 - t_host2) * 1e3,
+                                        'kv_cache': not no_cache}
             out_codes = codes[:, : run.pl_max + n_new].clone()
             self.last_generate_stats['host_tail_ms'] = (time.perf_counter() - t_host4) * 1e3
             self.last_generate_stats['host_outside_ms'] = (self.last_generate_stats['host_setup_ms']
