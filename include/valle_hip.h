@@ -29,8 +29,9 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 128            /* 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
-#define VH_MAX_TABLES 8           /* EnCodec @6 kbps: 8 codebooks (valle/config.py:15-17) */
+#define VH_VERSION 129            /* 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
+#define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
 
 enum { VH_OK = 0, VH_EINVAL = -1, VH_EALIGN = -2, VH_EUNSUPPORTED = -3, VH_ELAUNCH = -4,
@@ -397,12 +398,26 @@ int vh_head_greedy(const float* x, int ldx, const float* proj_w, float* logits, 
  * always keeps the largest), torch.multinomial and the log-prob gather; then the bookkeeping of
  * vh_greedy_step plus sum_logprobs[b] += logprob while row b has not finished (valle_ar.py:167).
  * Randomness is a counter-based generator keyed on (seed, row, audio_pos[b]) — replaying a captured
- * graph draws fresh numbers; the stream is NOT torch's, so parity is distributional.  V <= 2048. */
+ * graph draws fresh numbers; the stream is NOT torch's, so parity is distributional.  V <= 2048 (wider rows: vh_sample_step_wide). */
 int vh_sample_step(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
                    float temperature, uint64_t seed, int64_t* codes, int64_t codes_stride,
                    int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                    const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
                    float* x_next, int B, int d, void* stream);
+
+/* ---- K12 (stochastic, wide): vh_sample_step for 1 <= V <= VH_SAMPLE_MAX_V --------------------------------
+ * Same signature and semantics as vh_sample_step (temperature, top-k with ties, top_k <= 0 keeps all, top-p, the draw
+ * from uniform01(seed, row, audio_pos[b]), the filtered log-prob, sum_logprobs, EOS, eos_count, the append, x_next,
+ * audio_pos / cache_len) for vocabularies up to 16384 entries.  One 1024-thread workgroup per row with the row's scores
+ * and indices in LDS (128 KiB); fast path (0 < top_k < V, top_p == 1): radix select of the k-th score and the draw over
+ * the survivors in index order; otherwise the survivors are sorted (descending, lower index first on ties) and the
+ * top-p cut and the draw are block-parallel scans.  Support and log-prob are vh_sample_step's; the token for a given
+ * seed is too unless the draw falls within fp32 rounding of a CDF boundary (the sums run in another order). */
+int vh_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
+                        float temperature, uint64_t seed, int64_t* codes, int64_t codes_stride,
+                        int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                        const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
+                        float* x_next, int B, int d, void* stream);
 
 /* ---- composite: one AR decode step / hipGraph replay ----------------------------------------
  * The 5 launches per layer of one decode step (LN1+QKV+append, decode attention, out-proj+
@@ -439,7 +454,8 @@ typedef struct {
     const int32_t *pos_base;          /* (B) or NULL */
     int64_t *codes;                   /* (B, codes_stride) growing code sequence */
     int64_t codes_stride;
-    /* sampling (valle/config.py:48-51): top_k == 1 → vh_greedy_step, else vh_sample_step */
+    /* sampling (valle/config.py:48-51): top_k == 1 → vh_greedy_step, else vh_sample_step (V <= 2048) or
+     * vh_sample_step_wide (V <= VH_SAMPLE_MAX_V; a wider V is refused when the decoder is created) */
     int top_k;
     float top_p, temperature;
     uint64_t seed;

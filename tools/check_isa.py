@@ -127,6 +127,38 @@ def compile_bf16_asm():
         return out.read_text()
 
 
+def compile_elementwise_asm():
+    with tempfile.TemporaryDirectory() as td:
+        out = Path(td) / 'elementwise.s'
+        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-S', '--cuda-device-only',
+                        '-mllvm', '-amdgpu-kernarg-preload-count=16',
+                        f'-I{REPO / "include"}', str(REPO / 'valle2_amd/csrc/elementwise.hip'), '-o', str(out)],
+                       check=True, capture_output=True)
+        return out.read_text()
+
+
+# kernels that index per-table / per-entry data with runtime indices and must keep them out of scratch: the 9..32-table
+# embedding sum (no per-table array) and the wide sampler (16 registers per lane in its compaction, fully unrolled)
+NO_SCRATCH_KERNELS = ['embed_sum_pe_many_kernel', 'sample_step_wide_kernel']
+
+
+def check_no_scratch(asm, names=NO_SCRATCH_KERNELS):
+    """No scratch access and a zero private segment in the named kernels (matched by their unmangled name)."""
+    problems = []
+    for name in names:
+        m = re.search(r'^(_Z\d+%s\w*):[^\n]*\n(.*?)^\.Lfunc_end' % re.escape(name), asm, re.S | re.M)
+        if not m:
+            problems.append(f'{name} not found')
+            continue
+        if any(l.strip().startswith(('scratch_', 'buffer_store', 'buffer_load')) for l in m.group(2).splitlines()):
+            problems.append(f'{name}: scratch access')
+        seg = re.search(r'\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel' % re.escape(m.group(1)), asm, re.S)
+        size = re.search(r'\.amdhsa_private_segment_fixed_size (\d+)', seg.group(1)) if seg else None
+        if size is None or int(size.group(1)) != 0:
+            problems.append(f'{name}: private segment {size.group(1) if size else "unknown"} bytes')
+    return problems
+
+
 def check_loop_waits(asm, kernels):
     """Round 6: fragments loaded BEFORE a tile loop and first used INSIDE it made the compiler's wait insertion put
     `s_waitcnt vmcnt(n)` in front of the first MFMAs of every iteration whenever a path around the pre-loop wait existed — a
@@ -180,6 +212,7 @@ if __name__ == '__main__':
     probs = check(compile_asm()) + check_attention(compile_attention_asm())
     probs += check_loop_waits(compile_attention_asm(), ATTN_WAIT_KERNELS) + check_loop_waits(compile_bf16_asm(), BF16_WAIT_KERNELS)
     probs += check_m0(compile_bf16_asm(), BF16_WAIT_KERNELS)
+    probs += check_no_scratch(compile_elementwise_asm())
     for p in probs:
         print('ISA check:', p)
     print('ISA check:', 'FAILED' if probs else 'ok')

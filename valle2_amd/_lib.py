@@ -164,6 +164,10 @@ SIGNATURES = {
     'vh_sample_step': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64,
                                  c_i64p, C.c_int64, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p,
                                  c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    # vocabularies wider than vh_sample_step's 2048 (ABI 129)
+    'vh_sample_step_wide': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64,
+                                      c_i64p, C.c_int64, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p,
+                                      c_f32p, C.c_int, C.c_int, C.c_void_p]),
     'vh_categorical_rows': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint32,
                                       c_i64p, C.c_int64, c_f32p, C.c_void_p]),
     'vh_adamw_ws_bytes': (C.c_size_t, []),

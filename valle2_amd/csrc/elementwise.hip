@@ -2,17 +2,22 @@
 // All HBM-bound row kernels: one wave64 per row, float4 per lane, wave-shuffle reductions.
 #include "vh_common.h"
 
+template <int CAP>
 struct TablePtrs {
-    const float* t[VH_MAX_TABLES];
-    int vocab[VH_MAX_TABLES];
+    const float* t[CAP];
+    int vocab[CAP];
 };
 
 // ---------------------------------------------------------------------------------------------
 // K1/K2  out[b, out_t0+t, :] = sum_j tables[j][ids[b,t,j], :] + pe[pos0+t, :]
 // grid: (ceil(T/4), B), block 256 = 4 waves, one wave per (b,t) row.
+// Two forms: embed_sum_pe_kernel<8> (up to 8 tables: every id read and checked once into a per-table array) and
+// embed_sum_pe_many_kernel (9 to VH_MAX_TABLES tables: no per-table array, which at 32 entries would live in scratch).
+// Both sum the codebooks in table order, then add the position row, then apply dropout: the same bits.
 // ---------------------------------------------------------------------------------------------
+template <int CAP>
 __global__ __launch_bounds__(256) void embed_sum_pe_kernel(
-    const int64_t* __restrict__ ids, int64_t ids_bs, int64_t ids_ts, int64_t ids_js, TablePtrs tabs,
+    const int64_t* __restrict__ ids, int64_t ids_bs, int64_t ids_ts, int64_t ids_js, TablePtrs<CAP> tabs,
     int n_tables, const float* __restrict__ pe, int pos0, const int32_t* __restrict__ lens,
     float* __restrict__ out, int64_t out_bs, int out_t0, int T, int d, int32_t* __restrict__ err_flag,
     const int32_t* __restrict__ row_pos0, const int32_t* __restrict__ row_t0, DropArgs drop) {
@@ -26,7 +31,7 @@ __global__ __launch_bounds__(256) void embed_sum_pe_kernel(
     const int64_t* idp = ids + b * ids_bs + t * ids_ts;
     // ids are range-checked here (the reference's nn.Embedding raises IndexError): an id outside its
     // table reads row 0 and raises the device flag the host polls at its next synchronisation
-    int64_t row[VH_MAX_TABLES];
+    int64_t row[CAP];
     bool bad = false;
     for (int j = 0; j < n_tables; ++j) {
         const int64_t id = idp[j * ids_js];
@@ -51,6 +56,42 @@ __global__ __launch_bounds__(256) void embed_sum_pe_kernel(
     }
 }
 
+// 9..VH_MAX_TABLES tables (EnCodec at 12 / 24 kbps: 16 / 32 codebooks): each table's id is read where it is used (one
+// wave-uniform load per table and column pass, from the L1 after the first pass) and range-checked there.
+__global__ __launch_bounds__(256) void embed_sum_pe_many_kernel(
+    const int64_t* __restrict__ ids, int64_t ids_bs, int64_t ids_ts, int64_t ids_js, TablePtrs<VH_MAX_TABLES> tabs,
+    int n_tables, const float* __restrict__ pe, int pos0, const int32_t* __restrict__ lens,
+    float* __restrict__ out, int64_t out_bs, int out_t0, int T, int d, int32_t* __restrict__ err_flag,
+    const int32_t* __restrict__ row_pos0, const int32_t* __restrict__ row_t0, DropArgs drop) {
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = blockIdx.y;
+    if (t >= T) return;
+    if (lens && t >= lens[b]) return;
+    if (row_pos0) pos0 = row_pos0[b];
+    if (row_t0) out_t0 = row_t0[b];
+    const int64_t* idp = ids + b * ids_bs + t * ids_ts;
+    float* orow = out + b * out_bs + (int64_t)(out_t0 + t) * d;
+    const float* prow = pe ? pe + (int64_t)(pos0 + t) * d : nullptr;
+    const uint32_t frow = (uint32_t)((b * out_bs) / d + out_t0 + t);
+    bool bad = false;
+    for (int c = lane * 4; c < d; c += 256) {
+        f32x4 acc = prow ? ld4(prow + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        auto gather = [&](int j) {
+            const int64_t id = idp[j * ids_js];
+            const bool ok = id >= 0 && id < tabs.vocab[j];
+            bad |= !ok;
+            return ld4(tabs.t[j] + (ok ? id : 0) * d + c);
+        };
+        f32x4 e = gather(0);
+        for (int j = 1; j < n_tables; ++j) e += gather(j);   // table order, as the form above
+        e += acc;
+        if (drop.thresh) e = e * vh_dropmul4(drop, frow, (uint32_t)c >> 2);
+        st4(orow + c, e);
+    }
+    if (bad && err_flag && lane == 0) atomicOr(err_flag, VH_DEVERR_EMBED_ID);
+}
+
 extern "C" int vh_embed_sum_pe(const int64_t* ids, int64_t ids_bstride, int64_t ids_tstride,
                                int64_t ids_jstride, const float* const* tables, const int32_t* vocab,
                                int n_tables, const float* pe, int pos0, const int32_t* lens, float* out,
@@ -70,18 +111,25 @@ extern "C" int vh_embed_sum_pe(const int64_t* ids, int64_t ids_bstride, int64_t 
         VH_REQUIRE(out_bstride % d == 0 && (int64_t)B * (out_bstride / d) < (1ll << 32), VH_EINVAL,
                    "vh_embed_sum_pe: dropout needs out_bstride %% d == 0");
     if (B == 0 || T == 0) return VH_OK;
-    TablePtrs tp{};
     for (int j = 0; j < n_tables; ++j) {
         VH_REQUIRE(tables[j] && vh_aligned16(tables[j]), VH_EALIGN,
                    "vh_embed_sum_pe: table %d null or unaligned", j);
         VH_REQUIRE(vocab[j] > 0, VH_EINVAL, "vh_embed_sum_pe: table %d has %d rows", j, vocab[j]);
-        tp.t[j] = tables[j];
-        tp.vocab[j] = vocab[j];
     }
     dim3 grid((T + 3) / 4, B);
-    hipLaunchKernelGGL(embed_sum_pe_kernel, grid, dim3(256), 0, (hipStream_t)stream, ids,
-                       ids_bstride, ids_tstride, ids_jstride, tp, n_tables, pe, pos0, lens, out,
-                       out_bstride, out_t0, T, d, err_flag, row_pos0, row_t0, da);
+    if (n_tables <= 8) {
+        TablePtrs<8> tp{};
+        for (int j = 0; j < n_tables; ++j) { tp.t[j] = tables[j]; tp.vocab[j] = vocab[j]; }
+        hipLaunchKernelGGL(embed_sum_pe_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, ids,
+                           ids_bstride, ids_tstride, ids_jstride, tp, n_tables, pe, pos0, lens, out,
+                           out_bstride, out_t0, T, d, err_flag, row_pos0, row_t0, da);
+    } else {
+        TablePtrs<VH_MAX_TABLES> tp{};
+        for (int j = 0; j < n_tables; ++j) { tp.t[j] = tables[j]; tp.vocab[j] = vocab[j]; }
+        hipLaunchKernelGGL(embed_sum_pe_many_kernel, grid, dim3(256), 0, (hipStream_t)stream, ids,
+                           ids_bstride, ids_tstride, ids_jstride, tp, n_tables, pe, pos0, lens, out,
+                           out_bstride, out_t0, T, d, err_flag, row_pos0, row_t0, da);
+    }
     VH_CHECK_LAUNCH("vh_embed_sum_pe");
     return VH_OK;
 }
@@ -594,6 +642,298 @@ extern "C" int vh_sample_step(const float* logits, int ldl, int V, int eos, int 
                               int32_t* cache_len, float* x_next, int B, int d, void* stream) {
     return vh_internal_sample_step(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, codes, codes_stride, eos_count,
                                    pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// K12 (stochastic, wide vocabularies)  vh_sample_step's semantics for 1 <= V <= VH_SAMPLE_MAX_V (16384).
+// One 1024-thread workgroup per row; the scores and their indices live in LDS (2 x 64 KiB at V = 16384; rows are far
+// fewer than CUs, so one workgroup per CU costs nothing):
+//   1. scores = logits / temperature into LDS, row maximum m;
+//   2. 0 < top_k < V: the key of the k-th largest score by the narrow kernel's 4 x 8-bit radix select;
+//   3. the survivors (score >= the k-th, ties kept; everything when top_k <= 0 or top_k >= V) are compacted in index
+//      order: every wave owns 64 x ceil(V / 1024) consecutive indices, a ballot per 64 of them and a scan over the 16
+//      wave counts give each survivor its slot — no per-thread cap;
+//   fast path (0 < top_k < V, top_p == 1): the draw walks the survivors in index order, as the narrow kernel's does;
+//   general path: bitonic sort of the survivors only, descending (ties: lower index first), then the top-p cut
+//      (suffix sums from the smallest, block-parallel) and the draw over the kept prefix of the sorted order.
+//   4. the draw: each thread sums exp(score - m) over a contiguous run, a block scan turns the run sums into CDF
+//      intervals, and the one thread whose interval holds u = uniform01(seed, row, audio_pos[b]) * total walks its
+//      run (the narrow kernel's general path does this on one thread over V entries).
+// No per-row state outlives the launch, so a captured graph replays as the narrow kernel's does.
+// ---------------------------------------------------------------------------------------------
+#define WIDE_THREADS 1024
+#define WIDE_WAVES (WIDE_THREADS / 64)
+#define WIDE_PER (VH_SAMPLE_MAX_V / WIDE_THREADS)   // indices per lane and 64-wide round of the compaction, at most
+
+// block-wide scan in thread order: *excl / return value = the exclusive / inclusive prefix of v, *total = the sum over
+// the block.  The values are consistent: a thread's excl is bit-equal to the previous thread's incl, the last thread's
+// incl to *total.  s_w holds WIDE_WAVES entries and may be reused once this returns.
+template <typename T>
+__device__ __forceinline__ T wide_block_scan(T v, T* s_w, T* excl, T* total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    T prev = __shfl_up(incl, 1, 64);
+    if (lane == 0) prev = 0;
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < WIDE_WAVES; ++w) {
+        if (w == wv) before = all;
+        all += s_w[w];
+    }
+    __syncthreads();
+    *excl = before + prev;
+    *total = all;
+    return before + incl;
+}
+
+// inverse CDF over the weights exp(s_val[j] - m), j < n, in array order: s_out[0] = the first j whose inclusive sum
+// exceeds u01 * total (the last entry when rounding leaves none), s_tot[0] = total.  Ends with a barrier.
+__device__ __forceinline__ void wide_draw(const float* s_val, int n, float m, float u01, float* s_w, int* s_out,
+                                          float* s_tot) {
+    const int tid = threadIdx.x;
+    const int per = (n + WIDE_THREADS - 1) / WIDE_THREADS;
+    const int j0 = min(n, tid * per), j1 = min(n, j0 + per);
+    float s = 0.f;
+    for (int j = j0; j < j1; ++j) s += expf(s_val[j] - m);
+    if (tid == 0) s_out[0] = n - 1;
+    float excl, total;
+    const float incl = wide_block_scan(s, s_w, &excl, &total);
+    const float u = u01 * total;
+    if (j1 > j0 && excl <= u && incl > u) {     // the intervals [excl, incl) tile [0, total): one owner at most
+        float acc = excl;
+        int pick = j1 - 1;
+        for (int j = j0; j < j1; ++j) {
+            acc += expf(s_val[j] - m);
+            if (acc > u) { pick = j; break; }
+        }
+        s_out[0] = pick;
+    }
+    if (tid == 0) s_tot[0] = total;
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
+    const float* __restrict__ logits, int ldl, int V, int eos, int top_k, float top_p, float inv_temp,
+    uint64_t seed, int64_t* __restrict__ codes, int64_t codes_stride, int32_t* __restrict__ eos_count,
+    const int32_t* __restrict__ pos_base, float* __restrict__ sum_logprobs,
+    const float* __restrict__ audio_emb, const float* __restrict__ pe, int32_t* __restrict__ audio_pos,
+    int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, const uint64_t* __restrict__ seed_dev) {
+    if (seed_dev) seed += *seed_dev;
+    __shared__ float s_val[VH_SAMPLE_MAX_V];
+    __shared__ int s_idx[VH_SAMPLE_MAX_V];
+    __shared__ int s_hist[256];
+    __shared__ float s_wf[WIDE_WAVES];
+    __shared__ int s_wi[WIDE_WAVES];
+    __shared__ float s_max[WIDE_WAVES];
+    __shared__ int s_sel[3];          // [0] chosen bin, [1] rank still wanted inside it, [2] pick (slot)
+    __shared__ float s_tot;
+    __shared__ int s_tok;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* lr = logits + (int64_t)b * ldl;
+    const int pos = audio_pos[b];
+
+    // 1. scores and their maximum
+    float vmax = -INFINITY;
+    for (int i = tid; i < V; i += WIDE_THREADS) {
+        const float x = lr[i] * inv_temp;
+        s_val[i] = x;
+        vmax = fmaxf(vmax, x);
+    }
+    vmax = wave_max(vmax);
+    if (lane == 0) s_max[wv] = vmax;
+    __syncthreads();
+    float m = s_max[0];
+#pragma unroll
+    for (int w = 1; w < WIDE_WAVES; ++w) m = fmaxf(m, s_max[w]);
+
+    // 2. key of the k-th largest score (survivors: key >= prefix; prefix 0 keeps every score)
+    uint32_t prefix = 0;
+    if (top_k > 0 && top_k < V) {
+        uint32_t mask = 0;
+        int want = top_k;                               // rank (from the top) of the k-th value among candidates
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) s_hist[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < V; i += WIDE_THREADS) {
+                const uint32_t key = okey(s_val[i]);
+                if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
+            }
+            __syncthreads();
+            if (wv == 0) {                              // lane l owns bins 255-4l .. 252-4l (descending)
+                int c[4], tot = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { c[j] = s_hist[255 - 4 * lane - j]; tot += c[j]; }
+                int incl = tot;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int up = __shfl_up(incl, o, 64);
+                    if (lane >= o) incl += up;
+                }
+                const int before = incl - tot;
+                if (before < want && incl >= want) {     // exactly one lane
+                    int acc = before;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (acc < want && acc + c[j] >= want) { s_sel[0] = 255 - 4 * lane - j; s_sel[1] = want - acc; }
+                        acc += c[j];
+                    }
+                }
+            }
+            __syncthreads();
+            prefix |= (uint32_t)s_sel[0] << shift;
+            mask |= 255u << shift;
+            want = s_sel[1];
+        }
+    }
+
+    // 3. compact the survivors in index order: (score, index) pairs into s_val[0..n) / s_idx[0..n)
+    const int per = (V + WIDE_THREADS - 1) / WIDE_THREADS;       // 64-wide rounds per wave
+    const int w0 = wv * 64 * per;
+    float v[WIDE_PER];
+    uint32_t keep = 0;
+    int cnt = 0;
+#pragma unroll
+    for (int r = 0; r < WIDE_PER; ++r) {
+        const int i = w0 + r * 64 + lane;
+        const bool in = r < per && i < V;
+        v[r] = in ? s_val[i] : 0.f;
+        const bool k = in && okey(v[r]) >= prefix;
+        keep |= (uint32_t)k << r;
+        cnt += __popcll(__ballot(k));
+    }
+    if (lane == 0) s_wi[wv] = cnt;
+    __syncthreads();                                   // every read of s_val above precedes the writes below
+    int at = 0, n = 0;
+#pragma unroll
+    for (int w = 0; w < WIDE_WAVES; ++w) {
+        if (w == wv) at = n;
+        n += s_wi[w];
+    }
+    const uint64_t below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int r = 0; r < WIDE_PER; ++r) {
+        const bool k = (keep >> r) & 1u;
+        const uint64_t bal = __ballot(k);
+        if (k) {
+            const int slot = at + __popcll(bal & below);
+            s_val[slot] = v[r];
+            s_idx[slot] = w0 + r * 64 + lane;
+        }
+        at += __popcll(bal);
+    }
+    __syncthreads();
+    const float u01 = uniform01(seed, (uint32_t)b, (uint32_t)pos);
+
+    if (top_k > 0 && top_k < V && top_p == 1.0f) {
+        // fast path: the draw over the survivors in index order
+        wide_draw(s_val, n, m, u01, s_wf, &s_sel[2], &s_tot);
+    } else {
+        // general path: sort the survivors descending (ties: lower index first) over the next power of two
+        int np2 = 1;
+        while (np2 < n) np2 <<= 1;
+        for (int i = n + tid; i < np2; i += WIDE_THREADS) { s_val[i] = -INFINITY; s_idx[i] = 0x7fffffff; }
+        __syncthreads();
+        for (int k = 2; k <= np2; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int q = tid; q < (np2 >> 1); q += WIDE_THREADS) {
+                    const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), p = i | j;   // the pair (i, i ^ j), i < p
+                    const bool desc = (i & k) == 0;
+                    const float a = s_val[i], c = s_val[p];
+                    const int ia = s_idx[i], ic = s_idx[p];
+                    const bool a_first = a > c || (a == c && ia < ic);   // a belongs before c
+                    if (desc ? !a_first : a_first) {
+                        s_val[i] = c; s_val[p] = a; s_idx[i] = ic; s_idx[p] = ia;
+                    }
+                }
+                __syncthreads();
+            }
+        int n_keep = n;
+        if (top_p >= 0.f && top_p <= 1.f) {
+            // drop entries from the smallest up while the cumulative probability of the dropped ones is <= 1 - top_p,
+            // always keeping the largest: n_keep = 1 + #{j >= 1 : sum_{i >= j} e_i > (1 - top_p) * total}.  Thread t
+            // owns the run that ends at n - t * run, so its exclusive prefix is the suffix sum after its run.
+            const int run = (n + WIDE_THREADS - 1) / WIDE_THREADS;
+            const int j1 = max(0, n - tid * run), j0 = max(0, j1 - run);
+            float s = 0.f;
+            for (int j = j1 - 1; j >= j0; --j) s += expf(s_val[j] - m);
+            float after, total;
+            wide_block_scan(s, s_wf, &after, &total);
+            const float limit = (1.0f - top_p) * total;
+            float tail = after;
+            int over = 0;
+            for (int j = j1 - 1; j >= j0; --j) {
+                tail += expf(s_val[j] - m);
+                over += j >= 1 && tail > limit;
+            }
+            int ex, n_over;
+            wide_block_scan(over, s_wi, &ex, &n_over);
+            n_keep = 1 + n_over;
+        }
+        wide_draw(s_val, n_keep, m, u01, s_wf, &s_sel[2], &s_tot);
+    }
+    const int slot = s_sel[2];
+    const int pick_tok = s_idx[slot];
+    const float pick_logprob = (s_val[slot] - m) - logf(s_tot);
+
+    if (tid == 0) {
+        int64_t* row = codes + (int64_t)b * codes_stride;
+        int tok = pick_tok;
+        const bool finished = row[pos - 1] == (int64_t)eos;
+        if (sum_logprobs && !finished) sum_logprobs[b] += pick_logprob;      // valle_ar.py:167
+        if (finished) tok = eos;                                             // valle_ar.py:168
+        row[pos] = tok;
+        if (tok == eos) atomicAdd(&eos_count[pos - (pos_base ? pos_base[b] : 0)], 1);
+        s_tok = tok;
+    }
+    __syncthreads();
+    const int tok = s_tok;
+    const float* er = audio_emb + (int64_t)tok * d;
+    const float* pr = pe + (int64_t)pos * d;
+    for (int c = tid * 4; c < d; c += 4 * WIDE_THREADS) {
+        const f32x4 e = ld4(er + c) + ld4(pr + c);
+        st4(x_next + (int64_t)b * d + c, e);
+    }
+    if (tid == 0) {
+        audio_pos[b] = pos + 1;
+        cache_len[b] += 1;
+    }
+}
+
+// vh_sample_step_wide with the seed = seed + *seed_dev (seed_dev may be NULL): the decoder plan's form (plan.hip)
+int vh_internal_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
+                                 float temperature, uint64_t seed, const uint64_t* seed_dev, int64_t* codes,
+                                 int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                                 const float* audio_emb, const float* pe, int32_t* audio_pos,
+                                 int32_t* cache_len, float* x_next, int B, int d, void* stream) {
+    VH_REQUIRE(logits && codes && eos_count && audio_emb && pe && audio_pos && cache_len && x_next,
+               VH_EINVAL, "vh_sample_step_wide: null pointer");
+    VH_REQUIRE(B > 0 && V > 0 && V <= VH_SAMPLE_MAX_V && ldl >= V && d > 0 && d % 4 == 0, VH_EINVAL,
+               "vh_sample_step_wide: bad dims B=%d V=%d (<= %d) ldl=%d d=%d", B, V, VH_SAMPLE_MAX_V, ldl, d);
+    VH_REQUIRE(temperature > 0.f, VH_EINVAL, "vh_sample_step_wide: temperature must be positive");
+    VH_REQUIRE(vh_aligned16(audio_emb) && vh_aligned16(pe) && vh_aligned16(x_next), VH_EALIGN,
+               "vh_sample_step_wide: audio_emb/pe/x_next must be 16-byte aligned");
+    hipLaunchKernelGGL(sample_step_wide_kernel, dim3(B), dim3(WIDE_THREADS), 0, (hipStream_t)stream, logits, ldl, V,
+                       eos, top_k, top_p, 1.0f / temperature, seed, codes, codes_stride, eos_count,
+                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, seed_dev);
+    VH_CHECK_LAUNCH("vh_sample_step_wide");
+    return VH_OK;
+}
+
+extern "C" int vh_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
+                                   float temperature, uint64_t seed, int64_t* codes, int64_t codes_stride,
+                                   int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                                   const float* audio_emb, const float* pe, int32_t* audio_pos,
+                                   int32_t* cache_len, float* x_next, int B, int d, void* stream) {
+    return vh_internal_sample_step_wide(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, codes, codes_stride,
+                                        eos_count, pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d,
+                                        stream);
 }
 
 

@@ -113,6 +113,8 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
     }
     VH_REQUIRE(d->top_k == 1 || d->temperature > 0.f, VH_EINVAL,
                "vh_ar_decoder: sampling (top_k=%d) needs temperature > 0", d->top_k);
+    VH_REQUIRE(d->top_k == 1 || d->V <= VH_SAMPLE_MAX_V, VH_EUNSUPPORTED,
+               "vh_ar_decoder: sampling (top_k=%d) serves V <= %d (VH_SAMPLE_MAX_V), got V=%d", d->top_k, VH_SAMPLE_MAX_V, d->V);
     if (d->head_ws) {
         VH_REQUIRE(d->top_k == 1 && d->B <= 64 && d->d_model <= 1024, VH_EUNSUPPORTED,
                    "vh_ar_decoder: head_ws (head + greedy step in one launch) is for top_k == 1, B <= 64, d_model <= 1024");
@@ -160,6 +162,11 @@ int vh_internal_sample_step(const float* logits, int ldl, int V, int eos, int to
                             const uint64_t* seed_dev, int64_t* codes, int64_t codes_stride, int32_t* eos_count,
                             const int32_t* pos_base, float* sum_logprobs, const float* audio_emb, const float* pe,
                             int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d, void* stream);   // elementwise.hip
+int vh_internal_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k, float top_p, float temperature,
+                                 uint64_t seed, const uint64_t* seed_dev, int64_t* codes, int64_t codes_stride,
+                                 int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs, const float* audio_emb,
+                                 const float* pe, int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d,
+                                 void* stream);   // elementwise.hip
 
 static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEvent_t>* ev,
                            std::vector<hipEvent_t>* kev = nullptr) {
@@ -274,6 +281,10 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
     if (d.top_k == 1)
         TRY(vh_greedy_step(d.logits, dec->ldl, d.V, d.eos, d.codes, d.codes_stride, d.eos_count,
                            d.pos_base, d.audio_emb, d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
+    else if (d.V > 2048)              // wider than vh_sample_step's LDS row (decoder_check bounds V by VH_SAMPLE_MAX_V)
+        TRY(vh_internal_sample_step_wide(d.logits, dec->ldl, d.V, d.eos, d.top_k, d.top_p, d.temperature, d.seed, d.seed_dev,
+                                         d.codes, d.codes_stride, d.eos_count, d.pos_base, d.sum_logprobs, d.audio_emb,
+                                         d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
     else
         TRY(vh_internal_sample_step(d.logits, dec->ldl, d.V, d.eos, d.top_k, d.top_p, d.temperature, d.seed, d.seed_dev,
                                     d.codes, d.codes_stride, d.eos_count, d.pos_base, d.sum_logprobs, d.audio_emb,

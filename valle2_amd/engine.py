@@ -167,7 +167,8 @@ def adaln_table(transformer, embedding):
     for ref, ver, key, table in state['tables']:
         if ref() is embedding and ver == embedding._version and key == pkey and table.device == embedding.device:
             return table
-    state['tables'] = [e for e in state['tables'] if e[0]() is not None and e[0]() is not embedding][-15:]
+    # (room for one table per stage of a 32-codebook NAR: 31 stage embeddings)
+    state['tables'] = [e for e in state['tables'] if e[0]() is not None and e[0]() is not embedding][-31:]
     if any(tuple(w.shape) != (2 * d, d) or not w.is_contiguous() or w.dtype != torch.float32 for w, _ in projs):
         raise _lib.VhError('adaln_table: project_layer weights must be contiguous fp32 (2 d, d)')
     ptrs = tuple(x for w, b in projs for x in (w.data_ptr(), b.data_ptr()))

@@ -17,6 +17,9 @@ MASK_FULL, MASK_PREFIX, MASK_EXPLICIT = 0, 1, 2
 H16 = _lib.h16_dtype()      # the 16-bit operand format of perf mode (float16 by default; the *_bf16 names are round 5's)
 ACT_NONE, ACT_GELU, ACT_GELU_BWD, ACT_GELU_D, ACT_MUL = 0, 1, 2, 3, 4
 HEAD_DIM = 64
+MAX_TABLES = 32           # VH_MAX_TABLES: codebooks one vh_embed_sum_pe sums (EnCodec at 24 kbps)
+SAMPLE_NARROW_V = 2048    # widest row vh_sample_step takes; wider rows go to vh_sample_step_wide
+SAMPLE_MAX_V = 16384      # VH_SAMPLE_MAX_V: widest row vh_sample_step_wide takes (num_audio_tokens <= 16383)
 
 
 def _f32(t, name):
@@ -42,6 +45,8 @@ def embed_sum_pe(ids, tables, pe, pos0, out, out_t0=0, lens=None, row_pos0=None,
         ids = ids.unsqueeze(-1)
     B, T, J = ids.shape
     n = len(tables)
+    if n > MAX_TABLES:
+        raise _lib.VhError(f'embed_sum_pe: {n} codebook tables; at most {MAX_TABLES} are summed (VH_MAX_TABLES)')
     if n > J and J != 1:
         raise _lib.VhError(f'{n} tables but ids has {J} codebooks')
     d = tables[0].shape[1]
@@ -592,14 +597,19 @@ def head_greedy(x, proj_w, logits, V, eos, codes, eos_count, audio_emb, pe, audi
 
 
 def sample_step(logits, V, eos, top_k, top_p, temperature, seed, codes, eos_count, sum_logprobs, audio_emb,
-                pe, audio_pos, cache_len, x_next, pos_base=None):
+                pe, audio_pos, cache_len, x_next, pos_base=None, wide=None):
+    """The stochastic decode step: `vh_sample_step` up to V = SAMPLE_NARROW_V, `vh_sample_step_wide` above it (up to
+    SAMPLE_MAX_V).  wide=True / False forces one kernel (tests compare the two at V <= 2048)."""
     B = logits.shape[0]
     d = x_next.shape[1]
-    check(_lib.lib().vh_sample_step(
+    if wide is None:
+        wide = V > SAMPLE_NARROW_V
+    name = 'vh_sample_step_wide' if wide else 'vh_sample_step'
+    check(getattr(_lib.lib(), name)(
         logits.data_ptr(), logits.stride(0), V, eos, int(top_k), float(top_p), float(temperature),
         int(seed) & (2 ** 64 - 1), ptr(codes), codes.stride(0), ptr(eos_count), ptr(pos_base),
         ptr(sum_logprobs), ptr(audio_emb), ptr(pe), ptr(audio_pos), ptr(cache_len), ptr(_f32(x_next, 'x_next')),
-        B, d, stream()), 'vh_sample_step')
+        B, d, stream()), name)
 
 
 def pad32(n):
