@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 129            /* 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 130            /* 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -203,7 +203,15 @@ int vh_linear_qkv(const float* A, int lda, const float* Wqkv, float* q_out, int 
  * vh_ln_fold prepares Wf (N,K), c1 (N), c2 (N) once per weight set (bias may be NULL);
  * vh_linear_folded / vh_linear_qkv_folded are vh_linear / vh_linear_qkv with (Wf, c1, c2) in
  * place of (W, bias, ln_gamma, ln_beta): mean / rstd are computed beside the products and applied
- * in the epilogue.  Supported: M <= 64, N % 16 == 0, K in {128, 256, 512, 1024}. */
+ * in the epilogue.  Supported: M <= 64, N % 16 == 0, K in {128, 256, 512, 1024}, and for vh_linear_folded /
+ * vh_linear_qkv_folded also K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} (K = 256 PW passes, PW in 5..8, one or two passes): 16 waves per 16 output columns, one or
+ * two passes over K, mean / variance from the operand fragments as one-pass sums about the mean of the row's first 32
+ * elements (the products run on x - that shift too, so the epilogue's correction is a fraction of the row's deviation);
+ * the shift being a mean of 32 of the row's own elements bounds the cancellation of the one-pass variance: (mean - shift)^2 <=
+ * K/32 var, at most 7 bits lost of 24 at K = 4096 even for a row whose first 32 elements are outliers;
+ * more than 16 rows run as row groups, so vh_linear_qkv_folded needs T == 1 there.  Deterministic (fixed summation
+ * order, no atomics).  The _hd and _kv16 forms and vh_ffn_decode keep K <= 1024.  Anything else: VH_EUNSUPPORTED with a
+ * message naming "folded LayerNorm". */
 int vh_ln_fold(const float* W, const float* gamma, const float* beta, const float* bias, float* Wf,
                float* c1, float* c2, int N, int K, void* stream);
 int vh_linear_folded(const float* A, int lda, const float* Wf, const float* c1, const float* c2,
@@ -439,6 +447,11 @@ typedef struct {
     const uint16_t *wqkv_f16, *wo16, *w1_f16, *w2_16;
 } vh_layer;
 
+/* d_model: head width 64 (d_model = 64 n_heads) up to 4096; other head widths up to 1024.  At d_model > 1024 (width 64 only) a
+ * layer with folded weights (d_model in the K set of vh_linear_folded) runs vh_linear_qkv_folded / vh_linear_folded at the wide K; a layer without
+ * them runs vh_layernorm into `attn` (free before the attention writes it and after the out-projection has read it) and
+ * the plain vh_linear_qkv / vh_linear: two more launches per layer, any d_model % 64 == 0.  kv_bf16, head_ws and the 16-bit
+ * weight copies are d_model <= 1024 forms.  d_model > 4096 is refused with a message naming 4096. */
 typedef struct {
     int B, d_model, n_heads, dff, n_layers, S_max, V, eos, n_split;
     float ln_eps;

@@ -159,6 +159,29 @@ def check_no_scratch(asm, names=NO_SCRATCH_KERNELS):
     return problems
 
 
+def check_wide_folded(asm):
+    """The folded-LayerNorm skinny GEMMs for 1024 < K <= 4096 (gemm_skinny_fast<1, 16, EPI_PLAIN | EPI_QKV, PW = 5..8, LN = 3>):
+    1024-thread workgroups, so a wave may hold 128 registers — PW = 8 keeps 64 of them as operand fragments.  All eight
+    instantiations must exist, stay within 128 VGPRs and touch no scratch (a spill is a memory round trip in a kernel that
+    is one round trip long)."""
+    problems = []
+    for epi in (0, 1):
+        for pw in (5, 6, 7, 8):
+            name = f'_Z16gemm_skinny_fastILi1ELi16ELi{epi}ELi{pw}ELi3ELi1ELb0EEvPKfS1_iiiii8GemmArgs6LnFuse'
+            m = re.search(r'^%s:[^\n]*\n(.*?)^\.Lfunc_end' % re.escape(name), asm, re.S | re.M)
+            seg = re.search(r'\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel' % re.escape(name), asm, re.S)
+            if not m or not seg:
+                problems.append(f'gemm_skinny_fast<1,16,{epi},{pw},3,1> not found')
+                continue
+            if any(l.strip().startswith('scratch_') for l in m.group(1).splitlines()):
+                problems.append(f'gemm_skinny_fast<1,16,{epi},{pw},3,1>: scratch access (register spill)')
+            priv = int(re.search(r'\.amdhsa_private_segment_fixed_size (\d+)', seg.group(1)).group(1))
+            vgpr = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', seg.group(1)).group(1))
+            if priv != 0 or vgpr > 128:
+                problems.append(f'gemm_skinny_fast<1,16,{epi},{pw},3,1>: private segment {priv} bytes, {vgpr} VGPRs (limit 128)')
+    return problems
+
+
 def check_loop_waits(asm, kernels):
     """Round 6: fragments loaded BEFORE a tile loop and first used INSIDE it made the compiler's wait insertion put
     `s_waitcnt vmcnt(n)` in front of the first MFMAs of every iteration whenever a path around the pre-loop wait existed — a
@@ -209,7 +232,8 @@ def check_m0(asm, kernels):
 
 
 if __name__ == '__main__':
-    probs = check(compile_asm()) + check_attention(compile_attention_asm())
+    gemm_asm = compile_asm()
+    probs = check(gemm_asm) + check_wide_folded(gemm_asm) + check_attention(compile_attention_asm())
     probs += check_loop_waits(compile_attention_asm(), ATTN_WAIT_KERNELS) + check_loop_waits(compile_bf16_asm(), BF16_WAIT_KERNELS)
     probs += check_m0(compile_bf16_asm(), BF16_WAIT_KERNELS)
     probs += check_no_scratch(compile_elementwise_asm())

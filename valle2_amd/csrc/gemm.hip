@@ -10,7 +10,8 @@
 //                         as the A operand so a lane's 4 results are 4 consecutive output columns; K over
 //                         the waves of a workgroup, reduced through LDS in fixed order; one workgroup per
 //                         (16 columns, 8..16 rows); LayerNorm in the operand load or folded into the
-//                         weights (vh_ln_fold); split-K slabs + splitk_reduce_kernel for K > 1024.
+//                         weights (vh_ln_fold; K up to 4096 with 16 waves, statistics from the operand fragments);
+//                         split-K slabs + splitk_reduce_kernel for K > 1024.
 //                         Latency-bound.
 //   * ffn_decode_kernel   FeedForward of the decode step as ONE launch split over dim_feedforward (ffn.hip).
 //   * gemm_skinny_kernel  the guarded generic version for K off the fast shapes.
@@ -928,6 +929,11 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs a, LnFuse
 //     3 = folded, statistics taken from the OPERAND FRAGMENTS (MT = 1): no second read of the rows — the rows are
 //         fresh data of the previous launch, written on other XCDs, and every KB a workgroup pulls of them costs
 //         (profiles/r3_probe_launch_floor.log: ~16 GB/s per CU); one-pass sums about the row's first element.
+//         NW = 8 for K <= 1024; NW = 16 for 1024 < K <= 4096 (K = 256·PW·passes): a lane adds the K / 64 elements it
+//         loads for the products anyway, over every pass, the wave folds its four k groups and the NW per-wave pairs
+//         are added in wave order — a fixed three-level sum, bit-reproducible, no atomics.  The NW = 16 form shifts by the
+//         mean of the row's first 32 elements and feeds x - shift to the products as well (see the body).  (The row-resident forms
+//         1 / 2 hold NJ = K / 64 float4 per lane: 256 registers at K = 4096.)
 //   W16: the weights are h16 (perf mode of the decode step, round 6): a fragment is 8 bytes per lane instead of 16 — half the
 //   bytes of the stream that bounds these kernels — widened to fp32 in registers right before its four MFMAs.
 template <int MT, int NW, int EPI, int PW, int LN, int NJ, bool W16 = false>
@@ -953,7 +959,7 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
     __shared__ __attribute__((aligned(16))) float red[NW][MT][64][4];
     __shared__ float s_mean[16 * MT], s_rstd[16 * MT];
     __shared__ __attribute__((aligned(16))) float pst[LN == 3 ? 16 : 1][2 * NW];   // LN == 3: (sum, sum of squares) per wave and row
-    static_assert(LN != 3 || (MT == 1 && NW == 8), "fragment statistics: one row tile, eight waves");
+    static_assert(LN != 3 || (MT == 1 && (NW == 8 || NW == 16)), "fragment statistics: one row tile, 8 or 16 waves");
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, g = lane >> 4;
     const int n0 = blockIdx.x * 16;
@@ -1012,7 +1018,23 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
     STAMP(0);
     if (ROWSTATS) ln_load(0);
     float shift = 0.f, fsa = 0.f, fsb = 0.f;               // LN == 3: statistics about the row's first element
-    if (LN == 3) shift = a.A[(int64_t)min(i, a.M - 1) * a.lda];
+    if (LN == 3) {
+        const float* r0 = a.A + (int64_t)min(i, a.M - 1) * a.lda;
+        if constexpr (NW == 16) {
+            // wide K: the shift is the mean of the row's first 32 elements (one 128-byte line, the same sum in every lane and
+            // wave of the row) and the PRODUCTS run on x - shift too: acc = (x - shift)·Wf, so the epilogue subtracts
+            // (mean - shift)·c1, a fraction of the row's deviation, instead of cancelling mean·c1 against an acc of that size
+            f32x4 h8[8];
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) h8[jj] = ld4(r0 + 4 * jj);
+            float hs = 0.f;
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) hs += (h8[jj].x + h8[jj].y) + (h8[jj].z + h8[jj].w);
+            shift = hs * (1.f / 32.f);
+        } else {
+            shift = r0[0];
+        }
+    }
     issue(0);
     // Epilogue operands (bias / residual / cache position) are fetched NOW by the lanes that will
     // finalise (wave w finalises m-tile w): loaded in the epilogue they would add one more
@@ -1076,6 +1098,7 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
                 const f32x4 t = xf[c][0] - shift;
                 fsa += (t.x + t.y) + (t.z + t.w);
                 fsb += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
+                if constexpr (NW == 16) xf[c][0] = t;
             }
         }
 #pragma unroll
@@ -1107,7 +1130,7 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
         f32x4 sacc = ld4(&red[0][mt][lane][0]);
 #pragma unroll
         for (int ww = 1; ww < NW; ++ww) sacc += ld4(&red[ww][mt][lane][0]);
-        if (LN == 3 && fin) {                // the 8 waves' partial sums, added in wave order
+        if (LN == 3 && fin) {                // the NW waves' partial sums, added in wave order
             f32x4 p[NW / 2];
 #pragma unroll
             for (int q4 = 0; q4 < NW / 2; ++q4) p[q4] = ld4(&pst[i][4 * q4]);
@@ -1116,8 +1139,13 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
 #pragma unroll
             for (int q4 = 1; q4 < NW / 2; ++q4) { sa += p[q4].x; sb += p[q4].y; sa += p[q4].z; sb += p[q4].w; }
             const float dm = sa / (float)a.K;
+            // One-pass variance about the shift.  NW == 16: the shift is the mean of 32 of the row's own elements, so those
+            // alone put at least 32/K dm^2 into the variance (their spread about the row mean is no less than 32 times their
+            // mean's distance from it): dm^2 / var <= K/32 <= 128 whatever the row holds, i.e. the subtraction loses at most
+            // log2(129) = 7 bits, never all of them.  The fmaxf only meets a CONSTANT row
+            // (every term exactly 0) and rounding of a variance below eps; it cannot hide a cancellation.
             const float var = fmaxf(sb / (float)a.K - dm * dm, 0.f);
-            sacc = (sacc - (shift + dm) * e_c1) * rsqrtf(var + ln.eps);
+            sacc = (sacc - (NW == 16 ? dm : shift + dm) * e_c1) * rsqrtf(var + ln.eps);
             if (IS_QKV(EPI)) sacc += e_bias;
         }
         if (LN == 2 && fin) {                // statistics were published before the barrier above
@@ -1363,6 +1391,11 @@ extern "C" size_t vh_linear_ex_ws_bytes(int M, int N, int K) {
     return split ? (size_t)(tiles - n_whole) * split * TM * TN * sizeof(float) : 0;
 }
 
+// K of the wide folded-LayerNorm form (gemm_skinny_fast<1, 16, .., PW, 3, 1>): 256 PW passes, PW in 5..8, one or two passes
+static bool folded_wide_k(int K) {
+    return K > 1024 && K <= 4096 && K % (K <= 2048 ? 256 : 512) == 0;
+}
+
 static int splitk_plan(int M, int N, int K) {
     // number of K slices (0 = do not split)
     if (M > 64) {
@@ -1428,7 +1461,8 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
         const bool has_ln = ln.gamma != nullptr || ln.c1 != nullptr;
         const bool fold = ln.c1 != nullptr;
         // one workgroup per (16 columns, 16 rows) instead of (16 columns, all rows): see the kernel
-        const bool rowgroups = vh_tuning(VH_TUNE_ROW_GROUPS) != 2 && mt >= 2 && (!wide || a.K % 2048 == 0) &&
+        // (the folded LayerNorm at K > 1024 is a one-row-tile kernel: every K of its set takes row groups)
+        const bool rowgroups = vh_tuning(VH_TUNE_ROW_GROUPS) != 2 && mt >= 2 && (!wide || a.K % 2048 == 0 || fold) &&
                                EPI != EPI_PARTIAL && (!IS_QKV(EPI) || a.T == 1);
         GemmArgs ag = a;                  // groups of 16 rows, or of 8 while that keeps the grid within the CUs
         if (rowgroups) {
@@ -1456,6 +1490,32 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
         VH_CHECK_LAUNCH(name);                                                 \
         return VH_OK;                                                          \
     } while (0)
+        if (fold && wide) {
+            // K = 256 PW passes with PW in 5..8 and one pass (1280 .. 2048) or two (2560, 3072, 3584, 4096): folded_wide_k,
+            // which check_folded enforced — any other K would make the pass loop read past the rows: 16 waves,
+            // passes, statistics from the fragments — one row tile per workgroup, more than 16 rows as row groups
+            if constexpr (EPI == EPI_PLAIN || EPI == EPI_QKV) {
+                if (a.w16) { vh_set_error("%s: no 16-bit-weight form of the folded LayerNorm at K=%d", name, a.K); return VH_EUNSUPPORTED; }
+                if (mt >= 2 && !rowgroups) {
+                    vh_set_error("%s: folded LayerNorm at K=%d serves more than 16 rows as row groups (T == 1, row groups enabled)",
+                                 name, a.K);
+                    return VH_EUNSUPPORTED;
+                }
+                const int passes = a.K <= 2048 ? 1 : 2, pw = a.K / (256 * passes);
+                if (!folded_wide_k(a.K) || pw < 5 || pw > 8 || 256 * pw * passes != a.K) {
+                    vh_set_error("%s: folded LayerNorm has no wide form for K=%d", name, a.K);
+                    return VH_EUNSUPPORTED;
+                }
+#define SFW(PW) hipLaunchKernelGGL((gemm_skinny_fast<1, 16, EPI, PW, 3, 1>), grid, dim3(1024), 0, s, SKINNY_ARGS(ag), ag, ln)
+                if (pw == 5) SFW(5); else if (pw == 6) SFW(6); else if (pw == 7) SFW(7); else SFW(8);
+#undef SFW
+                VH_CHECK_LAUNCH(name);
+                return VH_OK;
+            } else {
+                vh_set_error("%s: folded LayerNorm at K=%d serves the fp32 forms (vh_linear_folded, vh_linear_qkv_folded)", name, a.K);
+                return VH_EUNSUPPORTED;
+            }
+        }
         if (has_ln) {  // K <= 1024 (check_gemm); statistics need K = 64*NJ
             if (fold && (rowgroups || mt == 1) && vh_tuning(VH_TUNE_LN_STATS) != 1) {   // statistics from the fragments
 #define SF3(NW, PW) do { SF(1, NW, PW, 3, 1); VH_CHECK_LAUNCH(name); return VH_OK; } while (0)
@@ -1647,10 +1707,10 @@ extern "C" int vh_ln_fold(const float* W, const float* gamma, const float* beta,
 
 static int check_folded(const char* name, const GemmArgs& a, const LnFuse& ln) {
     VH_REQUIRE(ln.c1 && ln.c2, VH_EINVAL, "%s: null c1/c2", name);
-    VH_REQUIRE(a.M <= 64 && a.N % 16 == 0 && (a.K == 128 || a.K == 256 || a.K == 512 || a.K == 1024),
-               VH_EUNSUPPORTED,
-               "%s: folded LayerNorm is the decode path: M <= 64, N %% 16 == 0, K in {128,256,512,1024} "
-               "(M=%d N=%d K=%d)", name, a.M, a.N, a.K);
+    const bool k_ok = a.K == 128 || a.K == 256 || a.K == 512 || a.K == 1024 || folded_wide_k(a.K);
+    VH_REQUIRE(a.M <= 64 && a.N % 16 == 0 && k_ok, VH_EUNSUPPORTED,
+               "%s: folded LayerNorm is the decode path: M <= 64, N %% 16 == 0, K in {128,256,512,1024} or a multiple of 256 "
+               "up to 2048 / of 512 up to 4096 (M=%d N=%d K=%d)", name, a.M, a.N, a.K);
     VH_REQUIRE(vh_aligned16(ln.c1) && vh_aligned16(ln.c2), VH_EALIGN, "%s: c1/c2 must be 16-byte aligned", name);
     return VH_OK;
 }

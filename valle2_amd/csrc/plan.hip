@@ -76,6 +76,10 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
                    VH_EINVAL, "vh_ar_decoder: head width %d with n_split=%d needs attn_partial of vh_attn_decode_hd_ws_bytes() = %zu "
                    "bytes (got %zu)", hd, d->n_split, vh_attn_decode_hd_ws_bytes(d->B, d->n_heads, hd, d->n_split),
                    d->attn_partial_bytes);
+    } else {
+        // width 64: the prompt pass (vh_layernorm) and the folded decode GEMMs end at 4096
+        VH_REQUIRE(d->d_model <= 4096, VH_EUNSUPPORTED, "vh_ar_decoder: d_model=%d: the cached decoder serves d_model <= 4096",
+                   d->d_model);
     }
     VH_REQUIRE(d->dff % 16 == 0 && d->V > 0 && d->S_max > 0 && d->n_split >= 1, VH_EINVAL,
                "vh_ar_decoder: bad dff/V/S_max/n_split");
@@ -92,6 +96,8 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
                        "vh_ar_decoder: ffn_ws needs the folded linear_1 weights (layer %d)", i);
     }
     if (d->kv_bf16) {
+        VH_REQUIRE(d->d_model <= 1024, VH_EUNSUPPORTED, "vh_ar_decoder: the bf16 K/V cache (perf mode) serves d_model <= 1024 (got %d)",
+                   d->d_model);
         VH_REQUIRE(d->n_split == 1, VH_EUNSUPPORTED, "vh_ar_decoder: the bf16 K/V cache has no key-split form (n_split=%d)",
                    d->n_split);
         for (int i = 0; i < d->n_layers; ++i)
@@ -178,7 +184,11 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
     // measured: +1.6 us per step at 12L/512d x 32 rows, but 1.2 us per LAYER slower at 24L/1024d x 8 rows (256 slices of
     // 16 columns, 8 MB of slabs: profiles/r3_ab_config5_ffn.log) — the default follows the measurements
     const int ffn_knob = vh_tuning(VH_TUNE_FFN_FUSED);
-    const bool ffn_fused = d.ffn_ws && ffn_knob != 1 && (d.d_model <= 512 || ffn_knob == 2);
+    const bool ffn_fused = d.ffn_ws && ffn_knob != 1 && (d.d_model <= 512 || (ffn_knob == 2 && d.d_model <= 1024));
+    // d_model > 1024 (width 64): the LayerNorm-in-the-operand-load GEMMs end at K = 1024.  Folded weights (d_model 1280 .. 2048 in steps of 256, 2560 .. 4096 in steps of 512)
+    // run the wide folded GEMMs; without them the step normalises into d.attn — free before the attention writes it and again
+    // once the out-projection has read it — and runs the plain GEMMs on that: two more launches per layer, any d_model % 64 == 0.
+    const bool ln_apart = D > 1024;
     // decode attention of one layer, optionally bracketed by events (vh_ar_decoder_profile_attn)
     auto attention = [&](const vh_layer& L) -> int {
         if (hd != VH_HEAD_DIM)
@@ -237,7 +247,11 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         else if (L.wqkv_f)
             TRY(vh_linear_qkv_folded(d.x, D, L.wqkv_f, L.qkv_c1, L.qkv_c2, d.q, D, L.kcache, L.vcache,
                                      d.cache_len, B, 1, D, d.n_heads, d.S_max, d.ln_eps, s));
-        else
+        else if (ln_apart) {
+            TRY(vh_layernorm(d.x, L.ln1_g, L.ln1_b, nullptr, nullptr, d.attn, B, D, d.ln_eps, s));
+            TRY(vh_linear_qkv(d.attn, D, L.wqkv, d.q, D, L.kcache, L.vcache, d.cache_len, B, 1, D, d.n_heads,
+                              d.S_max, nullptr, nullptr, nullptr, nullptr, 0.f, s));
+        } else
             TRY(vh_linear_qkv(d.x, D, L.wqkv, d.q, D, L.kcache, L.vcache, d.cache_len, B, 1, D, d.n_heads,
                               d.S_max, L.ln1_g, L.ln1_b, nullptr, nullptr, d.ln_eps, s));
         TRY(run_attention(L));
@@ -261,7 +275,11 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         if (L.w1_f)
             TRY(vh_linear_folded(d.x, D, L.w1_f, L.w1_c1, L.w1_c2, nullptr, 0, d.hidden, d.dff, B, d.dff, D,
                                  VH_ACT_GELU_ERF, d.ln_eps, s));
-        else
+        else if (ln_apart) {
+            TRY(vh_layernorm(d.x, L.ln2_g, L.ln2_b, nullptr, nullptr, d.attn, B, D, d.ln_eps, s));
+            TRY(vh_linear(d.attn, D, L.w1, L.b1, nullptr, 0, d.hidden, d.dff, B, d.dff, D, VH_ACT_GELU_ERF,
+                          nullptr, nullptr, nullptr, nullptr, 0.f, s));
+        } else
             TRY(vh_linear(d.x, D, L.w1, L.b1, nullptr, 0, d.hidden, d.dff, B, d.dff, D, VH_ACT_GELU_ERF,
                           L.ln2_g, L.ln2_b, nullptr, nullptr, d.ln_eps, s));
         TRY(vh_linear_ws(d.hidden, d.dff, L.w2, L.b2, d.x, D, d.x, D, B, D, d.dff, VH_ACT_NONE, d.gemm_ws,

@@ -105,13 +105,25 @@ def invalidate_derived(module=None):
         _DERIVED.pop(module, None)
 
 
+MAX_DECODE_D_MODEL = 4096       # vh_layernorm (the prompt pass) and the wide folded decode GEMMs end here (plan.hip decoder_check)
+
+
+WIDE_FOLD_MAX_ROWS = 16         # decode rows up to which a d_model > 1024 step takes the folded GEMMs (ArDecoder)
+
+
+def folded_width(d: int) -> bool:
+    """K of the folded-LayerNorm decode GEMMs (gemm.hip check_folded): the four narrow shapes, or 256 PW passes with PW in 5..8 and one or
+    two passes — a multiple of 256 from 1280 to 2048, of 512 from 2560 to 4096 (16 waves, statistics from the operand fragments)."""
+    return d in (128, 256, 512, 1024) or (1024 < d <= MAX_DECODE_D_MODEL and d % (256 if d <= 2048 else 512) == 0)
+
+
 def folded_layer_norms(transformer):
     """Per layer ((Wqkv∘γ1, c1, c2), (W1∘γ2, c1, c2)) for the decode step, or None when the shape is
-    outside the folded kernels (d_model not in {128,256,512,1024}) or the norms are adaptive.  Cached
-    on the module and rebuilt when any of the source parameters changed (optimizer step, load)."""
+    outside the folded kernels (d_model not in {128,256,512,1024} and not one of 1280 .. 2048 in steps of 256 / 2560 .. 4096 in steps of 512) or the
+    norms are adaptive.  Cached on the module and rebuilt when any of the source parameters changed (optimizer step, load)."""
     layers = list(transformer.layers)
     d = transformer.hparams.d_model
-    if (not FOLD_LAYERNORM or d not in (128, 256, 512, 1024) or transformer.hparams.dim_feedforward % 16
+    if (not FOLD_LAYERNORM or not folded_width(d) or transformer.hparams.dim_feedforward % 16
             or any(hasattr(l.norm1, 'project_layer') for l in layers)):
         return None
     srcs = [(l.norm1.weight, l.norm1.bias, l.self_attn.qkv.weight, l.norm2.weight, l.norm2.bias,
@@ -306,6 +318,18 @@ class ForwardScratch:
         self.ws_bytes = max(L.vh_linear_ws_bytes(rows, d, d), L.vh_linear_ws_bytes(rows, d, dff),
                             L.vh_linear_ws_bytes(rows, dff, d))
         self.ws = torch.zeros(self.ws_bytes // 4, device=device, dtype=torch.float32) if self.ws_bytes else None
+        self.d, self.dff = d, dff
+
+    def fit(self, rows):
+        """Make the GEMM workspace fit a forward over `rows` <= the constructor's rows: the split-K plan of vh_linear_ws cuts
+        K >= 1024 deeper the FEWER output tiles there are, so a shorter forward can need more than the longest one."""
+        L = _lib.lib()
+        need = max(L.vh_linear_ws_bytes(rows, self.d, self.d), L.vh_linear_ws_bytes(rows, self.d, self.dff),
+                   L.vh_linear_ws_bytes(rows, self.dff, self.d))
+        if need > self.ws_bytes:
+            self.ws_bytes = need
+            self.ws = torch.zeros(need // 4, device=self.xn.device, dtype=torch.float32)
+        return self
 
 
 def transformer_forward(transformer, x, cache: KVCache, *, mode, x_len=0, x_len_dev=None,
@@ -402,14 +426,15 @@ def shared_prompt_fits(batch: int, n_heads: int, prefix_len: int) -> bool:
 
 def cached_decode_supported(cfg) -> bool:
     """Whether ValleAR.generate_batch decodes `cfg` on the native K/V cache and the hipGraph decoder (pure Python: the
-    rule of plan.hip's decoder_check).  Width 64: config.use_kv_cache, as always.  Other head widths d_model / n_heads:
+    rule of plan.hip's decoder_check).  Width 64: config.use_kv_cache up to d_model 4096 (above 1024 the step runs the wide
+    folded GEMMs where `folded_width(d_model)`, else LayerNorm and the plain GEMMs as separate launches).  Other head widths d_model / n_heads:
     a multiple of 4 from 16 to 256 with d_model % 16 == 0 and d_model <= 1024 (the LayerNorm-fused decode GEMMs);
     anything else recomputes every step."""
     if not cfg.use_kv_cache:
         return False
     d, h = int(cfg.d_model), int(cfg.n_heads)
     if h > 0 and d == h * HEAD_DIM:
-        return True
+        return d <= MAX_DECODE_D_MODEL
     if h <= 0 or d % h:
         return False
     hd = d // h
@@ -527,13 +552,18 @@ class ArDecoder:
         self.seed_dev = torch.tensor([int(seed)], dtype=torch.int64).to(dev) if self.sampling[0] != 1 else None
         self.codes, self.cache, self.cache_len, self.audio_pos = codes, cache, cache_len, audio_pos
         self.pos_base = pos_base
-        self._folded = folded_layer_norms(model.transformer)   # kept alive: the table holds raw pointers
+        # (above 1024 the folded GEMMs are one-row-tile kernels: more than 16 rows run as row groups that each stream the
+        # weights, and measured slower than LayerNorm + the plain GEMMs there — profiles/r7_wide_d_model.log)
+        wide_unfolded = d > 1024 and batch > WIDE_FOLD_MAX_ROWS
+        self._folded = None if wide_unfolded else folded_layer_norms(model.transformer)   # kept alive: the table holds raw pointers
+        self.ln_folded = self._folded is not None          # False above 1024: LayerNorm + plain GEMMs as separate launches
         self.kv_bf16 = cache.bf16
         if self.kv_bf16 and (self._folded is None or self.n_split != 1):
             raise _lib.VhError('perf mode (bf16 K/V cache) needs the folded LayerNorm weights and rows x heads >= 256 '
                                f'(one (row, head) per workgroup: n_split = {self.n_split})')
         # FeedForward of a layer as one launch split over dim_feedforward + the slab reduce (vh_ffn_decode)
-        ffn_bytes = _lib.lib().vh_ffn_decode_ws_bytes(batch, d, dff) if self._folded is not None else 0
+        # (d_model <= 1024: vh_ffn_decode's shape set; the plan takes it at d_model <= 512)
+        ffn_bytes = _lib.lib().vh_ffn_decode_ws_bytes(batch, d, dff) if self._folded is not None and d <= 1024 else 0
         self.ffn_ws = torch.empty(ffn_bytes // 4, **f32) if ffn_bytes else None
         # opt-in (VALLE2_HEAD_FUSED=1): head + greedy step as one launch (vh_head_greedy; DESIGN.md 3.20 has the A/B)
         self.head_ws = None

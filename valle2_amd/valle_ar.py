@@ -18,7 +18,7 @@ import torch.nn as nn
 from torch import optim
 
 from . import _lib, dropout, kernels
-from .engine import (ArDecoder, ForwardScratch, ForwardScratch16, KVCache, StepSampler, cached_decode_supported,
+from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, StepSampler, cached_decode_supported,
                      perf_forward_supported,
                      shared_prompt_fits,
                      transformer_forward, transformer_forward_bf16)
@@ -361,6 +361,8 @@ class ValleAR(_Base):
         while done < run.max_new:
             t = done
             xs = (torch.zeros if run.ragged else torch.empty)(B, s0 + t, d, device=dev, dtype=torch.float32)
+            if scratch is not None:
+                scratch.fit(B * (s0 + t))
             if not run.ragged:
                 self._embed_rows(run.text_ids, codes[:, :run.pl_max + t], xs)
                 transformer_forward(self.transformer, xs, cache, mode=kernels.MASK_PREFIX, scratch=scratch, **run.fwd)
@@ -429,6 +431,10 @@ class ValleAR(_Base):
         run.hd_cached = other_width and cached_decode_supported(cfg)
         run.any_head_dim = other_width and not run.hd_cached
         hd = cfg.d_model // cfg.n_heads if cfg.n_heads else 0
+        if not other_width and cfg.d_model > MAX_DECODE_D_MODEL:
+            # (cached_decode_supported is False there, but the recompute path's vh_layernorm ends at 4096 as well)
+            raise ValueError(f'd_model {cfg.d_model}: generation serves d_model <= {MAX_DECODE_D_MODEL} (the LayerNorm kernel of '
+                             'the prompt pass and the decode GEMMs end there)')
         no_cache = not cfg.use_kv_cache or run.any_head_dim
         if no_cache and (perf_mode or profile_attn or forced is not None or shared_prompt):
             raise ValueError('use_kv_cache=False (or a head width the cached decoder does not serve) recomputes every step '
@@ -436,6 +442,9 @@ class ValleAR(_Base):
         if run.hd_cached and (perf_mode or shared_prompt):
             raise ValueError(f'head width {hd}: perf_mode and shared_prompt are width-64 forms of the cached decoder '
                              '(this width decodes fp32 rows, each with its own prompt K/V)')
+        if perf_mode and cfg.d_model > 1024:
+            raise ValueError(f'd_model {cfg.d_model}: perf_mode (the bf16 K/V cache of the decode step) serves d_model <= 1024; '
+                             'wider models decode fp32')
         if B > MAX_DECODE_ROWS:
             if shared_prompt or forced is not None:
                 raise ValueError(f'shared_prompt / forced serve at most {MAX_DECODE_ROWS} rows')
@@ -546,6 +555,7 @@ class ValleAR(_Base):
             self.last_generate_stats = {'steps_run': done, 'tokens_appended': n_new, 'n_split': dec.n_split,
                                         'ffn_fused': dec.ffn_ws is not None and cfg.d_model <= 512, 'kv_bf16': dec.kv_bf16,
                                         'decode_w16': bool(getattr(dec, 'w16', False)),
+                                        'ln_folded': bool(getattr(dec, 'ln_folded', False)),
                                         'head_fused': dec.head_ws is not None,
                                         'prefill_bf16': run.perf_prefill, 'shared_prompt': run.shared, 'logits': kept,
                                         'prefill_ms': marks[0].elapsed_time(marks[1]),
