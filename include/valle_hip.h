@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 130            /* 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 131            /* 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -363,13 +363,29 @@ int vh_attn_decode_hd(const float* q, int ldq, const float* kcache, const float*
  *                            64, stream stride S_src * 64) into a bf16 cache (stream stride S_dst * 64), round to
  *                            nearest even: the prompt pass runs in fp32 and is narrowed once;
  *   vh_linear_qkv_folded_kv16  vh_linear_qkv_folded for one new row per sequence with the K / V rows appended as bf16;
- *   vh_attn_decode_kv16      vh_attn_decode (one (b, head) per workgroup, no key split) over the bf16 cache. */
+ *   vh_attn_decode_kv16      vh_attn_decode (one (b, head) per workgroup, no key split) over the bf16 cache;
+ *   vh_attn_decode_kv16_split  the same with the key range of a (b, head) split over n_split = 1..16 workgroups (ranges of
+ *                            32-key chunks; n_split == 1 IS vh_attn_decode_kv16's launch, bit for bit).  For n_split > 1
+ *                            `partial` must hold vh_attn_decode_ws_bytes(B, n_heads, n_split) bytes (partial_bytes says how
+ *                            many it holds; no initialisation needed); the records are added in split order by a second
+ *                            launch: deterministic, results differ from the unsplit form's by summation order only;
+ *   vh_attn_decode_shared_kv16  vh_attn_decode_shared over 16-bit prefix and suffix caches: the prompt's K / V are read once
+ *                            per step for all beams at half the bytes, widened to fp32 in registers (q is NOT rounded: fp32
+ *                            arithmetic on the rounded cache).  Same records, same bound ceil(prefix_len / 32) +
+ *                            n_split_suffix <= 256 (n_split_suffix = 1..16), same workspace (vh_attn_decode_shared_ws_bytes). */
 int vh_kv_to_bf16(const float* src, uint16_t* dst, int n_streams, int rows, int S_src, int S_dst, void* stream);
 int vh_linear_qkv_folded_kv16(const float* A, int lda, const float* Wf, const float* c1, const float* c2, float* q_out,
                               int ldq, uint16_t* kcache16, uint16_t* vcache16, const int32_t* cache_len, int B,
                               int d_model, int n_heads, int S_max, float ln_eps, void* stream);
 int vh_attn_decode_kv16(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, float* out, int ldo,
                         const int32_t* cache_len, int len_bias, int B, int n_heads, int S_max, void* stream);
+int vh_attn_decode_kv16_split(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, float* out, int ldo,
+                              const int32_t* cache_len, int len_bias, int B, int n_heads, int S_max, int n_split,
+                              void* partial, size_t partial_bytes, void* stream);
+int vh_attn_decode_shared_kv16(const float* q, int ldq, const uint16_t* kprefix16, const uint16_t* vprefix16, int prefix_len,
+                               int prefix_S, const uint16_t* ksuffix16, const uint16_t* vsuffix16, float* out, int ldo,
+                               const int32_t* suffix_len, int len_bias, int B, int n_heads, int S_suf, int n_split_suffix,
+                               void* partial, size_t partial_bytes, void* stream);
 
 /* ---- K12/K13: greedy sampling + decode-state update + next-token embedding ------------------
  * replaces topk_sampling(top_k=1) (valle/models/utils.py:46-68: argmax, lowest index on ties),
@@ -478,14 +494,17 @@ typedef struct {
     void *ffn_ws;
     size_t ffn_ws_bytes;
     /* perf mode (opt-in): nonzero = every layer's kcache / vcache point at bf16 caches (B,h,S_max,64) and the step
-     * runs vh_linear_qkv_folded_kv16 + vh_attn_decode_kv16; needs folded weights in every layer and n_split == 1. */
+     * runs vh_linear_qkv_folded_kv16 + vh_attn_decode_kv16; needs folded weights in every layer.  n_split > 1: the attention is
+     * vh_attn_decode_kv16_split and attn_partial must hold vh_attn_decode_ws_bytes(B, n_heads, n_split) bytes
+     * (attn_partial_bytes says how many it holds).  With prefix_len > 0: see below. */
     int kv_bf16;
     /* shared prompt (the reference's generate(): ONE utterance replicated over num_beams rows, valle_ar.py:135-138 — every
      * beam's prompt K/V is the same bits).  prefix_len > 0: the first prefix_len keys of every row live ONCE in
      * layers[i].kprefix / vprefix ((1, h, prefix_S, 64)); layers[i].kcache / vcache are (B, h, S_max, 64) caches of the
      * GENERATED rows only, cache_len[b] counts those, and the step's attention is vh_attn_decode_shared (n_split = key
      * splits of the suffix part).  attn_partial must hold vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split)
-     * bytes (attn_partial_bytes says how many it holds).  Not with kv_bf16. */
+     * bytes (attn_partial_bytes says how many it holds).  With kv_bf16 the prefix caches are 16-bit as well (kprefix / vprefix
+     * then point at uint16_t data) and the attention is vh_attn_decode_shared_kv16: same bound, same workspace. */
     int prefix_len, prefix_S;
     size_t attn_partial_bytes;
     /* optional (opt-in): zeroed workspace of vh_head_greedy_ws_bytes(B, V) bytes; with it and top_k == 1 the head and the

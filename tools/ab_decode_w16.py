@@ -21,7 +21,7 @@ def main():
     from valle2_amd import ConfigValle, engine, get_model_class, synth
     for name, kw, rows, text, frames, new in (
             ('configs[1] 12L/512d x 32 rows', dict(d_model=512, n_heads=8, dim_feedforward=2048, num_layers=12), 32, 256, 767, 512),
-            ('24L/1024d x 16 rows (configs[4] model; perf mode wants rows x heads >= 256)', dict(d_model=1024, n_heads=16, dim_feedforward=4096, num_layers=24), 16, 400, 225, 512)):
+            ('24L/1024d x 16 rows (configs[4] model; rows x heads = 256: perf mode without key splits)', dict(d_model=1024, n_heads=16, dim_feedforward=4096, num_layers=24), 16, 400, 225, 512)):
         cfg = ConfigValle(**kw, dropout=0.0, norm='LayerNorm', num_beams=rows, top_k=1, max_audio_len=new)
         sd = synth.silence_eos(synth.make_state_dict(cfg, 'ValleAR', seed=0, rich=False), cfg)
         m = get_model_class('ValleAR')(cfg)

@@ -182,6 +182,34 @@ def check_wide_folded(asm):
     return problems
 
 
+# perf mode with key splits / a shared prompt: the two ring16 split shapes and the two-role shared kernel over 16-bit caches
+PERF_MODE_BEAMS_KERNELS = {'attn_decode_ring16_split_kernel': 2, 'attn_shared16_kernel': 1}
+
+
+def check_perf_mode_beams(asm, max_vgprs=256):
+    """The 16-bit key-split and shared-prompt decode kernels (csrc/attention.hip): every instantiation exists, touches no
+    scratch (zero private segment, no scratch_ instruction) and allocates at most 256 vector registers (AGPRs included:
+    .amdhsa_next_free_vgpr counts the unified file, rounded up to 8) — two waves per SIMD of the 512-register file."""
+    problems = []
+    for name, n_expected in PERF_MODE_BEAMS_KERNELS.items():
+        found = re.findall(r'^(_Z\d+%s\w*):[^\n]*\n(.*?)^\.Lfunc_end' % re.escape(name), asm, re.S | re.M)
+        if len(found) != n_expected:
+            problems.append(f'{name}: expected {n_expected} instantiation(s), found {len(found)}')
+        for mangled, body in found:
+            if any(l.strip().startswith('scratch_') for l in body.splitlines()):
+                problems.append(f'{mangled}: scratch access (register spill)')
+            seg = re.search(r'\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel' % re.escape(mangled), asm, re.S)
+            if not seg:
+                problems.append(f'{mangled}: no kernel descriptor')
+                continue
+            priv = int(re.search(r'\.amdhsa_private_segment_fixed_size (\d+)', seg.group(1)).group(1))
+            vgpr = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', seg.group(1)).group(1))
+            alloc = (vgpr + 7) // 8 * 8
+            if priv != 0 or alloc > max_vgprs:
+                problems.append(f'{mangled}: private segment {priv} bytes, {vgpr} VGPRs (limit {max_vgprs}: 2 waves per SIMD)')
+    return problems
+
+
 def check_loop_waits(asm, kernels):
     """Round 6: fragments loaded BEFORE a tile loop and first used INSIDE it made the compiler's wait insertion put
     `s_waitcnt vmcnt(n)` in front of the first MFMAs of every iteration whenever a path around the pre-loop wait existed — a
@@ -237,6 +265,7 @@ if __name__ == '__main__':
     probs += check_loop_waits(compile_attention_asm(), ATTN_WAIT_KERNELS) + check_loop_waits(compile_bf16_asm(), BF16_WAIT_KERNELS)
     probs += check_m0(compile_bf16_asm(), BF16_WAIT_KERNELS)
     probs += check_no_scratch(compile_elementwise_asm())
+    probs += check_perf_mode_beams(compile_attention_asm())
     for p in probs:
         print('ISA check:', p)
     print('ISA check:', 'FAILED' if probs else 'ok')

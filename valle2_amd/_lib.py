@@ -139,6 +139,12 @@ SIGNATURES = {
                                             C.c_void_p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     'vh_attn_decode_kv16': (C.c_int, [c_f32p, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_int, c_i32p, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_void_p]),
+    # perf mode with key splits / a shared prompt (ABI 131)
+    'vh_attn_decode_kv16_split': (C.c_int, [c_f32p, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_int, c_i32p, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'vh_attn_decode_shared_kv16': (C.c_int, [c_f32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             c_f32p, C.c_int, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_size_t, C.c_void_p]),
     'vh_attn_decode_ws_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'vh_attn_decode_shared_ws_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'vh_attn_decode_shared': (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int,

@@ -313,6 +313,9 @@ __device__ __forceinline__ float row8_sum(float v) {
 #define BF_LO(w) vh_h16_lo(w)
 #define BF_HI(w) vh_h16_hi(w)
 
+// (TWIN: ring16_range below carries the same load / reduce / fold / cross-wave combine for a chunk range — the key-split and
+// shared-prompt forms.  This kernel is kept as it was so that vh_attn_decode_kv16 stays bit-identical; a change to the burst
+// loop here belongs there too.)
 template <int NW, int D>
 __global__ __launch_bounds__(NW * 64) void attn_decode_ring16_kernel(
     const float* __restrict__ q, int ldq, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
@@ -466,6 +469,151 @@ __global__ __launch_bounds__(64) void attn_decode_combine_kernel(
     out[(int64_t)b * ldo + head * HD + tid] = O / L;
 }
 
+// Key range [c_begin, c_end) of 32-key chunks of ONE (row, head) stream of the 16-bit cache, by the NW waves of a workgroup: the
+// ring16 kernel's burst loop (8 lanes per key, non-temporal 16-byte loads, D register sets per wave, fp32 arithmetic on the
+// widened values) without its speculative first bursts — a key split does not know its chunks before it knows the length.
+// kb / vb: the stream's first row; loads are clamped to the row's last key and the keys past the length are SELECTED away (the
+// rows behind them may hold NaN / Inf).  On return threads tid < 64 hold column tid of the workgroup's record: O (unnormalised),
+// M (scores in log2 units; -inf for an empty range) and L.  Every thread of the workgroup must call it (one barrier inside).
+// (TWIN of the body of attn_decode_ring16_kernel above, which stays untouched for bit-identity of vh_attn_decode_kv16: what differs
+// is the chunk range, the absent speculative bursts and where the result goes.  Keep the two burst loops in step.)
+template <int NW, int D>
+__device__ __forceinline__ void ring16_range(const float* __restrict__ qrow, const uint16_t* __restrict__ kb,
+                                             const uint16_t* __restrict__ vb, int len, int c_begin, int c_end, float* s_m,
+                                             float* s_l, float (*s_o)[HD], float& M, float& L, float& O) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c8 = lane & 7, kg = lane >> 3;
+    kb += 8 * c8;
+    vb += 8 * c8;
+    constexpr int LPS = 4;                                         // 8 keys per wave-instruction
+    u32x4 kf[D][LPS], vf[D][LPS];
+    const int key_limit = len - 1;
+    auto load = [&](int c, u32x4 (&kq)[LPS], u32x4 (&vq)[LPS]) {
+        const int key0 = c * 32 + kg;
+#pragma unroll
+        for (int i = 0; i < LPS; ++i) {
+            const int key = min(key0 + 8 * i, key_limit);
+            kq[i] = ld16_stream(kb + (int64_t)key * HD);
+            vq[i] = ld16_stream(vb + (int64_t)key * HD);
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < D - 1; ++j)
+        if (c_begin + w + j * NW < c_end) load(c_begin + w + j * NW, kf[j], vf[j]);
+    const float qscale = 0.125f * LOG2E;
+    const f32x4 qa = ld4(qrow + 8 * c8) * qscale, qb = ld4(qrow + 8 * c8 + 4) * qscale;
+
+    float m = NEG_INF, l = 0.f;
+    f32x4 oa = {0.f, 0.f, 0.f, 0.f}, ob = {0.f, 0.f, 0.f, 0.f};
+    auto reduce = [&](int c, const u32x4 (&kq)[LPS], const u32x4 (&vq)[LPS]) {
+        const int key0 = c * 32 + kg;
+        const bool whole = c * 32 + 32 <= len;
+        float sc[LPS];
+        float cmax = NEG_INF;
+#pragma unroll
+        for (int i = 0; i < LPS; ++i) {
+            const u32x4 kk = kq[i];
+            float d = BF_LO(kk.x) * qa.x + BF_HI(kk.x) * qa.y + BF_LO(kk.y) * qa.z + BF_HI(kk.y) * qa.w;
+            d += BF_LO(kk.z) * qb.x + BF_HI(kk.z) * qb.y + BF_LO(kk.w) * qb.z + BF_HI(kk.w) * qb.w;
+            d = row8_sum(d);
+            sc[i] = (whole || key0 + 8 * i < len) ? d : NEG_INF;
+            cmax = fmaxf(cmax, sc[i]);
+        }
+        cmax = fmaxf(cmax, __shfl_xor(cmax, 8, 64));
+        cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
+        cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
+        const float m_new = fmaxf(m, cmax);                        // finite: chunk c < ceil(len / 32) holds >= 1 valid key
+        const float alpha = vh_exp2(m - m_new);
+        oa *= alpha; ob *= alpha;
+        l *= alpha;
+#pragma unroll
+        for (int i = 0; i < LPS; ++i) {
+            const float p = vh_exp2(sc[i] - m_new);
+            l += p;
+            u32x4 vv = vq[i];
+            if (!(whole || key0 + 8 * i < len)) vv = u32x4{0u, 0u, 0u, 0u};   // rows beyond the length: select, not * 0
+            oa += f32x4{BF_LO(vv.x), BF_HI(vv.x), BF_LO(vv.y), BF_HI(vv.y)} * p;
+            ob += f32x4{BF_LO(vv.z), BF_HI(vv.z), BF_LO(vv.w), BF_HI(vv.w)} * p;
+        }
+        m = m_new;
+    };
+    for (int c0 = c_begin + w; c0 < c_end; c0 += D * NW) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            const int c = c0 + j * NW;
+            if (c < c_end) {
+                const int cn = c + (D - 1) * NW;
+                if (cn < c_end) load(cn, kf[(j + D - 1) % D], vf[(j + D - 1) % D]);
+                reduce(c, kf[j], vf[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int sh = 8; sh <= 32; sh <<= 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            oa[j] += __shfl_xor(oa[j], sh, 64);
+            ob[j] += __shfl_xor(ob[j], sh, 64);
+        }
+        l += __shfl_xor(l, sh, 64);
+    }
+    if (lane < 8) { st4(&s_o[w][8 * c8], oa); st4(&s_o[w][8 * c8 + 4], ob); }
+    if (lane == 0) { s_m[w] = m; s_l[w] = l; }
+    __syncthreads();
+    M = s_m[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) M = fmaxf(M, s_m[k]);
+    L = 0.f;
+    O = 0.f;
+    if (tid < HD) {
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            const float wgt = s_m[k] == NEG_INF ? 0.f : vh_exp2(s_m[k] - M);   // (a wave without a chunk; M itself is -inf only
+            L += s_l[k] * wgt;                                                  //  for an empty range)
+            O += s_o[k][tid] * wgt;
+        }
+    }
+}
+
+// Key-split form of the ring16 kernel: grid (n_split, B h); split s of a (row, head) takes chunks [s cps, (s + 1) cps) of its
+// ceil(len / 32) and writes one PART_LD record (o[64], m, l) — the layout attn_decode_combine_kernel reads.  A split without keys
+// leaves m = -inf and weighs nothing.
+template <int NW, int D>
+__global__ __launch_bounds__(NW * 64) void attn_decode_ring16_split_kernel(
+    const float* __restrict__ q, int ldq, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
+    const int32_t* __restrict__ cache_len, int len_bias, int n_heads, int S_max, int n_split, float* __restrict__ partial) {
+    __shared__ float s_m[NW], s_l[NW];
+    __shared__ __attribute__((aligned(16))) float s_o[NW][HD];
+    const int bh = blockIdx.y, b = bh / n_heads, head = bh - b * n_heads;
+    const int split = blockIdx.x;
+    const int len = min(cache_len[b] + len_bias, S_max);           // (never a row beyond the allocation)
+    const int nchunks = (len + 31) / 32;
+    const int cps = (nchunks + n_split - 1) / n_split;
+    const int c_begin = split * cps;
+    const int c_end = min(nchunks, c_begin + cps);
+    float M, L, O;
+    ring16_range<NW, D>(q + (int64_t)b * ldq + head * HD, kc + (int64_t)bh * S_max * HD, vc + (int64_t)bh * S_max * HD, len,
+                        c_begin, c_end, s_m, s_l, s_o, M, L, O);
+    const int tid = threadIdx.x;
+    if (tid < HD) {
+        float* pr = partial + ((int64_t)bh * n_split + split) * PART_LD;
+        pr[tid] = O;
+        if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
+    }
+}
+
+static void launch_ring16(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, float* out, int ldo,
+                          const int32_t* cache_len, int len_bias, int B, int n_heads, int S_max, void* stream) {
+#define AD16(NW, D)                                                                                                  \
+    hipExtLaunchKernelGGL((attn_decode_ring16_kernel<NW, D>), dim3(1, B * n_heads), dim3(NW * 64), 0, (hipStream_t)stream, \
+                          g_attn_ev[0], g_attn_ev[1], 0, q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, n_heads, \
+                          S_max)
+    // ring shape (waves x register sets of 32 keys): 8 x 2 as the fp32 kernel; 16 x 1, 16 x 2, 8 x 3, 8 x 4 and 4 x 4
+    // measured within 3 % of it (461-477 us per decode step, profiles/r3_ab_decode_perf_mode.log)
+    AD16(8, 2);
+#undef AD16
+}
+
 extern "C" int vh_attn_decode_kv16(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16,
                                    float* out, int ldo, const int32_t* cache_len, int len_bias, int B, int n_heads,
                                    int S_max, void* stream) {
@@ -476,15 +624,45 @@ extern "C" int vh_attn_decode_kv16(const float* q, int ldq, const uint16_t* kcac
                ldq, ldo);
     VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kcache16) && vh_aligned16(vcache16), VH_EALIGN,
                "vh_attn_decode_kv16: pointers must be 16-byte aligned");
-#define AD16(NW, D)                                                                                                  \
-    hipExtLaunchKernelGGL((attn_decode_ring16_kernel<NW, D>), dim3(1, B * n_heads), dim3(NW * 64), 0, (hipStream_t)stream, \
-                          g_attn_ev[0], g_attn_ev[1], 0, q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, n_heads, \
-                          S_max)
-    // ring shape (waves x register sets of 32 keys): 8 x 2 as the fp32 kernel; 16 x 1, 16 x 2, 8 x 3, 8 x 4 and 4 x 4
-    // measured within 3 % of it (461-477 us per decode step, profiles/r3_ab_decode_perf_mode.log)
-    AD16(8, 2);
-#undef AD16
+    launch_ring16(q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, B, n_heads, S_max, stream);
     VH_CHECK_LAUNCH("vh_attn_decode_kv16");
+    return VH_OK;
+}
+
+extern "C" size_t vh_attn_decode_ws_bytes(int B, int n_heads, int n_split);
+
+extern "C" int vh_attn_decode_kv16_split(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16,
+                                         float* out, int ldo, const int32_t* cache_len, int len_bias, int B, int n_heads,
+                                         int S_max, int n_split, void* partial, size_t partial_bytes, void* stream) {
+    VH_REQUIRE(q && kcache16 && vcache16 && out && cache_len, VH_EINVAL, "vh_attn_decode_kv16_split: null pointer");
+    VH_REQUIRE(B > 0 && n_heads > 0 && S_max > 0 && (len_bias == 0 || len_bias == 1), VH_EINVAL,
+               "vh_attn_decode_kv16_split: bad dims B=%d h=%d S_max=%d len_bias=%d", B, n_heads, S_max, len_bias);
+    VH_REQUIRE(n_split >= 1 && n_split <= 16, VH_EINVAL, "vh_attn_decode_kv16_split: n_split=%d (1..16)", n_split);
+    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL,
+               "vh_attn_decode_kv16_split: ldq=%d ldo=%d", ldq, ldo);
+    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kcache16) && vh_aligned16(vcache16) && vh_aligned16(partial), VH_EALIGN,
+               "vh_attn_decode_kv16_split: pointers must be 16-byte aligned");
+    if (n_split == 1) {                                   // the launch of vh_attn_decode_kv16, bit for bit
+        launch_ring16(q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, B, n_heads, S_max, stream);
+        VH_CHECK_LAUNCH("vh_attn_decode_kv16_split");
+        return VH_OK;
+    }
+    VH_REQUIRE(partial && partial_bytes >= vh_attn_decode_ws_bytes(B, n_heads, n_split), VH_EINVAL,
+               "vh_attn_decode_kv16_split: n_split=%d needs a workspace of %zu bytes (got %zu)", n_split,
+               vh_attn_decode_ws_bytes(B, n_heads, n_split), partial ? partial_bytes : (size_t)0);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(n_split, B * n_heads);
+    // few workgroups -> 8 waves each (the ring16 shape: a (row, head, split) may own a CU); many -> 4 waves, several per CU.
+    // The threshold is the fp32 launch's rule (vh_attn_decode: `big`), taken over as it stands: NOT measured for the 16-bit stream.
+#define AD16S(NW)                                                                                                       \
+    hipExtLaunchKernelGGL((attn_decode_ring16_split_kernel<NW, 2>), grid, dim3(NW * 64), 0, s, g_attn_ev[0], g_attn_ev[1], 0, q, \
+                          ldq, kcache16, vcache16, cache_len, len_bias, n_heads, S_max, n_split, (float*)partial)
+    if ((int64_t)B * n_heads * n_split < 1024) AD16S(8); else AD16S(4);
+#undef AD16S
+    // records added in split order by the combine launch of the fp32 form: deterministic
+    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * n_heads), dim3(64), 0, s, (const float*)partial, out, ldo, n_heads,
+                       n_split);
+    VH_CHECK_LAUNCH("vh_attn_decode_kv16_split");
     return VH_OK;
 }
 
@@ -1851,5 +2029,169 @@ extern "C" int vh_attn_decode_shared(const float* q, int ldq, const float* kpref
     hipLaunchKernelGGL(attn_records_merge_kernel, dim3(B * n_heads), dim3(256), 0, s, (const float*)partial, out, ldo, n_heads,
                        n_tot);
     VH_CHECK_LAUNCH("vh_attn_decode_shared");
+    return VH_OK;
+}
+
+// =============================================================================================
+// The same two-role launch over 16-bit caches (perf mode with a shared prompt): the prompt's K / V tiles are loaded ONCE as
+// 16-bit and widened to fp32 in registers, then go through the same fp32 MFMA score and output products with the beams as lanes
+// (q is not rounded: fp32 arithmetic on the rounded cache); the beams' own rows run the ring16 burst loop with key splits.
+// Records, merge launch and workspace are the fp32 form's.
+// =============================================================================================
+struct Shared16Args {
+    const float* q; int ldq;
+    const uint16_t* kp; const uint16_t* vp;      // prefix (1, h, prefix_S, 64), 16-bit
+    int prefix_len, prefix_S;
+    const uint16_t* ks; const uint16_t* vs;      // suffix (B, h, S_suf, 64), 16-bit
+    const int32_t* suffix_len; int len_bias;
+    int S_suf, n_split;
+    float* partial;
+    int n_heads, B, n_pb, n_tot, prefix_wgs;
+};
+
+__device__ __forceinline__ void shared16_prefix_role(const Shared16Args& a, int wg, int lane, int w) {
+    const int head = wg % a.n_heads, blk = (wg / a.n_heads) * 4 + w;
+    if (blk >= a.n_pb) return;                               // (wave-uniform; no barrier in this role)
+    const int r = lane & 31, hh = lane >> 5;
+    const uint16_t* kb = a.kp + (int64_t)head * a.prefix_S * HD;
+    const uint16_t* vb = a.vp + (int64_t)head * a.prefix_S * HD;
+    const int k0 = blk * 32;
+    const float qscale = 0.125f * LOG2E;
+    // K fragment (A operand): key k0 + r, d = 32 hh + j: 64 bytes = four 16-byte loads, widened; rows beyond the prompt repeat
+    // its last row (masked below)
+    f32x4 kf[8];
+    {
+        const uint16_t* kr = kb + (int64_t)min(k0 + r, a.prefix_len - 1) * HD + 32 * hh;
+        u32x4 kw[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) kw[j] = *reinterpret_cast<const u32x4*>(kr + 8 * j);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            kf[2 * j] = f32x4{BF_LO(kw[j].x), BF_HI(kw[j].x), BF_LO(kw[j].y), BF_HI(kw[j].y)};
+            kf[2 * j + 1] = f32x4{BF_LO(kw[j].z), BF_HI(kw[j].z), BF_LO(kw[j].w), BF_HI(kw[j].w)};
+        }
+    }
+    // V^T operand values (the fp32 kernel's pairing of keys and accumulator registers), one 16-bit element per load: half the
+    // bytes of the fp32 form at the SAME 32 load instructions per lane (K above went from eight loads to four) — the first thing
+    // to look at in a kernel trace of this role
+    float vf[2][16];
+#pragma unroll
+    for (int x = 0; x < 16; ++x) {
+        const int key = min(k0 + (x & 3) + 8 * (x >> 2) + 4 * hh, a.prefix_len - 1);
+        vf[0][x] = BF_LO((uint32_t)vb[(int64_t)key * HD + r]);
+        vf[1][x] = BF_LO((uint32_t)vb[(int64_t)key * HD + 32 + r]);
+    }
+    const bool whole = k0 + 32 <= a.prefix_len;              // wave-uniform
+    for (int qb = 0; qb * 32 < a.B; ++qb) {
+        const int b = min(qb * 32 + r, a.B - 1);             // lanes beyond B repeat the last beam (never stored)
+        f32x16 s;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[e] = 0.f;
+        {
+            const float* qr = a.q + (int64_t)b * a.ldq + head * HD + 32 * hh;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const f32x4 qf = ld4(qr + 4 * j) * qscale;
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j].x, qf.x, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j].y, qf.y, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j].z, qf.z, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j].w, qf.w, s, 0, 0, 0);
+            }
+        }
+        // D reg x of lane (r = beam, hh): key k0 + (x & 3) + 8 (x >> 2) + 4 hh
+        float m = NEG_INF;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            if (!whole && k0 + (x & 3) + 8 * (x >> 2) + 4 * hh >= a.prefix_len) s[x] = NEG_INF;
+            m = fmaxf(m, s[x]);
+        }
+        m = fmaxf(m, __shfl_xor(m, 32, 64));                 // the beam's other key half; finite: key k0 < prefix_len
+        float l = 0.f;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            s[x] = vh_exp2(s[x] - m);
+            l += s[x];
+        }
+        l += __shfl_xor(l, 32, 64);
+        f32x16 o0, o1;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { o0[e] = 0.f; o1[e] = 0.f; }
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {                       // O^T += V^T P^T: P^T is the B operand as it lies
+            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[0][x], s[x], o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[1][x], s[x], o1, 0, 0, 0);
+        }
+        if (qb * 32 + r < a.B) {
+            float* pr = a.partial + (((int64_t)b * a.n_heads + head) * a.n_tot + blk) * PART_LD;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                st4(pr + 8 * g4 + 4 * hh, f32x4{o0[4 * g4], o0[4 * g4 + 1], o0[4 * g4 + 2], o0[4 * g4 + 3]});
+                st4(pr + 32 + 8 * g4 + 4 * hh, f32x4{o1[4 * g4], o1[4 * g4 + 1], o1[4 * g4 + 2], o1[4 * g4 + 3]});
+            }
+            if (hh == 0) { pr[HD] = m; pr[HD + 1] = l; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void attn_shared16_kernel(Shared16Args a) {
+    constexpr int NW = 4;
+    __shared__ float s_m[NW], s_l[NW];
+    __shared__ __attribute__((aligned(16))) float s_o[NW][HD];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if ((int)blockIdx.x < a.prefix_wgs) {                    // workgroup-uniform
+        shared16_prefix_role(a, blockIdx.x, lane, w);
+        return;
+    }
+    // ---- suffix role: (beam, head) x key split over the beam's own rows (the ring16 burst loop)
+    const int unit = blockIdx.x - a.prefix_wgs;
+    const int split = unit % a.n_split, bh = unit / a.n_split;
+    const int b = bh / a.n_heads, head = bh - b * a.n_heads;
+    const int len = min(a.suffix_len[b] + a.len_bias, a.S_suf);
+    const int nchunks = (len + 31) >> 5;
+    const int cps = (nchunks + a.n_split - 1) / a.n_split;
+    const int c_begin = split * cps, c_end = min(nchunks, c_begin + cps);
+    float M, L, O;
+    ring16_range<NW, 2>(a.q + (int64_t)b * a.ldq + head * HD, a.ks + (int64_t)bh * a.S_suf * HD,
+                        a.vs + (int64_t)bh * a.S_suf * HD, len, c_begin, c_end, s_m, s_l, s_o, M, L, O);
+    if (tid >= HD) return;
+    float* pr = a.partial + ((int64_t)bh * a.n_tot + a.n_pb + split) * PART_LD;
+    pr[tid] = O;
+    if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
+}
+
+extern "C" int vh_attn_decode_shared_kv16(const float* q, int ldq, const uint16_t* kprefix16, const uint16_t* vprefix16,
+                                          int prefix_len, int prefix_S, const uint16_t* ksuffix16, const uint16_t* vsuffix16,
+                                          float* out, int ldo, const int32_t* suffix_len, int len_bias, int B, int n_heads,
+                                          int S_suf, int n_split_suffix, void* partial, size_t partial_bytes, void* stream) {
+    VH_REQUIRE(q && kprefix16 && vprefix16 && ksuffix16 && vsuffix16 && out && suffix_len && partial, VH_EINVAL,
+               "vh_attn_decode_shared_kv16: null pointer");
+    VH_REQUIRE(n_split_suffix >= 1 && n_split_suffix <= 16, VH_EINVAL, "vh_attn_decode_shared_kv16: n_split=%d (1..16)",
+               n_split_suffix);
+    VH_REQUIRE(B > 0 && B <= 64 && n_heads > 0 && prefix_len > 0 && prefix_len <= prefix_S && S_suf > 0, VH_EINVAL,
+               "vh_attn_decode_shared_kv16: bad dims B=%d h=%d prefix=%d/%d S_suf=%d n_split=%d", B, n_heads, prefix_len,
+               prefix_S, S_suf, n_split_suffix);
+    const int n_pb = (prefix_len + 31) / 32, n_tot = n_pb + n_split_suffix;
+    VH_REQUIRE(n_tot <= 256, VH_EUNSUPPORTED,
+               "vh_attn_decode_shared_kv16: %d prefix blocks + %d splits exceed the 256 records one merge serves", n_pb,
+               n_split_suffix);
+    VH_REQUIRE(len_bias == 0 || len_bias == 1, VH_EINVAL, "vh_attn_decode_shared_kv16: len_bias=%d", len_bias);
+    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL,
+               "vh_attn_decode_shared_kv16: ldq=%d ldo=%d", ldq, ldo);
+    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kprefix16) && vh_aligned16(vprefix16) && vh_aligned16(ksuffix16) &&
+                   vh_aligned16(vsuffix16) && vh_aligned16(partial), VH_EALIGN,
+               "vh_attn_decode_shared_kv16: pointers must be 16-byte aligned");
+    VH_REQUIRE(partial_bytes >= vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split_suffix), VH_EINVAL,
+               "vh_attn_decode_shared_kv16: workspace of %zu bytes, need %zu", partial_bytes,
+               vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split_suffix));
+    hipStream_t s = (hipStream_t)stream;
+    const int prefix_wgs = (n_pb + 3) / 4 * n_heads;
+    Shared16Args a{q, ldq, kprefix16, vprefix16, prefix_len, prefix_S, ksuffix16, vsuffix16, suffix_len, len_bias, S_suf,
+                   n_split_suffix, (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs};
+    // (the events of vh_ar_decoder_profile_attn bracket this launch: the step's attention kernel in this form)
+    hipExtLaunchKernelGGL(attn_shared16_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s, g_attn_ev[0],
+                          g_attn_ev[1], 0, a);
+    hipLaunchKernelGGL(attn_records_merge_kernel, dim3(B * n_heads), dim3(256), 0, s, (const float*)partial, out, ldo, n_heads,
+                       n_tot);
+    VH_CHECK_LAUNCH("vh_attn_decode_shared_kv16");
     return VH_OK;
 }

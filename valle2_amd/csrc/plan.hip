@@ -98,13 +98,16 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
     if (d->kv_bf16) {
         VH_REQUIRE(d->d_model <= 1024, VH_EUNSUPPORTED, "vh_ar_decoder: the bf16 K/V cache (perf mode) serves d_model <= 1024 (got %d)",
                    d->d_model);
-        VH_REQUIRE(d->n_split == 1, VH_EUNSUPPORTED, "vh_ar_decoder: the bf16 K/V cache has no key-split form (n_split=%d)",
-                   d->n_split);
         for (int i = 0; i < d->n_layers; ++i)
             VH_REQUIRE(d->layers[i].wqkv_f, VH_EINVAL, "vh_ar_decoder: the bf16 K/V cache needs folded weights (layer %d)", i);
+        VH_REQUIRE(d->n_split <= 16, VH_EUNSUPPORTED, "vh_ar_decoder: the bf16 K/V cache serves n_split 1..16 (got %d)", d->n_split);
+        // key splits over the 16-bit cache (vh_attn_decode_kv16_split); a shared prompt's workspace is checked below
+        VH_REQUIRE(d->n_split == 1 || d->prefix_len > 0 ||
+                       (d->attn_partial && d->attn_partial_bytes >= vh_attn_decode_ws_bytes(d->B, d->n_heads, d->n_split)),
+                   VH_EINVAL, "vh_ar_decoder: the bf16 K/V cache with n_split=%d needs attn_partial of vh_attn_decode_ws_bytes() = "
+                   "%zu bytes (got %zu)", d->n_split, vh_attn_decode_ws_bytes(d->B, d->n_heads, d->n_split), d->attn_partial_bytes);
     }
     if (d->prefix_len > 0) {
-        VH_REQUIRE(!d->kv_bf16, VH_EUNSUPPORTED, "vh_ar_decoder: the shared prompt has no bf16 form");
         VH_REQUIRE((d->prefix_len + 31) / 32 + d->n_split <= 256, VH_EUNSUPPORTED,
                    "vh_ar_decoder: a shared prompt of %d keys with %d suffix splits exceeds the 256 records vh_attn_decode_shared merges",
                    d->prefix_len, d->n_split);
@@ -194,6 +197,15 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         if (hd != VH_HEAD_DIM)
             return vh_attn_decode_hd(d.q, D, L.kcache, L.vcache, d.attn, D, d.cache_len, 1, B, d.n_heads, hd, d.S_max,
                                      (float)(1.0 / sqrt((double)hd)), d.n_split, d.attn_partial, d.attn_partial_bytes, s);
+        if (d.kv_bf16 && d.prefix_len > 0)   // perf mode over a shared prompt: 16-bit prefix and suffix caches
+            return vh_attn_decode_shared_kv16(d.q, D, (const uint16_t*)L.kprefix, (const uint16_t*)L.vprefix, d.prefix_len,
+                                              d.prefix_S, (const uint16_t*)L.kcache, (const uint16_t*)L.vcache, d.attn, D,
+                                              d.cache_len, 1, B, d.n_heads, d.S_max, d.n_split, d.attn_partial,
+                                              d.attn_partial_bytes, s);
+        if (d.kv_bf16 && d.n_split > 1)
+            return vh_attn_decode_kv16_split(d.q, D, (const uint16_t*)L.kcache, (const uint16_t*)L.vcache, d.attn, D,
+                                             d.cache_len, 1, B, d.n_heads, d.S_max, d.n_split, d.attn_partial,
+                                             d.attn_partial_bytes, s);
         if (d.kv_bf16)
             return vh_attn_decode_kv16(d.q, D, (const uint16_t*)L.kcache, (const uint16_t*)L.vcache, d.attn, D, d.cache_len,
                                        1, B, d.n_heads, d.S_max, s);

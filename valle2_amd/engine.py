@@ -51,6 +51,16 @@ class KVCache:
                                        self.s_max, self.s_max, s_max, stream()), 'vh_kv_to_bf16')
         return out
 
+    def narrow_into(self, dst: 'KVCache'):
+        """`narrowed` into an existing 16-bit cache of the same streams and at least this cache's rows (a decoder slot keeps
+        its 16-bit prefix cache across calls: the captured graphs point at it)."""
+        if self.bf16 or not dst.bf16 or dst.s_max < self.s_max or self.head_dim != HEAD_DIM or \
+                (dst.n_layers, dst.batch, dst.n_heads, dst.head_dim) != (self.n_layers, self.batch, self.n_heads, self.head_dim):
+            raise _lib.VhError('KVCache.narrow_into: an fp32 width-64 cache into a 16-bit cache of the same streams')
+        check(_lib.lib().vh_kv_to_bf16(ptr(self.buf), ptr(dst.buf), self.n_layers * 2 * self.batch * self.n_heads,
+                                       self.s_max, self.s_max, dst.s_max, stream()), 'vh_kv_to_bf16')
+        return dst
+
     def k(self, i):
         return self.buf[i, 0]
 
@@ -510,7 +520,8 @@ class ArDecoder:
                  n_split=None, use_graph=True, seed=0, prefix: KVCache | None = None, prefix_len=0):
         """prefix / prefix_len: SHARED-PROMPT decoding (the beams of ONE utterance, valle_ar.py:135-138): `prefix` is a
         one-row cache holding the prompt's K/V (its first prefix_len rows), `cache` then holds only the generated rows of
-        every beam (s_max = its capacity) and cache_len counts those."""
+        every beam (s_max = its capacity) and cache_len counts those.  A 16-bit `cache` is perf mode; it takes key splits
+        (rows x heads below 256) and a 16-bit `prefix` — the two caches must have the same dtype."""
         cfg = model.config
         dev = cache.buf.device
         d, dff, V = cfg.d_model, cfg.dim_feedforward, cfg.num_audio_tokens + 1
@@ -519,7 +530,8 @@ class ArDecoder:
         self.n_split = n_split or pick_n_split(batch * cfg.n_heads)
         if prefix is not None and n_split is None:
             # shared prompt: the beams' own rows are short streams — two workgroups per CU keep twice the loads in flight
-            # (32 beams x 8 heads: 436.8 us per step with one split, 420.9 with two, 426.9 with four)
+            # (32 beams x 8 heads: 436.8 us per step with one split, 420.9 with two, 426.9 with four — fp32 caches; a 16-bit
+            # cache takes the same split counts here and in pick_n_split, which nobody has tuned for the half-width streams)
             self.n_split = shared_n_split(batch, cfg.n_heads)
         f32 = dict(device=dev, dtype=torch.float32)
         self.x = torch.empty(batch, d, **f32)
@@ -537,8 +549,11 @@ class ArDecoder:
             n = _lib.lib().vh_attn_decode_hd_ws_bytes(batch, cfg.n_heads, hd, self.n_split)
             self.partial = torch.empty(max(n, 16) // 4, **f32) if n else None
         elif prefix is not None:
-            if prefix.bf16 or cache.bf16 or prefix.batch != 1 or prefix.n_layers != cfg.num_layers or not 0 < prefix_len <= prefix.s_max:
-                raise _lib.VhError('shared-prompt decoding: a one-row fp32 prefix cache holding prefix_len rows')
+            if prefix.bf16 != cache.bf16:
+                raise _lib.VhError(f'shared-prompt decoding: the prefix cache ({prefix.buf.dtype}) and the beams\' cache '
+                                   f'({cache.buf.dtype}) must have the same dtype')
+            if prefix.batch != 1 or prefix.n_layers != cfg.num_layers or not 0 < prefix_len <= prefix.s_max:
+                raise _lib.VhError('shared-prompt decoding: a one-row prefix cache holding prefix_len rows')
             self.partial = kernels.attn_decode_shared_ws(batch, cfg.n_heads, self.prefix_len, self.n_split, dev)
         else:
             self.partial = kernels.attn_decode_ws(batch, cfg.n_heads, self.n_split, dev)
@@ -558,9 +573,10 @@ class ArDecoder:
         self._folded = None if wide_unfolded else folded_layer_norms(model.transformer)   # kept alive: the table holds raw pointers
         self.ln_folded = self._folded is not None          # False above 1024: LayerNorm + plain GEMMs as separate launches
         self.kv_bf16 = cache.bf16
-        if self.kv_bf16 and (self._folded is None or self.n_split != 1):
-            raise _lib.VhError('perf mode (bf16 K/V cache) needs the folded LayerNorm weights and rows x heads >= 256 '
-                               f'(one (row, head) per workgroup: n_split = {self.n_split})')
+        if self.kv_bf16 and self._folded is None:
+            raise _lib.VhError('perf mode (16-bit K/V cache) needs the folded LayerNorm weights')
+        if self.kv_bf16 and not 1 <= self.n_split <= 16:
+            raise _lib.VhError(f'perf mode (16-bit K/V cache) serves n_split 1..16 (got {self.n_split})')
         # FeedForward of a layer as one launch split over dim_feedforward + the slab reduce (vh_ffn_decode)
         # (d_model <= 1024: vh_ffn_decode's shape set; the plan takes it at d_model <= 512)
         ffn_bytes = _lib.lib().vh_ffn_decode_ws_bytes(batch, d, dff) if self._folded is not None and d <= 1024 else 0

@@ -478,16 +478,48 @@ def attn_decode_shared(q, kprefix, vprefix, prefix_len, ksuffix, vsuffix, out, s
     return out
 
 
-def attn_decode_kv16(q, kcache16, vcache16, out, cache_len, len_bias):
-    """attn_decode over a bf16 K/V cache (perf mode); one (row, head) per workgroup."""
+def attn_decode_kv16(q, kcache16, vcache16, out, cache_len, len_bias, n_split=1, partial=None):
+    """attn_decode over a 16-bit K/V cache (perf mode).  n_split == 1: one (row, head) per workgroup (vh_attn_decode_kv16);
+    n_split 2..16: the key range of a (row, head) split over n_split workgroups whose records a second launch adds in split
+    order (vh_attn_decode_kv16_split; `partial`: attn_decode_ws(), allocated here when None)."""
     B, n_heads, S_max, hd = kcache16.shape
     if hd != HEAD_DIM or kcache16.dtype != H16 or vcache16.dtype != H16 or q.shape[0] != B:
         raise _lib.VhError('attn_decode_kv16: bf16 caches (B, h, S_max, 64)')
     if cache_len.dtype != torch.int32 or cache_len.numel() != B:
         raise _lib.VhError('attn_decode_kv16: cache_len must be int32 (B)')
-    check(_lib.lib().vh_attn_decode_kv16(_dev_f32(q, 'q'), q.stride(0), ptr(kcache16), ptr(vcache16), _dev_f32(out, 'out'),
-                                         out.stride(0), ptr(cache_len), len_bias, B, n_heads, S_max, stream()),
-          'vh_attn_decode_kv16')
+    if n_split == 1 and partial is None:
+        check(_lib.lib().vh_attn_decode_kv16(_dev_f32(q, 'q'), q.stride(0), ptr(kcache16), ptr(vcache16), _dev_f32(out, 'out'),
+                                             out.stride(0), ptr(cache_len), len_bias, B, n_heads, S_max, stream()),
+              'vh_attn_decode_kv16')
+        return out
+    if partial is None and 1 < n_split <= 16:
+        partial = attn_decode_ws(B, n_heads, n_split, q.device)
+    check(_lib.lib().vh_attn_decode_kv16_split(
+        _dev_f32(q, 'q'), q.stride(0), ptr(kcache16), ptr(vcache16), _dev_f32(out, 'out'), out.stride(0), ptr(cache_len),
+        len_bias, B, n_heads, S_max, n_split, ptr(partial), partial.numel() * 4 if partial is not None else 0, stream()),
+        'vh_attn_decode_kv16_split')
+    return out
+
+
+def attn_decode_shared_kv16(q, kprefix16, vprefix16, prefix_len, ksuffix16, vsuffix16, out, suffix_len, len_bias, n_split=1,
+                            partial=None):
+    """`attn_decode_shared` over 16-bit caches (perf mode with a shared prompt): kprefix16 / vprefix16 (1, h, prefix_S, 64) and
+    ksuffix16 / vsuffix16 (B, h, S_suf, 64) in the library's 16-bit format; q, the softmax and the accumulators fp32."""
+    B, n_heads, S_suf, hd = ksuffix16.shape
+    if hd != HEAD_DIM or tuple(kprefix16.shape[:2]) != (1, n_heads) or kprefix16.shape[3] != HEAD_DIM or q.shape[0] != B or \
+            kprefix16.shape != vprefix16.shape or ksuffix16.shape != vsuffix16.shape:
+        raise _lib.VhError(f'attn_decode_shared_kv16: prefix {tuple(kprefix16.shape)} suffix {tuple(ksuffix16.shape)} '
+                           f'q {tuple(q.shape)}')
+    if any(t.dtype != H16 for t in (kprefix16, vprefix16, ksuffix16, vsuffix16)):
+        raise _lib.VhError(f'attn_decode_shared_kv16: prefix and suffix caches must be {H16}')
+    if suffix_len.dtype != torch.int32 or suffix_len.numel() != B:
+        raise _lib.VhError('attn_decode_shared_kv16: suffix_len must be int32 (B)')
+    if partial is None:
+        partial = attn_decode_shared_ws(B, n_heads, prefix_len, n_split, q.device)
+    check(_lib.lib().vh_attn_decode_shared_kv16(
+        _dev_f32(q, 'q'), q.stride(0), ptr(kprefix16), ptr(vprefix16), prefix_len, kprefix16.shape[2], ptr(ksuffix16),
+        ptr(vsuffix16), _dev_f32(out, 'out'), out.stride(0), ptr(suffix_len), len_bias, B, n_heads, S_suf, n_split, ptr(partial),
+        partial.numel() * 4, stream()), 'vh_attn_decode_shared_kv16')
     return out
 
 

@@ -187,9 +187,13 @@ class ValleAR(_Base):
     # ------------------------------------------------------------------------------------
     @_on_device
     @torch.inference_mode()
-    def generate(self, prompt_tokens, prompt_codes, target_tokens=None):
+    def generate(self, prompt_tokens, prompt_codes, target_tokens=None, *, perf_mode=False):
         """valle_ar.py:92-180 — one utterance replicated over `num_beams` rows; returns the 1-D
         int64 first-codebook tokens of the best beam with EOS stripped.
+
+        perf_mode (keyword-only, default off; True or 'kv' as in `generate_batch`): the decode steps stream a 16-bit K/V
+        cache — with the shared prompt below, the prompt's K/V are read once per step AND at half the bytes.  Off, this runs
+        exactly what it always ran.
 
         The beams share one prompt, so (SHARED_PROMPT, default on) the prompt pass runs for ONE row and its K/V are read
         once per decode step for all beams (`generate_batch(..., shared_prompt=True)`); the beams themselves — their
@@ -203,7 +207,8 @@ class ValleAR(_Base):
         shared = SHARED_PROMPT and self.config.use_kv_cache and self.config.d_model == self.config.n_heads * kernels.HEAD_DIM
         # (a prompt beyond the shared kernel's record bound — 7680 keys at 4 beams x 8 heads — decodes as independent rows)
         shared = shared and shared_prompt_fits(beams, self.config.n_heads, int(text.shape[0]) + int(prompt_codes.shape[0]) + 1)   # + BOS
-        rows = self.generate_batch([text] * beams, [prompt_codes[..., 0]] * beams, shared_prompt=shared and beams <= MAX_DECODE_ROWS)
+        rows = self.generate_batch([text] * beams, [prompt_codes[..., 0]] * beams, shared_prompt=shared and beams <= MAX_DECODE_ROWS,
+                                   perf_mode=perf_mode)
         # beams → one sequence (valle_ar.py:174-180); with top_k=1 every log-prob is exactly 0
         sum_logprobs = self.last_generate_stats['sum_logprobs']
         prompt_len = prompt_codes.shape[0] + 1
@@ -292,8 +297,10 @@ class ValleAR(_Base):
             cache = KVCache(cfg.num_layers, B, cfg.n_heads, s_max, dev, head_dim=cfg.d_model // cfg.n_heads)
         elif run.shared:
             # ONE row through the prompt pass: its K/V are the prefix every beam reads; the beams' cache holds generated rows only
-            prefix = KVCache(cfg.num_layers, 1, cfg.n_heads, (s0 + 31) // 32 * 32, dev)
-            cache = KVCache(cfg.num_layers, B, cfg.n_heads, (run.max_new + 1 + 31) // 32 * 32, dev)
+            # (perf mode: both 16-bit)
+            kv_dtype = kernels.H16 if run.perf_mode else torch.float32
+            prefix = KVCache(cfg.num_layers, 1, cfg.n_heads, (s0 + 31) // 32 * 32, dev, dtype=kv_dtype)
+            cache = KVCache(cfg.num_layers, B, cfg.n_heads, (run.max_new + 1 + 31) // 32 * 32, dev, dtype=kv_dtype)
         elif run.perf_prefill:
             cache = KVCache(cfg.num_layers, B, cfg.n_heads, s_max, dev, dtype=kernels.H16)
         else:
@@ -313,8 +320,15 @@ class ValleAR(_Base):
             run.lens = torch.tensor([t + p for t, p in zip(run.txs, run.pls)], **i32)
             run.fwd = dict(x_len_dev=torch.tensor(run.txs, **i32), kv_len=run.lens)
         if run.perf_prefill:
-            transformer_forward_bf16(self.transformer, x, cache, mode=kernels.MASK_PREFIX,
-                                     scratch=ForwardScratch16(B * s0, d, cfg.dim_feedforward, dev), **run.fwd)
+            # (shared prompt: the ONE row's pass on the 16-bit matrix cores writes straight into the 16-bit prefix cache)
+            transformer_forward_bf16(self.transformer, x, prefix if run.shared else cache, mode=kernels.MASK_PREFIX,
+                                     scratch=ForwardScratch16(rows * s0, d, cfg.dim_feedforward, dev), **run.fwd)
+        elif run.shared and run.perf_mode:
+            # perf_mode='kv' over a shared prompt: the fp32 pass of the one row, its K/V narrowed once into the 16-bit prefix
+            wide = KVCache(cfg.num_layers, 1, cfg.n_heads, prefix.s_max, dev)
+            transformer_forward(self.transformer, x, wide, mode=kernels.MASK_PREFIX,
+                                scratch=ForwardScratch(s0, d, cfg.dim_feedforward, dev), **run.fwd)
+            wide.narrow_into(prefix)
         else:
             scratch = None if run.any_head_dim or run.hd_cached else ForwardScratch(rows * s0, d, cfg.dim_feedforward, dev)
             transformer_forward(self.transformer, x, prefix if run.shared else cache, mode=kernels.MASK_PREFIX,
@@ -325,7 +339,7 @@ class ValleAR(_Base):
             last = x[:, -1].expand(B, d)                  # every beam starts from the one prompt row's last hidden state
         else:
             last = x[:, -1]
-        if run.perf_mode and not run.perf_prefill:
+        if run.perf_mode and not run.perf_prefill and not run.shared:
             cache = cache.narrowed(s_max)                 # fp32 prompt K/V -> the bf16 cache of the decode steps
         return cache, prefix, last.contiguous()
 
@@ -408,14 +422,17 @@ class ValleAR(_Base):
         accumulators and residual stream; engine.transformer_forward_bf16) and writes its K/V straight into the bf16 cache
         the decode steps stream; the decode steps' weights and arithmetic stay fp32.  perf_mode='kv': only the cache is bf16
         (the fp32 prompt pass, its K/V narrowed once — round 3's form).  Greedy tokens are then NOT guaranteed to be the
-        reference's (teacher-forced logits agree to 5e-2).
+        reference's (teacher-forced logits agree to 5e-2).  Any row count 1..64: below 256 (row, head) pairs the 16-bit cache
+        is read with key splits (`last_generate_stats['n_split']`).
         forced (max_new,) int64 + keep_logits (step indices): TEACHER FORCING for the tolerance tests — step t appends
         forced[t] whatever the head says (steps run eagerly, one at a time) and the logits (B, V) the head produced at
         the steps listed in keep_logits are left in `last_generate_stats['logits']`.
         shared_prompt=True: the caller vouches that every row has the SAME text and prompt (the beams of one utterance,
         valle_ar.py:135-138; checked: equal lengths and equal ids) — the prompt pass then runs for one row and every decode
         step reads the prompt's K/V once for all rows (vh_attn_decode_shared); rows still sample, append and score
-        independently.  fp32 (no perf_mode), cached decoder only."""
+        independently.  Cached decoder only; combines with perf_mode (True and 'kv'): the one-row prompt pass then fills a
+        16-bit prefix cache (on the 16-bit matrix cores, or fp32 and narrowed once for 'kv') and the beams' own rows are 16-bit
+        too (vh_attn_decode_shared_kv16).  Rows of different lengths are refused."""
         self._require_layernorm()
         cfg = self.config
         dev = self.device
@@ -460,15 +477,17 @@ class ValleAR(_Base):
         run.perf_mode = perf_mode
         run.perf_prefill = bool(perf_mode) and perf_mode != 'kv' and perf_forward_supported(cfg)
         run.shared = bool(shared_prompt)
-        if run.shared and (perf_mode or run.ragged):
-            raise ValueError('shared_prompt: identical rows, fp32')
+        if run.shared and run.ragged:
+            raise ValueError('shared_prompt: identical rows (equal text and prompt lengths)')
         t_host0 = time.perf_counter()
         # a decoder per shape survives the call (graphs, caches, counters: _DecodeSlot) unless the call is one of the
         # measurement / test forms that drive the decoder by hand
         slot_key = slot = None
-        if not (no_cache or forced is not None or profile_attn or (perf_mode and not run.perf_prefill)):
+        # (perf_mode='kv' with rows of their own narrows into a fresh cache per call: no slot; over a shared prompt it narrows into
+        # the slot's 16-bit prefix)
+        if not (no_cache or forced is not None or profile_attn or (perf_mode and not run.perf_prefill and not run.shared)):
             slot_key = (B, run.s0 if run.shared else None, run.s_max, run.pl_max + run.max_new, run.max_new, run.shared,
-                        run.perf_prefill, bool(use_graph), int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature),
+                        run.perf_prefill, bool(perf_mode), bool(use_graph), int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature),
                         str(dev), _lib.TUNING_EPOCH, tuple(os.environ.get(k) for k in _DECODER_ENV), self._weights_key())
             slot = self._acquire_slot(slot_key)
         run.slot = slot
