@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 131            /* 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 132            /* 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -342,6 +342,26 @@ int vh_attn_decode_shared(const float* q, int ldq, const float* kprefix, const f
                           int prefix_S, const float* ksuffix, const float* vsuffix, float* out, int ldo,
                           const int32_t* suffix_len, int len_bias, int B, int n_heads, int S_suf, int n_split_suffix,
                           void* partial, size_t partial_bytes, void* stream);
+/* ---- decode attention over several shared prompts (the beams of SEVERAL utterances) ------------------------------------
+ * vh_attn_decode_shared for G = B / beams utterances in one call: row b is a beam of utterance (group) b / beams, and its
+ * first prefix_len[b / beams] keys are that utterance's prompt.  kprefix / vprefix (G, h, prefix_S, 64): one prompt per group,
+ * read once per step for the group's beams (the columns of a score tile are the beams of ONE group; a second pass serves beams
+ * 32..63).  prefix_len: DEVICE int32 (G), 1 <= prefix_len[g] <= prefix_cap (a larger value is cut at prefix_cap) — a captured
+ * step serves later calls whose prompts have other lengths.  prefix_cap (host, 1 <= prefix_cap <= prefix_S) sizes the grid
+ * and the record stride: ceil(prefix_cap / 32) + n_split_suffix <= 256 slots per (row, head).  ksuffix / vsuffix, suffix_len,
+ * len_bias, n_split_suffix and out as in vh_attn_decode_shared.  The same two launches: prefix workgroups (group, head, four
+ * 32-key blocks) and suffix workgroups (row, head, split) in one, the merge per (row, head) in the other.  A block wholly
+ * beyond its group's prefix_len loads nothing and writes no record, and the merge of a row reads only the slots its group
+ * wrote: the workspace needs no initialisation and may hold anything, as may every cache row beyond a length.  fp32,
+ * deterministic (no atomics, fixed merge order).  beams == 1 (no sharing) and G == 1 are legal; for G == 1 the records and
+ * their order are vh_attn_decode_shared's.  B <= 64, B % beams == 0.
+ * partial: vh_attn_decode_shared_groups_ws_bytes() = B h (ceil(prefix_cap / 32) + n_split_suffix) records of 72 floats. */
+size_t vh_attn_decode_shared_groups_ws_bytes(int B, int n_heads, int prefix_cap, int n_split_suffix);
+int vh_attn_decode_shared_groups(const float* q, int ldq, const float* kprefix, const float* vprefix,
+                                 const int32_t* prefix_len, int prefix_cap, int prefix_S, const float* ksuffix,
+                                 const float* vsuffix, float* out, int ldo, const int32_t* suffix_len, int len_bias, int B,
+                                 int beams, int n_heads, int S_suf, int n_split_suffix, void* partial, size_t partial_bytes,
+                                 void* stream);
 /* ---- decode attention at a head width other than 64 ------------------------------------------------------------------
  * vh_attn_decode's contract over fp32 caches (B, h, S_max, head_dim): keys 0 .. cache_len[b] + len_bias - 1 of row b,
  * out (B, ldo) at columns head * head_dim.  scale is the softmax scale (callers pass (float)(1 / sqrt((double)head_dim)),
@@ -517,6 +537,15 @@ typedef struct {
     const uint64_t *seed_dev;
     /* optional (with kv_bf16): an h16 copy of proj_w (V, d) for the head GEMM of the step */
     const uint16_t *proj_w16;
+    /* grouped shared prompts (several utterances, each replicated over beams_per_group rows; 0 = the forms above).
+     * n_groups > 0: B == n_groups * beams_per_group, row b belongs to group b / beams_per_group; layers[i].kprefix / vprefix
+     * are (n_groups, h, prefix_S, 64) with group g's prompt in its first prefix_lens[g] rows (DEVICE int32 (n_groups), read
+     * by every step: the caller rewrites it between calls); prefix_cap (<= prefix_S) bounds every length.  kcache / vcache,
+     * cache_len and n_split as with prefix_len > 0, which must be 0 here.  The step's attention is
+     * vh_attn_decode_shared_groups; attn_partial must hold vh_attn_decode_shared_groups_ws_bytes(B, n_heads, prefix_cap,
+     * n_split) bytes.  fp32 caches at head width 64 only: kv_bf16 and other head widths are refused. */
+    int n_groups, beams_per_group, prefix_cap;
+    const int32_t *prefix_lens;
 } vh_ar_decoder_desc;
 
 typedef struct vh_ar_decoder vh_ar_decoder;

@@ -55,6 +55,7 @@ class VhArDecoderDesc(C.Structure):
         ('sum_logprobs', C.c_void_p), ('ffn_ws', C.c_void_p), ('ffn_ws_bytes', C.c_size_t), ('kv_bf16', C.c_int),
         ('prefix_len', C.c_int), ('prefix_S', C.c_int), ('attn_partial_bytes', C.c_size_t),
         ('head_ws', C.c_void_p), ('head_ws_bytes', C.c_size_t), ('seed_dev', C.c_void_p), ('proj_w16', C.c_void_p),
+        ('n_groups', C.c_int), ('beams_per_group', C.c_int), ('prefix_cap', C.c_int), ('prefix_lens', C.c_void_p),
     ]
 
 
@@ -149,6 +150,11 @@ SIGNATURES = {
     'vh_attn_decode_shared_ws_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'vh_attn_decode_shared': (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int,
                                         c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # several utterances' beams, each group over its own prompt (ABI 132)
+    'vh_attn_decode_shared_groups_ws_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'vh_attn_decode_shared_groups': (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p,
+                                               C.c_int, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_size_t, C.c_void_p]),
     'vh_attn_decode': (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, c_i32p, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # a head width other than 64 (ABI 128)

@@ -160,6 +160,32 @@ def synthesize(ar, nar, prompt_tokens: Tensor, prompt, target_tokens: Tensor, co
     return out, codec.decode(out.to(_codec_device(codec, out.device)))
 
 
+@torch.inference_mode()
+def synthesize_many(ar, nar, items, codec=None, greedy_nar: bool = False):
+    """`synthesize` for several utterances at once: items = [(prompt_tokens, prompt, target_tokens), ...] with `prompt` as in
+    `synthesize`.  AR: ValleAR.generate_many (one grouped decode, every utterance's beams over its own prompt K/V); NAR: one
+    ragged ValleNAR.generate_batch over all utterances.  Returns a list, per utterance what `synthesize` returns."""
+    cfg = ar.config
+    utts = []
+    for prompt_tokens, prompt, target_tokens in items:
+        if prompt.dtype.is_floating_point:
+            if codec is None:
+                raise ValueError('synthesize_many: a waveform prompt needs a codec to encode it')
+            prompt = codec.encode(prompt)
+        utts.append((prompt_tokens, to_prompt_codes(prompt, cfg), target_tokens))                 # codes (T, Q)
+    firsts = ar.generate_many(utts)                                                     # per utterance (Ty,) first codebook
+    for i, first in enumerate(firsts):
+        if first.numel() == 0:
+            raise RuntimeError(f'synthesize: the AR model emitted EOS at its first step (no frames to refine) for utterance {i}')
+    dev = firsts[0].device
+    codes = nar.generate_batch([torch.cat([pt.to(dev), tt.to(dev)]) for pt, _, tt in utts], [pc.to(dev) for _, pc, _ in utts],
+                               firsts, greedy=greedy_nar)
+    outs = [from_generated(c, cfg) for c in codes]                                      # (Q, Ty) each
+    if codec is None:
+        return outs
+    return [(o, codec.decode(o.to(_codec_device(codec, o.device)))) for o in outs]
+
+
 def _codec_device(codec, default):
     """Where the codec's model lives (its first parameter), `default` for a parameter-free stand-in."""
     params = getattr(getattr(codec, 'model', None), 'parameters', None)

@@ -1776,21 +1776,42 @@ struct SharedArgs {
     int S_suf, n_split;
     float* partial;
     int n_heads, B, n_pb, n_tot, prefix_wgs;     // n_pb: 32-key blocks of the prefix; prefix_wgs = ceil(n_pb / 4) * n_heads
+    // grouped form (vh_attn_decode_shared_groups) only: kp / vp are (n_groups, h, prefix_S, 64), group g's prompt holds
+    // group_len[g] keys (device array), rows g * beams .. g * beams + beams - 1 are its beams; n_pb counts the blocks of the
+    // prefix CAPACITY and prefix_wgs = ceil(n_pb / 4) * n_heads * n_groups
+    const int32_t* group_len; int n_groups, beams;
 };
 
+// GROUPS = false: the one shared prompt of SharedArgs::prefix_len keys, columns = all B rows.  GROUPS = true: workgroup
+// (group, head, four blocks); the prompt, its length and the columns are the group's own.
+template <bool GROUPS>
 __device__ __forceinline__ void shared_prefix_role(const SharedArgs& a, int wg, int lane, int w) {
-    const int head = wg % a.n_heads, blk = (wg / a.n_heads) * 4 + w;
+    const int head = wg % a.n_heads;
+    int blk, grp = 0, plen = a.prefix_len, nb = a.B;
+    if constexpr (GROUPS) {
+        const int t = wg / a.n_heads;
+        grp = t % a.n_groups;
+        blk = (t / a.n_groups) * 4 + w;
+        plen = min(a.group_len[grp], a.prefix_len);          // (prefix_len holds the capacity; a length beyond it is cut there)
+        nb = a.beams;
+        // a block wholly beyond the group's own prompt: no load, no record — the merge never reads this group's slots
+        // from ceil(plen / 32) on
+        if (blk * 32 >= plen) return;
+    } else {
+        blk = (wg / a.n_heads) * 4 + w;
+    }
     if (blk >= a.n_pb) return;                               // (wave-uniform; no barrier in this role)
     const int r = lane & 31, hh = lane >> 5;
-    const float* kb = a.kp + (int64_t)head * a.prefix_S * HD;
-    const float* vb = a.vp + (int64_t)head * a.prefix_S * HD;
+    const int row0 = grp * nb;                               // the first of the nb rows that attend this prompt
+    const float* kb = a.kp + ((int64_t)grp * a.n_heads + head) * a.prefix_S * HD;
+    const float* vb = a.vp + ((int64_t)grp * a.n_heads + head) * a.prefix_S * HD;
     const int k0 = blk * 32;
     const float qscale = 0.125f * LOG2E;
     // K fragment (A operand): key k0 + r, d = 32 hh + j; rows beyond the prompt repeat its last row (masked below).  The k
     // index of the product is only summed over, so both operands simply use the same d per (hh, j).
     f32x4 kf[8];
     {
-        const float* kr = kb + (int64_t)min(k0 + r, a.prefix_len - 1) * HD + 32 * hh;
+        const float* kr = kb + (int64_t)min(k0 + r, plen - 1) * HD + 32 * hh;
 #pragma unroll
         for (int j = 0; j < 8; ++j) kf[j] = ld4(kr + 4 * j);
     }
@@ -1799,13 +1820,13 @@ __device__ __forceinline__ void shared_prefix_role(const SharedArgs& a, int wg, 
     float vf[2][16];
 #pragma unroll
     for (int x = 0; x < 16; ++x) {
-        const int key = min(k0 + (x & 3) + 8 * (x >> 2) + 4 * hh, a.prefix_len - 1);
+        const int key = min(k0 + (x & 3) + 8 * (x >> 2) + 4 * hh, plen - 1);
         vf[0][x] = vb[(int64_t)key * HD + r];
         vf[1][x] = vb[(int64_t)key * HD + 32 + r];
     }
-    const bool whole = k0 + 32 <= a.prefix_len;              // wave-uniform
-    for (int qb = 0; qb * 32 < a.B; ++qb) {
-        const int b = min(qb * 32 + r, a.B - 1);             // lanes beyond B repeat the last beam (never stored)
+    const bool whole = k0 + 32 <= plen;                      // wave-uniform
+    for (int qb = 0; qb * 32 < nb; ++qb) {
+        const int b = row0 + min(qb * 32 + r, nb - 1);       // lanes beyond the beams repeat the last one (never stored)
         f32x16 s;
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[e] = 0.f;
@@ -1824,7 +1845,7 @@ __device__ __forceinline__ void shared_prefix_role(const SharedArgs& a, int wg, 
         float m = NEG_INF;
 #pragma unroll
         for (int x = 0; x < 16; ++x) {
-            if (!whole && k0 + (x & 3) + 8 * (x >> 2) + 4 * hh >= a.prefix_len) s[x] = NEG_INF;
+            if (!whole && k0 + (x & 3) + 8 * (x >> 2) + 4 * hh >= plen) s[x] = NEG_INF;
             m = fmaxf(m, s[x]);
         }
         m = fmaxf(m, __shfl_xor(m, 32, 64));                 // the beam's other key half; finite: key k0 < prefix_len
@@ -1843,7 +1864,7 @@ __device__ __forceinline__ void shared_prefix_role(const SharedArgs& a, int wg, 
             o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[0][x], s[x], o0, 0, 0, 0);
             o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[1][x], s[x], o1, 0, 0, 0);
         }
-        if (qb * 32 + r < a.B) {
+        if (qb * 32 + r < nb) {
             float* pr = a.partial + (((int64_t)b * a.n_heads + head) * a.n_tot + blk) * PART_LD;
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -1855,13 +1876,14 @@ __device__ __forceinline__ void shared_prefix_role(const SharedArgs& a, int wg, 
     }
 }
 
-__global__ __launch_bounds__(256) void attn_shared_kernel(SharedArgs a) {
+template <bool GROUPS>
+__device__ __forceinline__ void attn_shared_body(const SharedArgs& a) {
     constexpr int NW = 4;
     __shared__ float s_m[NW], s_l[NW];
     __shared__ __attribute__((aligned(16))) float s_o[NW][HD];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if ((int)blockIdx.x < a.prefix_wgs) {                    // workgroup-uniform
-        shared_prefix_role(a, blockIdx.x, lane, w);
+        shared_prefix_role<GROUPS>(a, blockIdx.x, lane, w);
         return;
     }
     // ---- suffix role: (beam, head) x key split over the beam's own rows (the burst kernel's body)
@@ -1950,23 +1972,35 @@ __global__ __launch_bounds__(256) void attn_shared_kernel(SharedArgs a) {
     if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
 }
 
+__global__ __launch_bounds__(256) void attn_shared_kernel(SharedArgs a) { attn_shared_body<false>(a); }
+// several utterances' beams, each group over its own prompt (vh_attn_decode_shared_groups)
+__global__ __launch_bounds__(256) void attn_shared_groups_kernel(SharedArgs a) { attn_shared_body<true>(a); }
+
 // out[b, head] = merge of the n_tot records of (b, head).  256 threads: one parallel pass over the (m, l) pairs gives the
 // weights and the denominator; thread group g = tid >> 6 then sums records g, g + 4, ... of column tid & 63 (independent
 // loads, issued back to back) and the four partial sums are added in group order.
-__global__ __launch_bounds__(256) void attn_records_merge_kernel(const float* __restrict__ partial, float* __restrict__ out,
-                                                                 int ldo, int n_heads, int n_tot) {
+//
+// The grouped form keeps n_slots = n_pb + n_split slots per (b, head), n_pb the blocks of the prefix CAPACITY, of which row
+// b's group wrote only its own n_first = ceil(group_len / 32) prefix records and the n_split suffix records.  The merge runs
+// over those n_tot = n_first + n_split records alone — record k lives in slot k, or from the first suffix record on in slot
+// k + (unwritten slots) — so an unwritten slot is never loaded (the workspace is not initialised, and a zero weight would
+// not stop a NaN).  The other forms: n_slots = n_first = n_tot, slot k is record k.
+__device__ __forceinline__ void records_merge_body(const float* __restrict__ partial, float* __restrict__ out, int ldo,
+                                                   int n_heads, int n_tot, int n_slots, int n_first) {
     __shared__ float s_w[256], s_red[8], s_part[4][HD];
     const int bh = blockIdx.x, b = bh / n_heads, head = bh - b * n_heads;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float* pr = partial + (int64_t)bh * n_tot * PART_LD;
+    const float* pr = partial + (int64_t)bh * n_slots * PART_LD;
+    const int skip = n_slots - n_tot;
+    auto slot = [&](int k) { return k < n_first ? k : k + skip; };
     // ONE memory round trip: the (m, l) pair of record tid and the first eight o values of this thread's column (records
     // w, w + 4, ..., w + 28) are requested together — the o values do not depend on the weights
     const bool have = tid < n_tot;
-    const float mk = have ? pr[tid * PART_LD + HD] : NEG_INF;
-    const float lk = have ? pr[tid * PART_LD + HD + 1] : 0.f;
+    const float mk = have ? pr[slot(tid) * PART_LD + HD] : NEG_INF;
+    const float lk = have ? pr[slot(tid) * PART_LD + HD + 1] : 0.f;
     float a8[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a8[j] = pr[min(w + 4 * j, n_tot - 1) * PART_LD + lane];
+    for (int j = 0; j < 8; ++j) a8[j] = pr[slot(min(w + 4 * j, n_tot - 1)) * PART_LD + lane];
     const float wm = wave_max(mk);
     if (lane == 0) s_red[w] = wm;
     __syncthreads();
@@ -1981,8 +2015,8 @@ __global__ __launch_bounds__(256) void attn_records_merge_kernel(const float* __
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc += a8[j] * s_w[w + 4 * j];
     for (int k = w + 32; k < n_tot; k += 16) {               // longer prompts: four more independent loads per pass
-        const float a0 = pr[k * PART_LD + lane], a1 = pr[min(k + 4, n_tot - 1) * PART_LD + lane];
-        const float a2 = pr[min(k + 8, n_tot - 1) * PART_LD + lane], a3 = pr[min(k + 12, n_tot - 1) * PART_LD + lane];
+        const float a0 = pr[slot(k) * PART_LD + lane], a1 = pr[slot(min(k + 4, n_tot - 1)) * PART_LD + lane];
+        const float a2 = pr[slot(min(k + 8, n_tot - 1)) * PART_LD + lane], a3 = pr[slot(min(k + 12, n_tot - 1)) * PART_LD + lane];
         acc += a0 * s_w[k];
         acc += a1 * s_w[min(k + 4, 255)];
         acc += a2 * s_w[min(k + 8, 255)];
@@ -1991,6 +2025,20 @@ __global__ __launch_bounds__(256) void attn_records_merge_kernel(const float* __
     s_part[w][lane] = acc;
     __syncthreads();
     if (tid < HD) out[(int64_t)b * ldo + head * HD + tid] = ((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) / L;
+}
+
+__global__ __launch_bounds__(256) void attn_records_merge_kernel(const float* __restrict__ partial, float* __restrict__ out,
+                                                                 int ldo, int n_heads, int n_tot) {
+    records_merge_body(partial, out, ldo, n_heads, n_tot, n_tot, n_tot);
+}
+
+__global__ __launch_bounds__(256) void attn_records_merge_groups_kernel(const float* __restrict__ partial, float* __restrict__ out,
+                                                                        int ldo, int n_heads, int n_pb, int n_split,
+                                                                        const int32_t* __restrict__ group_len, int beams) {
+    const int b = blockIdx.x / n_heads;
+    const int n_first = min((max(group_len[b / beams], 0) + 31) >> 5, n_pb);     // the prefix records this row's group wrote
+                                                                                  // (cut at the capacity as the prefix role cuts)
+    records_merge_body(partial, out, ldo, n_heads, n_first + n_split, n_pb + n_split, n_first);
 }
 
 extern "C" size_t vh_attn_decode_shared_ws_bytes(int B, int n_heads, int prefix_len, int n_split_suffix) {
@@ -2022,13 +2070,57 @@ extern "C" int vh_attn_decode_shared(const float* q, int ldq, const float* kpref
     hipStream_t s = (hipStream_t)stream;
     const int prefix_wgs = (n_pb + 3) / 4 * n_heads;
     SharedArgs a{q, ldq, kprefix, vprefix, prefix_len, prefix_S, ksuffix, vsuffix, suffix_len, len_bias, S_suf, n_split_suffix,
-                 (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs};
+                 (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs, nullptr, 1, B};
     // (the events of vh_ar_decoder_profile_attn bracket this launch: the step's attention kernel in this form)
     hipExtLaunchKernelGGL(attn_shared_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s, g_attn_ev[0],
                           g_attn_ev[1], 0, a);
     hipLaunchKernelGGL(attn_records_merge_kernel, dim3(B * n_heads), dim3(256), 0, s, (const float*)partial, out, ldo, n_heads,
                        n_tot);
     VH_CHECK_LAUNCH("vh_attn_decode_shared");
+    return VH_OK;
+}
+
+// ---- several utterances at once: B = n_groups * beams rows, rows g * beams .. g * beams + beams - 1 over group g's prompt ----
+extern "C" size_t vh_attn_decode_shared_groups_ws_bytes(int B, int n_heads, int prefix_cap, int n_split_suffix) {
+    return vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_cap, n_split_suffix);
+}
+
+extern "C" int vh_attn_decode_shared_groups(const float* q, int ldq, const float* kprefix, const float* vprefix,
+                                            const int32_t* prefix_len, int prefix_cap, int prefix_S, const float* ksuffix,
+                                            const float* vsuffix, float* out, int ldo, const int32_t* suffix_len, int len_bias,
+                                            int B, int beams, int n_heads, int S_suf, int n_split_suffix, void* partial,
+                                            size_t partial_bytes, void* stream) {
+    VH_REQUIRE(q && kprefix && vprefix && prefix_len && ksuffix && vsuffix && out && suffix_len && partial, VH_EINVAL,
+               "vh_attn_decode_shared_groups: null pointer");
+    VH_REQUIRE(B > 0 && B <= 64 && n_heads > 0 && prefix_cap > 0 && prefix_cap <= prefix_S && S_suf > 0 &&
+                   n_split_suffix >= 1 && n_split_suffix <= 64, VH_EINVAL,
+               "vh_attn_decode_shared_groups: bad dims B=%d h=%d prefix_cap=%d/%d S_suf=%d n_split=%d", B, n_heads, prefix_cap,
+               prefix_S, S_suf, n_split_suffix);
+    VH_REQUIRE(beams >= 1 && B % beams == 0, VH_EINVAL,
+               "vh_attn_decode_shared_groups: B=%d is not a multiple of beams=%d (the rows of a group)", B, beams);
+    const int n_pb = (prefix_cap + 31) / 32, n_tot = n_pb + n_split_suffix, n_groups = B / beams;
+    VH_REQUIRE(n_tot <= 256, VH_EUNSUPPORTED,
+               "vh_attn_decode_shared_groups: %d prefix blocks + %d splits exceed the 256 records one merge serves", n_pb,
+               n_split_suffix);
+    VH_REQUIRE(len_bias == 0 || len_bias == 1, VH_EINVAL, "vh_attn_decode_shared_groups: len_bias=%d", len_bias);
+    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL,
+               "vh_attn_decode_shared_groups: ldq=%d ldo=%d", ldq, ldo);
+    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kprefix) && vh_aligned16(vprefix) && vh_aligned16(ksuffix) &&
+                   vh_aligned16(vsuffix) && vh_aligned16(partial), VH_EALIGN,
+               "vh_attn_decode_shared_groups: pointers must be 16-byte aligned");
+    VH_REQUIRE(partial_bytes >= vh_attn_decode_shared_groups_ws_bytes(B, n_heads, prefix_cap, n_split_suffix), VH_EINVAL,
+               "vh_attn_decode_shared_groups: workspace of %zu bytes, need %zu", partial_bytes,
+               vh_attn_decode_shared_groups_ws_bytes(B, n_heads, prefix_cap, n_split_suffix));
+    hipStream_t s = (hipStream_t)stream;
+    const int prefix_wgs = (n_pb + 3) / 4 * n_heads * n_groups;
+    SharedArgs a{q, ldq, kprefix, vprefix, prefix_cap, prefix_S, ksuffix, vsuffix, suffix_len, len_bias, S_suf, n_split_suffix,
+                 (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs, prefix_len, n_groups, beams};
+    // (the events of vh_ar_decoder_profile_attn bracket this launch, as in the other forms)
+    hipExtLaunchKernelGGL(attn_shared_groups_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s,
+                          g_attn_ev[0], g_attn_ev[1], 0, a);
+    hipLaunchKernelGGL(attn_records_merge_groups_kernel, dim3(B * n_heads), dim3(256), 0, s, (const float*)partial, out, ldo,
+                       n_heads, n_pb, n_split_suffix, prefix_len, beams);
+    VH_CHECK_LAUNCH("vh_attn_decode_shared_groups");
     return VH_OK;
 }
 

@@ -71,6 +71,8 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
                    hd);
         VH_REQUIRE(d->prefix_len == 0, VH_EUNSUPPORTED,
                    "vh_ar_decoder: the shared prompt (prefix_len=%d) is width 64 only (head width %d)", d->prefix_len, hd);
+        VH_REQUIRE(d->n_groups == 0, VH_EUNSUPPORTED,
+                   "vh_ar_decoder: grouped shared prompts (n_groups=%d) are width 64 only (head width %d)", d->n_groups, hd);
         VH_REQUIRE(d->n_split == 1 ||
                        (d->attn_partial && d->attn_partial_bytes >= vh_attn_decode_hd_ws_bytes(d->B, d->n_heads, hd, d->n_split)),
                    VH_EINVAL, "vh_ar_decoder: head width %d with n_split=%d needs attn_partial of vh_attn_decode_hd_ws_bytes() = %zu "
@@ -119,6 +121,30 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
         for (int i = 0; i < d->n_layers; ++i)
             VH_REQUIRE(d->layers[i].kprefix && d->layers[i].vprefix, VH_EINVAL,
                        "vh_ar_decoder: shared prompt needs kprefix / vprefix in every layer (layer %d)", i);
+    }
+    VH_REQUIRE(d->n_groups >= 0, VH_EINVAL, "vh_ar_decoder: n_groups=%d", d->n_groups);
+    if (d->n_groups > 0) {
+        VH_REQUIRE(!d->kv_bf16, VH_EUNSUPPORTED,
+                   "vh_ar_decoder: grouped shared prompts (n_groups=%d) with kv_bf16 (perf mode) are not served: fp32 caches only",
+                   d->n_groups);
+        VH_REQUIRE(d->prefix_len == 0, VH_EINVAL, "vh_ar_decoder: n_groups=%d with prefix_len=%d (one form or the other)",
+                   d->n_groups, d->prefix_len);
+        VH_REQUIRE(d->beams_per_group >= 1 && d->B == d->n_groups * d->beams_per_group, VH_EINVAL,
+                   "vh_ar_decoder: B=%d is not n_groups=%d x beams_per_group=%d", d->B, d->n_groups, d->beams_per_group);
+        VH_REQUIRE(d->prefix_cap >= 1 && d->prefix_cap <= d->prefix_S && d->prefix_lens, VH_EINVAL,
+                   "vh_ar_decoder: grouped shared prompts need prefix_lens and 1 <= prefix_cap=%d <= prefix_S=%d", d->prefix_cap,
+                   d->prefix_S);
+        VH_REQUIRE((d->prefix_cap + 31) / 32 + d->n_split <= 256, VH_EUNSUPPORTED,
+                   "vh_ar_decoder: a prefix capacity of %d keys with %d suffix splits exceeds the 256 records "
+                   "vh_attn_decode_shared_groups merges", d->prefix_cap, d->n_split);
+        VH_REQUIRE(d->attn_partial &&
+                       d->attn_partial_bytes >= vh_attn_decode_shared_groups_ws_bytes(d->B, d->n_heads, d->prefix_cap, d->n_split),
+                   VH_EINVAL, "vh_ar_decoder: grouped shared prompts of capacity %d need attn_partial of "
+                   "vh_attn_decode_shared_groups_ws_bytes() = %zu bytes (got %zu)", d->prefix_cap,
+                   vh_attn_decode_shared_groups_ws_bytes(d->B, d->n_heads, d->prefix_cap, d->n_split), d->attn_partial_bytes);
+        for (int i = 0; i < d->n_layers; ++i)
+            VH_REQUIRE(d->layers[i].kprefix && d->layers[i].vprefix, VH_EINVAL,
+                       "vh_ar_decoder: grouped shared prompts need kprefix / vprefix in every layer (layer %d)", i);
     }
     VH_REQUIRE(d->top_k == 1 || d->temperature > 0.f, VH_EINVAL,
                "vh_ar_decoder: sampling (top_k=%d) needs temperature > 0", d->top_k);
@@ -209,6 +235,10 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         if (d.kv_bf16)
             return vh_attn_decode_kv16(d.q, D, (const uint16_t*)L.kcache, (const uint16_t*)L.vcache, d.attn, D, d.cache_len,
                                        1, B, d.n_heads, d.S_max, s);
+        if (d.n_groups > 0)          // the beams of several utterances: each group's prompt K/V read once for its beams
+            return vh_attn_decode_shared_groups(d.q, D, L.kprefix, L.vprefix, d.prefix_lens, d.prefix_cap, d.prefix_S, L.kcache,
+                                                L.vcache, d.attn, D, d.cache_len, 1, B, d.beams_per_group, d.n_heads, d.S_max,
+                                                d.n_split, d.attn_partial, d.attn_partial_bytes, s);
         if (d.prefix_len > 0)        // the beams of one utterance: prompt K/V read once, each beam's own rows after it
             return vh_attn_decode_shared(d.q, D, L.kprefix, L.vprefix, d.prefix_len, d.prefix_S, L.kcache, L.vcache, d.attn, D,
                                          d.cache_len, 1, B, d.n_heads, d.S_max, d.n_split, d.attn_partial,

@@ -434,6 +434,21 @@ def shared_prompt_fits(batch: int, n_heads: int, prefix_len: int) -> bool:
     return (prefix_len + 31) // 32 + shared_n_split(batch, n_heads) <= SHARED_MAX_RECORDS
 
 
+GROUP_PREFIX_STEP = 128           # grouped shared prompts: the prefix capacity is the longest prompt rounded up to this many keys
+
+
+def group_prefix_cap(longest: int) -> int:
+    """Prefix capacity (keys per group in the prefix cache, and what sizes the decode grid and the record stride) for prompts of
+    at most `longest` keys: the next multiple of GROUP_PREFIX_STEP.  The decoder slot is keyed on it, not on the lengths, so
+    calls whose prompts differ under one capacity replay the same captured graphs."""
+    return -(-int(longest) // GROUP_PREFIX_STEP) * GROUP_PREFIX_STEP
+
+
+def grouped_prompts_fit(batch: int, n_heads: int, prefix_cap: int) -> bool:
+    """`shared_prompt_fits` for vh_attn_decode_shared_groups: the record slots of the prefix CAPACITY + the suffix splits."""
+    return (prefix_cap + 31) // 32 + shared_n_split(batch, n_heads) <= SHARED_MAX_RECORDS
+
+
 def cached_decode_supported(cfg) -> bool:
     """Whether ValleAR.generate_batch decodes `cfg` on the native K/V cache and the hipGraph decoder (pure Python: the
     rule of plan.hip's decoder_check).  Width 64: config.use_kv_cache up to d_model 4096 (above 1024 the step runs the wide
@@ -517,11 +532,17 @@ class ArDecoder:
     per row per step, the whole step enqueued natively and replayed as a hipGraph."""
 
     def __init__(self, model, batch, s_max, codes, cache: KVCache, cache_len, audio_pos, pos_base,
-                 n_split=None, use_graph=True, seed=0, prefix: KVCache | None = None, prefix_len=0):
+                 n_split=None, use_graph=True, seed=0, prefix: KVCache | None = None, prefix_len=0,
+                 prefix_lens=None, prefix_cap=0, beams=1):
         """prefix / prefix_len: SHARED-PROMPT decoding (the beams of ONE utterance, valle_ar.py:135-138): `prefix` is a
         one-row cache holding the prompt's K/V (its first prefix_len rows), `cache` then holds only the generated rows of
         every beam (s_max = its capacity) and cache_len counts those.  A 16-bit `cache` is perf mode; it takes key splits
-        (rows x heads below 256) and a 16-bit `prefix` — the two caches must have the same dtype."""
+        (rows x heads below 256) and a 16-bit `prefix` — the two caches must have the same dtype.
+
+        prefix_lens / prefix_cap / beams: GROUPED shared prompts (several utterances, each replicated over `beams` rows):
+        `prefix` is then a G-row cache, G = batch // beams, prefix_lens the int32 device tensor (G) of the prompts' lengths
+        — read by every step, so the caller rewrites it between calls — and prefix_cap (<= prefix.s_max) bounds them.  fp32
+        caches only; prefix_len is not used."""
         cfg = model.config
         dev = cache.buf.device
         d, dff, V = cfg.d_model, cfg.dim_feedforward, cfg.num_audio_tokens + 1
@@ -540,6 +561,8 @@ class ArDecoder:
         self.hidden = torch.empty(batch, dff, **f32)
         self.logits = torch.zeros(batch, self.ldl, **f32)
         self.prefix, self.prefix_len = prefix, int(prefix_len)
+        self.prefix_lens, self.prefix_cap, self.beams = prefix_lens, int(prefix_cap), int(beams)
+        self.grouped = prefix_lens is not None
         self.head_dim = hd = d // cfg.n_heads
         if hd != HEAD_DIM:
             # a head width other than 64: vh_attn_decode_hd over an fp32 cache of that width; no shared prompt, no bf16 cache
@@ -548,6 +571,17 @@ class ArDecoder:
                                    'and no bf16 (perf-mode) cache')
             n = _lib.lib().vh_attn_decode_hd_ws_bytes(batch, cfg.n_heads, hd, self.n_split)
             self.partial = torch.empty(max(n, 16) // 4, **f32) if n else None
+        elif self.grouped:
+            if prefix is None or prefix.bf16 or cache.bf16:
+                raise _lib.VhError('grouped shared prompts: fp32 prefix and row caches (no perf mode)')
+            if self.beams < 1 or batch % self.beams or prefix.batch * self.beams != batch or prefix.n_layers != cfg.num_layers or \
+                    not 0 < self.prefix_cap <= prefix.s_max:
+                raise _lib.VhError(f'grouped shared prompts: {batch} rows = {prefix.batch} prefix rows x beams={self.beams}, '
+                                   f'capacity {self.prefix_cap} of {prefix.s_max}')
+            if prefix_lens.dtype != torch.int32 or prefix_lens.numel() != prefix.batch or not prefix_lens.is_cuda:
+                raise _lib.VhError('grouped shared prompts: prefix_lens must be an int32 device tensor, one entry per group')
+            self.prefix_len = 0
+            self.partial = kernels.attn_decode_shared_groups_ws(batch, cfg.n_heads, self.prefix_cap, self.n_split, dev)
         elif prefix is not None:
             if prefix.bf16 != cache.bf16:
                 raise _lib.VhError(f'shared-prompt decoding: the prefix cache ({prefix.buf.dtype}) and the beams\' cache '
@@ -615,6 +649,8 @@ class ArDecoder:
             sum_logprobs=ptr(self.sum_logprobs), ffn_ws=ptr(self.ffn_ws), ffn_ws_bytes=ffn_bytes,
             kv_bf16=int(self.kv_bf16), prefix_len=self.prefix_len if prefix is not None else 0,
             prefix_S=prefix.s_max if prefix is not None else 0,
+            n_groups=prefix.batch if self.grouped else 0, beams_per_group=self.beams if self.grouped else 0,
+            prefix_cap=self.prefix_cap if self.grouped else 0, prefix_lens=ptr(prefix_lens) if self.grouped else None,
             attn_partial_bytes=self.partial.numel() * 4 if self.partial is not None else 0,
             head_ws=ptr(self.head_ws), head_ws_bytes=self.head_ws.numel() * 4 if self.head_ws is not None else 0)
         self._desc = desc

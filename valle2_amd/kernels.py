@@ -501,6 +501,60 @@ def attn_decode_kv16(q, kcache16, vcache16, out, cache_len, len_bias, n_split=1,
     return out
 
 
+def attn_decode_shared_groups_ws(B, n_heads, prefix_cap, n_split, device):
+    """Record workspace of `attn_decode_shared_groups` (vh_attn_decode_shared_groups_ws_bytes), as a float32 tensor."""
+    n = _lib.lib().vh_attn_decode_shared_groups_ws_bytes(B, n_heads, prefix_cap, n_split)
+    return torch.empty(max(n, 16) // 4, device=device, dtype=torch.float32)
+
+
+def attn_decode_shared_groups(q, kprefix, vprefix, prefix_len, prefix_cap, ksuffix, vsuffix, out, suffix_len, len_bias, beams,
+                              n_split=1, partial=None):
+    """One-query attention of B = G * beams rows, rows g * beams .. g * beams + beams - 1 over THEIR prompt (kprefix /
+    vprefix (G, h, prefix_S, 64), first prefix_len[g] rows; prefix_len an int32 DEVICE tensor (G), every entry in
+    1..prefix_cap) followed by each row's own rows (ksuffix / vsuffix (B, h, S_suf, 64), suffix_len[b] + len_bias of them).
+
+    vh_attn_decode_shared_groups serves at most 64 rows per call (the decoder never holds more).  More rows than that go
+    through it here in consecutive calls of whole groups, at most 64 rows each, every call on its rows' own part of
+    `partial` (the workspace of all B rows) — the same chunking as generate_batch(beams=n) applies to a whole decode."""
+    B, n_heads, S_suf, hd = ksuffix.shape
+    if beams < 1 or B % beams:
+        raise _lib.VhError(f'attn_decode_shared_groups: {B} rows are not a multiple of beams={beams}')
+    if B > 64:
+        if beams > 64:
+            raise _lib.VhError(f'attn_decode_shared_groups: beams={beams}: a group holds at most 64 rows')
+        if partial is None:
+            partial = attn_decode_shared_groups_ws(B, n_heads, prefix_cap, n_split, q.device)
+        per_row = _lib.lib().vh_attn_decode_shared_groups_ws_bytes(1, n_heads, prefix_cap, n_split) // 4    # floats
+        if per_row == 0 or q.shape[0] != B or out.shape[0] != B or kprefix.shape[0] != B // beams or vprefix.shape[0] != B // beams or \
+                prefix_len.numel() != B // beams or suffix_len.numel() != B or partial.numel() < B * per_row:
+            raise _lib.VhError(f'attn_decode_shared_groups: prefix {tuple(kprefix.shape)} suffix {tuple(ksuffix.shape)} '
+                               f'q {tuple(q.shape)} beams {beams} workspace {partial.numel() * 4} bytes')
+        step = 64 // beams                                       # whole groups per call
+        for g0 in range(0, B // beams, step):
+            g1 = min(g0 + step, B // beams)
+            r = slice(g0 * beams, g1 * beams)
+            attn_decode_shared_groups(q[r], kprefix[g0:g1], vprefix[g0:g1], prefix_len[g0:g1], prefix_cap, ksuffix[r], vsuffix[r],
+                                      out[r], suffix_len[r], len_bias, beams, n_split,
+                                      partial[r.start * per_row:r.stop * per_row])
+        return out
+    G = B // beams
+    if hd != HEAD_DIM or tuple(kprefix.shape[:2]) != (G, n_heads) or kprefix.shape[3] != HEAD_DIM or q.shape[0] != B or \
+            kprefix.shape != vprefix.shape or ksuffix.shape != vsuffix.shape:
+        raise _lib.VhError(f'attn_decode_shared_groups: prefix {tuple(kprefix.shape)} suffix {tuple(ksuffix.shape)} '
+                           f'q {tuple(q.shape)} beams {beams}')
+    if prefix_len.dtype != torch.int32 or prefix_len.numel() != G or not prefix_len.is_cuda:
+        raise _lib.VhError('attn_decode_shared_groups: prefix_len must be an int32 device tensor (G)')
+    if suffix_len.dtype != torch.int32 or suffix_len.numel() != B:
+        raise _lib.VhError('attn_decode_shared_groups: suffix_len must be int32 (B)')
+    if partial is None:
+        partial = attn_decode_shared_groups_ws(B, n_heads, prefix_cap, n_split, q.device)
+    check(_lib.lib().vh_attn_decode_shared_groups(
+        _dev_f32(q, 'q'), q.stride(0), ptr(kprefix), ptr(vprefix), ptr(prefix_len), prefix_cap, kprefix.shape[2], ptr(ksuffix),
+        ptr(vsuffix), _dev_f32(out, 'out'), out.stride(0), ptr(suffix_len), len_bias, B, beams, n_heads, S_suf, n_split,
+        ptr(partial), partial.numel() * 4, stream()), 'vh_attn_decode_shared_groups')
+    return out
+
+
 def attn_decode_shared_kv16(q, kprefix16, vprefix16, prefix_len, ksuffix16, vsuffix16, out, suffix_len, len_bias, n_split=1,
                             partial=None):
     """`attn_decode_shared` over 16-bit caches (perf mode with a shared prompt): kprefix16 / vprefix16 (1, h, prefix_S, 64) and

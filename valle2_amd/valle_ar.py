@@ -9,6 +9,8 @@ step (valle_ar.py:169-170).
 """
 from __future__ import annotations
 
+import functools
+import inspect
 import os
 import threading
 import time
@@ -19,7 +21,7 @@ from torch import optim
 
 from . import _lib, dropout, kernels
 from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, StepSampler, cached_decode_supported,
-                     perf_forward_supported,
+                     group_prefix_cap, grouped_prompts_fit, perf_forward_supported,
                      shared_prompt_fits,
                      transformer_forward, transformer_forward_bf16)
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device, device_mirror
@@ -52,6 +54,7 @@ class _DecodeSlot:
 
     def __init__(self):
         self.codes = self.cache = self.prefix = self.cache_len = self.audio_pos = self.pos_base = self.dec = None
+        self.group_len = None                                # grouped shared prompts: the device lengths the captured steps read
         self.busy = False
         self.uses = 0
 
@@ -64,6 +67,20 @@ class _DecodeSlot:
 _DECODER_ENV = ('VALLE2_HEAD_FUSED', 'VALLE2_SHARED_SPLIT', 'VALLE2_FOLD_LN', 'VALLE2_DECODE_W16')   # environment knobs read when a decoder is built
 DECODER_SLOTS = int(os.environ.get('VALLE2_DECODER_SLOTS', '2'))    # decoders kept per model (0: build one per call, as before)
 _SLOT_LOCK = threading.Lock()
+
+
+def _beams_refused_early(fn):
+    """generate_batch(beams=n > 1): the refusals that need only the arguments and the config come before anything touches
+    a device (the wrappers below move the call to the HIP device first)."""
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        if kwargs.get('beams', 1) != 1:
+            a = sig.bind(self, *args, **kwargs).arguments
+            self._check_beams(a['beams'], a.get('shared_prompt', False), a.get('perf_mode', False), a.get('forced'))
+        return fn(self, *args, **kwargs)
+    return wrapper
 
 
 class ValleAR(_Base):
@@ -216,14 +233,65 @@ class ValleAR(_Base):
         best = best[prompt_len:]
         return best[best != self.eos_token]
 
-    def _generate_in_groups(self, texts, first_codes, max_new, use_graph, perf_mode):
+    @_on_device
+    @torch.inference_mode()
+    def generate_many(self, utterances, *, beams=None):
+        """`generate()` for several utterances in one decode: utterances = [(prompt_tokens, prompt_codes, target_tokens |
+        None), ...], each replicated over `beams` rows (default config.num_beams) that share its prompt's K/V
+        (`generate_batch(..., beams=n)`).  Returns a list of 1-D int64 tensors, per utterance what generate() returns: the
+        best beam by get_best_beam over that utterance's rows and scores, prompt cut, EOS stripped."""
+        beams = self.config.num_beams if beams is None else int(beams)
+        texts, firsts = [], []
+        for prompt_tokens, prompt_codes, target_tokens in utterances:
+            assert prompt_tokens.dim() == 1, 'Prompt tokens should be 1D tensor.'
+            assert prompt_codes.dim() == 2, 'Prompt codes should be 2D tensor.'
+            if target_tokens is not None:
+                assert target_tokens.dim() == 1, 'Target tokens should be 1D tensor.'
+            texts.append(prompt_tokens if target_tokens is None else torch.cat((prompt_tokens, target_tokens), dim=0))
+            firsts.append(prompt_codes[..., 0])
+        rows = self.generate_batch(texts, firsts, beams=beams)
+        stats = self.last_generate_stats
+        out = []
+        for g in range(len(texts)):
+            sl = slice(g * beams, (g + 1) * beams)
+            best = get_best_beam(rows[sl], stats['sum_logprobs'][sl].to(rows.device), self.eos_token, self.config.length_penalty)
+            best = best[stats['prompt_lens'][g * beams]:]
+            out.append(best[best != self.eos_token])
+        return out
+
+    def _check_beams(self, beams, shared_prompt=False, perf_mode=False, forced=None):
+        """The refusals of generate_batch(beams=n): pure Python, no device."""
+        cfg = self.config
+        if not isinstance(beams, int) or isinstance(beams, bool) or beams < 1:
+            raise ValueError(f'generate_batch: beams={beams!r} (an integer >= 1)')
+        if beams == 1:
+            return
+        if beams > MAX_DECODE_ROWS:
+            raise ValueError(f'generate_batch: beams={beams}: the beams of an utterance decode in one launch of at most '
+                             f'{MAX_DECODE_ROWS} rows')
+        if shared_prompt:
+            raise ValueError(f'generate_batch: beams={beams} with shared_prompt=True: shared_prompt takes the replicated rows of '
+                             'ONE utterance, beams takes the utterances themselves and replicates them')
+        if perf_mode:
+            raise ValueError(f'generate_batch: beams={beams} with perf_mode={perf_mode!r}: grouped shared prompts decode on fp32 '
+                             'caches only (perf_mode serves generate() and independent rows)')
+        if forced is not None:
+            raise ValueError(f'generate_batch: beams={beams} with forced: teacher forcing drives independent rows')
+        if not cfg.use_kv_cache or cfg.d_model != cfg.n_heads * kernels.HEAD_DIM or cfg.d_model > MAX_DECODE_D_MODEL:
+            raise ValueError(f'generate_batch: beams={beams} with use_kv_cache={cfg.use_kv_cache}, d_model={cfg.d_model}, '
+                             f'n_heads={cfg.n_heads}: grouped shared prompts need the cached decoder at head width '
+                             f'{kernels.HEAD_DIM} (d_model <= {MAX_DECODE_D_MODEL})')
+
+    def _generate_in_groups(self, texts, first_codes, max_new, use_graph, perf_mode, beams=1):
         """More rows than one decode launch serves (64: 4 MFMA row tiles): consecutive groups of 64 rows; rows are
-        independent, so the result is what one pass would give."""
-        B, dev = len(texts), self.device
+        independent, so the result is what one pass would give.  beams > 1: consecutive chunks of whole utterances, 64 // beams
+        of them per launch."""
+        B, dev = len(texts) * beams, self.device
         parts, stats = [], []
-        for r0 in range(0, B, MAX_DECODE_ROWS):
-            parts.append(self.generate_batch(texts[r0:r0 + MAX_DECODE_ROWS], first_codes[r0:r0 + MAX_DECODE_ROWS],
-                                             max_new=max_new, use_graph=use_graph, perf_mode=perf_mode))
+        per = MAX_DECODE_ROWS // beams
+        for r0 in range(0, len(texts), per):
+            parts.append(self.generate_batch(texts[r0:r0 + per], first_codes[r0:r0 + per],
+                                             max_new=max_new, use_graph=use_graph, perf_mode=perf_mode, beams=beams))
             stats.append(self.last_generate_stats)
         width = max(p.shape[1] for p in parts)
         out = torch.full((B, width), self.eos_token, device=dev, dtype=torch.int64)
@@ -235,6 +303,7 @@ class ValleAR(_Base):
         merged['prompt_lens'] = [x for st in stats for x in st['prompt_lens']]
         merged['sum_logprobs'] = torch.cat([st['sum_logprobs'] for st in stats])
         merged['tokens_appended'] = max(st['tokens_appended'] for st in stats)
+        merged['groups'] = sum(st['groups'] for st in stats)
         self.last_generate_stats = merged
         return out
 
@@ -301,22 +370,28 @@ class ValleAR(_Base):
             kv_dtype = kernels.H16 if run.perf_mode else torch.float32
             prefix = KVCache(cfg.num_layers, 1, cfg.n_heads, (s0 + 31) // 32 * 32, dev, dtype=kv_dtype)
             cache = KVCache(cfg.num_layers, B, cfg.n_heads, (run.max_new + 1 + 31) // 32 * 32, dev, dtype=kv_dtype)
+        elif run.grouped:
+            # one row per UTTERANCE through the prompt pass, into a prefix cache of run.cap keys per utterance; the beams' cache
+            # holds generated rows only
+            prefix = KVCache(cfg.num_layers, run.G, cfg.n_heads, run.cap, dev)
+            cache = KVCache(cfg.num_layers, B, cfg.n_heads, (run.max_new + 1 + 31) // 32 * 32, dev)
         elif run.perf_prefill:
             cache = KVCache(cfg.num_layers, B, cfg.n_heads, s_max, dev, dtype=kernels.H16)
         else:
             cache = KVCache(cfg.num_layers, B, cfg.n_heads, s0 if run.perf_mode else s_max, dev)
-        rows = 1 if run.shared else B
+        n = run.beams                                     # rows per utterance (1 unless grouped)
+        rows = 1 if run.shared else run.G
         if not run.ragged:
             run.text_ids = torch.stack(texts[:rows])
-            codes[:, 1:run.pl_max] = torch.stack(first_codes)
+            codes[:, 1:run.pl_max] = torch.stack(first_codes).repeat_interleave(n, 0) if run.grouped else torch.stack(first_codes)
             x = torch.empty(rows, s0, d, device=dev, dtype=torch.float32)
-            self._embed_rows(run.text_ids, codes[:rows, :run.pl_max], x)
+            self._embed_rows(run.text_ids, codes[:rows * n:n, :run.pl_max], x)
             run.fwd = dict(x_len=run.txs[0])
         else:
-            x = torch.zeros(B, s0, d, device=dev, dtype=torch.float32)
-            for b in range(B):
-                codes[b, 1:run.pls[b]] = first_codes[b]
-                self._embed_rows(texts[b].unsqueeze(0), codes[b:b + 1, :run.pls[b]], x[b:b + 1])
+            x = torch.zeros(run.G, s0, d, device=dev, dtype=torch.float32)
+            for b in range(run.G):
+                codes[b * n:(b + 1) * n, 1:run.pls[b]] = first_codes[b]
+                self._embed_rows(texts[b].unsqueeze(0), codes[b * n:b * n + 1, :run.pls[b]], x[b:b + 1])
             run.lens = torch.tensor([t + p for t, p in zip(run.txs, run.pls)], **i32)
             run.fwd = dict(x_len_dev=torch.tensor(run.txs, **i32), kv_len=run.lens)
         if run.perf_prefill:
@@ -331,14 +406,16 @@ class ValleAR(_Base):
             wide.narrow_into(prefix)
         else:
             scratch = None if run.any_head_dim or run.hd_cached else ForwardScratch(rows * s0, d, cfg.dim_feedforward, dev)
-            transformer_forward(self.transformer, x, prefix if run.shared else cache, mode=kernels.MASK_PREFIX,
+            transformer_forward(self.transformer, x, prefix if run.shared or run.grouped else cache, mode=kernels.MASK_PREFIX,
                                 scratch=scratch, **run.fwd)
         if run.ragged:
-            last = x[torch.arange(B, device=dev), run.lens.long() - 1]
+            last = x[torch.arange(run.G, device=dev), run.lens.long() - 1]
         elif run.shared:
             last = x[:, -1].expand(B, d)                  # every beam starts from the one prompt row's last hidden state
         else:
             last = x[:, -1]
+        if run.grouped:
+            last = last.repeat_interleave(n, 0)           # every beam starts from its utterance's last hidden row
         if run.perf_mode and not run.perf_prefill and not run.shared:
             cache = cache.narrowed(s_max)                 # fp32 prompt K/V -> the bf16 cache of the decode steps
         return cache, prefix, last.contiguous()
@@ -406,10 +483,11 @@ class ValleAR(_Base):
                 return done, int(full[0])
         return done, None
 
+    @_beams_refused_early
     @_on_device
     @torch.inference_mode()
     def generate_batch(self, texts, first_codes, max_new=None, use_graph=True, profile_attn=False, perf_mode=False,
-                       forced=None, keep_logits=(), shared_prompt=False):
+                       forced=None, keep_logits=(), shared_prompt=False, *, beams=1):
         """Batched greedy decoding of B independent rows (extension; `generate` is built on it).
         texts[b]: 1-D int64 text ids; first_codes[b]: 1-D int64 first-codebook prompt (no BOS).
         Rows may differ in text and prompt length.  Returns codes (B, max_prompt_len + n_new) int64
@@ -432,14 +510,23 @@ class ValleAR(_Base):
         step reads the prompt's K/V once for all rows (vh_attn_decode_shared); rows still sample, append and score
         independently.  Cached decoder only; combines with perf_mode (True and 'kv'): the one-row prompt pass then fills a
         16-bit prefix cache (on the 16-bit matrix cores, or fp32 and narrowed once for 'kv') and the beams' own rows are 16-bit
-        too (vh_attn_decode_shared_kv16).  Rows of different lengths are refused."""
+        too (vh_attn_decode_shared_kv16).  Rows of different lengths are refused.
+        beams=n > 1 (keyword-only): texts / first_codes hold G UTTERANCES (texts and prompts of any lengths) and the call
+        decodes G * n rows, row g * n + j being beam j of utterance g — `generate()`'s replication for several utterances at
+        once.  The prompt pass runs for the G rows and every decode step reads each utterance's prompt K/V once for its n
+        beams (vh_attn_decode_shared_groups); the result and `last_generate_stats` are laid out as for G * n independent rows
+        (`prompt_lens`, `sum_logprobs` per row) plus `groups`, `beams` and `grouped_shared` (False when a prompt beyond the
+        kernel's record bound sent the call down the independent-rows path).  More than 64 rows decode in consecutive chunks
+        of whole utterances.  fp32 cached decoder at head width 64 only: shared_prompt, perf_mode and forced are refused."""
         self._require_layernorm()
         cfg = self.config
         dev = self.device
         B = len(texts)
         if B == 0 or len(first_codes) != B:
             raise ValueError('generate_batch: texts and first_codes must be non-empty lists of equal length')
+        self._check_beams(beams, shared_prompt, perf_mode, forced)
         run = _Run()
+        run.G, run.beams, run.grouped = B, beams, beams > 1                # utterances, rows of each
         run.B, run.max_new = B, cfg.max_audio_len if max_new is None else max_new
         # a head width other than 64 (modules.py:109-111 allows it): a multiple of 4 from 16 to 256 at d_model <= 1024 decodes on
         # the cached decoder with the _hd kernels (hd_cached; the prompt pass runs on the general kernels and fills the cache);
@@ -462,6 +549,8 @@ class ValleAR(_Base):
         if perf_mode and cfg.d_model > 1024:
             raise ValueError(f'd_model {cfg.d_model}: perf_mode (the bf16 K/V cache of the decode step) serves d_model <= 1024; '
                              'wider models decode fp32')
+        if run.grouped and B * beams > MAX_DECODE_ROWS:
+            return self._generate_in_groups(texts, first_codes, run.max_new, use_graph, perf_mode, beams=beams)
         if B > MAX_DECODE_ROWS:
             if shared_prompt or forced is not None:
                 raise ValueError(f'shared_prompt / forced serve at most {MAX_DECODE_ROWS} rows')
@@ -479,6 +568,18 @@ class ValleAR(_Base):
         run.shared = bool(shared_prompt)
         if run.shared and run.ragged:
             raise ValueError('shared_prompt: identical rows (equal text and prompt lengths)')
+        run.row_pls = run.pls
+        if run.grouped:
+            # the prefix capacity (what the decoder is built and keyed for): the longest context rounded up to 128 keys
+            run.cap = group_prefix_cap(run.s0)
+            if not grouped_prompts_fit(B * beams, cfg.n_heads, run.cap):
+                # beyond the 256 records one merge serves: the same rows, each with its own prompt pass and K/V
+                out = self.generate_batch([t for t in texts for _ in range(beams)], [c for c in first_codes for _ in range(beams)],
+                                          max_new=max_new, use_graph=use_graph, profile_attn=profile_attn)
+                self.last_generate_stats.update(groups=run.G, beams=beams, grouped_shared=False)
+                return out
+            B = run.B = run.G * beams
+            run.row_pls = [p for p in run.pls for _ in range(beams)]
         t_host0 = time.perf_counter()
         # a decoder per shape survives the call (graphs, caches, counters: _DecodeSlot) unless the call is one of the
         # measurement / test forms that drive the decoder by hand
@@ -486,8 +587,11 @@ class ValleAR(_Base):
         # (perf_mode='kv' with rows of their own narrows into a fresh cache per call: no slot; over a shared prompt it narrows into
         # the slot's 16-bit prefix)
         if not (no_cache or forced is not None or profile_attn or (perf_mode and not run.perf_prefill and not run.shared)):
-            slot_key = (B, run.s0 if run.shared else None, run.s_max, run.pl_max + run.max_new, run.max_new, run.shared,
-                        run.perf_prefill, bool(perf_mode), bool(use_graph), int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature),
+            # (grouped shared prompts: the prefix CAPACITY stands for every length — prompts of other lengths under the same
+            # capacity reuse the slot and its captured graphs)
+            slot_key = (B, run.s0 if run.shared else None, None if run.grouped else run.s_max,
+                        (run.cap if run.grouped else run.pl_max) + run.max_new, run.max_new, run.shared,
+                        (run.G, beams, run.cap) if run.grouped else None, run.perf_prefill, bool(perf_mode), bool(use_graph), int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature),
                         str(dev), _lib.TUNING_EPOCH, tuple(os.environ.get(k) for k in _DECODER_ENV), self._weights_key())
             slot = self._acquire_slot(slot_key)
         run.slot = slot
@@ -496,7 +600,8 @@ class ValleAR(_Base):
             codes = slot.codes
             codes.fill_(self.eos_token)
         else:
-            codes = torch.full((B, run.pl_max + run.max_new), self.eos_token, device=dev, dtype=torch.int64)
+            codes = torch.full((B, (run.cap if run.grouped else run.pl_max) + run.max_new), self.eos_token, device=dev,
+                               dtype=torch.int64)
         codes[:, 0] = self.bos_token                                   # valle_ar.py:115-117
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]   # prefill | decode phase times
         marks[0].record()
@@ -508,16 +613,25 @@ class ValleAR(_Base):
         # (the decode loop's small state goes up BEFORE the prompt pass is enqueued: a host->device copy behind it
         # would hold the host until the pass has finished, and the decoder is built and captured during the pass)
         # cache_len: rows in the cache the decode steps append to (+1 by the sample step); shared prompt: generated rows only
-        first_len = [-1] * B if run.shared else [t + p - 1 for t, p in zip(run.txs, run.pls)]
+        first_len = [-1] * B if run.shared or run.grouped else [t + p - 1 for t, p in zip(run.txs, run.pls)]
+        group_len = None
         if reuse:
             cache_len, audio_pos, pos_base = slot.cache_len, slot.audio_pos, slot.pos_base
             cache_len.copy_(torch.tensor(first_len, dtype=torch.int32), non_blocking=True)
-            audio_pos.copy_(torch.tensor(run.pls, dtype=torch.int32), non_blocking=True)
+            audio_pos.copy_(torch.tensor(run.row_pls, dtype=torch.int32), non_blocking=True)
             pos_base.copy_(audio_pos)
         else:
             cache_len = _lib.to_device_async(torch.tensor(first_len, dtype=torch.int32), dev)
-            audio_pos = _lib.to_device_async(torch.tensor(run.pls, dtype=torch.int32), dev)
+            audio_pos = _lib.to_device_async(torch.tensor(run.row_pls, dtype=torch.int32), dev)
             pos_base = audio_pos.clone()
+        if run.grouped:
+            # the prompts' lengths, where the (captured) decode steps read them
+            lens = torch.tensor([t + p for t, p in zip(run.txs, run.pls)], dtype=torch.int32)
+            if reuse:
+                group_len = slot.group_len
+                group_len.copy_(lens, non_blocking=True)
+            else:
+                group_len = _lib.to_device_async(lens, dev).clone()      # (its own storage: it outlives the call in the slot)
         # sampling seed drawn from torch's generator, so torch.manual_seed() makes a run repeatable
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if cfg.top_k != 1 else 0
         if reuse:
@@ -537,13 +651,15 @@ class ValleAR(_Base):
         else:
             try:
                 dec = ArDecoder(self, B, cache.s_max, codes, cache, cache_len, audio_pos, pos_base,
-                                use_graph=use_graph and not no_cache, seed=seed, prefix=prefix, prefix_len=run.s0)
+                                use_graph=use_graph and not no_cache, seed=seed, prefix=prefix, prefix_len=run.s0,
+                                **(dict(prefix_lens=group_len, prefix_cap=run.cap, beams=beams) if run.grouped else {}))
             except BaseException:
                 self._release_slot(slot_key, slot, False)
                 raise
             if slot is not None:
                 slot.codes, slot.cache, slot.prefix, slot.dec = codes, cache, prefix, dec
                 slot.cache_len, slot.audio_pos, slot.pos_base = cache_len, audio_pos, pos_base
+                slot.group_len = group_len
         if slot is not None:
             slot.uses += 1
         try:
@@ -581,7 +697,8 @@ class ValleAR(_Base):
                                         'decode_ms': marks[1].elapsed_time(marks[2]),
                                         'attn_mean_ms': attn_ms, 'attn_floor_ms': attn_floor_ms,
                                         'attn_kernel_ms': attn_kernel_ms, 's0': run.s0,
-                                        'prompt_lens': run.pls,
+                                        'prompt_lens': run.row_pls,
+                                        'groups': run.G, 'beams': beams, 'grouped_shared': run.grouped,
                                         'sum_logprobs': dec.sum_logprobs.clone(),
                                         # host time this call spent OUTSIDE enqueueing the prompt pass and the replays and
                                         # waiting for them: set-up of the call's state + building / capturing the decoder
