@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 132            /* 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 133            /* 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -203,14 +203,16 @@ int vh_linear_qkv(const float* A, int lda, const float* Wqkv, float* q_out, int 
  * vh_ln_fold prepares Wf (N,K), c1 (N), c2 (N) once per weight set (bias may be NULL);
  * vh_linear_folded / vh_linear_qkv_folded are vh_linear / vh_linear_qkv with (Wf, c1, c2) in
  * place of (W, bias, ln_gamma, ln_beta): mean / rstd are computed beside the products and applied
- * in the epilogue.  Supported: M <= 64, N % 16 == 0, K in {128, 256, 512, 1024}, and for vh_linear_folded /
+ * in the epilogue.  Supported: M <= 64, N % 16 == 0, K in {128, 256, 512, 1024}; at head width 64 (vh_linear_folded,
+ * vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) also K in {640, 768, 896} (K = 128 PW, PW in 5..7, eight waves, one pass,
+ * fp32 weights only); and for vh_linear_folded /
  * vh_linear_qkv_folded also K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} (K = 256 PW passes, PW in 5..8, one or two passes): 16 waves per 16 output columns, one or
  * two passes over K, mean / variance from the operand fragments as one-pass sums about the mean of the row's first 32
  * elements (the products run on x - that shift too, so the epilogue's correction is a fraction of the row's deviation);
  * the shift being a mean of 32 of the row's own elements bounds the cancellation of the one-pass variance: (mean - shift)^2 <=
  * K/32 var, at most 7 bits lost of 24 at K = 4096 even for a row whose first 32 elements are outliers;
  * more than 16 rows run as row groups, so vh_linear_qkv_folded needs T == 1 there.  Deterministic (fixed summation
- * order, no atomics).  The _hd and _kv16 forms and vh_ffn_decode keep K <= 1024.  Anything else: VH_EUNSUPPORTED with a
+ * order, no atomics).  The _kv16 form and vh_ffn_decode keep K <= 1024 (with 640, 768 and 896), the _hd form K in {128, 256, 512, 1024}.  Anything else: VH_EUNSUPPORTED with a
  * message naming "folded LayerNorm". */
 int vh_ln_fold(const float* W, const float* gamma, const float* beta, const float* bias, float* Wf,
                float* c1, float* c2, int N, int K, void* stream);
@@ -250,7 +252,7 @@ int vh_kv_store(const float* qkv, int ld, float* kcache, float* vcache, int B, i
  * boundary and the (M, dff) hidden activation never exists in memory.  A second small launch adds the slabs
  * in slice order (bitwise reproducible, no atomics) with b2 and the residual x.  out may alias x.
  * x (M, d_model) ldx; w1f (dff, d_model); w2 (d_model, dff) as stored; c1, c2 (dff); b2 (d_model) | NULL.
- * Supported: M <= 64, d_model in {128, 256, 512, 1024}, dff % 16 == 0, dff / 16 <= 1024 slices.
+ * Supported: M <= 64, d_model in {128, 256, 512, 640, 768, 896, 1024}, dff % 16 == 0, dff / 16 <= 1024 slices.
  * workspace: vh_ffn_decode_ws_bytes(M, d_model, dff) bytes (no initialisation needed). */
 size_t vh_ffn_decode_ws_bytes(int M, int d_model, int dff);
 int vh_ffn_decode(const float* x, int ldx, const float* w1f, const float* c1, const float* c2, const float* w2,

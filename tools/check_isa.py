@@ -182,6 +182,59 @@ def check_wide_folded(asm):
     return problems
 
 
+def compile_ffn_asm():
+    with tempfile.TemporaryDirectory() as td:
+        out = Path(td) / 'ffn.s'
+        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-S', '--cuda-device-only',
+                        '-mllvm', '-amdgpu-kernarg-preload-count=16',
+                        f'-I{REPO / "include"}', str(REPO / 'valle2_amd/csrc/ffn.hip'), '-o', str(out)],
+                       check=True, capture_output=True)
+        return out.read_text()
+
+
+# d_model 640 / 768 / 896 (PW = d / 128): per EPI (plain, QKV, QKV16) the fragment-statistics form and the row-resident forms at
+# MT 1 / 2 / 4 with NJ = d / 64; the fused FeedForward at 16 and 32 hidden columns per workgroup.  fp32 weights only.
+BASE_FOLD_PW = (5, 6, 7)
+# (MT = 4 at PW = 7 would spill: launch_gemm does not build it and serves those row counts as row groups)
+BASE_FOLD_GEMMS = [(mt, epi, pw, ln, nj) for epi in (0, 1, 3) for pw in BASE_FOLD_PW
+                   for mt, ln, nj in [(1, 3, 1), (1, 2, 2 * pw), (2, 2, 2 * pw), (4, 2, 2 * pw)] if (mt, pw) != (4, 7)]
+BASE_FOLD_FFNS = [(128 * pw, sw) for pw in BASE_FOLD_PW for sw in (16, 32)]
+
+
+def check_base_folded(asm):
+    """The folded-LayerNorm skinny GEMMs and the fused FeedForward at d_model 640 / 768 / 896 (`asm`: the listings of gemm.hip
+    and ffn.hip, concatenated).  Every instantiation must exist, touch no scratch and stay within the registers its workgroup
+    size leaves a wave — the cap of check_wide_folded: 512 registers per SIMD over the workgroup's waves per SIMD, 128 for its
+    sixteen waves, 256 for the eight waves here (the row-resident MT = 4 form at PW = 6 stands at 244-246; at PW = 7 it would
+    need scratch and must NOT exist).  No 16-bit-weight form may exist at these widths."""
+    problems = []
+    cap = 512 * 4 // 8
+    names = [(f'gemm_skinny_fast<{mt},8,{epi},{pw},{ln},{nj}>',
+              f'_Z16gemm_skinny_fastILi{mt}ELi8ELi{epi}ELi{pw}ELi{ln}ELi{nj}ELb0EEvPKfS1_iiiii8GemmArgs6LnFuse')
+             for mt, epi, pw, ln, nj in BASE_FOLD_GEMMS]
+    names += [(f'ffn_decode_kernel<{d},{sw}>', f'_Z17ffn_decode_kernelILi{d}ELi{sw}ELb0EEvPKfS1_S1_iii7FfnArgs') for d, sw in BASE_FOLD_FFNS]
+    for shown, name in names:
+        m = re.search(r'^%s:[^\n]*\n(.*?)^\.Lfunc_end' % re.escape(name), asm, re.S | re.M)
+        seg = re.search(r'\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel' % re.escape(name), asm, re.S)
+        if not m or not seg:
+            problems.append(f'{shown} not found')
+            continue
+        if any(l.strip().startswith('scratch_') for l in m.group(1).splitlines()):
+            problems.append(f'{shown}: scratch access (register spill)')
+        priv = int(re.search(r'\.amdhsa_private_segment_fixed_size (\d+)', seg.group(1)).group(1))
+        vgpr = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', seg.group(1)).group(1))
+        if priv != 0 or vgpr > cap:
+            problems.append(f'{shown}: private segment {priv} bytes, {vgpr} VGPRs (limit {cap})')
+    if re.search(r'^_Z16gemm_skinny_fastILi4ELi8ELi\dELi7ELi2ELi14E', asm, re.M):
+        problems.append('gemm_skinny_fast<4, 8, .., PW = 7, LN = 2>: the refused (K = 896, four row tiles) form is built')
+    for pw in BASE_FOLD_PW:
+        if re.search(r'^_Z16gemm_skinny_fastILi\dELi8ELi\dELi%dELi[23]ELi\d+ELb1E' % pw, asm, re.M):
+            problems.append(f'gemm_skinny_fast<.., PW = {pw}, LN = 2 | 3, W16>: a 16-bit-weight form exists')
+        if re.search(r'^_Z17ffn_decode_kernelILi%dELi\d+ELb1E' % (128 * pw), asm, re.M):
+            problems.append(f'ffn_decode_kernel<{128 * pw}, .., W16>: a 16-bit-weight form exists')
+    return problems
+
+
 # perf mode with key splits / a shared prompt: the two ring16 split shapes and the two-role shared kernel over 16-bit caches
 PERF_MODE_BEAMS_KERNELS = {'attn_decode_ring16_split_kernel': 2, 'attn_shared16_kernel': 1}
 
@@ -261,7 +314,7 @@ def check_m0(asm, kernels):
 
 if __name__ == '__main__':
     gemm_asm = compile_asm()
-    probs = check(gemm_asm) + check_wide_folded(gemm_asm) + check_attention(compile_attention_asm())
+    probs = check(gemm_asm) + check_wide_folded(gemm_asm) + check_base_folded(gemm_asm + compile_ffn_asm()) + check_attention(compile_attention_asm())
     probs += check_loop_waits(compile_attention_asm(), ATTN_WAIT_KERNELS) + check_loop_waits(compile_bf16_asm(), BF16_WAIT_KERNELS)
     probs += check_m0(compile_bf16_asm(), BF16_WAIT_KERNELS)
     probs += check_no_scratch(compile_elementwise_asm())

@@ -227,7 +227,8 @@ __global__ __launch_bounds__(256) void ffn_reduce_kernel(const float* __restrict
 
 // hidden columns per workgroup (0 = unsupported shape) and rows per workgroup
 static int ffn_plan(int M, int d_model, int dff, int* rg_rows) {
-    if (M < 1 || M > 64 || !(d_model == 128 || d_model == 256 || d_model == 512 || d_model == 1024) || dff % 16 != 0 ||
+    const bool base = d_model == 640 || d_model == 768 || d_model == 896;      // 10 / 12 / 14 heads of width 64
+    if (M < 1 || M > 64 || !(d_model == 128 || d_model == 256 || d_model == 512 || d_model == 1024 || base) || dff % 16 != 0 ||
         dff / 16 > 1024)
         return 0;
     const int rg8 = (M + 7) / 8, rg16 = (M + 15) / 16;
@@ -257,7 +258,7 @@ static int ffn_decode_launch(const float* x, int ldx, const float* w1f, const fl
     int rg_rows = 0;
     const int sw = ffn_plan(M, d_model, dff, &rg_rows);
     VH_REQUIRE(sw != 0, VH_EUNSUPPORTED,
-               "vh_ffn_decode: M=%d d_model=%d dff=%d (1 <= M <= 64, d_model in {128,256,512,1024}, dff %% 16 == 0, "
+               "vh_ffn_decode: M=%d d_model=%d dff=%d (1 <= M <= 64, d_model in {128,256,512,640,768,896,1024}, dff %% 16 == 0, "
                "dff <= 16384)", M, d_model, dff);
     VH_REQUIRE(ldx >= d_model && ldo >= d_model && ldx % 4 == 0 && ldo % 4 == 0, VH_EINVAL, "vh_ffn_decode: ldx=%d ldo=%d",
                ldx, ldo);
@@ -281,10 +282,24 @@ static int ffn_decode_launch(const float* x, int ldx, const float* w1f, const fl
         if (sw == 16) FFN(DD, 16);             \
         else FFN(DD, 32);                      \
     } while (0)
+    // 640 / 768 / 896: fp32 weights only (no 16-bit-weight instantiation)
+#define FFN_B(DD)                                                                                                    \
+    do {                                                                                                            \
+        if (w16) {                                                                                                  \
+            vh_set_error("vh_ffn_decode: no 16-bit-weight form at d_model=%d", d_model);                            \
+            return VH_EUNSUPPORTED;                                                                                 \
+        }                                                                                                           \
+        if (sw == 16) hipLaunchKernelGGL((ffn_decode_kernel<DD, 16>), grid, dim3(512), 0, s, x, w1f, w2, ldx, M, dff, a); \
+        else hipLaunchKernelGGL((ffn_decode_kernel<DD, 32>), grid, dim3(512), 0, s, x, w1f, w2, ldx, M, dff, a);   \
+    } while (0)
     if (d_model == 128) FFN_D(128);
     else if (d_model == 256) FFN_D(256);
     else if (d_model == 512) FFN_D(512);
+    else if (d_model == 640) FFN_B(640);
+    else if (d_model == 768) FFN_B(768);
+    else if (d_model == 896) FFN_B(896);
     else FFN(1024, 16);
+#undef FFN_B
 #undef FFN_D
 #undef FFN
     hipLaunchKernelGGL(ffn_reduce_kernel, dim3(M * (d_model / 64)), dim3(256), 0, s, (const float*)workspace, n_slices, x,

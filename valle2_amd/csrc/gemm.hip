@@ -960,6 +960,10 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
     __shared__ float s_mean[16 * MT], s_rstd[16 * MT];
     __shared__ __attribute__((aligned(16))) float pst[LN == 3 ? 16 : 1][2 * NW];   // LN == 3: (sum, sum of squares) per wave and row
     static_assert(LN != 3 || (MT == 1 && (NW == 8 || NW == 16)), "fragment statistics: one row tile, 8 or 16 waves");
+    // K = 128 PW with PW in 5..7 at eight waves (640 / 768 / 896, folded forms only): the products run on x - shift as in the
+    // 16-wave form, so a row whose mean exceeds its deviation does not cancel mean·c1 against an accumulator of that size
+    constexpr bool BASE_K = NW == 8 && PW >= 5 && PW <= 7 && LN >= 2;
+    constexpr bool XSHIFT3 = LN == 3 && (NW == 16 || BASE_K);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, g = lane >> 4;
     const int n0 = blockIdx.x * 16;
@@ -1002,6 +1006,14 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
     auto ln_reduce = [&](int r0) {
         // DPP row g of the wave reduces activation row 4*w + g (two-pass mean / centred variance)
         const int row = (r0 * NW + w) * 4 + g;
+        if constexpr (BASE_K) {
+            // statistics about the row's shift too (shift2's expression on the same four elements, held by the first lane of the
+            // DPP row): the mean published below is mean - shift, what the epilogue needs, free of the rounding of a large mean
+            const float h = ((v[0].x + v[0].y) + (v[0].z + v[0].w)) * 0.25f;
+            const float sh = __shfl(h, lane & 48, 64);
+#pragma unroll
+            for (int jj = 0; jj < NJ; ++jj) v[jj] = v[jj] - sh;
+        }
         float sum = 0.f;
 #pragma unroll
         for (int jj = 0; jj < NJ; ++jj) sum += (v[jj].x + v[jj].y) + (v[jj].z + v[jj].w);
@@ -1020,8 +1032,8 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
     float shift = 0.f, fsa = 0.f, fsb = 0.f;               // LN == 3: statistics about the row's first element
     if (LN == 3) {
         const float* r0 = a.A + (int64_t)min(i, a.M - 1) * a.lda;
-        if constexpr (NW == 16) {
-            // wide K: the shift is the mean of the row's first 32 elements (one 128-byte line, the same sum in every lane and
+        if constexpr (XSHIFT3) {
+            // wide K (and 640 / 768 / 896): the shift is the mean of the row's first 32 elements (one 128-byte line, the same sum in every lane and
             // wave of the row) and the PRODUCTS run on x - shift too: acc = (x - shift)·Wf, so the epilogue subtracts
             // (mean - shift)·c1, a fraction of the row's deviation, instead of cancelling mean·c1 against an acc of that size
             f32x4 h8[8];
@@ -1033,6 +1045,14 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
             shift = hs * (1.f / 32.f);
         } else {
             shift = r0[0];
+        }
+    }
+    float shift2[MT];                                       // LN == 2 at 640 / 768 / 896: the mean of the row's first four elements
+    if constexpr (LN == 2 && BASE_K) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const f32x4 h4 = ld4(a.A + (int64_t)min(mt * 16 + i, a.M - 1) * a.lda);
+            shift2[mt] = ((h4.x + h4.y) + (h4.z + h4.w)) * 0.25f;
         }
     }
     issue(0);
@@ -1098,8 +1118,14 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
                 const f32x4 t = xf[c][0] - shift;
                 fsa += (t.x + t.y) + (t.z + t.w);
                 fsb += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
-                if constexpr (NW == 16) xf[c][0] = t;
+                if constexpr (XSHIFT3) xf[c][0] = t;
             }
+        }
+        if constexpr (LN == 2 && BASE_K) {
+#pragma unroll
+            for (int c = 0; c < PW; ++c)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) xf[c][mt] = xf[c][mt] - shift2[mt];
         }
 #pragma unroll
         for (int c = 0; c < PW; ++c) {
@@ -1145,11 +1171,11 @@ __device__ __forceinline__ void skinny_body(GemmArgs a, LnFuse ln, const HeadSte
             // log2(129) = 7 bits, never all of them.  The fmaxf only meets a CONSTANT row
             // (every term exactly 0) and rounding of a variance below eps; it cannot hide a cancellation.
             const float var = fmaxf(sb / (float)a.K - dm * dm, 0.f);
-            sacc = (sacc - (NW == 16 ? dm : shift + dm) * e_c1) * rsqrtf(var + ln.eps);
+            sacc = (sacc - (XSHIFT3 ? dm : shift + dm) * e_c1) * rsqrtf(var + ln.eps);
             if (IS_QKV(EPI)) sacc += e_bias;
         }
         if (LN == 2 && fin) {                // statistics were published before the barrier above
-            const float mu = s_mean[em], rs = s_rstd[em];
+            const float mu = s_mean[em], rs = s_rstd[em];   // (BASE_K: mean - shift2 of the row, as the products ran on x - shift2)
             sacc = (sacc - mu * e_c1) * rs;  // e_bias = c2 is added below
             if (IS_QKV(EPI)) sacc += e_bias;
         }
@@ -1462,7 +1488,9 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
         const bool fold = ln.c1 != nullptr;
         // one workgroup per (16 columns, 16 rows) instead of (16 columns, all rows): see the kernel
         // (the folded LayerNorm at K > 1024 is a one-row-tile kernel: every K of its set takes row groups)
-        const bool rowgroups = vh_tuning(VH_TUNE_ROW_GROUPS) != 2 && mt >= 2 && (!wide || a.K % 2048 == 0 || fold) &&
+        // (folded K = 896 above 32 rows: the row-resident MT = 4 form would spill, so those row counts take row groups whatever the knob says)
+        const bool no_mt4 = fold && a.K == 896 && mt >= 3;
+        const bool rowgroups = (vh_tuning(VH_TUNE_ROW_GROUPS) != 2 || no_mt4) && mt >= 2 && (!wide || a.K % 2048 == 0 || fold) &&
                                EPI != EPI_PARTIAL && (!IS_QKV(EPI) || a.T == 1);
         GemmArgs ag = a;                  // groups of 16 rows, or of 8 while that keeps the grid within the CUs
         if (rowgroups) {
@@ -1487,6 +1515,29 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
         else if (mt == 1) SF(1, NW, PW, LN, NJ);                               \
         else if (mt == 2) SF(2, NW, PW, LN, NJ);                               \
         else SF(4, NW, PW, LN, NJ);                                            \
+        VH_CHECK_LAUNCH(name);                                                 \
+        return VH_OK;                                                          \
+    } while (0)
+        // K in {640, 768, 896} = 128 PW, PW in 5..7: the folded forms at eight waves and ONE pass, fp32 weights only (no 16-bit-weight
+        // instantiation).  768 could also run PW 3 x 2 passes; the compiled counts decide: one pass holds 109 (LN = 3) / 250 (LN = 2,
+        // MT = 4) VGPRs, the two-pass form some 30 / 80 fewer, both without scratch and both one 512-thread workgroup per CU (256
+        // registers a wave), so the form with one memory round trip is taken.  PW = 7 at MT = 4 (xf alone is 112 registers) needs
+        // 80-88 bytes of scratch at 256 VGPRs: that pair is not built — more than 32 rows at K = 896 run as row groups (no_mt4
+        // above), and a QKV product with T > 1 of that size is refused (tools/check_isa.py check_base_folded).
+#define SFB(MT, PW, LN, NJ)                                                                                                      \
+    do {                                                                                                                        \
+        if (ag.w16) { vh_set_error("%s: no 16-bit-weight form of the folded LayerNorm at K=%d", name, a.K); return VH_EUNSUPPORTED; } \
+        hipLaunchKernelGGL((gemm_skinny_fast<MT, 8, EPI, PW, LN, NJ>), grid, dim3(512), 0, s, SKINNY_ARGS(ag), ag, ln);            \
+    } while (0)
+#define SFB_MT(PW, NJ)                                                         \
+    do {                                                                       \
+        if (rowgroups || mt == 1) SFB(1, PW, 2, NJ);                           \
+        else if (mt == 2) SFB(2, PW, 2, NJ);                                   \
+        else if constexpr ((PW) == 7) {                                        \
+            vh_set_error("%s: folded LayerNorm at K=%d serves more than 32 rows as row groups only (T == 1): the four-row-tile form " \
+                         "does not fit the register file", name, a.K);         \
+            return VH_EUNSUPPORTED;                                            \
+        } else SFB(4, PW, 2, NJ);                                              \
         VH_CHECK_LAUNCH(name);                                                 \
         return VH_OK;                                                          \
     } while (0)
@@ -1524,13 +1575,26 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
                 if (a.K == 512) SF3(8, 4);
                 if (a.K == 1024) SF3(8, 4);
 #undef SF3
+                if constexpr (EPI != EPI_QKV_HD) {          // K = 128 PW, PW in 5..7, one pass
+#define SFB3(PW) do { SFB(1, PW, 3, 1); VH_CHECK_LAUNCH(name); return VH_OK; } while (0)
+                    if (a.K == 640) SFB3(5);
+                    if (a.K == 768) SFB3(6);
+                    if (a.K == 896) SFB3(7);
+#undef SFB3
+                }
             }
             if (fold) {
                 if (a.K == 128) SF_MT(8, 1, 2, 2);
                 if (a.K == 256) SF_MT(8, 2, 2, 4);
                 if (a.K == 512) SF_MT(8, 4, 2, 8);
                 if (a.K == 1024) SF_MT(8, 4, 2, 16);
-                vh_set_error("%s: folded LayerNorm needs K in {128,256,512,1024} (K=%d)", name, a.K);
+                if constexpr (EPI != EPI_QKV_HD) {          // the row-resident forms of 640 / 768 / 896 (NJ = K / 64)
+                    if (a.K == 640) SFB_MT(5, 10);
+                    if (a.K == 768) SFB_MT(6, 12);
+                    if (a.K == 896) SFB_MT(7, 14);
+                }
+                vh_set_error("%s: folded LayerNorm needs K in {128,256,512,640,768,896,1024} at head width 64, {128,256,512,1024} at "
+                             "any other (K=%d)", name, a.K);
                 return VH_EUNSUPPORTED;
             }
             if (a.K == 128) SF_MT(8, 1, 1, 2);
@@ -1551,8 +1615,10 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
         }
 #undef SF_MT
 #undef SF
+#undef SFB_MT
+#undef SFB
         if constexpr (EPI == EPI_QKV16) {
-            vh_set_error("%s: bf16 K/V append needs the folded LayerNorm shapes (K in {128,256,512,1024})", name);
+            vh_set_error("%s: bf16 K/V append needs the folded LayerNorm shapes (K in {128,256,512,640,768,896,1024})", name);
             return VH_EUNSUPPORTED;
         } else {
         // ---- generic guarded kernel for every other K (multiple of 16)
@@ -1707,9 +1773,10 @@ extern "C" int vh_ln_fold(const float* W, const float* gamma, const float* beta,
 
 static int check_folded(const char* name, const GemmArgs& a, const LnFuse& ln) {
     VH_REQUIRE(ln.c1 && ln.c2, VH_EINVAL, "%s: null c1/c2", name);
-    const bool k_ok = a.K == 128 || a.K == 256 || a.K == 512 || a.K == 1024 || folded_wide_k(a.K);
+    const bool k_ok = a.K == 128 || a.K == 256 || a.K == 512 || a.K == 640 || a.K == 768 || a.K == 896 || a.K == 1024 ||
+                      folded_wide_k(a.K);
     VH_REQUIRE(a.M <= 64 && a.N % 16 == 0 && k_ok, VH_EUNSUPPORTED,
-               "%s: folded LayerNorm is the decode path: M <= 64, N %% 16 == 0, K in {128,256,512,1024} or a multiple of 256 "
+               "%s: folded LayerNorm is the decode path: M <= 64, N %% 16 == 0, K in {128,256,512,640,768,896,1024} or a multiple of 256 "
                "up to 2048 / of 512 up to 4096 (M=%d N=%d K=%d)", name, a.M, a.N, a.K);
     VH_REQUIRE(vh_aligned16(ln.c1) && vh_aligned16(ln.c2), VH_EALIGN, "%s: c1/c2 must be 16-byte aligned", name);
     return VH_OK;

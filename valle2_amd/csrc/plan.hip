@@ -213,7 +213,9 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
     // measured: +1.6 us per step at 12L/512d x 32 rows, but 1.2 us per LAYER slower at 24L/1024d x 8 rows (256 slices of
     // 16 columns, 8 MB of slabs: profiles/r3_ab_config5_ffn.log) — the default follows the measurements
     const int ffn_knob = vh_tuning(VH_TUNE_FFN_FUSED);
-    const bool ffn_fused = d.ffn_ws && ffn_knob != 1 && (d.d_model <= 512 || (ffn_knob == 2 && d.d_model <= 1024));
+    // (640 / 768 / 896 take it as 512 does: their unfused route is linear_1 + split-K linear_2 + reduce, one launch more)
+    const bool ffn_fused = d.ffn_ws && ffn_knob != 1 && (d.d_model <= 512 || d.d_model == 640 || d.d_model == 768 || d.d_model == 896 ||
+                                                        (ffn_knob == 2 && d.d_model <= 1024));
     // d_model > 1024 (width 64): the LayerNorm-in-the-operand-load GEMMs end at K = 1024.  Folded weights (d_model 1280 .. 2048 in steps of 256, 2560 .. 4096 in steps of 512)
     // run the wide folded GEMMs; without them the step normalises into d.attn — free before the attention writes it and again
     // once the out-projection has read it — and runs the plain GEMMs on that: two more launches per layer, any d_model % 64 == 0.

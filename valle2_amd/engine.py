@@ -121,15 +121,23 @@ MAX_DECODE_D_MODEL = 4096       # vh_layernorm (the prompt pass) and the wide fo
 WIDE_FOLD_MAX_ROWS = 16         # decode rows up to which a d_model > 1024 step takes the folded GEMMs (ArDecoder)
 
 
+BASE_FOLD_WIDTHS = (640, 768, 896)      # 10 / 12 / 14 heads of width 64: the folded chain of 512 at PW 5..7 (fp32 weights only)
+
+
+def ffn_fused_width(d: int) -> bool:
+    """d_model at which the decoder plan takes vh_ffn_decode by default (plan.hip decoder_enqueue)."""
+    return d <= 512 or d in BASE_FOLD_WIDTHS
+
+
 def folded_width(d: int) -> bool:
-    """K of the folded-LayerNorm decode GEMMs (gemm.hip check_folded): the four narrow shapes, or 256 PW passes with PW in 5..8 and one or
+    """K of the folded-LayerNorm decode GEMMs (gemm.hip check_folded): the four narrow shapes, 640 / 768 / 896, or 256 PW passes with PW in 5..8 and one or
     two passes — a multiple of 256 from 1280 to 2048, of 512 from 2560 to 4096 (16 waves, statistics from the operand fragments)."""
-    return d in (128, 256, 512, 1024) or (1024 < d <= MAX_DECODE_D_MODEL and d % (256 if d <= 2048 else 512) == 0)
+    return d in (128, 256, 512, 1024) or d in BASE_FOLD_WIDTHS or (1024 < d <= MAX_DECODE_D_MODEL and d % (256 if d <= 2048 else 512) == 0)
 
 
 def folded_layer_norms(transformer):
     """Per layer ((Wqkv∘γ1, c1, c2), (W1∘γ2, c1, c2)) for the decode step, or None when the shape is
-    outside the folded kernels (d_model not in {128,256,512,1024} and not one of 1280 .. 2048 in steps of 256 / 2560 .. 4096 in steps of 512) or the
+    outside the folded kernels (d_model not in {128,256,512,640,768,896,1024} and not one of 1280 .. 2048 in steps of 256 / 2560 .. 4096 in steps of 512) or the
     norms are adaptive.  Cached on the module and rebuilt when any of the source parameters changed (optimizer step, load)."""
     layers = list(transformer.layers)
     d = transformer.hparams.d_model
@@ -604,6 +612,8 @@ class ArDecoder:
         # (above 1024 the folded GEMMs are one-row-tile kernels: more than 16 rows run as row groups that each stream the
         # weights, and measured slower than LayerNorm + the plain GEMMs there — profiles/r7_wide_d_model.log)
         wide_unfolded = d > 1024 and batch > WIDE_FOLD_MAX_ROWS
+        # (640 / 768 / 896 are folded at head width 64 only: vh_linear_qkv_folded_hd has no form there, other widths keep the fused-LayerNorm GEMMs)
+        wide_unfolded = wide_unfolded or (hd != HEAD_DIM and d in BASE_FOLD_WIDTHS)
         self._folded = None if wide_unfolded else folded_layer_norms(model.transformer)   # kept alive: the table holds raw pointers
         self.ln_folded = self._folded is not None          # False above 1024: LayerNorm + plain GEMMs as separate launches
         self.kv_bf16 = cache.bf16
@@ -622,7 +632,7 @@ class ArDecoder:
         self._table = layer_table(model.transformer, cache, self._folded)
         # perf mode, second half: the step's four matrices (and the head) as h16 — half the weight bytes per launch
         self._w16 = self._proj16 = None
-        if self.kv_bf16 and DECODE_W16 and self.ffn_ws is not None and d <= 1024 and cfg.dim_feedforward % 16 == 0:
+        if self.kv_bf16 and DECODE_W16 and self.ffn_ws is not None and d in (128, 256, 512, 1024) and cfg.dim_feedforward % 16 == 0:
             self._w16 = decode_weights16(model.transformer, self._folded)
             for i, (wq, wo, w1, w2) in enumerate(self._w16):
                 self._table[i].wqkv_f16, self._table[i].wo16 = ptr(wq), ptr(wo)

@@ -21,7 +21,7 @@ from torch import optim
 
 from . import _lib, dropout, kernels
 from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, StepSampler, cached_decode_supported,
-                     group_prefix_cap, grouped_prompts_fit, perf_forward_supported,
+                     group_prefix_cap, grouped_prompts_fit, perf_forward_supported, ffn_fused_width,
                      shared_prompt_fits,
                      transformer_forward, transformer_forward_bf16)
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device, device_mirror
@@ -688,7 +688,7 @@ class ValleAR(_Base):
             t_host4 = time.perf_counter()
             _lib.raise_device_errors(dev)                 # ids that were already on the device: checked in-kernel
             self.last_generate_stats = {'steps_run': done, 'tokens_appended': n_new, 'n_split': dec.n_split,
-                                        'ffn_fused': dec.ffn_ws is not None and cfg.d_model <= 512, 'kv_bf16': dec.kv_bf16,
+                                        'ffn_fused': dec.ffn_ws is not None and ffn_fused_width(cfg.d_model), 'kv_bf16': dec.kv_bf16,
                                         'decode_w16': bool(getattr(dec, 'w16', False)),
                                         'ln_folded': bool(getattr(dec, 'ln_folded', False)),
                                         'head_fused': dec.head_ws is not None,
