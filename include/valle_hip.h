@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 133            /* 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 134            /* 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -357,6 +357,10 @@ int vh_attn_decode_shared(const float* q, int ldq, const float* kprefix, const f
  * wrote: the workspace needs no initialisation and may hold anything, as may every cache row beyond a length.  fp32,
  * deterministic (no atomics, fixed merge order).  beams == 1 (no sharing) and G == 1 are legal; for G == 1 the records and
  * their order are vh_attn_decode_shared's.  B <= 64, B % beams == 0.
+ * prefix_len[g] <= 0 PARKS group g (ABI 134; queued decoding keeps the rows of a group without an utterance in the launch):
+ * neither its prefix nor its suffix workgroups load anything or write a record, and the merge writes exactly 0.0 into its
+ * rows without reading a slot — no K/V bytes, and finite rows whatever the caches and the workspace hold.  For every group
+ * with prefix_len[g] >= 1 the records, their order and the output bits are what they were before.
  * partial: vh_attn_decode_shared_groups_ws_bytes() = B h (ceil(prefix_cap / 32) + n_split_suffix) records of 72 floats. */
 size_t vh_attn_decode_shared_groups_ws_bytes(int B, int n_heads, int prefix_cap, int n_split_suffix);
 int vh_attn_decode_shared_groups(const float* q, int ldq, const float* kprefix, const float* vprefix,
@@ -423,6 +427,41 @@ int vh_greedy_step(const float* logits, int ldl, int V, int eos, int64_t* codes,
                    int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base,
                    const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
                    float* x_next, int B, int d, void* stream);
+
+/* ---- queued decoding: poll and re-arm the groups of a decode launch (ABI 134) -------------------------------------------
+ * The B rows of a grouped decode (vh_attn_decode_shared_groups) are G = B / beams groups, group g the rows g * beams ..
+ * g * beams + beams - 1.  Between two replays of the captured step the host may hand a finished group's rows to another
+ * utterance: every per-row quantity the step reads (codes, cache_len, audio_pos, pos_base, prefix_lens) is a device array.
+ *
+ * vh_decode_groups_poll (one launch, one wave per group, plain stores, deterministic):
+ *   group_done[g]  = 1 when every beam's latest token codes[b][audio_pos[b] - 1] is eos, or when every beam has produced
+ *                    audio_pos[b] - pos_base[b] >= max_new tokens; else 0 (an audio_pos outside 1 .. codes_width reads nothing
+ *                    and counts as not finished);
+ *   group_steps[g] = max over the group's beams of audio_pos[b] - pos_base[b];
+ *   maxima[0..3]   = max cache_len and max audio_pos over ALL rows, then the same two over the rows of groups that are not
+ *                    done (-2^30 when there is none).  The host re-arms or parks every done group before it replays, so
+ *                    maxima[2] + n <= S_suf and maxima[3] + n <= codes_width bound the next n steps' K/V appends, token
+ *                    writes and positional rows; maxima[0..1] are the high-water marks.
+ * It replaces the eos_count[step] == B scan of the static schedule, which has no meaning once rows start at different steps.
+ *
+ * vh_decode_group_reset (one launch, one workgroup per row of the group):
+ *   prompt_len >= 1 (BOS + prompt_len - 1 first-codebook ids in `prompt`, a device array): for the group's rows
+ *     codes[b][0 .. codes_width) = BOS, prompt, then eos to the end; cache_len[b] = 0; audio_pos[b] = pos_base[b] =
+ *     prompt_len; sum_logprobs[b] = 0; prefix_lens[group] = prefix_len (the keys of the group's region of the prefix cache:
+ *     text + BOS + prompt, >= prompt_len).  The row's first sample (vh_greedy_step / vh_sample_step on the group's rows) then
+ *     writes codes[b][prompt_len]; hand it a scratch counter in place of cache_len — the first sample appends no K/V row, and
+ *     cache_len[b] = 0 is where the first replayed step appends.
+ *   prompt_len == 0 parks the group: prefix_lens[group] = 0 (see vh_attn_decode_shared_groups) and for its rows
+ *     codes[b][pos_base[b]] = eos, audio_pos[b] = pos_base[b] + 1, cache_len[b] = 0 — the state of a fresh row whose first
+ *     token was EOS.  Nothing else of codes is touched: every further step finds EOS at audio_pos - 1 and writes EOS at
+ *     audio_pos.  Called again at every poll it rewinds the rows, so a parked row never moves more than the steps between two
+ *     polls from its base.  sum_logprobs is left as it is.  (A pos_base outside 1 .. codes_width - 2 is pulled into it.) */
+int vh_decode_groups_poll(const int64_t* codes, int64_t codes_stride, int codes_width, const int32_t* cache_len,
+                          const int32_t* audio_pos, const int32_t* pos_base, int eos, int B, int beams, int max_new,
+                          int32_t* group_done, int32_t* group_steps, int32_t* maxima, void* stream);
+int vh_decode_group_reset(int64_t* codes, int64_t codes_stride, int codes_width, const int64_t* prompt, int prompt_len,
+                          int prefix_len, int bos, int eos, int group, int B, int beams, int32_t* cache_len,
+                          int32_t* audio_pos, int32_t* pos_base, float* sum_logprobs, int32_t* prefix_lens, void* stream);
 
 /* ---- K11 + K12/K13 in ONE launch (opt-in; DESIGN.md 3.20 has the A/B) -----------------------------
  * logits[b,:V] = x[b,:] . proj_w^T (the head: no bias, valle_ar.py:29,158) and, in the same launch, everything

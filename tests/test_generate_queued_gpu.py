@@ -1,0 +1,385 @@
+"""Queued decoding on the GPU: the poll and reset kernels element by element, parked groups in
+vh_attn_decode_shared_groups (exact zeros, nothing read, the live groups' bits unchanged), and ValleAR.generate_queued
+against the CPU oracle, generate_many and engine.plan_queue — refills, draining with parked groups, decoder reuse, sampling,
+and codec_io.synthesize_queued."""
+import pytest
+import torch
+
+from tests.golden import cases as C
+from tests.oracle_runners import load_golden
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+MARGIN = 1e-4
+POLL = 32
+EOS, BOS = 1024, 1025
+
+
+def _i32(x):
+    return torch.tensor(x, dtype=torch.int32)
+
+
+# ---- vh_decode_groups_poll ----------------------------------------------------------------------------------------------
+def test_poll_kernel_flags_steps_and_maxima():
+    from valle2_amd import kernels as K
+    G, beams, width, max_new = 5, 3, 40, 10
+    B = G * beams
+    gen = torch.Generator().manual_seed(5)
+    codes = torch.randint(0, EOS, (B, width), generator=gen)                 # no EOS anywhere unless placed below
+    pos_base = _i32([4 + (5 * b) % 7 for b in range(B)])
+    for g in range(G):
+        pos_base[g * beams:(g + 1) * beams] = pos_base[g * beams]            # the beams of a group share their prompt
+    steps = _i32([4, 4, 4, 6, 6, 6, 10, 10, 10, 1, 1, 1, 7, 7, 7])            # tokens produced so far, per row
+    audio_pos = pos_base + steps
+    cache_len = steps - 1
+    for b in (0, 1, 2, 3, 5):                                                # group 0: all beams at EOS; group 1: beam 4 is not
+        codes[b, int(audio_pos[b]) - 1] = EOS
+    # group 2: at max_new without EOS; group 3: fresh; group 4: parked below and rewound to the fresh state
+    dev = lambda t: t.to(DEV)
+    codes_d, cl_d, ap_d, pb_d = dev(codes), dev(cache_len), dev(audio_pos), dev(pos_base)
+    slp = torch.arange(B, dtype=torch.float32, device=DEV)
+    plens = _i32([9, 9, 9, 9, 9]).to(DEV)
+    K.decode_group_reset(codes_d, 4, beams, None, 0, BOS, EOS, cl_d, ap_d, pb_d, slp, plens)
+    # the reference, in torch on the CPU, from the arrays as the poll finds them
+    c, cl, ap, pb = codes_d.cpu(), cl_d.cpu(), ap_d.cpu(), pb_d.cpu()
+    assert ap[12:].tolist() == (pb[12:] + 1).tolist() and cl[12:].tolist() == [0, 0, 0] and plens.cpu().tolist() == [9, 9, 9, 9, 0]
+    want_done, want_steps, live = [], [], []
+    for g in range(G):
+        rows = range(g * beams, (g + 1) * beams)
+        at_eos = all(int(c[b, int(ap[b]) - 1]) == EOS for b in rows)
+        capped = all(int(ap[b] - pb[b]) >= max_new for b in rows)
+        want_done.append(int(at_eos or capped))
+        want_steps.append(max(int(ap[b] - pb[b]) for b in rows))
+        if not want_done[-1]:
+            live += list(rows)
+    assert want_done == [1, 0, 1, 0, 1] and want_steps == [4, 6, 10, 1, 1]
+    want_max = [int(cl.max()), int(ap.max()), int(cl[live].max()), int(ap[live].max())]
+    outs = []
+    for _ in range(2):
+        out = torch.full((4 + 2 * G,), -7, dtype=torch.int32, device=DEV)
+        K.decode_groups_poll(codes_d, cl_d, ap_d, pb_d, EOS, beams, max_new, out)
+        outs.append(out.cpu())
+    got = outs[0].tolist()
+    assert got[:4] == want_max and got[4:4 + G] == want_done and got[4 + G:] == want_steps, (got, want_max, want_done, want_steps)
+    assert torch.equal(outs[0], outs[1])
+    assert torch.equal(codes_d.cpu(), c) and torch.equal(ap_d.cpu(), ap)     # the poll writes nothing but its outputs
+    # every group done: the maxima over the rows that step on are "none"
+    K.decode_groups_poll(codes_d, cl_d, ap_d, pb_d, EOS, beams, 1, out)
+    assert out.cpu().tolist()[2:4] == [K.POLL_NONE, K.POLL_NONE] and out.cpu().tolist()[4:4 + G] == [1] * G
+
+
+# ---- vh_decode_group_reset ----------------------------------------------------------------------------------------------
+def _reset_state(G, beams, width, seed):
+    gen = torch.Generator().manual_seed(seed)
+    B = G * beams
+    return dict(codes=torch.randint(0, EOS, (B, width), generator=gen), cache_len=torch.randint(1, 30, (B,), generator=gen).int(),
+                audio_pos=torch.randint(9, 17, (B,), generator=gen).int(), pos_base=torch.randint(3, 8, (B,), generator=gen).int(),
+                slp=-torch.rand(B, generator=gen) - 0.5, plens=torch.randint(20, 90, (G,), generator=gen).int())
+
+
+def _run_reset(st, g, beams, prompt, prefix_len):
+    from valle2_amd import kernels as K
+    d = {k: v.to(DEV) for k, v in st.items()}
+    K.decode_group_reset(d['codes'], g, beams, None if prompt is None else prompt.to(DEV), prefix_len, BOS, EOS, d['cache_len'],
+                         d['audio_pos'], d['pos_base'], d['slp'], d['plens'])
+    return {k: v.cpu() for k, v in d.items()}
+
+
+def test_reset_kernel_rearms_one_group_and_touches_nothing_else():
+    G, beams, width = 3, 2, 21
+    st = _reset_state(G, beams, width, seed=11)
+    prompt = torch.tensor([17, 1023, 0, 512])                                # BOS + 4 ids: prompt_len 5
+    got = _run_reset(st, 1, beams, prompt, 23)
+    want = {k: v.clone() for k, v in st.items()}
+    for b in (2, 3):
+        want['codes'][b] = EOS
+        want['codes'][b, 0] = BOS
+        want['codes'][b, 1:5] = prompt
+        want['cache_len'][b], want['audio_pos'][b], want['pos_base'][b], want['slp'][b] = 0, 5, 5, 0.0
+    want['plens'][1] = 23
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
+    # BOS alone (an empty prompt) is legal: prompt_len 1
+    got = _run_reset(st, 2, beams, torch.empty(0, dtype=torch.int64), 9)
+    assert got['codes'][4].tolist() == [BOS] + [EOS] * (width - 1) and got['audio_pos'][4:].tolist() == [1, 1]
+    assert torch.equal(got['codes'][:4], st['codes'][:4]) and got['plens'].tolist() == st['plens'].tolist()[:2] + [9]
+
+
+def test_reset_kernel_parks_one_group_and_touches_nothing_else():
+    G, beams, width = 3, 2, 21
+    st = _reset_state(G, beams, width, seed=12)
+    got = _run_reset(st, 1, beams, None, 0)
+    want = {k: v.clone() for k, v in st.items()}
+    for b in (2, 3):
+        p = int(st['pos_base'][b])
+        want['codes'][b, p] = EOS                                            # where the row's first generated token stood
+        want['audio_pos'][b], want['cache_len'][b] = p + 1, 0
+    want['plens'][1] = 0
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
+
+
+# ---- parked groups in vh_attn_decode_shared_groups -------------------------------------------------------------------------
+def _parked_case(G, beams, h, plens, seed):
+    """KERNEL_CASES-style inputs: NaN (K) / Inf (V) beyond every length and in a parked group's WHOLE prefix and suffix, and
+    the float64 reference of the live rows."""
+    B, d, S_suf = G * beams, 64 * h, 96
+    cap = max(max(plens), 1)
+    prefix_S = (cap + 31) // 32 * 32 + 32
+    gen = torch.Generator().manual_seed(seed)
+    q = torch.randn(B, d, generator=gen)
+    kp, vp = torch.randn(G, h, prefix_S, 64, generator=gen), torch.randn(G, h, prefix_S, 64, generator=gen)
+    ks, vs = torch.randn(B, h, S_suf, 64, generator=gen), torch.randn(B, h, S_suf, 64, generator=gen)
+    slen = _i32([(7 * i) % 90 for i in range(B)])
+    ref = torch.zeros(B, d, dtype=torch.float64)
+    for b in range(B):
+        n, grp = int(slen[b]) + 1, b // beams
+        if plens[grp] == 0:
+            n = 0
+        else:
+            kk = torch.cat([kp[grp, :, :plens[grp]], ks[b, :, :n]], dim=1).double()
+            vv = torch.cat([vp[grp, :, :plens[grp]], vs[b, :, :n]], dim=1).double()
+            s = (q[b].double().view(h, 1, 64) @ kk.transpose(-1, -2)) / 8.0
+            ref[b] = (torch.softmax(s, dim=-1) @ vv).reshape(d)
+        ks[b, :, n:] = float('nan')
+        vs[b, :, n:] = float('inf')
+    for grp in range(G):
+        kp[grp, :, plens[grp]:] = float('nan')
+        vp[grp, :, plens[grp]:] = float('inf')
+    return cap, [t.to(DEV) for t in (q, kp, vp, ks, vs, slen)], ref
+
+
+def _attend(K, q, kp, vp, plens, cap, ks, vs, slen, beams, n_split):
+    B, h = q.shape[0], ks.shape[1]
+    ws = K.attn_decode_shared_groups_ws(B, h, cap, n_split, DEV).fill_(float('nan'))
+    out = torch.full((B, 64 * h), float('nan'), device=DEV)
+    K.attn_decode_shared_groups(q, kp, vp, _i32(plens).to(DEV), cap, ks, vs, out, slen, 1, beams, n_split=n_split, partial=ws)
+    return out
+
+
+@pytest.mark.parametrize('beams,n_split', [(4, 1), (4, 2), (33, 2)], ids=['split1', 'split2', 'second_lane_pass'])
+def test_parked_group_reads_nothing_and_its_rows_are_zero(beams, n_split):
+    from valle2_amd import kernels as K
+    G, h, plens = 3, 2, [33, 0, 100]
+    cap, (q, kp, vp, ks, vs, slen), ref = _parked_case(G, beams, h, plens, seed=2024 + beams)
+    out = _attend(K, q, kp, vp, plens, cap, ks, vs, slen, beams, n_split)
+    parked = slice(beams, 2 * beams)
+    live = torch.cat([torch.arange(0, beams), torch.arange(2 * beams, 3 * beams)]).to(DEV)
+    assert bool((out[parked] == 0.0).all()) and not bool(torch.signbit(out[parked]).any()), 'parked rows must be exactly +0.0'
+    assert bool(torch.isfinite(out).all()), 'garbage of the parked group or beyond a length leaked into the output'
+    err = (out.cpu().double() - ref).abs().max().item()
+    print(f'beams={beams} n_split={n_split}: max |err| vs float64 = {err:.3e}')
+    torch.testing.assert_close(out.cpu().double(), ref, atol=2e-5, rtol=0)
+    # the live groups alone: the same records merged in the same order
+    two = [0, 2]
+    alone = _attend(K, q[live].contiguous(), kp[two].contiguous(), vp[two].contiguous(), [plens[0], plens[2]], cap,
+                    ks[live].contiguous(), vs[live].contiguous(), slen[live].contiguous(), beams, n_split)
+    assert torch.equal(out[live], alone)
+    assert torch.equal(out, _attend(K, q, kp, vp, plens, cap, ks, vs, slen, beams, n_split)), 'deterministic'
+
+
+def test_all_groups_parked_gives_all_zeros():
+    from valle2_amd import kernels as K
+    cap, (q, kp, vp, ks, vs, slen), _ = _parked_case(3, 4, 2, [0, 0, 0], seed=77)
+    out = _attend(K, q, kp, vp, [0, 0, 0], kp.shape[2], ks, vs, slen, 4, 2)
+    assert bool((out == 0.0).all())
+
+
+# ---- model --------------------------------------------------------------------------------------------------------------
+def _build(kw, sd):
+    from valle2_amd import get_model_class
+    m = get_model_class('ValleAR')(C.cfg_of(kw))
+    m.load_state_dict(sd)
+    return m.to(DEV).eval()
+
+
+def _same_up_to_a_near_tie(got, want, margins):
+    """Token for token, except from a step whose oracle top-2 margin is below 1e-4 (a near-tie may fall either way and
+    everything after it follows).  Returns whether a near-tie had to excuse a difference."""
+    got, want = got.cpu(), want.cpu()
+    n = min(len(got), len(want))
+    bad = (got[:n] != want[:n]).nonzero()
+    if bad.numel() == 0:
+        assert len(got) == len(want), (got, want)
+        return False
+    assert float(margins[int(bad[0])]) < MARGIN, (int(bad[0]), float(margins[int(bad[0])]), got, want)
+    return True
+
+
+# (text tokens, target tokens, prompt frames, seed): on the planted-EOS model below the oracle stops these after
+# 24, 69, 18, 23, 74, 17 steps (SIX) and 22, 16, 21 (MORE) — asserted in the fixture
+SIX = [(9, 10, 17, 1301), (12, 12, 61, 1305), (5, 13, 23, 1307), (13, 9, 18, 1312), (20, 8, 56, 1310), (9, 12, 24, 1318)]
+MORE = [(17, 8, 19, 1323), (13, 11, 25, 1329), (4, 7, 20, 1334)]
+
+
+@pytest.fixture(scope='module')
+def queue():
+    """The greedy AR_TINY-sized model of test_eos_one_utterance_stops_early_beside_one_that_does_not (a planted EOS row in
+    the head), max_audio_len 96, nine utterances under one prefix capacity, the oracle's tokens + margins (CPU, once)."""
+    from oracle import valle_oracle as O
+    from valle2_amd import engine, synth
+    gold = load_golden('ar_generate_eos')
+    kw, sd, _ = C.ar_eos_inputs(gold['eos_row'])
+    kw = dict(kw, num_beams=3, max_audio_len=96)
+    cfg = C.cfg_of(kw)
+    utts = [synth.synth_utterance(cfg, a, b, f, seed=s) for a, b, f, s in SIX + MORE]
+    refs = []
+    for u in utts:
+        trace = {}
+        refs.append((O.ar_generate(sd, C.cfg_of(dict(kw, num_beams=1)), *u, trace=trace), trace['margin']))
+    lengths = [min(len(t) + 1, cfg.max_audio_len) for t, _ in refs]          # steps up to and including EOS
+    assert sum(n < 32 for n in lengths[:6]) >= 2 and sum(n >= 64 for n in lengths[:6]) >= 2, f'inputs drifted: {lengths}'
+    assert all(float(torch.as_tensor(m).min()) >= MARGIN for _, m in refs[:6]), 'inputs drifted: a near-tie among the six'
+    ctx = [len(u[0]) + len(u[2]) + u[1].shape[0] + 1 for u in utts]
+    assert len({engine.group_prefix_cap(c) for c in ctx}) == 1
+    return kw, sd, [tuple(t.to(DEV) for t in u) for u in utts], refs, lengths
+
+
+def _check_six(outs, refs):
+    excused = sum(_same_up_to_a_near_tie(o, *r) for o, r in zip(outs, refs))
+    assert excused == 0, 'the six were chosen with every oracle margin >= 1e-4: nothing to excuse'
+
+
+@pytest.fixture(scope='module')
+def six_on_two_slots(queue):
+    kw, sd, utts, refs, lengths = queue
+    m = _build(kw, sd)
+    outs = m.generate_queued(utts[:6], beams=3, slots=2)
+    return m, outs, dict(m.last_generate_stats)
+
+
+def test_tokens_refills_and_steps_follow_the_plan(queue, six_on_two_slots):
+    from valle2_amd import engine
+    kw, sd, utts, refs, lengths = queue
+    m, outs, st = six_on_two_slots
+    assert len(outs) == 6 and all(o.dim() == 1 and o.dtype == torch.int64 for o in outs)
+    _check_six(outs, refs[:6])
+    assert st['queued'] is True and st['slots'] == 2 and st['beams'] == 3 and st['decoder_reused'] is False
+    assert st['refills'] == 4
+    iv, total = engine.plan_queue(lengths[:6], 2, POLL, 96)
+    print('lengths', lengths[:6], 'plan', iv, total, 'stats', {k: st[k] for k in ('steps', 'polls', 'refills', 'parked_group_steps',
+                                                                              'max_cache_len', 'max_audio_pos', 's_suf', 'codes_width')})
+    assert st['steps'] == total and st['polls'] == total // POLL and st['intervals'] == iv
+    assert st['steps'] < engine.chunk_schedule_steps(lengths[:6], 2, POLL, 96)
+    assert 0 < st['max_cache_len'] <= st['s_suf'] and 0 < st['max_audio_pos'] < st['codes_width']
+    assert st['sum_logprobs'].shape == (18,) and len(st['prompt_lens']) == 18
+
+
+def test_generate_many_gives_the_same_lists(queue, six_on_two_slots):
+    kw, sd, utts, refs, lengths = queue
+    _, outs, _ = six_on_two_slots
+    many = _build(kw, sd).generate_many(utts[:6], beams=3)
+    assert len(many) == 6
+    for a, b in zip(outs, many):
+        assert torch.equal(a, b)
+
+
+def test_eager_steps_give_the_graph_replays_tokens(queue, six_on_two_slots):
+    kw, sd, utts, refs, lengths = queue
+    _, outs, st = six_on_two_slots
+    m = _build(kw, sd)
+    eager = m._generate_queued(utts[:6], 3, 2, use_graph=False)
+    assert m.last_generate_stats['steps'] == st['steps'] and m.last_generate_stats['refills'] == 4
+    for a, b in zip(outs, eager):
+        assert torch.equal(a, b)
+
+
+def test_draining_parks_groups_and_saved_rows_are_unaffected(queue, six_on_two_slots):
+    from valle2_amd import engine
+    kw, sd, utts, refs, lengths = queue
+    _, outs2, _ = six_on_two_slots
+    m = _build(kw, sd)
+    outs = m.generate_queued(utts[:5], beams=3, slots=4)
+    st = m.last_generate_stats
+    iv, total = engine.plan_queue(lengths[:5], 4, POLL, 96)
+    assert st['refills'] == 1 and st['steps'] == total and st['intervals'] == iv
+    # three groups end up parked while the longest finishes: every block a slot spends without an utterance
+    want_parked = sum(total - POLL * max(e for s, _, e in iv if s == slot) for slot in range(4))
+    assert st['parked_group_steps'] == want_parked > 0
+    assert sum(1 for slot in range(4) if max(e for s, _, e in iv if s == slot) < total // POLL) == 3
+    _check_six(outs, refs[:5])
+    for a, b in zip(outs, outs2[:5]):                                        # as the run on two slots, parked cycling or not
+        assert torch.equal(a, b)
+    assert st['max_cache_len'] <= st['s_suf'] and st['max_audio_pos'] < st['codes_width']
+
+
+def test_second_call_reuses_the_decoder_and_generate_many_keeps_its_own(queue):
+    kw, sd, utts, refs, lengths = queue
+    m = _build(kw, sd)
+    m.generate_queued(utts[:3], beams=3, slots=2)
+    assert m.last_generate_stats['decoder_reused'] is False
+    dec = [s.dec for s in m._decode_slots.values()]
+    assert len(dec) == 1 and dec[0]._captured
+    many = m.generate_many(utts[6:8], beams=3)                               # two groups as well: a slot of its own
+    assert m.last_generate_stats['decoder_reused'] is False and len(m._decode_slots) == 2
+    outs = m.generate_queued(utts[6:9], beams=3, slots=2)                    # other utterances, the same capacity and shape
+    st = m.last_generate_stats
+    assert st['decoder_reused'] is True and st['slot_uses'] == 2 and st['refills'] == 1
+    assert any(s.dec is dec[0] for s in m._decode_slots.values()) and len(m._decode_slots) == 2, 'nothing was built or captured'
+    for o, r in zip(outs, refs[6:9]):
+        _same_up_to_a_near_tie(o, *r)
+    for a, b in zip(outs[:2], many):
+        assert torch.equal(a, b)
+    m.generate_many(utts[6:8], beams=3)
+    assert m.last_generate_stats['decoder_reused'] is True and not m.last_generate_stats.get('queued', False)
+
+
+def test_one_utterance_and_more_slots_than_utterances(queue):
+    kw, sd, utts, refs, lengths = queue
+    m = _build(kw, sd)
+    one = m.generate_queued(utts[1:2], beams=3)
+    assert len(one) == 1 and m.last_generate_stats['slots'] == 1 and m.last_generate_stats['refills'] == 0
+    assert torch.equal(one[0], m.generate_many(utts[1:2], beams=3)[0])
+    three = m.generate_queued(utts[:3], beams=3, slots=8)
+    st = m.last_generate_stats
+    assert st['slots'] == 3 and st['refills'] == 0 and st['queued'] is True
+    for a, b in zip(three, m.generate_many(utts[:3], beams=3)):
+        assert torch.equal(a, b)
+
+
+def test_sampling_repeats_under_a_seed_and_graph_equals_eager():
+    from valle2_amd import synth
+    kw = dict(C.AR_TINY, top_k=50, num_beams=4, max_audio_len=40)             # 40: rows reach max_new INSIDE a block
+    cfg = C.cfg_of(kw)
+    sd = synth.silence_eos(synth.make_state_dict(cfg, 'ValleAR', seed=31, rich=True), cfg)
+    utts = [tuple(t.to(DEV) for t in synth.synth_utterance(cfg, 6 + 3 * i, 5 + 2 * i, 20 + 23 * i, seed=700 + i)) for i in range(3)]
+    m = _build(kw, sd)
+    runs = []
+    for use_graph in (True, False, True):
+        torch.manual_seed(4321)
+        outs = m._generate_queued(utts, 4, 2, use_graph=use_graph)
+        st = m.last_generate_stats
+        runs.append(([o.cpu() for o in outs], st['sum_logprobs'].cpu()))
+        assert st['refills'] == 1 and st['queued'] is True
+    outs, scores = runs[0]
+    assert scores.shape == (12,) and bool((scores < 0).all())
+    for other, other_scores in runs[1:]:                                     # eager = graph; the same seed again = the same draw
+        assert all(torch.equal(a, b) for a, b in zip(outs, other)) and torch.equal(scores, other_scores)
+    for g in range(3):
+        assert len({float(x) for x in scores[4 * g:4 * g + 4]}) > 1, 'sampled beams of a group must differ'
+    torch.manual_seed(99)
+    assert not torch.equal(m.generate_queued(utts, beams=4, slots=2)[0].cpu(), outs[0]) or \
+        not torch.equal(m.last_generate_stats['sum_logprobs'].cpu(), scores)
+
+
+def test_synthesize_queued_equals_synthesize_many():
+    from valle2_amd import ConfigValle, codec_io as CIO, get_model_class, synth
+    base = dict(d_model=128, n_heads=2, dim_feedforward=256, num_layers=2, dropout=0.0)
+    ar_cfg = ConfigValle(**base, norm='LayerNorm', num_beams=2, top_k=1, max_audio_len=12)
+    nar_cfg = ConfigValle(**base, norm='AdaptiveLayerNorm')
+    ar = get_model_class('ValleAR')(ar_cfg)
+    ar.load_state_dict(synth.silence_eos(synth.make_state_dict(ar_cfg, 'ValleAR', seed=1), ar_cfg))
+    nar = get_model_class('ValleNAR')(nar_cfg)
+    nar.load_state_dict(synth.make_state_dict(nar_cfg, 'ValleNAR', seed=2))
+    ar, nar = ar.to(DEV).eval(), nar.to(DEV).eval()
+    items = []
+    for i in range(2):
+        pt, pc, tt = synth.synth_utterance(ar_cfg, 5 + 2 * i, 7 - i, 9 + 6 * i, seed=60 + i)
+        items.append((pt.to(DEV), pc.T.contiguous().to(DEV), tt.to(DEV)))          # codec layout (Q, T)
+    many = CIO.synthesize_many(ar, nar, items, greedy_nar=True)
+    for slots in (None, 1):
+        queued = CIO.synthesize_queued(ar, nar, items, greedy_nar=True, slots=slots)
+        assert ar.last_generate_stats['queued'] is True and ar.last_generate_stats['slots'] == (2 if slots is None else 1)
+        assert len(queued) == 2
+        for a, b in zip(queued, many):
+            assert torch.equal(a, b)

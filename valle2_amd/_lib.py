@@ -169,6 +169,11 @@ SIGNATURES = {
     'vh_greedy_step': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_i64p, C.c_int64, c_i32p,
                                  c_i32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int,
                                  C.c_void_p]),
+    # queued decoding: poll and re-arm the groups of a decode launch (ABI 134)
+    'vh_decode_groups_poll': (C.c_int, [c_i64p, C.c_int64, C.c_int, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        c_i32p, c_i32p, c_i32p, C.c_void_p]),
+    'vh_decode_group_reset': (C.c_int, [c_i64p, C.c_int64, C.c_int, c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, c_i32p, c_i32p, c_i32p, c_f32p, c_i32p, C.c_void_p]),
     'vh_head_greedy_ws_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'vh_head_greedy': (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_i64p, C.c_int64, c_i32p,
                                  c_i32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,

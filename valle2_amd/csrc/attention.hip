@@ -1890,6 +1890,11 @@ __device__ __forceinline__ void attn_shared_body(const SharedArgs& a) {
     const int unit = blockIdx.x - a.prefix_wgs;
     const int split = unit % a.n_split, bh = unit / a.n_split;
     const int b = bh / a.n_heads, head = bh - b * a.n_heads;
+    // a parked group (prefix length <= 0): its rows attend nothing — no load of q, K or V, no record (workgroup-uniform,
+    // before the barrier below; the merge writes the rows' zeros without reading a slot)
+    if constexpr (GROUPS) {
+        if (a.group_len[b / a.beams] <= 0) return;
+    }
     const int c16 = lane & 15, g = lane >> 4;
     const int len = a.suffix_len[b] + a.len_bias;
     const int nchunks = (len + 31) >> 5;
@@ -2036,8 +2041,15 @@ __global__ __launch_bounds__(256) void attn_records_merge_groups_kernel(const fl
                                                                         int ldo, int n_heads, int n_pb, int n_split,
                                                                         const int32_t* __restrict__ group_len, int beams) {
     const int b = blockIdx.x / n_heads;
-    const int n_first = min((max(group_len[b / beams], 0) + 31) >> 5, n_pb);     // the prefix records this row's group wrote
-                                                                                  // (cut at the capacity as the prefix role cuts)
+    const int glen = group_len[b / beams];
+    if (glen <= 0) {
+        // a parked group wrote no record at all: exactly 0.0 for its rows and no slot read (records_merge_body would divide
+        // by a denominator built from slots nobody wrote)
+        if (threadIdx.x < HD) out[(int64_t)b * ldo + (blockIdx.x - b * n_heads) * HD + threadIdx.x] = 0.f;
+        return;
+    }
+    const int n_first = min((glen + 31) >> 5, n_pb);         // the prefix records this row's group wrote (cut at the capacity
+                                                             // as the prefix role cuts)
     records_merge_body(partial, out, ldo, n_heads, n_first + n_split, n_pb + n_split, n_first);
 }
 

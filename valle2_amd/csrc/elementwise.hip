@@ -1014,3 +1014,147 @@ extern "C" int vh_categorical_rows(const float* logits, int ld, int V, int rows,
     VH_CHECK_LAUNCH("vh_categorical_rows");
     return VH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Queued decoding (ValleAR.generate_queued): the rows of a decode launch are G = B / beams groups, each group the beams of
+// one utterance, and a group that has finished hands its rows to a waiting utterance while the others keep stepping.
+//   decode_groups_poll_kernel   what the host needs to know at a poll, in one launch and one small read: per group whether it
+//                               is done and how many tokens it has produced, and the largest cache_len / audio_pos — over
+//                               all rows (the high-water marks) and over the rows of groups that are NOT done (the rows that
+//                               step on from where they stand: what the host bounds before it replays).
+//   decode_group_reset_kernel   re-arms the rows of one group for a new utterance, or parks them.
+// Plain loads and stores, no atomics: the same state gives the same bits.
+// ---------------------------------------------------------------------------------------------
+#define POLL_NONE (-(1 << 30))     // a maximum over no rows
+
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// One workgroup of four waves; wave w takes groups w, w + 4, ... (a group is never split over waves), its lanes the beams.
+__global__ __launch_bounds__(256) void decode_groups_poll_kernel(
+    const int64_t* __restrict__ codes, int64_t codes_stride, int codes_width, const int32_t* __restrict__ cache_len,
+    const int32_t* __restrict__ audio_pos, const int32_t* __restrict__ pos_base, int eos, int n_groups, int beams,
+    int max_new, int32_t* __restrict__ group_done, int32_t* __restrict__ group_steps, int32_t* __restrict__ maxima) {
+    __shared__ int s_max[4][4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int m_cl = POLL_NONE, m_ap = POLL_NONE, live_cl = POLL_NONE, live_ap = POLL_NONE;
+    for (int g = w; g < n_groups; g += 4) {                  // wave-uniform trip count
+        int not_eos = 0, steps_min = 0x7fffffff, steps_max = POLL_NONE, cl = POLL_NONE, ap = POLL_NONE;
+        for (int j = lane; j < beams; j += 64) {
+            const int b = g * beams + j;
+            const int pos = audio_pos[b], steps = pos - pos_base[b];
+            // the latest token; a position outside the row reads nothing and counts as "not finished"
+            const bool at_eos = pos >= 1 && pos <= codes_width && codes[(int64_t)b * codes_stride + pos - 1] == (int64_t)eos;
+            not_eos |= at_eos ? 0 : 1;
+            steps_min = min(steps_min, steps);
+            steps_max = max(steps_max, steps);
+            cl = max(cl, cache_len[b]);
+            ap = max(ap, pos);
+        }
+        not_eos = wave_max_i32(not_eos);
+        steps_min = -wave_max_i32(-steps_min);
+        steps_max = wave_max_i32(steps_max);
+        cl = wave_max_i32(cl);
+        ap = wave_max_i32(ap);
+        const int done = (!not_eos || steps_min >= max_new) ? 1 : 0;
+        if (lane == 0) {
+            group_done[g] = done;
+            group_steps[g] = steps_max;
+        }
+        m_cl = max(m_cl, cl);
+        m_ap = max(m_ap, ap);
+        if (!done) {
+            live_cl = max(live_cl, cl);
+            live_ap = max(live_ap, ap);
+        }
+    }
+    if (lane == 0) { s_max[w][0] = m_cl; s_max[w][1] = m_ap; s_max[w][2] = live_cl; s_max[w][3] = live_ap; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        maxima[k] = max(max(s_max[0][k], s_max[1][k]), max(s_max[2][k], s_max[3][k]));
+    }
+}
+
+extern "C" int vh_decode_groups_poll(const int64_t* codes, int64_t codes_stride, int codes_width, const int32_t* cache_len,
+                                     const int32_t* audio_pos, const int32_t* pos_base, int eos, int B, int beams, int max_new,
+                                     int32_t* group_done, int32_t* group_steps, int32_t* maxima, void* stream) {
+    VH_REQUIRE(codes && cache_len && audio_pos && pos_base && group_done && group_steps && maxima, VH_EINVAL,
+               "vh_decode_groups_poll: null pointer");
+    VH_REQUIRE(B > 0 && codes_width > 0 && codes_stride >= codes_width && eos >= 0, VH_EINVAL,
+               "vh_decode_groups_poll: bad dims B=%d codes_width=%d codes_stride=%lld eos=%d", B, codes_width,
+               (long long)codes_stride, eos);
+    VH_REQUIRE(beams >= 1 && B % beams == 0, VH_EINVAL,
+               "vh_decode_groups_poll: B=%d is not a multiple of beams=%d (the rows of a group)", B, beams);
+    VH_REQUIRE(max_new >= 0, VH_EINVAL, "vh_decode_groups_poll: max_new=%d", max_new);
+    VH_REQUIRE((reinterpret_cast<uintptr_t>(codes) & 7u) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(cache_len) | reinterpret_cast<uintptr_t>(audio_pos) |
+                     reinterpret_cast<uintptr_t>(pos_base) | reinterpret_cast<uintptr_t>(group_done) |
+                     reinterpret_cast<uintptr_t>(group_steps) | reinterpret_cast<uintptr_t>(maxima)) & 3u) == 0,
+               VH_EALIGN, "vh_decode_groups_poll: codes must be 8-byte aligned, the int32 arrays 4-byte aligned");
+    hipLaunchKernelGGL(decode_groups_poll_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, codes, codes_stride, codes_width,
+                       cache_len, audio_pos, pos_base, eos, B / beams, beams, max_new, group_done, group_steps, maxima);
+    VH_CHECK_LAUNCH("vh_decode_groups_poll");
+    return VH_OK;
+}
+
+// One workgroup per beam row of the group.  prompt_len >= 1: the row becomes BOS + the prompt's prompt_len - 1 ids + EOS to
+// its end, the counters those of a row before its first sample.  prompt_len == 0: parked — see the header.
+__global__ __launch_bounds__(256) void decode_group_reset_kernel(
+    int64_t* __restrict__ codes, int64_t codes_stride, int codes_width, const int64_t* __restrict__ prompt, int prompt_len,
+    int prefix_len, int bos, int eos, int group, int beams, int32_t* __restrict__ cache_len, int32_t* __restrict__ audio_pos,
+    int32_t* __restrict__ pos_base, float* __restrict__ sum_logprobs, int32_t* __restrict__ prefix_lens) {
+    const int b = group * beams + blockIdx.x, tid = threadIdx.x;
+    int64_t* row = codes + (int64_t)b * codes_stride;
+    if (prompt_len >= 1) {
+        for (int c = tid; c < codes_width; c += 256)
+            row[c] = c == 0 ? (int64_t)bos : (c < prompt_len ? prompt[c - 1] : (int64_t)eos);
+        if (tid == 0) {
+            cache_len[b] = 0;
+            audio_pos[b] = prompt_len;
+            pos_base[b] = prompt_len;
+            sum_logprobs[b] = 0.f;
+        }
+    } else if (tid == 0) {
+        // parked: EOS where the row's first generated token stood and the counters of a fresh row behind it — every further
+        // step finds EOS at audio_pos - 1 and writes EOS at audio_pos, over and over the same few places between two rewinds
+        const int p = min(max(pos_base[b], 1), codes_width - 2);      // (a base outside the row is pulled into it)
+        row[p] = (int64_t)eos;
+        pos_base[b] = p;
+        audio_pos[b] = p + 1;
+        cache_len[b] = 0;
+    }
+    if (blockIdx.x == 0 && tid == 0) prefix_lens[group] = prompt_len >= 1 ? prefix_len : 0;
+}
+
+extern "C" int vh_decode_group_reset(int64_t* codes, int64_t codes_stride, int codes_width, const int64_t* prompt,
+                                     int prompt_len, int prefix_len, int bos, int eos, int group, int B, int beams,
+                                     int32_t* cache_len, int32_t* audio_pos, int32_t* pos_base, float* sum_logprobs,
+                                     int32_t* prefix_lens, void* stream) {
+    VH_REQUIRE(codes && cache_len && audio_pos && pos_base && sum_logprobs && prefix_lens && (prompt || prompt_len <= 1),
+               VH_EINVAL, "vh_decode_group_reset: null pointer");
+    VH_REQUIRE(B > 0 && codes_width >= 3 && codes_stride >= codes_width && eos >= 0 && bos >= 0, VH_EINVAL,
+               "vh_decode_group_reset: bad dims B=%d codes_width=%d codes_stride=%lld eos=%d bos=%d", B, codes_width,
+               (long long)codes_stride, eos, bos);
+    VH_REQUIRE(beams >= 1 && B % beams == 0, VH_EINVAL,
+               "vh_decode_group_reset: B=%d is not a multiple of beams=%d (the rows of a group)", B, beams);
+    VH_REQUIRE(group >= 0 && group < B / beams, VH_EINVAL, "vh_decode_group_reset: group=%d of %d", group, B / beams);
+    VH_REQUIRE(prompt_len >= 0 && prompt_len < codes_width, VH_EINVAL,
+               "vh_decode_group_reset: prompt_len=%d (BOS + prompt) must leave room in a row of %d", prompt_len, codes_width);
+    VH_REQUIRE(prompt_len == 0 ? prefix_len == 0 : prefix_len >= prompt_len, VH_EINVAL,
+               "vh_decode_group_reset: prefix_len=%d with prompt_len=%d (text + BOS + prompt keys; 0 parks the group)",
+               prefix_len, prompt_len);
+    VH_REQUIRE(((reinterpret_cast<uintptr_t>(codes) | reinterpret_cast<uintptr_t>(prompt)) & 7u) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(cache_len) | reinterpret_cast<uintptr_t>(audio_pos) |
+                     reinterpret_cast<uintptr_t>(pos_base) | reinterpret_cast<uintptr_t>(sum_logprobs) |
+                     reinterpret_cast<uintptr_t>(prefix_lens)) & 3u) == 0,
+               VH_EALIGN, "vh_decode_group_reset: codes / prompt must be 8-byte aligned, the 32-bit arrays 4-byte aligned");
+    hipLaunchKernelGGL(decode_group_reset_kernel, dim3(beams), dim3(256), 0, (hipStream_t)stream, codes, codes_stride,
+                       codes_width, prompt, prompt_len, prefix_len, bos, eos, group, beams, cache_len, audio_pos, pos_base,
+                       sum_logprobs, prefix_lens);
+    VH_CHECK_LAUNCH("vh_decode_group_reset");
+    return VH_OK;
+}

@@ -61,6 +61,16 @@ class KVCache:
                                        self.s_max, self.s_max, dst.s_max, stream()), 'vh_kv_to_bf16')
         return dst
 
+    def group_view(self, g):
+        """A one-row KVCache over row g's streams of this cache (no copy): a prompt pass writes ONE group's region of a grouped
+        prefix cache through it — the refill of generate_queued — while the decoder's layer table keeps pointing at the whole."""
+        if not 0 <= g < self.batch:
+            raise _lib.VhError(f'KVCache.group_view: row {g} of {self.batch}')
+        view = object.__new__(KVCache)
+        view.buf = self.buf[:, :, g:g + 1]
+        view.n_layers, view.batch, view.n_heads, view.s_max, view.head_dim = self.n_layers, 1, self.n_heads, self.s_max, self.head_dim
+        return view
+
     def k(self, i):
         return self.buf[i, 0]
 
@@ -455,6 +465,83 @@ def group_prefix_cap(longest: int) -> int:
 def grouped_prompts_fit(batch: int, n_heads: int, prefix_cap: int) -> bool:
     """`shared_prompt_fits` for vh_attn_decode_shared_groups: the record slots of the prefix CAPACITY + the suffix splits."""
     return (prefix_cap + 31) // 32 + shared_n_split(batch, n_heads) <= SHARED_MAX_RECORDS
+
+
+# ---- queued decoding (ValleAR.generate_queued): which utterance holds which slot between which polls -------------------------
+def queue_polls(length: int, poll: int, max_new: int) -> int:
+    """Polls (blocks of `poll` replayed steps) a slot is held by an utterance that finishes after `length` tokens — the step
+    at which its last beam emits EOS, counted from 1 — cut at max_new.  The first token comes from the prompt pass, so a
+    slot that has run k blocks has produced 1 + k * poll tokens, and the host sees the utterance done at the first poll
+    k >= 1 with 1 + k * poll >= min(length, max_new) (the host looks after every block, so a slot is held for one at least)."""
+    n = max(1, min(int(length), int(max_new)))
+    return max(1, -(-(n - 1) // int(poll)))
+
+
+def queue_steps_cap(max_new: int, poll: int) -> int:
+    """Steps a row of the queued form may run before the host rewinds or re-arms it: whole polls covering max_new.  The suffix
+    cache, the codes rows and the positions are sized for this many plus one."""
+    return -(-int(max_new) // int(poll)) * int(poll)
+
+
+class QueueSchedule:
+    """The bookkeeping of queued decoding, pure Python: `slots` slots, utterances handed out in input order.  The first
+    min(n, slots) start at poll 0; `retire(slot, poll)` ends the slot's utterance at that poll and starts the next waiting one
+    there (returned), or leaves the slot parked (None).  generate_queued drives it from the device's done flags, plan_queue
+    from given lengths: the same rules either way."""
+
+    def __init__(self, n_utterances: int, slots: int):
+        if slots < 1 or n_utterances < 1:
+            raise ValueError(f'QueueSchedule: {n_utterances} utterances on {slots} slots')
+        self.n, self.slots = int(n_utterances), int(slots)
+        self.holder = [i if i < self.n else None for i in range(self.slots)]      # utterance in each slot (None: parked)
+        self.start = {i: 0 for i in range(min(self.n, self.slots))}
+        self.slot_of = {i: i for i in range(min(self.n, self.slots))}
+        self.end = {}
+        self.next = min(self.n, self.slots)
+        self.refills = 0
+
+    def retire(self, slot: int, poll: int):
+        u = self.holder[slot]
+        if u is None:
+            raise ValueError(f'QueueSchedule: slot {slot} holds nothing at poll {poll}')
+        self.end[u] = int(poll)
+        nxt = None
+        if self.next < self.n:
+            nxt, self.next = self.next, self.next + 1
+            self.start[nxt], self.slot_of[nxt] = int(poll), slot
+            self.refills += 1
+        self.holder[slot] = nxt
+        return nxt
+
+    @property
+    def finished(self) -> bool:
+        return all(h is None for h in self.holder)
+
+    def intervals(self):
+        return [(self.slot_of[u], self.start[u], self.end[u]) for u in range(self.n)]
+
+
+def plan_queue(lengths, slots: int, poll: int, max_new: int):
+    """The schedule generate_queued follows for utterances that finish after `lengths` tokens (see queue_polls): returns
+    ([(slot, start poll, end poll) per utterance], total decode steps replayed = poll * the latest end).  Done slots are
+    served in slot order at every poll, as the decode loop serves them."""
+    sched = QueueSchedule(len(lengths), min(int(slots), len(lengths)))
+    p = 0
+    while not sched.finished:
+        for slot in range(sched.slots):
+            u = sched.holder[slot]
+            if u is not None and p - sched.start[u] >= queue_polls(lengths[u], poll, max_new):
+                sched.retire(slot, p)
+        if not sched.finished:
+            p += 1
+    iv = sched.intervals()
+    return iv, int(poll) * max(e for _, _, e in iv)
+
+
+def chunk_schedule_steps(lengths, per: int, poll: int, max_new: int) -> int:
+    """Decode steps of the static schedule in the same units (whole polls): consecutive chunks of `per` utterances, each run
+    until its longest utterance is done — generate_many's schedule (which cuts its last block at max_new)."""
+    return sum(int(poll) * max(queue_polls(n, poll, max_new) for n in lengths[i:i + per]) for i in range(0, len(lengths), per))
 
 
 def cached_decode_supported(cfg) -> bool:

@@ -511,7 +511,7 @@ def attn_decode_shared_groups(q, kprefix, vprefix, prefix_len, prefix_cap, ksuff
                               n_split=1, partial=None):
     """One-query attention of B = G * beams rows, rows g * beams .. g * beams + beams - 1 over THEIR prompt (kprefix /
     vprefix (G, h, prefix_S, 64), first prefix_len[g] rows; prefix_len an int32 DEVICE tensor (G), every entry in
-    1..prefix_cap) followed by each row's own rows (ksuffix / vsuffix (B, h, S_suf, 64), suffix_len[b] + len_bias of them).
+    1..prefix_cap, or 0 for a PARKED group: nothing of it is read and its rows of `out` are exactly 0.0) followed by each row's own rows (ksuffix / vsuffix (B, h, S_suf, 64), suffix_len[b] + len_bias of them).
 
     vh_attn_decode_shared_groups serves at most 64 rows per call (the decoder never holds more).  More rows than that go
     through it here in consecutive calls of whole groups, at most 64 rows each, every call on its rows' own part of
@@ -696,6 +696,57 @@ def sample_step(logits, V, eos, top_k, top_p, temperature, seed, codes, eos_coun
         int(seed) & (2 ** 64 - 1), ptr(codes), codes.stride(0), ptr(eos_count), ptr(pos_base),
         ptr(sum_logprobs), ptr(audio_emb), ptr(pe), ptr(audio_pos), ptr(cache_len), ptr(_f32(x_next, 'x_next')),
         B, d, stream()), name)
+
+
+POLL_NONE = -(1 << 30)            # vh_decode_groups_poll: a maximum over no rows
+
+
+def _i32_dev(t, n, what):
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_cuda:
+        raise _lib.VhError(f'{what} must be an int32 device tensor of {n} entries')
+    return ptr(t)
+
+
+def decode_groups_poll(codes, cache_len, audio_pos, pos_base, eos, beams, max_new, out):
+    """vh_decode_groups_poll into ONE int32 device tensor `out` of 4 + 2 G entries (one small read per poll): the four maxima
+    (cache_len and audio_pos over all rows, then over the rows of groups that are not done; POLL_NONE over no rows),
+    group_done (G), group_steps (G).  codes (B, width) int64, G = B // beams."""
+    B, width = codes.shape
+    if beams < 1 or B % beams:
+        raise _lib.VhError(f'decode_groups_poll: {B} rows are not a multiple of beams={beams}')
+    G = B // beams
+    if codes.dtype != torch.int64 or codes.stride(1) != 1:
+        raise _lib.VhError('decode_groups_poll: codes must be int64 rows')
+    _i32_dev(out, 4 + 2 * G, 'decode_groups_poll: out')
+    check(_lib.lib().vh_decode_groups_poll(
+        codes.data_ptr(), codes.stride(0), width, _i32_dev(cache_len, B, 'decode_groups_poll: cache_len'),
+        _i32_dev(audio_pos, B, 'decode_groups_poll: audio_pos'), _i32_dev(pos_base, B, 'decode_groups_poll: pos_base'),
+        int(eos), B, int(beams), int(max_new), out[4:4 + G].data_ptr(), out[4 + G:].data_ptr(), out.data_ptr(), stream()),
+        'vh_decode_groups_poll')
+    return out
+
+
+def decode_group_reset(codes, group, beams, prompt, prefix_len, bos, eos, cache_len, audio_pos, pos_base, sum_logprobs,
+                       prefix_lens):
+    """vh_decode_group_reset on rows group * beams .. of codes (B, width) int64.  prompt: int64 device tensor of the new
+    utterance's first-codebook ids (the row becomes BOS + prompt, EOS beyond; prefix_len = text + BOS + prompt keys), or None to
+    PARK the group (prefix_lens[group] = 0, the rows rewound to a fresh row that holds EOS)."""
+    B, width = codes.shape
+    if beams < 1 or B % beams:
+        raise _lib.VhError(f'decode_group_reset: {B} rows are not a multiple of beams={beams}')
+    if codes.dtype != torch.int64 or codes.stride(1) != 1:
+        raise _lib.VhError('decode_group_reset: codes must be int64 rows')
+    if prompt is not None and (prompt.dtype != torch.int64 or prompt.dim() != 1 or not prompt.is_cuda or not prompt.is_contiguous()):
+        raise _lib.VhError('decode_group_reset: prompt must be a 1-D int64 device tensor')
+    if sum_logprobs.dtype != torch.float32 or sum_logprobs.numel() != B:
+        raise _lib.VhError('decode_group_reset: sum_logprobs must be float32 (B)')
+    prompt_len = 0 if prompt is None else prompt.numel() + 1
+    check(_lib.lib().vh_decode_group_reset(
+        codes.data_ptr(), codes.stride(0), width, ptr(prompt) if prompt is not None and prompt.numel() else None, prompt_len,
+        int(prefix_len) if prompt is not None else 0, int(bos), int(eos), int(group), B, int(beams),
+        _i32_dev(cache_len, B, 'decode_group_reset: cache_len'), _i32_dev(audio_pos, B, 'decode_group_reset: audio_pos'),
+        _i32_dev(pos_base, B, 'decode_group_reset: pos_base'), ptr(sum_logprobs),
+        _i32_dev(prefix_lens, B // beams, 'decode_group_reset: prefix_lens'), stream()), 'vh_decode_group_reset')
 
 
 def pad32(n):

@@ -20,9 +20,9 @@ import torch.nn as nn
 from torch import optim
 
 from . import _lib, dropout, kernels
-from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, StepSampler, cached_decode_supported,
-                     group_prefix_cap, grouped_prompts_fit, perf_forward_supported, ffn_fused_width,
-                     shared_prompt_fits,
+from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, QueueSchedule, StepSampler,
+                     cached_decode_supported, group_prefix_cap, grouped_prompts_fit, perf_forward_supported, ffn_fused_width,
+                     queue_steps_cap, shared_prompt_fits,
                      transformer_forward, transformer_forward_bf16)
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device, device_mirror
 from .utils import get_best_beam
@@ -55,6 +55,7 @@ class _DecodeSlot:
     def __init__(self):
         self.codes = self.cache = self.prefix = self.cache_len = self.audio_pos = self.pos_base = self.dec = None
         self.group_len = None                                # grouped shared prompts: the device lengths the captured steps read
+        self.queue = None                                    # generate_queued: the poll buffers (device + pinned host) and the first-sample scratch
         self.busy = False
         self.uses = 0
 
@@ -258,6 +259,251 @@ class ValleAR(_Base):
             best = best[stats['prompt_lens'][g * beams]:]
             out.append(best[best != self.eos_token])
         return out
+
+    def generate_queued(self, utterances, *, beams=None, slots=None):
+        """`generate_many` with the rows kept busy: `slots` utterances (default min(len(utterances), 64 // beams); 1 <= slots *
+        beams <= 64) decode at once, and whenever the host polls (every EOS_POLL steps) an utterance whose beams have all
+        emitted EOS — or that has run max_audio_len steps — is saved and its rows handed to the next waiting utterance: a
+        one-row prompt pass into that group's region of the prefix cache, the head and the first sample on its rows, the rows'
+        counters re-armed (vh_decode_group_reset).  With nothing waiting the group is PARKED (prefix length 0: the decode
+        attention reads nothing for it) and rewound at every poll.  One decoder, one set of captured graphs, replayed between
+        polls and never re-captured.  Same arguments and result as generate_many; what it serves is the grouped form: fp32,
+        head width 64, use_kv_cache=True, d_model <= 4096, greedy and sampled.  A longest prompt whose capacity is beyond the
+        256 records of the grouped merge falls back to generate_many (`last_generate_stats['queued']` is False).
+
+        Greedy tokens do not depend on the schedule.  SAMPLED tokens do: the sampler keys its draws on (seed, row index it is
+        given, position), the decode steps hand it the decoder's rows and a refill's first sample the group's rows 0 .. beams
+        - 1, so an utterance's draws depend on the slot it lands in and on whether it started the call or refilled a slot
+        (the same list, slots and seed give the same output).
+
+        `last_generate_stats`: queued, slots, refills, polls, steps (decode steps replayed), parked_group_steps, max_cache_len
+        / max_audio_pos (largest values any row reached) beside s_suf / codes_width (what they must stay within), intervals
+        ((slot, start poll, end poll) per utterance), sum_logprobs and prompt_lens per row in utterance order."""
+        beams = self.config.num_beams if beams is None else beams
+        self._check_queued(beams, slots)
+        return self._generate_queued(utterances, beams, slots)
+
+    def _check_queued(self, beams, slots):
+        """The refusals of generate_queued: pure Python, no device."""
+        cfg = self.config
+        if not isinstance(beams, int) or isinstance(beams, bool) or beams < 1:
+            raise ValueError(f'generate_queued: beams={beams!r} (an integer >= 1)')
+        if slots is not None and (not isinstance(slots, int) or isinstance(slots, bool) or slots < 1):
+            raise ValueError(f'generate_queued: slots={slots!r} (an integer >= 1)')
+        if (1 if slots is None else slots) * beams > MAX_DECODE_ROWS:
+            raise ValueError(f'generate_queued: slots={slots} with beams={beams}: the slots decode in one launch of at most '
+                             f'{MAX_DECODE_ROWS} rows (1 <= slots * beams <= {MAX_DECODE_ROWS})')
+        if not cfg.use_kv_cache or cfg.d_model != cfg.n_heads * kernels.HEAD_DIM or cfg.d_model > MAX_DECODE_D_MODEL:
+            raise ValueError(f'generate_queued: beams={beams} with use_kv_cache={cfg.use_kv_cache}, d_model={cfg.d_model}, '
+                             f'n_heads={cfg.n_heads}: queued decoding needs the cached decoder at head width '
+                             f'{kernels.HEAD_DIM} (d_model <= {MAX_DECODE_D_MODEL})')
+
+    def _queue_first_sample(self, dec, rows, last, scratch_len):
+        """Head + first sample for the rows of ONE group (ArDecoder.sample_from on row slices).  scratch_len stands in for
+        cache_len: the first sample appends no K/V row, and vh_decode_group_reset left cache_len where the first step appends."""
+        m = dec._keep
+        kernels.linear(last, m[0], out=dec.logits[rows, : dec.V])
+        if dec.sampling[0] == 1:
+            kernels.greedy_step(dec.logits[rows], dec.V, self.eos_token, dec.codes[rows], dec.eos_count, m[1], m[2],
+                                dec.audio_pos[rows], scratch_len, dec.x[rows], pos_base=dec.pos_base[rows])
+        else:
+            top_k, top_p, temp, seed = dec.sampling
+            kernels.sample_step(dec.logits[rows], dec.V, self.eos_token, top_k, top_p, temp, seed, dec.codes[rows],
+                                dec.eos_count, dec.sum_logprobs[rows], m[1], m[2], dec.audio_pos[rows], scratch_len,
+                                dec.x[rows], pos_base=dec.pos_base[rows])
+
+    @_on_device
+    @torch.inference_mode()
+    def _generate_queued(self, utterances, beams, slots, use_graph=True):
+        """generate_queued behind its refusals (use_graph=False steps eagerly: the tests' second arm)."""
+        self._require_layernorm()
+        self._check_queued(beams, slots)
+        cfg, dev, d = self.config, self.device, self.config.d_model
+        texts, firsts = [], []
+        for prompt_tokens, prompt_codes, target_tokens in utterances:
+            assert prompt_tokens.dim() == 1, 'Prompt tokens should be 1D tensor.'
+            assert prompt_codes.dim() == 2, 'Prompt codes should be 2D tensor.'
+            if target_tokens is not None:
+                assert target_tokens.dim() == 1, 'Target tokens should be 1D tensor.'
+            texts.append(prompt_tokens if target_tokens is None else torch.cat((prompt_tokens, target_tokens), dim=0))
+            firsts.append(prompt_codes[..., 0])
+        n = len(texts)
+        if n == 0:
+            raise ValueError('generate_queued: utterances must be a non-empty list')
+        slots = min(n, MAX_DECODE_ROWS // beams if slots is None else slots)
+        B, max_new, poll = slots * beams, cfg.max_audio_len, EOS_POLL
+        txs = [int(t.shape[0]) for t in texts]
+        pls = [int(c.shape[0]) + 1 for c in firsts]                        # BOS + prompt
+        ctx = [t + p for t, p in zip(txs, pls)]
+        cap = group_prefix_cap(max(ctx))                                   # of the longest prompt of the CALL: any refill fits
+        if not grouped_prompts_fit(B, cfg.n_heads, cap):
+            out = self.generate_many(utterances, beams=beams)
+            self.last_generate_stats.update(queued=False)
+            return out
+        # every row may run whole polls up to the one that covers max_new before the host rewinds or re-arms it
+        steps_cap = queue_steps_cap(max_new, poll)
+        s_suf, width = (steps_cap + 1 + 31) // 32 * 32, cap + steps_cap + 1
+        if max(pls) + steps_cap + 1 > self.audio_position_emb.pe.shape[0] or max(txs) > self.tokens_position_emb.pe.shape[0]:
+            raise _lib.VhError('sequence exceeds the positional table (max_len 5000)')
+        run = _Run()
+        run.G, run.beams, run.grouped, run.B = slots, beams, True, B
+        run.max_new = steps_cap                                            # (sizes the suffix cache in _prompt_pass)
+        run.hd_cached = run.any_head_dim = run.shared = run.perf_prefill = False
+        run.perf_mode = False
+        run.txs, run.pls = txs[:slots], pls[:slots]
+        run.ragged = len(set(run.txs)) > 1 or len(set(run.pls)) > 1
+        run.pl_max, run.s0, run.cap = max(run.pls), max(ctx[:slots]), cap
+        run.s_max = 0
+        slot_key = ('queued', B, slots, beams, cap, width, s_suf, max_new, bool(use_graph), int(cfg.top_k), float(cfg.tok_p),
+                    float(cfg.temperature), str(dev), _lib.TUNING_EPOCH, tuple(os.environ.get(k) for k in _DECODER_ENV),
+                    self._weights_key())
+        slot = self._acquire_slot(slot_key)
+        run.slot = slot
+        reuse = slot is not None and slot.dec is not None
+        ok, dec = False, None
+        try:
+            i32 = dict(dtype=torch.int32)
+            if reuse:
+                codes = slot.codes
+                codes.fill_(self.eos_token)
+            else:
+                codes = torch.full((B, width), self.eos_token, device=dev, dtype=torch.int64)
+            codes[:, 0] = self.bos_token
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            marks[0].record()
+            texts = [kernels.ids_to_device(t, dev, cfg.vocab_size, 'text ids') for t in texts]
+            firsts = [kernels.ids_to_device(c, dev, cfg.num_audio_tokens, 'prompt codes').contiguous() for c in firsts]
+            row_pls = [p for p in run.pls for _ in range(beams)]
+            if reuse:
+                cache_len, audio_pos, pos_base, group_len = slot.cache_len, slot.audio_pos, slot.pos_base, slot.group_len
+                cache_len.fill_(-1)
+                audio_pos.copy_(torch.tensor(row_pls, **i32), non_blocking=True)
+                pos_base.copy_(audio_pos)
+                group_len.copy_(torch.tensor(ctx[:slots], **i32), non_blocking=True)
+                poll_dev, poll_host, first_len = slot.queue
+            else:
+                cache_len = torch.full((B,), -1, device=dev, **i32)
+                audio_pos = _lib.to_device_async(torch.tensor(row_pls, **i32), dev).clone()
+                pos_base = audio_pos.clone()
+                group_len = _lib.to_device_async(torch.tensor(ctx[:slots], **i32), dev).clone()
+                poll_dev = torch.zeros(4 + 2 * slots, device=dev, **i32)
+                poll_host = torch.zeros(4 + 2 * slots, **i32).pin_memory()
+                first_len = torch.zeros(beams, device=dev, **i32)
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if cfg.top_k != 1 else 0
+            if reuse:
+                slot.dec.reset(seed)
+            cache, prefix, last = self._prompt_pass(run, texts[:slots], firsts[:slots], codes)
+            if reuse:
+                dec = slot.dec
+            else:
+                dec = ArDecoder(self, B, cache.s_max, codes, cache, cache_len, audio_pos, pos_base, use_graph=use_graph, seed=seed,
+                                prefix=prefix, prefix_len=0, prefix_lens=group_len, prefix_cap=cap, beams=beams)
+                if slot is not None:
+                    slot.codes, slot.cache, slot.prefix, slot.dec = codes, cache, prefix, dec
+                    slot.cache_len, slot.audio_pos, slot.pos_base, slot.group_len = cache_len, audio_pos, pos_base, group_len
+                    slot.queue = (poll_dev, poll_host, first_len)
+            if slot is not None:
+                slot.uses += 1
+            if cache.s_max != s_suf or codes.shape[1] != width:
+                raise _lib.VhError(f'generate_queued: suffix cache of {cache.s_max} rows / codes of {codes.shape[1]}, expected '
+                                   f'{s_suf} / {width}')
+            dec.capture()
+            dec.sample_from(last)
+            del last
+            marks[1].record()
+            sampled = cfg.top_k != 1
+            sched = QueueSchedule(n, slots)
+            saved, at_cap = {}, {}
+            scratch = None
+            polls = steps = parked_steps = 0
+            max_cl = max_ap = kernels.POLL_NONE
+            live_cl, live_ap = 0, max(run.pls) + 1                         # the fresh rows the first sample leaves
+            gap_s, t_gap = 0.0, None
+            p = 0
+            while not sched.finished:
+                # the rows that step on stand at most here; every other row was re-armed or rewound to a fresh row below
+                if live_cl + poll > s_suf or live_ap + poll > width:
+                    raise _lib.VhError(f'generate_queued: a row at cache_len {live_cl} / audio_pos {live_ap} cannot run {poll} more '
+                                       f'steps within a suffix cache of {s_suf} rows and codes of {width} (a scheduling bug: '
+                                       'nothing was replayed)')
+                held = [g for g in range(slots) if sched.holder[g] is not None]
+                # sampled rows that reach max_new inside this block: their scores are taken AT max_new (the steps between it
+                # and the poll would add log-probabilities of tokens that are cut)
+                capping = [g for g in held if 1 + (p - sched.start[sched.holder[g]] + 1) * poll > max_new] if sampled else []
+                to_cap = max_new - 1 - (p - sched.start[sched.holder[capping[0]]]) * poll if capping else 0
+                if t_gap is not None:
+                    gap_s += time.perf_counter() - t_gap
+                if 0 < to_cap < poll:
+                    dec.run(to_cap)
+                    for g in capping:
+                        at_cap[sched.holder[g]] = dec.sum_logprobs[g * beams:(g + 1) * beams].clone()
+                    dec.run(poll - to_cap)
+                else:
+                    dec.run(poll)
+                steps += poll
+                parked_steps += (slots - len(held)) * poll
+                p += 1
+                kernels.decode_groups_poll(codes, cache_len, audio_pos, pos_base, self.eos_token, beams, max_new, poll_dev)
+                poll_host.copy_(poll_dev, non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                t_gap = time.perf_counter()
+                polls += 1
+                got = poll_host.tolist()
+                max_cl, max_ap = max(max_cl, got[0]), max(max_ap, got[1])
+                live_cl, live_ap = got[2], got[3]
+                for g in range(slots):
+                    u = sched.holder[g]
+                    rows = slice(g * beams, (g + 1) * beams)
+                    if u is None:                                          # parked: rewound, so that it never leaves its rows
+                        kernels.decode_group_reset(codes, g, beams, None, 0, self.bos_token, self.eos_token, cache_len, audio_pos,
+                                                   pos_base, dec.sum_logprobs, group_len)
+                        continue
+                    if not got[4 + g]:
+                        continue
+                    saved[u] = (codes[rows, :pls[u] + min(got[4 + slots + g], max_new)].clone(),
+                                at_cap.pop(u) if u in at_cap else dec.sum_logprobs[rows].clone())
+                    nxt = sched.retire(g, p)
+                    if nxt is None:
+                        kernels.decode_group_reset(codes, g, beams, None, 0, self.bos_token, self.eos_token, cache_len, audio_pos,
+                                                   pos_base, dec.sum_logprobs, group_len)
+                        continue
+                    # refill: re-arm the rows, one-row prompt pass into the group's region of the prefix cache, first sample
+                    kernels.decode_group_reset(codes, g, beams, firsts[nxt], ctx[nxt], self.bos_token, self.eos_token, cache_len,
+                                               audio_pos, pos_base, dec.sum_logprobs, group_len)
+                    x = torch.empty(1, ctx[nxt], d, device=dev, dtype=torch.float32)
+                    self._embed_rows(texts[nxt].unsqueeze(0), codes[g * beams:g * beams + 1, :pls[nxt]], x)
+                    if scratch is None:
+                        scratch = ForwardScratch(max(ctx), d, cfg.dim_feedforward, dev)
+                    transformer_forward(self.transformer, x, prefix.group_view(g), mode=kernels.MASK_PREFIX,
+                                        scratch=scratch.fit(ctx[nxt]), x_len=txs[nxt])
+                    self._queue_first_sample(dec, rows, x[:, -1].expand(beams, d).contiguous(), first_len)
+                    live_cl, live_ap = max(live_cl, 0), max(live_ap, pls[nxt] + 1)
+            done_mark = torch.cuda.Event(enable_timing=True)
+            done_mark.record()
+            done_mark.synchronize()
+            _lib.raise_device_errors(dev)
+            outs, scores, prompt_lens = [], [], []
+            for u in range(n):
+                rows_u, sc = saved[u]
+                best = get_best_beam(rows_u, sc, self.eos_token, cfg.length_penalty)
+                best = best[pls[u]:]
+                outs.append(best[best != self.eos_token])
+                scores.append(sc)
+                prompt_lens += [pls[u]] * beams
+            self.last_generate_stats = {
+                'queued': True, 'slots': slots, 'beams': beams, 'groups': n, 'refills': sched.refills, 'polls': polls,
+                'steps': steps, 'parked_group_steps': parked_steps, 'max_cache_len': max_cl, 'max_audio_pos': max_ap,
+                's_suf': s_suf, 'codes_width': width, 'prefix_cap': cap, 'intervals': sched.intervals(),
+                'sum_logprobs': torch.cat(scores), 'prompt_lens': prompt_lens, 'grouped_shared': True,
+                'decoder_reused': bool(reuse), 'slot_uses': slot.uses if slot is not None else 0,
+                'n_split': dec.n_split, 'prefill_ms': marks[0].elapsed_time(marks[1]),
+                'decode_ms': marks[1].elapsed_time(done_mark), 'poll_gap_ms': gap_s * 1e3, 'kv_cache': True}
+            ok = True
+            return outs
+        finally:
+            if dec is not None and (slot is None or dec is not slot.dec):
+                dec.close()
+            self._release_slot(slot_key, slot, ok)
 
     def _check_beams(self, beams, shared_prompt=False, perf_mode=False, forced=None):
         """The refusals of generate_batch(beams=n): pure Python, no device."""
