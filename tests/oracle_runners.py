@@ -1,6 +1,8 @@
 """Run oracle/ on the golden cases' inputs (same keys as tests/golden/cases.REFERENCE_RUNNERS)."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -266,3 +268,159 @@ ORACLE_RUNNERS = {
     'ar_generate_tiny': ar_generate_tiny, 'ar_generate_mid': ar_generate_mid,
     'ar_generate_eos': ar_generate_eos, 'nar': nar, 'sampling': sampling,
 }
+
+
+# ---- sampled decoding audited against the oracle ---------------------------------------------------------------------------
+AUDIT_DELTA = 1e-4          # the suite's bound between device and oracle logits at these sizes (MARGIN in the grouped / queued tests)
+
+
+class AuditError(AssertionError):
+    """audit_sampled_rows found a token outside the oracle's support ('support: ...') or a score outside its interval
+    ('score: ...')."""
+
+
+AUDIT_MAX_NEW = 40         # rows reach max_new inside the second 32-step block
+AUDIT_MODEL_SEED = 41
+# (text a, text b, prompt frames) for synth.synth_utterance: contexts (text + BOS + prompt) of 20, 42, 64, 86 and 100 positions
+AUDIT_UTTS = [(6, 5, 8), (9, 7, 25), (12, 9, 42), (15, 11, 59), (18, 13, 68)]
+
+
+def _audit_model_table():
+    from tests.golden.gen_golden_base_d_model import BASE
+    from tests.golden.gen_golden_codebooks import AR_V4096
+    from tests.golden.gen_golden_head_dim_decode import HD_DECODE
+    from tests.golden.gen_golden_wide_d_model import WIDE
+    # model -> (config, head scale, EOS row gain).  The scale brings the oracle's logit standard deviation at the prompts' last
+    # positions to about 2.2 (as drawn it is 0.155, 0.37, 0.235, 0.515, 0.68, 0.97 and 0.16: measured on the CPU, float64).
+    # The gain multiplies the EOS row once more: as drawn, the oracle's own sampling (top_k 50, 40 steps) ends one row in
+    # seventy by EOS at d_model 128 and none at 768; with the gain, rows of one prompt end either way
+    return {
+        'd128': (C.AR_TINY, 14.0, 2.0),
+        'd512': (dict(C.AR_MID, num_layers=2), 6.0, 2.0),
+        'w128': (dict(HD_DECODE['w128'], num_layers=2), 9.4, 2.0),            # 256 / 2 heads: head width 128
+        'd768': (BASE['d768'], 4.3, -2.0),                                    # the fast decode chain
+        'd1152': (WIDE['d1152'], 3.2, 1.0),                                   # LayerNorm apart
+        'd1536': (WIDE['d1536'], 2.25, 2.0),                                  # wide, LayerNorm folded
+        'v4096': (AR_V4096, 13.7, 4.0),                                       # vh_sample_step_wide
+    }
+
+
+def audit_inputs(model):
+    """(config kwargs, state dict, five utterances) of audit model `model`: 2 layers, synth.make_state_dict(rich=True), the
+    head multiplied so that the next-token distributions are peaked — asserted here, on the CPU: the float64 oracle's logits at
+    every prompt's last position have a standard deviation of 1.5 .. 3 (with the flat logits of std=0.02 every token scores
+    about -log(50) under any history and an audit would see nothing).  The EOS row is not silenced; it carries a gain of its
+    own on top (the table above), so that rows draw EOS within the 40 steps often enough for a case to audit rows that end
+    either way."""
+    from valle2_amd import synth
+    kw, scale, eos_gain = _audit_model_table()[model]
+    kw = dict(kw, max_audio_len=AUDIT_MAX_NEW, tok_p=1.0)
+    assert kw['num_layers'] == 2
+    cfg = C.cfg_of(kw)
+    sd = synth.make_state_dict(cfg, 'ValleAR', seed=AUDIT_MODEL_SEED, rich=True)
+    sd['proj.weight'] = sd['proj.weight'] * scale
+    sd['proj.weight'][cfg.num_audio_tokens] *= eos_gain
+    utts = [synth.synth_utterance(cfg, a, b, f, seed=2600 + i) for i, (a, b, f) in enumerate(AUDIT_UTTS)]
+    for pt, pc, tt in utts:
+        ctx = len(pt) + len(tt) + pc.shape[0] + 1
+        std = head_logit_std(sd, cfg, torch.cat([pt, tt]), pc[:, 0])
+        assert 20 <= ctx <= 100 and 1.5 <= std <= 3.0, f'inputs drifted: {model} context {ctx}, logit std {std:.3f}'
+    return kw, sd, utts
+
+
+def _forced_logits64(sd, cfg, text, codes_rows):
+    """float64 oracle logits (n, T, V + 1) of rows teacher-forced through O.ar_logits: codes_rows is a list of 1-D id tensors
+    (BOS first) over one text; shorter rows are padded (the mask is causal: a row's own positions do not see the pad)."""
+    sd64 = {k: v.double() for k, v in sd.items()}
+    lens = torch.tensor([len(c) for c in codes_rows])
+    codes = torch.zeros(len(codes_rows), int(lens.max()), dtype=torch.int64)
+    for r, c in enumerate(codes_rows):
+        codes[r, :len(c)] = c
+    text = text.cpu().long()
+    batch = {'tokens': text[None].repeat(len(codes_rows), 1), 'tokens_lens': torch.full((len(codes_rows),), len(text)),
+             'codes': codes, 'codes_lens': lens}
+    with torch.no_grad():
+        return O.ar_logits(sd64, cfg, batch).permute(0, 2, 1)
+
+
+def head_logit_std(sd, cfg, text, prompt_first):
+    """Standard deviation over the vocabulary of the float64 oracle's logits at the prompt's last position."""
+    row = torch.cat([torch.tensor([cfg.num_audio_tokens + 1]), prompt_first.cpu().long()])
+    return float(_forced_logits64(sd, cfg, text, [row])[0, -1].std())
+
+
+def audit_sampled_rows(sd, cfg, text, rows, scores, prompt_len, max_new, top_k, tok_p, temperature, delta):
+    """Audit sampled rows of ONE utterance against the float64 oracle, on the CPU.
+
+    rows (n, width) int64: BOS, the prompt's first-codebook codes (prompt_len ids in all), what was generated, EOS padding;
+    scores (n,): the decoder's sum_logprobs.  Each row is cut after its first generated EOS, or at prompt_len + max_new, and
+    teacher-forced through O.ar_logits with the state dict in float64; the logits at audio position j are the distribution
+    of token j + 1, so step s (token prompt_len + s) is read at position prompt_len - 1 + s.  Counted steps: up to and
+    including the draw that produces EOS, nothing after it, nothing at or beyond max_new.
+
+    support: at every counted step the token's scaled logit (logit / temperature) is at least the oracle's top_k-th largest
+    scaled logit minus delta / temperature (top_k = 0: every token is in the support).  Top-p is not audited: tok_p = 1.0.
+    score: the row's score lies in [sum(lo) - tol, sum(hi) + tol], lo / hi being the token's log-probability under the largest
+    support consistent with delta (every logit >= kth - delta / T) and the smallest (every logit >= kth + delta / T, plus the
+    token itself — and, top-k keeping at least k tokens, as many more at kth - delta / T as bring it to k members: without
+    them the k-th token itself would be left out at every step and the interval would be its probability wide, per step);
+    tol = 2 * delta / temperature * (counted steps): one delta on the token's logit and one on the log-sum-exp, per step.
+
+    Returns one report per row: dict(steps, end ('eos' | 'cap'), lo, hi, tol, score, off (score minus the interval's
+    midpoint)).  Raises AuditError naming the row, the step, the token, the oracle's k-th logit and the token's logit."""
+    if tok_p != 1.0:
+        raise ValueError('audit_sampled_rows: top-p support is not audited (tok_p must be 1.0)')
+    eos, V = cfg.num_audio_tokens, cfg.num_audio_tokens + 1
+    rows = torch.as_tensor(rows).cpu().long()
+    scores = torch.as_tensor(scores).detach().cpu().double()
+    n = rows.shape[0]
+    if scores.shape != (n,):
+        raise ValueError(f'audit_sampled_rows: {n} rows, scores of shape {tuple(scores.shape)}')
+    counts, ends = [], []
+    for r in range(n):
+        gen = rows[r, prompt_len:prompt_len + max_new]
+        hit = (gen == eos).nonzero()
+        if hit.numel():
+            counts.append(int(hit[0]) + 1)
+            ends.append('eos')
+        else:
+            if gen.numel() < max_new:
+                raise ValueError(f'audit_sampled_rows: row {r} holds {gen.numel()} generated tokens without an EOS, max_new={max_new}')
+            counts.append(max_new)
+            ends.append('cap')
+    logits = _forced_logits64(sd, cfg, text, [rows[r, :prompt_len + counts[r] - 1] for r in range(n)])
+    w = delta / temperature
+    report = []
+    for r in range(n):
+        lo = hi = 0.0
+        for s in range(counts[r]):
+            x = logits[r, prompt_len - 1 + s] / temperature
+            tok = int(rows[r, prompt_len + s])
+            if not 0 <= tok < V:
+                raise AuditError(f'support: row {r} step {s} token {tok}: not a token of the head (0..{V - 1})')
+            if top_k > 0:
+                k = min(top_k, V)
+                kth = torch.topk(x, k)[0][-1]
+                if x[tok] < kth - w:
+                    raise AuditError(f'support: row {r} step {s} token {tok}: its scaled logit {float(x[tok]):.6f} is below the '
+                                     f"oracle's {k}-th largest {float(kth):.6f} minus delta/T {w:.1e} (rank "
+                                     f'{int((x > x[tok]).sum()) + 1} of {V})')
+                big, small = x >= kth - w, x >= kth + w
+                small[tok] = True
+                lse_small = torch.logsumexp(x[small], 0)
+                if int(small.sum()) < k:                                     # top-k keeps at least k tokens, each >= kth - w
+                    lse_small = torch.logaddexp(lse_small, math.log(k - int(small.sum())) + kth - w)
+                lo += float(x[tok] - torch.logsumexp(x[big], 0))
+                hi += float(x[tok] - lse_small)
+            else:
+                lp = float(x[tok] - torch.logsumexp(x, 0))
+                lo, hi = lo + lp, hi + lp
+        tol = 2 * w * counts[r]
+        got = float(scores[r])
+        rep = dict(steps=counts[r], end=ends[r], lo=lo, hi=hi, tol=tol, score=got, off=got - 0.5 * (lo + hi))
+        if not lo - tol <= got <= hi + tol:
+            raise AuditError(f'score: row {r}: device score {got:.6f} outside [{lo - tol:.6f}, {hi + tol:.6f}] (the oracle over '
+                             f'{counts[r]} counted steps, ended by {ends[r]}: lo {lo:.6f} hi {hi:.6f} tol {tol:.1e}; off the '
+                             f'midpoint by {rep["off"]:+.6f})')
+        report.append(rep)
+    return report

@@ -278,7 +278,9 @@ class ValleAR(_Base):
 
         `last_generate_stats`: queued, slots, refills, polls, steps (decode steps replayed), parked_group_steps, max_cache_len
         / max_audio_pos (largest values any row reached) beside s_suf / codes_width (what they must stay within), intervals
-        ((slot, start poll, end poll) per utterance), sum_logprobs and prompt_lens per row in utterance order."""
+        ((slot, start poll, end poll) per utterance), sum_logprobs and prompt_lens per row in utterance order, rows (per
+        utterance in input order, the saved (beams, length) int64 tokens its best beam was chosen from: BOS + prompt + what was
+        generated, cut at max_audio_len; a call that fell back to generate_many records none)."""
         beams = self.config.num_beams if beams is None else beams
         self._check_queued(beams, slots)
         return self._generate_queued(utterances, beams, slots)
@@ -494,7 +496,8 @@ class ValleAR(_Base):
                 'queued': True, 'slots': slots, 'beams': beams, 'groups': n, 'refills': sched.refills, 'polls': polls,
                 'steps': steps, 'parked_group_steps': parked_steps, 'max_cache_len': max_cl, 'max_audio_pos': max_ap,
                 's_suf': s_suf, 'codes_width': width, 'prefix_cap': cap, 'intervals': sched.intervals(),
-                'sum_logprobs': torch.cat(scores), 'prompt_lens': prompt_lens, 'grouped_shared': True,
+                'sum_logprobs': torch.cat(scores), 'prompt_lens': prompt_lens, 'rows': [saved[u][0] for u in range(n)],
+                'grouped_shared': True,
                 'decoder_reused': bool(reuse), 'slot_uses': slot.uses if slot is not None else 0,
                 'n_split': dec.n_split, 'prefill_ms': marks[0].elapsed_time(marks[1]),
                 'decode_ms': marks[1].elapsed_time(done_mark), 'poll_gap_ms': gap_s * 1e3, 'kv_cache': True}
