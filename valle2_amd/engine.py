@@ -603,17 +603,22 @@ class StepSampler:
         self._keep = (model.proj.weight.detach(), model.audio_emb.weight.detach(), model.audio_position_emb.pe)
         self.n_split, self.ffn_ws, self.kv_bf16, self.head_ws = 0, None, False, None
 
-    def sample_from(self, hidden_last):
+    def sample_from(self, hidden_last, rows=slice(None), cache_len=None):
+        """Head + first sample on the last hidden rows of a prompt pass (the tail of step 0), for the decode rows `rows`:
+        the one Python call site of the sample kernels.  cache_len stands in for the rows' own counter (generate_queued's
+        refill: the first sample appends no K/V row, and vh_decode_group_reset left cache_len where the first step appends).
+        The sampler keys its draws on the row index within what it is handed."""
         m = self._keep
-        kernels.linear(hidden_last, m[0], out=self.logits[:, : self.V])
+        cache_len = self.cache_len[rows] if cache_len is None else cache_len
+        kernels.linear(hidden_last, m[0], out=self.logits[rows, : self.V])
         if self.sampling[0] == 1:
-            kernels.greedy_step(self.logits, self.V, self.eos, self.codes, self.eos_count, m[1], m[2],
-                                self.audio_pos, self.cache_len, self.x, pos_base=self.pos_base)
+            kernels.greedy_step(self.logits[rows], self.V, self.eos, self.codes[rows], self.eos_count, m[1], m[2],
+                                self.audio_pos[rows], cache_len, self.x[rows], pos_base=self.pos_base[rows])
         else:
             top_k, top_p, temp, seed = self.sampling
-            kernels.sample_step(self.logits, self.V, self.eos, top_k, top_p, temp, seed, self.codes,
-                                self.eos_count, self.sum_logprobs, m[1], m[2], self.audio_pos,
-                                self.cache_len, self.x, pos_base=self.pos_base)
+            kernels.sample_step(self.logits[rows], self.V, self.eos, top_k, top_p, temp, seed, self.codes[rows],
+                                self.eos_count, self.sum_logprobs[rows], m[1], m[2], self.audio_pos[rows],
+                                cache_len, self.x[rows], pos_base=self.pos_base[rows])
 
     def capture(self):
         pass
@@ -622,9 +627,10 @@ class StepSampler:
         pass
 
 
-class ArDecoder:
+class ArDecoder(StepSampler):
     """The AR decode loop of valle/models/valle_ar.py:141-171 for B independent rows, one token
-    per row per step, the whole step enqueued natively and replayed as a hipGraph."""
+    per row per step, the whole step enqueued natively and replayed as a hipGraph.  The head + first sample after a prompt
+    pass is StepSampler's (`sample_from`, over the same buffer names)."""
 
     def __init__(self, model, batch, s_max, codes, cache: KVCache, cache_len, audio_pos, pos_base,
                  n_split=None, use_graph=True, seed=0, prefix: KVCache | None = None, prefix_len=0,
@@ -641,7 +647,7 @@ class ArDecoder:
         cfg = model.config
         dev = cache.buf.device
         d, dff, V = cfg.d_model, cfg.dim_feedforward, cfg.num_audio_tokens + 1
-        self.B, self.V, self.d = batch, V, d
+        self.B, self.V, self.d, self.eos = batch, V, d, cfg.num_audio_tokens
         self.ldl = (V + 3) // 4 * 4
         self.n_split = n_split or pick_n_split(batch * cfg.n_heads)
         if prefix is not None and n_split is None:
@@ -773,19 +779,6 @@ class ArDecoder:
         self.sampling = self.sampling[:3] + (int(seed),)
         if self.seed_dev is not None:
             self.seed_dev.copy_(torch.tensor([int(seed)], dtype=torch.int64), non_blocking=True)
-
-    def sample_from(self, hidden_last):
-        """Head + greedy step on the last hidden row of a prefill (the tail of step 0)."""
-        m = self._keep
-        kernels.linear(hidden_last, m[0], out=self.logits[:, : self.V])
-        if self.sampling[0] == 1:
-            kernels.greedy_step(self.logits, self.V, self._desc.eos, self.codes, self.eos_count, m[1], m[2],
-                                self.audio_pos, self.cache_len, self.x, pos_base=self.pos_base)
-        else:
-            top_k, top_p, temp, seed = self.sampling
-            kernels.sample_step(self.logits, self.V, self._desc.eos, top_k, top_p, temp, seed, self.codes,
-                                self.eos_count, self.sum_logprobs, m[1], m[2], self.audio_pos,
-                                self.cache_len, self.x, pos_base=self.pos_base)
 
     def capture(self):
         """Record the step graphs now (host work only: capture enqueues nothing).  generate_batch calls it right after
