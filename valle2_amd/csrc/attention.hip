@@ -30,7 +30,70 @@
 // =============================================================================================
 #define PART_LD 72  // floats per partial record: o[64], m, l, pad
 
-template <int NW, bool NT>
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 ld16_stream(const uint16_t* p) {
+    return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+}
+// sum over the 8 lanes of a half DPP row (lanes 8j .. 8j+7)
+__device__ __forceinline__ float row8_sum(float v) {
+    v += dpp_get<0xB1, 0xF>(v, 0.f);
+    v += dpp_get<0x4E, 0xF>(v, 0.f);
+    v += dpp_get<0x141, 0xF>(v, 0.f);     // row_half_mirror: lane i <-> 7 - i inside each half row
+    return v;
+}
+#define BF_LO(w) vh_h16_lo(w)
+#define BF_HI(w) vh_h16_hi(w)
+
+// ---- what every decode form ends with ----
+// The NW waves of a workgroup left their (o, m, l) in LDS (a barrier lies between): thread tid < 64 merges column tid.  A wave
+// without a chunk holds m = -inf and weighs nothing; M itself is -inf only for an empty key range.
+// FMA_O: whether O += o_k * w_k rounds once (fma) or twice.  The compiler used to choose, differently from kernel to kernel
+// (once where O is divided by L in place and in the 16-bit shared-prompt kernel, twice in the other record writers); the
+// result bits are the contract, so each caller states what its kernel has always computed.  L rounds once everywhere.
+template <int NW, bool FMA_O>
+__device__ __forceinline__ void wave_merge(const float* s_m, const float* s_l, const float (*s_o)[HD], int tid, float& M,
+                                           float& L, float& O) {
+    M = s_m[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) M = fmaxf(M, s_m[k]);
+    L = 0.f;
+    O = 0.f;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const float wgt = s_m[k] == NEG_INF ? 0.f : vh_exp2(s_m[k] - M);
+        L = __builtin_fmaf(s_l[k], wgt, L);
+        if constexpr (FMA_O) {
+            O = __builtin_fmaf(s_o[k][tid], wgt, O);
+        } else {
+#pragma clang fp contract(off)
+            const float t = s_o[k][tid] * wgt;
+            O = O + t;
+        }
+    }
+}
+// column tid < 64 of one PART_LD record: O unnormalised, M in log2 units, L
+__device__ __forceinline__ void write_record(float* pr, int tid, float O, float M, float L) {
+    pr[tid] = O;
+    if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
+}
+// column tid of the n_split records at pr, added IN SPLIT ORDER and normalised; ldg is how a float is loaded
+template <class Ld>
+__device__ __forceinline__ float combine_splits(const float* pr, int n_split, int tid, Ld ldg) {
+    float M = NEG_INF;
+    for (int k = 0; k < n_split; ++k) M = fmaxf(M, ldg(pr + k * PART_LD + HD));
+    float L = 0.f, O = 0.f;
+    for (int k = 0; k < n_split; ++k) {
+        const float ms = ldg(pr + k * PART_LD + HD);
+        const float wgt = ms == NEG_INF ? 0.f : vh_exp2(ms - M);
+        L += ldg(pr + k * PART_LD + HD + 1) * wgt;
+        O += ldg(pr + k * PART_LD + tid) * wgt;
+    }
+    return O / L;
+}
+
+// Burst form (round 1): every wave requests a whole 32-key chunk with predicated loads, waits for it, reduces it and asks again.
+// Serves key splits and more (b, head) pairs than CUs (vh_attn_decode).
+template <int NW>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
     const float* __restrict__ q, int ldq, const float* __restrict__ kc,
     const float* __restrict__ vc, float* __restrict__ out, int ldo,
@@ -63,13 +126,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
         for (int i = 0; i < 8; ++i) {
             const int key = key0 + 4 * i;
             const bool in = key < len;
-            if (NT) {
-                kf[i] = in ? ld4_stream(kb + (int64_t)key * HD) : f32x4{0.f, 0.f, 0.f, 0.f};
-                vf[i] = in ? ld4_stream(vb + (int64_t)key * HD) : f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-                kf[i] = in ? ld4(kb + (int64_t)key * HD) : f32x4{0.f, 0.f, 0.f, 0.f};
-                vf[i] = in ? ld4(vb + (int64_t)key * HD) : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
+            kf[i] = in ? ld4_stream(kb + (int64_t)key * HD) : f32x4{0.f, 0.f, 0.f, 0.f};
+            vf[i] = in ? ld4_stream(vb + (int64_t)key * HD) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
         float s[8];
         float cmax = NEG_INF;
@@ -105,22 +163,12 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
     if (lane == 0) { s_m[w] = m; s_l[w] = l; }
     __syncthreads();
     if (tid < HD) {
-        float M = s_m[0];
-#pragma unroll
-        for (int k = 1; k < NW; ++k) M = fmaxf(M, s_m[k]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            const float wgt = s_m[k] == NEG_INF ? 0.f : vh_exp2(s_m[k] - M);
-            L += s_l[k] * wgt;
-            O += s_o[k][tid] * wgt;
-        }
+        float M, L, O;
+        wave_merge<NW, true>(s_m, s_l, s_o, tid, M, L, O);
         if (n_split == 1) {
             out[(int64_t)b * ldo + head * HD + tid] = O / L;
         } else if (arrived == nullptr) {                     // two-launch form: plain stores, the next launch reads them
-            float* pr = partial + ((int64_t)bh * n_split + split) * PART_LD;
-            pr[tid] = O;
-            if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
+            write_record(partial + ((int64_t)bh * n_split + split) * PART_LD, tid, O, M, L);
         } else {                                             // handed to another workgroup of THIS launch: write-through
             float* pr = partial + ((int64_t)bh * n_split + split) * PART_LD;
             __hip_atomic_store(pr + tid, O, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -150,104 +198,159 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
     __syncthreads();
     if (!s_last) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (no instruction: keeps the loads below the ticket)
-    if (tid < HD) {
-        const float* pr = partial + (int64_t)bh * n_split * PART_LD;
-        auto ldg = [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-        float M = NEG_INF;
-        for (int k = 0; k < n_split; ++k) M = fmaxf(M, ldg(pr + k * PART_LD + HD));
-        float L = 0.f, O = 0.f;
-        for (int k = 0; k < n_split; ++k) {
-            const float ms = ldg(pr + k * PART_LD + HD);
-            const float wgt = ms == NEG_INF ? 0.f : vh_exp2(ms - M);
-            L += ldg(pr + k * PART_LD + HD + 1) * wgt;
-            O += ldg(pr + k * PART_LD + tid) * wgt;
-        }
-        out[(int64_t)b * ldo + head * HD + tid] = O / L;
-    }
+    if (tid < HD)
+        out[(int64_t)b * ldo + head * HD + tid] = combine_splits(
+            partial + (int64_t)bh * n_split * PART_LD, n_split, tid,
+            [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
 }
 
-// Ring variant (round 2).  The burst kernel has its 256 KB per CU in flight only at the moment its 16 waves have
+__global__ __launch_bounds__(64) void attn_decode_combine_kernel(
+    const float* __restrict__ partial, float* __restrict__ out, int ldo, int n_heads, int n_split) {
+    const int bh = blockIdx.x, b = bh / n_heads, head = bh - b * n_heads;
+    const int tid = threadIdx.x;
+    out[(int64_t)b * ldo + head * HD + tid] =
+        combine_splits(partial + (int64_t)bh * n_split * PART_LD, n_split, tid, [](const float* p) { return *p; });
+}
+
+// Ring form (round 2).  The burst kernel has its 256 KB per CU in flight only at the moment its 16 waves have
 // all just issued; each wave then waits for its whole burst, reduces it, and only then asks again, and its very first
 // request waits for a dependent load of cache_len[b].  Here a wave owns a ring of D register sets of 32 keys each:
-// D-1 bursts are always outstanding while one is reduced, and the first D-1 bursts are issued BEFORE the context
+// D-1 bursts are always outstanding while one is reduced, and with SPEC the first D-1 bursts are issued BEFORE the context
 // length is known (addresses clamped inside the cache allocation; what lies beyond the row's length is masked once
 // the length has arrived), so the stream starts with the kernel.  The read ceiling of this part is 6.3-6.5 TB/s
 // for any read-only kernel (tools/probe_read_bw.hip, corrected: its first version dropped loop remainders and
 // reported 8 TB/s); the 8 x 2 ring reaches 6.0-6.1 TB/s inside the decode step.
-template <int NW, int D, int CK = 32>
-__global__ __launch_bounds__(NW * 64) void attn_decode_ring_kernel(
-    const float* __restrict__ q, int ldq, const float* __restrict__ kc,
-    const float* __restrict__ vc, float* __restrict__ out, int ldo,
-    const int32_t* __restrict__ cache_len, int len_bias, int n_heads, int S_max, int n_split,
-    float* __restrict__ partial) {
+//
+// One body serves the fp32 cache and the 16-bit cache of perf mode (half the bytes of the stream that bounds the decode step; q,
+// the softmax and the accumulators stay fp32).  What differs is the lane map.  Either way a wave-instruction moves 1 KiB:
+//   float     a key row is 256 B = 16 lanes x 16 B: lane l holds dimensions 4 (l & 15) .. +3 of key (l >> 4) of a group of 4 keys
+//   uint16_t  a key row is 128 B =  8 lanes x 16 B: lane l holds dimensions 8 (l & 7) .. +7 of key (l >> 3) of a group of 8 keys
+template <class T> struct KvLanes;
+__device__ __forceinline__ f32x4 fma4(f32x4 a, float b, f32x4 c) { return __builtin_elementwise_fma(a, f32x4{b, b, b, b}, c); }
+// o * alpha + v * p, the step of the online softmax that takes in a set's first key.  One of the two products is rounded before
+// the fma; which one used to be the compiler's choice, and it chose differently for the fp32 shared-prompt suffix (o * alpha
+// rounded: ALPHA_FMA = false) than for every other ring form (v * p rounded).  The result bits are the contract: pinned here.
+template <bool ALPHA_FMA>
+__device__ __forceinline__ f32x4 rescale_add(f32x4 o, float alpha, f32x4 v, float p) {
+#pragma clang fp contract(off)
+    if constexpr (ALPHA_FMA) {
+        const f32x4 t = v * p;
+        return fma4(o, alpha, t);
+    } else {
+        const f32x4 t = o * alpha;
+        return fma4(v, p, t);
+    }
+}
+template <> struct KvLanes<float> {
+    typedef f32x4 Raw;                                             // what one lane loads of a key row
+    static constexpr int LK = 16, NV = 1;                          // lanes per key; f32x4 per lane once widened
+    static __device__ __forceinline__ Raw load(const float* p) { return ld4_stream(p); }
+    static __device__ __forceinline__ Raw zero() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+    static __device__ __forceinline__ float dot(const Raw& k, const f32x4 (&q)[NV]) {
+        const f32x4 t = k * q[0];
+        return row16_sum((t.x + t.y) + (t.z + t.w));
+    }
+    static __device__ __forceinline__ void widen(const Raw& v, f32x4 (&o)[NV]) { o[0] = v; }
+};
+template <> struct KvLanes<uint16_t> {
+    typedef u32x4 Raw;
+    static constexpr int LK = 8, NV = 2;
+    static __device__ __forceinline__ Raw load(const uint16_t* p) { return ld16_stream(p); }
+    static __device__ __forceinline__ Raw zero() { return u32x4{0u, 0u, 0u, 0u}; }
+    static __device__ __forceinline__ float dot(const Raw& kk, const f32x4 (&q)[NV]) {
+        float d = BF_LO(kk.x) * q[0].x + BF_HI(kk.x) * q[0].y + BF_LO(kk.y) * q[0].z + BF_HI(kk.y) * q[0].w;
+        d += BF_LO(kk.z) * q[1].x + BF_HI(kk.z) * q[1].y + BF_LO(kk.w) * q[1].z + BF_HI(kk.w) * q[1].w;
+        return row8_sum(d);
+    }
+    static __device__ __forceinline__ void widen(const Raw& v, f32x4 (&o)[NV]) {
+        o[0] = f32x4{BF_LO(v.x), BF_HI(v.x), BF_LO(v.y), BF_HI(v.y)};
+        o[1] = f32x4{BF_LO(v.z), BF_HI(v.z), BF_LO(v.w), BF_HI(v.w)};
+    }
+};
+
+struct KeyRange { int len, c_begin, c_end; };   // the row's keys, and the 32-key chunks [c_begin, c_end) of them to reduce
+
+// Chunks [c_begin, c_end) of ONE (row, head) stream, by the NW waves of a workgroup.  qrow: the head's 64 query values; kb / vb:
+// the stream's first row.  `range` gives the row's length and the chunk range; it is evaluated AFTER the speculative bursts of
+// SPEC (chunks w, w + NW, ... whatever the length is: c_begin must be 0, and until the length is there loads are clamped to row
+// S_max - 1) and before anything else.  No load is predicated: loads are clamped to the row's last key and the keys past the
+// length are SELECTED away (the rows behind them may hold NaN / Inf).  On return threads tid < 64 hold column tid of the
+// workgroup's record: O (unnormalised), M (scores in log2 units; -inf for an empty range) and L.  Every thread of the workgroup
+// must call it (one barrier inside).  ALPHA_FMA: see rescale_add; FMA_O: see wave_merge.
+template <class T, int NW, int D, bool SPEC, bool ALPHA_FMA, bool FMA_O, class RangeFn>
+__device__ __forceinline__ void ring_range(const float* __restrict__ qrow, const T* __restrict__ kb, const T* __restrict__ vb,
+                                           int S_max, RangeFn range, float& M, float& L, float& O) {
+    typedef KvLanes<T> KV;
+    typedef typename KV::Raw Raw;
+    constexpr int LK = KV::LK, NV = KV::NV;
+    constexpr int KPI = 64 / LK, LPS = 32 / KPI, DPL = HD / LK;    // keys per wave-instruction; loads per set and operand; dims per lane
     __shared__ float s_m[NW], s_l[NW];
     __shared__ __attribute__((aligned(16))) float s_o[NW][HD];
-    const int bh = blockIdx.y, b = bh / n_heads, head = bh - b * n_heads;
-    const int split = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int c16 = lane & 15, g = lane >> 4;
-    const float* kb = kc + (int64_t)bh * S_max * HD + 4 * c16;
-    const float* vb = vc + (int64_t)bh * S_max * HD + 4 * c16;
-
-    constexpr int LPS = CK / 4;                                    // loads per set and operand: 4 keys per wave instruction
-    f32x4 kf[D][LPS], vf[D][LPS];
+    const int col = lane & (LK - 1), kg = lane / LK;
+    kb += DPL * col;
+    vb += DPL * col;
+    Raw kf[D][LPS], vf[D][LPS];
     int key_limit = S_max - 1;                                     // before the length is known: stay inside the allocation
-    auto load = [&](int c, f32x4 (&kq)[LPS], f32x4 (&vq)[LPS]) {  // unconditional loads, clamped row index
-        const int key0 = c * CK + g;
+    auto load = [&](int c, Raw (&kq)[LPS], Raw (&vq)[LPS]) {       // unconditional loads, clamped row index
+        const int key0 = c * 32 + kg;
 #pragma unroll
         for (int i = 0; i < LPS; ++i) {
-            const int key = min(key0 + 4 * i, key_limit);
-            kq[i] = ld4_stream(kb + (int64_t)key * HD);
-            vq[i] = ld4_stream(vb + (int64_t)key * HD);
+            const int key = min(key0 + KPI * i, key_limit);
+            kq[i] = KV::load(kb + (int64_t)key * HD);
+            vq[i] = KV::load(vb + (int64_t)key * HD);
         }
     };
-    // speculative start (n_split == 1: the wave's chunks are w, w + NW, ... whatever the length is)
-    const bool spec = n_split == 1;
-    if (spec) {
+    if constexpr (SPEC) {
 #pragma unroll
         for (int j = 0; j < D - 1; ++j) load(w + j * NW, kf[j], vf[j]);
     }
-    const int len = cache_len[b] + len_bias;
-    const int nchunks = (len + CK - 1) / CK;
-    const int cps = (nchunks + n_split - 1) / n_split;
-    const int c_begin = split * cps;
-    const int c_end = min(nchunks, c_begin + cps);
+    const KeyRange kr = range();
+    const int len = kr.len, c_begin = kr.c_begin, c_end = kr.c_end;
     key_limit = len - 1;                 // from here on the tail re-reads the row's last key instead of rows beyond it
-    const float qscale = 0.125f * LOG2E;
-    const f32x4 q4 = ld4(q + (int64_t)b * ldq + head * HD + 4 * c16) * qscale;
-    if (!spec) {
+    if constexpr (!SPEC) {
 #pragma unroll
         for (int j = 0; j < D - 1; ++j)
             if (c_begin + w + j * NW < c_end) load(c_begin + w + j * NW, kf[j], vf[j]);
     }
+    const float qscale = 0.125f * LOG2E;  // 1/sqrt(64), folded with log2(e) for exp2
+    f32x4 qv[NV];
+#pragma unroll
+    for (int n = 0; n < NV; ++n) qv[n] = ld4(qrow + DPL * col + 4 * n) * qscale;
 
     float m = NEG_INF, l = 0.f;
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    auto reduce = [&](int c, const f32x4 (&kq)[LPS], const f32x4 (&vq)[LPS]) {
-        const int key0 = c * CK + g;
-        const bool whole = c * CK + CK <= len;                    // wave-uniform: no masking for interior chunks
+    f32x4 o[NV];
+#pragma unroll
+    for (int n = 0; n < NV; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto reduce = [&](int c, const Raw (&kq)[LPS], const Raw (&vq)[LPS]) {
+        const int key0 = c * 32 + kg;
+        const bool whole = c * 32 + 32 <= len;                     // wave-uniform: no masking for interior chunks
         float sc[LPS];
         float cmax = NEG_INF;
 #pragma unroll
         for (int i = 0; i < LPS; ++i) {
-            const f32x4 t = kq[i] * q4;
-            const float d = row16_sum((t.x + t.y) + (t.z + t.w));
-            sc[i] = (whole || key0 + 4 * i < len) ? d : NEG_INF;
+            const float d = KV::dot(kq[i], qv);
+            sc[i] = (whole || key0 + KPI * i < len) ? d : NEG_INF;
             cmax = fmaxf(cmax, sc[i]);
         }
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
-        const float m_new = fmaxf(m, cmax);  // finite: chunk c < nchunks holds >= 1 valid key
+#pragma unroll
+        for (int sh = LK; sh <= 32; sh <<= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, sh, 64));
+        const float m_new = fmaxf(m, cmax);                        // finite: chunk c < ceil(len / 32) holds >= 1 valid key
         const float alpha = vh_exp2(m - m_new);
-        o *= alpha;
-        l *= alpha;
+        float p[LPS];
+#pragma unroll
+        for (int i = 0; i < LPS; ++i) p[i] = vh_exp2(sc[i] - m_new);
+        l = __builtin_fmaf(l, alpha, p[0]);                        // l = l * alpha + sum p, o = o * alpha + sum v p: left to right
+#pragma unroll
+        for (int i = 1; i < LPS; ++i) l += p[i];
 #pragma unroll
         for (int i = 0; i < LPS; ++i) {
-            const float p = vh_exp2(sc[i] - m_new);
-            l += p;
             // rows beyond the length hold whatever the allocation held (possibly NaN): select, do not multiply by 0
-            const f32x4 vv = (whole || key0 + 4 * i < len) ? vq[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-            o += vv * p;
+            const Raw vv = (whole || key0 + KPI * i < len) ? vq[i] : KV::zero();
+            f32x4 vw[NV];
+            KV::widen(vv, vw);
+#pragma unroll
+            for (int n = 0; n < NV; ++n) o[n] = i == 0 ? rescale_add<ALPHA_FMA>(o[n], alpha, vw[n], p[0]) : fma4(vw[n], p[i], o[n]);
         }
         m = m_new;
     };
@@ -256,169 +359,82 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_ring_kernel(
         for (int j = 0; j < D; ++j) {
             const int c = c0 + j * NW;
             if (c < c_end) {
-                const int cn = c + (D - 1) * NW;                 // the burst that keeps D - 1 outstanding
+                const int cn = c + (D - 1) * NW;                   // the burst that keeps D - 1 outstanding
                 if (cn < c_end) load(cn, kf[(j + D - 1) % D], vf[(j + D - 1) % D]);
                 reduce(c, kf[j], vf[j]);
             }
         }
     }
+    // fold the key groups of the wave (lanes l, l ^ LK, ..., l ^ 32 hold the same dimensions)
 #pragma unroll
-    for (int sh = 16; sh <= 32; sh <<= 1) {
-        o.x += __shfl_xor(o.x, sh, 64); o.y += __shfl_xor(o.y, sh, 64);
-        o.z += __shfl_xor(o.z, sh, 64); o.w += __shfl_xor(o.w, sh, 64);
+    for (int sh = LK; sh <= 32; sh <<= 1) {
+#pragma unroll
+        for (int n = 0; n < NV; ++n) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[n][j] += __shfl_xor(o[n][j], sh, 64);
+        }
         l += __shfl_xor(l, sh, 64);
     }
-    if (lane < 16) st4(&s_o[w][4 * c16], o);
+    if (lane < LK) {
+#pragma unroll
+        for (int n = 0; n < NV; ++n) st4(&s_o[w][DPL * col + 4 * n], o[n]);
+    }
     if (lane == 0) { s_m[w] = m; s_l[w] = l; }
     __syncthreads();
-    if (tid < HD) {
-        float M = s_m[0];
-#pragma unroll
-        for (int k = 1; k < NW; ++k) M = fmaxf(M, s_m[k]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            const float wgt = s_m[k] == NEG_INF ? 0.f : vh_exp2(s_m[k] - M);
-            L += s_l[k] * wgt;
-            O += s_o[k][tid] * wgt;
-        }
-        if (n_split == 1) {
-            out[(int64_t)b * ldo + head * HD + tid] = O / L;
-        } else {
-            float* pr = partial + ((int64_t)bh * n_split + split) * PART_LD;
-            pr[tid] = O;
-            if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
-        }
-    }
+    M = NEG_INF;
+    L = 0.f;
+    O = 0.f;
+    if (tid < HD) wave_merge<NW, FMA_O>(s_m, s_l, s_o, tid, M, L, O);
 }
 
-// =============================================================================================
-// perf mode: the same single-row attention over a bf16 K/V cache (B, h, S_max, 64) — half the bytes of the stream
-// that bounds the decode step; q, the softmax and the accumulators stay fp32.  A key row is 64 x 2 B = 128 B = 8
-// lanes x 16 B: lane l holds dimensions 8 (l & 7) .. +7 of key (l >> 3) of a group of 8 keys, so one wave-instruction
-// still moves 1 KiB.  Ring of D register sets of 32 keys (4 loads per operand and set), speculative first bursts
-// before the row's length is known, non-temporal loads — the structure of attn_decode_ring_kernel.
-// =============================================================================================
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 ld16_stream(const uint16_t* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+// whole row, speculative start: the default of vh_attn_decode (fp32 cache) and vh_attn_decode_kv16
+template <class T, int NW, int D>
+__device__ __forceinline__ void decode_ring_body(const float* __restrict__ q, int ldq, const T* __restrict__ kc,
+                                                 const T* __restrict__ vc, float* __restrict__ out, int ldo,
+                                                 const int32_t* __restrict__ cache_len, int len_bias, int n_heads, int S_max) {
+    const int bh = blockIdx.y, b = bh / n_heads, head = bh - b * n_heads;
+    float M, L, O;
+    ring_range<T, NW, D, true, true, true>(q + (int64_t)b * ldq + head * HD, kc + (int64_t)bh * S_max * HD, vc + (int64_t)bh * S_max * HD,
+                               S_max, [&] {
+                                   const int len = cache_len[b] + len_bias;
+                                   return KeyRange{len, 0, (len + 31) / 32};
+                               }, M, L, O);
+    const int tid = threadIdx.x;
+    if (tid < HD) out[(int64_t)b * ldo + head * HD + tid] = O / L;
 }
-// sum over the 8 lanes of a half DPP row (lanes 8j .. 8j+7)
-__device__ __forceinline__ float row8_sum(float v) {
-    v += dpp_get<0xB1, 0xF>(v, 0.f);
-    v += dpp_get<0x4E, 0xF>(v, 0.f);
-    v += dpp_get<0x141, 0xF>(v, 0.f);     // row_half_mirror: lane i <-> 7 - i inside each half row
-    return v;
+template <int NW, int D>
+__global__ __launch_bounds__(NW * 64) void attn_decode_ring_kernel(
+    const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, float* __restrict__ out,
+    int ldo, const int32_t* __restrict__ cache_len, int len_bias, int n_heads, int S_max) {
+    decode_ring_body<float, NW, D>(q, ldq, kc, vc, out, ldo, cache_len, len_bias, n_heads, S_max);
 }
-#define BF_LO(w) vh_h16_lo(w)
-#define BF_HI(w) vh_h16_hi(w)
-
-// (TWIN: ring16_range below carries the same load / reduce / fold / cross-wave combine for a chunk range — the key-split and
-// shared-prompt forms.  This kernel is kept as it was so that vh_attn_decode_kv16 stays bit-identical; a change to the burst
-// loop here belongs there too.)
 template <int NW, int D>
 __global__ __launch_bounds__(NW * 64) void attn_decode_ring16_kernel(
     const float* __restrict__ q, int ldq, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
     float* __restrict__ out, int ldo, const int32_t* __restrict__ cache_len, int len_bias, int n_heads, int S_max) {
-    __shared__ float s_m[NW], s_l[NW];
-    __shared__ __attribute__((aligned(16))) float s_o[NW][HD];
-    const int bh = blockIdx.y, b = bh / n_heads, head = bh - b * n_heads;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int c8 = lane & 7, kg = lane >> 3;
-    const uint16_t* kb = kc + (int64_t)bh * S_max * HD + 8 * c8;
-    const uint16_t* vb = vc + (int64_t)bh * S_max * HD + 8 * c8;
-    constexpr int LPS = 4;                                         // 8 keys per wave-instruction
-    u32x4 kf[D][LPS], vf[D][LPS];
-    int key_limit = S_max - 1;
-    auto load = [&](int c, u32x4 (&kq)[LPS], u32x4 (&vq)[LPS]) {
-        const int key0 = c * 32 + kg;
-#pragma unroll
-        for (int i = 0; i < LPS; ++i) {
-            const int key = min(key0 + 8 * i, key_limit);
-            kq[i] = ld16_stream(kb + (int64_t)key * HD);
-            vq[i] = ld16_stream(vb + (int64_t)key * HD);
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < D - 1; ++j) load(w + j * NW, kf[j], vf[j]);
-    const int len = cache_len[b] + len_bias;
-    const int c_end = (len + 31) / 32;
-    key_limit = len - 1;
-    const float qscale = 0.125f * LOG2E;
-    const float* qp = q + (int64_t)b * ldq + head * HD + 8 * c8;
-    const f32x4 qa = ld4(qp) * qscale, qb = ld4(qp + 4) * qscale;
+    decode_ring_body<uint16_t, NW, D>(q, ldq, kc, vc, out, ldo, cache_len, len_bias, n_heads, S_max);
+}
 
-    float m = NEG_INF, l = 0.f;
-    f32x4 oa = {0.f, 0.f, 0.f, 0.f}, ob = {0.f, 0.f, 0.f, 0.f};
-    auto reduce = [&](int c, const u32x4 (&kq)[LPS], const u32x4 (&vq)[LPS]) {
-        const int key0 = c * 32 + kg;
-        const bool whole = c * 32 + 32 <= len;
-        float sc[LPS];
-        float cmax = NEG_INF;
-#pragma unroll
-        for (int i = 0; i < LPS; ++i) {
-            const u32x4 kk = kq[i];
-            float d = BF_LO(kk.x) * qa.x + BF_HI(kk.x) * qa.y + BF_LO(kk.y) * qa.z + BF_HI(kk.y) * qa.w;
-            d += BF_LO(kk.z) * qb.x + BF_HI(kk.z) * qb.y + BF_LO(kk.w) * qb.z + BF_HI(kk.w) * qb.w;
-            d = row8_sum(d);
-            sc[i] = (whole || key0 + 8 * i < len) ? d : NEG_INF;
-            cmax = fmaxf(cmax, sc[i]);
-        }
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 8, 64));
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
-        const float m_new = fmaxf(m, cmax);
-        const float alpha = vh_exp2(m - m_new);
-        oa *= alpha; ob *= alpha;
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < LPS; ++i) {
-            const float p = vh_exp2(sc[i] - m_new);
-            l += p;
-            u32x4 vv = vq[i];
-            if (!(whole || key0 + 8 * i < len)) vv = u32x4{0u, 0u, 0u, 0u};   // rows beyond the length: select, not * 0
-            oa += f32x4{BF_LO(vv.x), BF_HI(vv.x), BF_LO(vv.y), BF_HI(vv.y)} * p;
-            ob += f32x4{BF_LO(vv.z), BF_HI(vv.z), BF_LO(vv.w), BF_HI(vv.w)} * p;
-        }
-        m = m_new;
-    };
-    for (int c0 = w; c0 < c_end; c0 += D * NW) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            const int c = c0 + j * NW;
-            if (c < c_end) {
-                const int cn = c + (D - 1) * NW;
-                if (cn < c_end) load(cn, kf[(j + D - 1) % D], vf[(j + D - 1) % D]);
-                reduce(c, kf[j], vf[j]);
-            }
-        }
-    }
-    // fold the 8 key groups of the wave (lanes l, l^8, l^16, l^32 hold the same dimensions)
-#pragma unroll
-    for (int sh = 8; sh <= 32; sh <<= 1) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            oa[j] += __shfl_xor(oa[j], sh, 64);
-            ob[j] += __shfl_xor(ob[j], sh, 64);
-        }
-        l += __shfl_xor(l, sh, 64);
-    }
-    if (lane < 8) { st4(&s_o[w][8 * c8], oa); st4(&s_o[w][8 * c8 + 4], ob); }
-    if (lane == 0) { s_m[w] = m; s_l[w] = l; }
-    __syncthreads();
-    if (tid < HD) {
-        float M = s_m[0];
-#pragma unroll
-        for (int k = 1; k < NW; ++k) M = fmaxf(M, s_m[k]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            const float wgt = s_m[k] == NEG_INF ? 0.f : vh_exp2(s_m[k] - M);
-            L += s_l[k] * wgt;
-            O += s_o[k][tid] * wgt;
-        }
-        out[(int64_t)b * ldo + head * HD + tid] = O / L;
-    }
+// Key-split form of the ring16 kernel: grid (n_split, B h); split s of a (row, head) takes chunks [s cps, (s + 1) cps) of its
+// ceil(len / 32) and writes one PART_LD record (o[64], m, l) — the layout attn_decode_combine_kernel reads.  A split without keys
+// leaves m = -inf and weighs nothing.  No speculative bursts: a key split does not know its chunks before it knows the length.
+template <int NW, int D>
+__global__ __launch_bounds__(NW * 64) void attn_decode_ring16_split_kernel(
+    const float* __restrict__ q, int ldq, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
+    const int32_t* __restrict__ cache_len, int len_bias, int n_heads, int S_max, int n_split, float* __restrict__ partial) {
+    const int bh = blockIdx.y, b = bh / n_heads, head = bh - b * n_heads;
+    const int split = blockIdx.x;
+    float M, L, O;
+    ring_range<uint16_t, NW, D, false, true, false>(q + (int64_t)b * ldq + head * HD, kc + (int64_t)bh * S_max * HD,
+                                       vc + (int64_t)bh * S_max * HD, S_max, [&] {
+                                           const int len = min(cache_len[b] + len_bias, S_max);   // (never a row beyond the allocation)
+                                           const int nchunks = (len + 31) / 32;
+                                           const int cps = (nchunks + n_split - 1) / n_split;
+                                           const int c_begin = split * cps;
+                                           return KeyRange{len, c_begin, min(nchunks, c_begin + cps)};
+                                       }, M, L, O);
+    const int tid = threadIdx.x;
+    if (tid < HD) write_record(partial + ((int64_t)bh * n_split + split) * PART_LD, tid, O, M, L);
 }
 
 // fp32 cache rows -> bf16 cache rows (round to nearest even): the prompt pass runs in fp32, its K/V are narrowed once
@@ -451,156 +467,6 @@ extern "C" int vh_kv_to_bf16(const float* src, uint16_t* dst, int n_streams, int
 
 static thread_local hipEvent_t g_attn_ev[2] = {nullptr, nullptr};
 void vh_internal_attn_decode_events(hipEvent_t start, hipEvent_t stop) { g_attn_ev[0] = start; g_attn_ev[1] = stop; }
-
-__global__ __launch_bounds__(64) void attn_decode_combine_kernel(
-    const float* __restrict__ partial, float* __restrict__ out, int ldo, int n_heads, int n_split) {
-    const int bh = blockIdx.x, b = bh / n_heads, head = bh - b * n_heads;
-    const int tid = threadIdx.x;
-    const float* pr = partial + (int64_t)bh * n_split * PART_LD;
-    float M = NEG_INF;
-    for (int s = 0; s < n_split; ++s) M = fmaxf(M, pr[s * PART_LD + HD]);
-    float L = 0.f, O = 0.f;
-    for (int s = 0; s < n_split; ++s) {
-        const float ms = pr[s * PART_LD + HD];
-        const float wgt = ms == NEG_INF ? 0.f : vh_exp2(ms - M);
-        L += pr[s * PART_LD + HD + 1] * wgt;
-        O += pr[s * PART_LD + tid] * wgt;
-    }
-    out[(int64_t)b * ldo + head * HD + tid] = O / L;
-}
-
-// Key range [c_begin, c_end) of 32-key chunks of ONE (row, head) stream of the 16-bit cache, by the NW waves of a workgroup: the
-// ring16 kernel's burst loop (8 lanes per key, non-temporal 16-byte loads, D register sets per wave, fp32 arithmetic on the
-// widened values) without its speculative first bursts — a key split does not know its chunks before it knows the length.
-// kb / vb: the stream's first row; loads are clamped to the row's last key and the keys past the length are SELECTED away (the
-// rows behind them may hold NaN / Inf).  On return threads tid < 64 hold column tid of the workgroup's record: O (unnormalised),
-// M (scores in log2 units; -inf for an empty range) and L.  Every thread of the workgroup must call it (one barrier inside).
-// (TWIN of the body of attn_decode_ring16_kernel above, which stays untouched for bit-identity of vh_attn_decode_kv16: what differs
-// is the chunk range, the absent speculative bursts and where the result goes.  Keep the two burst loops in step.)
-template <int NW, int D>
-__device__ __forceinline__ void ring16_range(const float* __restrict__ qrow, const uint16_t* __restrict__ kb,
-                                             const uint16_t* __restrict__ vb, int len, int c_begin, int c_end, float* s_m,
-                                             float* s_l, float (*s_o)[HD], float& M, float& L, float& O) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int c8 = lane & 7, kg = lane >> 3;
-    kb += 8 * c8;
-    vb += 8 * c8;
-    constexpr int LPS = 4;                                         // 8 keys per wave-instruction
-    u32x4 kf[D][LPS], vf[D][LPS];
-    const int key_limit = len - 1;
-    auto load = [&](int c, u32x4 (&kq)[LPS], u32x4 (&vq)[LPS]) {
-        const int key0 = c * 32 + kg;
-#pragma unroll
-        for (int i = 0; i < LPS; ++i) {
-            const int key = min(key0 + 8 * i, key_limit);
-            kq[i] = ld16_stream(kb + (int64_t)key * HD);
-            vq[i] = ld16_stream(vb + (int64_t)key * HD);
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < D - 1; ++j)
-        if (c_begin + w + j * NW < c_end) load(c_begin + w + j * NW, kf[j], vf[j]);
-    const float qscale = 0.125f * LOG2E;
-    const f32x4 qa = ld4(qrow + 8 * c8) * qscale, qb = ld4(qrow + 8 * c8 + 4) * qscale;
-
-    float m = NEG_INF, l = 0.f;
-    f32x4 oa = {0.f, 0.f, 0.f, 0.f}, ob = {0.f, 0.f, 0.f, 0.f};
-    auto reduce = [&](int c, const u32x4 (&kq)[LPS], const u32x4 (&vq)[LPS]) {
-        const int key0 = c * 32 + kg;
-        const bool whole = c * 32 + 32 <= len;
-        float sc[LPS];
-        float cmax = NEG_INF;
-#pragma unroll
-        for (int i = 0; i < LPS; ++i) {
-            const u32x4 kk = kq[i];
-            float d = BF_LO(kk.x) * qa.x + BF_HI(kk.x) * qa.y + BF_LO(kk.y) * qa.z + BF_HI(kk.y) * qa.w;
-            d += BF_LO(kk.z) * qb.x + BF_HI(kk.z) * qb.y + BF_LO(kk.w) * qb.z + BF_HI(kk.w) * qb.w;
-            d = row8_sum(d);
-            sc[i] = (whole || key0 + 8 * i < len) ? d : NEG_INF;
-            cmax = fmaxf(cmax, sc[i]);
-        }
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 8, 64));
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
-        const float m_new = fmaxf(m, cmax);                        // finite: chunk c < ceil(len / 32) holds >= 1 valid key
-        const float alpha = vh_exp2(m - m_new);
-        oa *= alpha; ob *= alpha;
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < LPS; ++i) {
-            const float p = vh_exp2(sc[i] - m_new);
-            l += p;
-            u32x4 vv = vq[i];
-            if (!(whole || key0 + 8 * i < len)) vv = u32x4{0u, 0u, 0u, 0u};   // rows beyond the length: select, not * 0
-            oa += f32x4{BF_LO(vv.x), BF_HI(vv.x), BF_LO(vv.y), BF_HI(vv.y)} * p;
-            ob += f32x4{BF_LO(vv.z), BF_HI(vv.z), BF_LO(vv.w), BF_HI(vv.w)} * p;
-        }
-        m = m_new;
-    };
-    for (int c0 = c_begin + w; c0 < c_end; c0 += D * NW) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            const int c = c0 + j * NW;
-            if (c < c_end) {
-                const int cn = c + (D - 1) * NW;
-                if (cn < c_end) load(cn, kf[(j + D - 1) % D], vf[(j + D - 1) % D]);
-                reduce(c, kf[j], vf[j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int sh = 8; sh <= 32; sh <<= 1) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            oa[j] += __shfl_xor(oa[j], sh, 64);
-            ob[j] += __shfl_xor(ob[j], sh, 64);
-        }
-        l += __shfl_xor(l, sh, 64);
-    }
-    if (lane < 8) { st4(&s_o[w][8 * c8], oa); st4(&s_o[w][8 * c8 + 4], ob); }
-    if (lane == 0) { s_m[w] = m; s_l[w] = l; }
-    __syncthreads();
-    M = s_m[0];
-#pragma unroll
-    for (int k = 1; k < NW; ++k) M = fmaxf(M, s_m[k]);
-    L = 0.f;
-    O = 0.f;
-    if (tid < HD) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            const float wgt = s_m[k] == NEG_INF ? 0.f : vh_exp2(s_m[k] - M);   // (a wave without a chunk; M itself is -inf only
-            L += s_l[k] * wgt;                                                  //  for an empty range)
-            O += s_o[k][tid] * wgt;
-        }
-    }
-}
-
-// Key-split form of the ring16 kernel: grid (n_split, B h); split s of a (row, head) takes chunks [s cps, (s + 1) cps) of its
-// ceil(len / 32) and writes one PART_LD record (o[64], m, l) — the layout attn_decode_combine_kernel reads.  A split without keys
-// leaves m = -inf and weighs nothing.
-template <int NW, int D>
-__global__ __launch_bounds__(NW * 64) void attn_decode_ring16_split_kernel(
-    const float* __restrict__ q, int ldq, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
-    const int32_t* __restrict__ cache_len, int len_bias, int n_heads, int S_max, int n_split, float* __restrict__ partial) {
-    __shared__ float s_m[NW], s_l[NW];
-    __shared__ __attribute__((aligned(16))) float s_o[NW][HD];
-    const int bh = blockIdx.y, b = bh / n_heads, head = bh - b * n_heads;
-    const int split = blockIdx.x;
-    const int len = min(cache_len[b] + len_bias, S_max);           // (never a row beyond the allocation)
-    const int nchunks = (len + 31) / 32;
-    const int cps = (nchunks + n_split - 1) / n_split;
-    const int c_begin = split * cps;
-    const int c_end = min(nchunks, c_begin + cps);
-    float M, L, O;
-    ring16_range<NW, D>(q + (int64_t)b * ldq + head * HD, kc + (int64_t)bh * S_max * HD, vc + (int64_t)bh * S_max * HD, len,
-                        c_begin, c_end, s_m, s_l, s_o, M, L, O);
-    const int tid = threadIdx.x;
-    if (tid < HD) {
-        float* pr = partial + ((int64_t)bh * n_split + split) * PART_LD;
-        pr[tid] = O;
-        if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
-    }
-}
 
 static void launch_ring16(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, float* out, int ldo,
                           const int32_t* cache_len, int len_bias, int B, int n_heads, int S_max, void* stream) {
@@ -717,11 +583,11 @@ extern "C" int vh_attn_decode(const float* q, int ldq, const float* kcache, cons
     if (variant != 1 && big && n_split == 1 && nw == 0) {
         const int waves = 8;
         hipExtLaunchKernelGGL((attn_decode_ring_kernel<8, 2>), grid, dim3(waves * 64), 0, s, g_attn_ev[0], g_attn_ev[1], 0, q,
-                              ldq, kcache, vcache, out, ldo, cache_len, len_bias, n_heads, S_max, n_split, (float*)partial);
+                              ldq, kcache, vcache, out, ldo, cache_len, len_bias, n_heads, S_max);
     } else {
         const int waves = nw ? nw : (big ? 16 : 4);
-        if (waves == 16) AD(attn_decode_kernel, 16, true); else if (waves == 8) AD(attn_decode_kernel, 8, true);
-        else AD(attn_decode_kernel, 4, true);
+        if (waves == 16) AD(attn_decode_kernel, 16); else if (waves == 8) AD(attn_decode_kernel, 8);
+        else AD(attn_decode_kernel, 4);
     }
 #undef AD
     if (n_split > 1 && !fused_combine)
@@ -1767,25 +1633,50 @@ extern "C" int vh_attn_rows_bwd_ws(const float* q, int ldq, const float* kcache,
 //                        here there are up to 157 + 64 records, each load a trip beyond the L1.)
 // Record format and units as the key-split decode kernels' (PART_LD floats: o[64], m, l; scores scaled by log2 e / 8).
 // =============================================================================================
+// T: float, or uint16_t for the 16-bit caches of perf mode (vh_attn_decode_shared_kv16) — the prompt's K / V tiles are loaded ONCE
+// as 16-bit and widened to fp32 in registers, then go through the same fp32 MFMA score and output products with the beams as lanes
+// (q is not rounded: fp32 arithmetic on the rounded cache; a bf16 MFMA would round q: not built); records, merge launch and
+// workspace are the fp32 form's.
+template <class T>
 struct SharedArgs {
     const float* q; int ldq;
-    const float* kp; const float* vp;            // prefix (1, h, prefix_S, 64)
+    const T* kp; const T* vp;                    // prefix (1, h, prefix_S, 64)
     int prefix_len, prefix_S;
-    const float* ks; const float* vs;            // suffix (B, h, S_suf, 64)
+    const T* ks; const T* vs;                    // suffix (B, h, S_suf, 64)
     const int32_t* suffix_len; int len_bias;
     int S_suf, n_split;
     float* partial;
     int n_heads, B, n_pb, n_tot, prefix_wgs;     // n_pb: 32-key blocks of the prefix; prefix_wgs = ceil(n_pb / 4) * n_heads
     // grouped form (vh_attn_decode_shared_groups) only: kp / vp are (n_groups, h, prefix_S, 64), group g's prompt holds
     // group_len[g] keys (device array), rows g * beams .. g * beams + beams - 1 are its beams; n_pb counts the blocks of the
-    // prefix CAPACITY and prefix_wgs = ceil(n_pb / 4) * n_heads * n_groups
+    // prefix CAPACITY and prefix_wgs = ceil(n_pb / 4) * n_heads * n_groups.  The other forms: nullptr, 1, B.
     const int32_t* group_len; int n_groups, beams;
 };
 
+// what the prefix role fetches differently per cache type: the 32 values kr[0 .. 31] of a key row as the K fragment (16-bit: 64
+// bytes = four 16-byte loads, widened), and one V element (16-bit: half the bytes of the fp32 form at the SAME 32 load instructions
+// per lane, while K went from eight loads to four — the first thing to look at in a kernel trace of this role)
+__device__ __forceinline__ void prefix_k_fragment(const float* kr, f32x4 (&kf)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) kf[j] = ld4(kr + 4 * j);
+}
+__device__ __forceinline__ void prefix_k_fragment(const uint16_t* kr, f32x4 (&kf)[8]) {
+    u32x4 kw[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) kw[j] = *reinterpret_cast<const u32x4*>(kr + 8 * j);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        kf[2 * j] = f32x4{BF_LO(kw[j].x), BF_HI(kw[j].x), BF_LO(kw[j].y), BF_HI(kw[j].y)};
+        kf[2 * j + 1] = f32x4{BF_LO(kw[j].z), BF_HI(kw[j].z), BF_LO(kw[j].w), BF_HI(kw[j].w)};
+    }
+}
+__device__ __forceinline__ float prefix_v(const float* p) { return *p; }
+__device__ __forceinline__ float prefix_v(const uint16_t* p) { return BF_LO((uint32_t)*p); }
+
 // GROUPS = false: the one shared prompt of SharedArgs::prefix_len keys, columns = all B rows.  GROUPS = true: workgroup
 // (group, head, four blocks); the prompt, its length and the columns are the group's own.
-template <bool GROUPS>
-__device__ __forceinline__ void shared_prefix_role(const SharedArgs& a, int wg, int lane, int w) {
+template <bool GROUPS, class T>
+__device__ __forceinline__ void shared_prefix_role(const SharedArgs<T>& a, int wg, int lane, int w) {
     const int head = wg % a.n_heads;
     int blk, grp = 0, plen = a.prefix_len, nb = a.B;
     if constexpr (GROUPS) {
@@ -1803,26 +1694,22 @@ __device__ __forceinline__ void shared_prefix_role(const SharedArgs& a, int wg, 
     if (blk >= a.n_pb) return;                               // (wave-uniform; no barrier in this role)
     const int r = lane & 31, hh = lane >> 5;
     const int row0 = grp * nb;                               // the first of the nb rows that attend this prompt
-    const float* kb = a.kp + ((int64_t)grp * a.n_heads + head) * a.prefix_S * HD;
-    const float* vb = a.vp + ((int64_t)grp * a.n_heads + head) * a.prefix_S * HD;
+    const T* kb = a.kp + ((int64_t)grp * a.n_heads + head) * a.prefix_S * HD;
+    const T* vb = a.vp + ((int64_t)grp * a.n_heads + head) * a.prefix_S * HD;
     const int k0 = blk * 32;
     const float qscale = 0.125f * LOG2E;
     // K fragment (A operand): key k0 + r, d = 32 hh + j; rows beyond the prompt repeat its last row (masked below).  The k
     // index of the product is only summed over, so both operands simply use the same d per (hh, j).
     f32x4 kf[8];
-    {
-        const float* kr = kb + (int64_t)min(k0 + r, plen - 1) * HD + 32 * hh;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) kf[j] = ld4(kr + 4 * j);
-    }
+    prefix_k_fragment(kb + (int64_t)min(k0 + r, plen - 1) * HD + 32 * hh, kf);
     // V^T operand values: product x pairs key base(x) (lanes hh = 0) with base(x) + 4 (lanes hh = 1), base(x) = (x & 3) +
     // 8 (x >> 2) — exactly the keys whose weights sit in accumulator register x of the two lane halves
     float vf[2][16];
 #pragma unroll
     for (int x = 0; x < 16; ++x) {
         const int key = min(k0 + (x & 3) + 8 * (x >> 2) + 4 * hh, plen - 1);
-        vf[0][x] = vb[(int64_t)key * HD + r];
-        vf[1][x] = vb[(int64_t)key * HD + 32 + r];
+        vf[0][x] = prefix_v(vb + (int64_t)key * HD + r);
+        vf[1][x] = prefix_v(vb + (int64_t)key * HD + 32 + r);
     }
     const bool whole = k0 + 32 <= plen;                      // wave-uniform
     for (int qb = 0; qb * 32 < nb; ++qb) {
@@ -1876,17 +1763,15 @@ __device__ __forceinline__ void shared_prefix_role(const SharedArgs& a, int wg, 
     }
 }
 
-template <bool GROUPS>
-__device__ __forceinline__ void attn_shared_body(const SharedArgs& a) {
-    constexpr int NW = 4;
-    __shared__ float s_m[NW], s_l[NW];
-    __shared__ __attribute__((aligned(16))) float s_o[NW][HD];
+template <bool GROUPS, class T>
+__device__ __forceinline__ void attn_shared_body(const SharedArgs<T>& a) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if ((int)blockIdx.x < a.prefix_wgs) {                    // workgroup-uniform
         shared_prefix_role<GROUPS>(a, blockIdx.x, lane, w);
         return;
     }
-    // ---- suffix role: (beam, head) x key split over the beam's own rows (the burst kernel's body)
+    // ---- suffix role: (beam, head) x key split over the beam's own rows: a 4 x 2 ring without speculative bursts (non-temporal
+    // loads: the beams' rows must not evict the weights)
     const int unit = blockIdx.x - a.prefix_wgs;
     const int split = unit % a.n_split, bh = unit / a.n_split;
     const int b = bh / a.n_heads, head = bh - b * a.n_heads;
@@ -1895,91 +1780,26 @@ __device__ __forceinline__ void attn_shared_body(const SharedArgs& a) {
     if constexpr (GROUPS) {
         if (a.group_len[b / a.beams] <= 0) return;
     }
-    const int c16 = lane & 15, g = lane >> 4;
-    const int len = a.suffix_len[b] + a.len_bias;
-    const int nchunks = (len + 31) >> 5;
-    const int cps = (nchunks + a.n_split - 1) / a.n_split;
-    const int c_begin = split * cps, c_end = min(nchunks, c_begin + cps);
-    const float qscale = 0.125f * LOG2E;
-    const f32x4 q4 = ld4(a.q + (int64_t)b * a.ldq + head * HD + 4 * c16) * qscale;
-    const float* kb = a.ks + (int64_t)bh * a.S_suf * HD + 4 * c16;
-    const float* vb = a.vs + (int64_t)bh * a.S_suf * HD + 4 * c16;
-    float m = NEG_INF, l = 0.f;
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    // two register sets: the next chunk of the wave is requested before the current one is reduced (rows beyond the length
-    // are clamped to the row's last key and masked below: no load is predicated)
-    f32x4 kf[2][8], vf[2][8];
-    auto load = [&](int c, f32x4 (&kq)[8], f32x4 (&vq)[8]) {
-        const int key0 = c * 32 + g;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int key = min(key0 + 4 * i, len - 1);
-            kq[i] = ld4_stream(kb + (int64_t)key * HD);      // (non-temporal: the beams' rows must not evict the weights)
-            vq[i] = ld4_stream(vb + (int64_t)key * HD);
-        }
-    };
-    auto reduce = [&](int c, const f32x4 (&kq)[8], const f32x4 (&vq)[8]) {
-        const int key0 = c * 32 + g;
-        float sc[8];
-        float cmax = NEG_INF;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const f32x4 t = kq[i] * q4;
-            const float d = row16_sum((t.x + t.y) + (t.z + t.w));
-            sc[i] = (key0 + 4 * i < len) ? d : NEG_INF;
-            cmax = fmaxf(cmax, sc[i]);
-        }
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
-        const float m_new = fmaxf(m, cmax);                  // finite: chunk c < nchunks holds >= 1 valid key
-        const float alpha = vh_exp2(m - m_new);
-        o *= alpha;
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float p = vh_exp2(sc[i] - m_new);          // 0 for a masked key (its clamped V row is finite)
-            l += p;
-            o += vq[i] * p;
-        }
-        m = m_new;
-    };
-    if (c_begin + w < c_end) load(c_begin + w, kf[0], vf[0]);
-    for (int c = c_begin + w; c < c_end; c += 2 * NW) {
-        if (c + NW < c_end) load(c + NW, kf[1], vf[1]);
-        reduce(c, kf[0], vf[0]);
-        if (c + NW < c_end) {
-            if (c + 2 * NW < c_end) load(c + 2 * NW, kf[0], vf[0]);
-            reduce(c + NW, kf[1], vf[1]);
-        }
-    }
-#pragma unroll
-    for (int sh = 16; sh <= 32; sh <<= 1) {
-        o.x += __shfl_xor(o.x, sh, 64); o.y += __shfl_xor(o.y, sh, 64);
-        o.z += __shfl_xor(o.z, sh, 64); o.w += __shfl_xor(o.w, sh, 64);
-        l += __shfl_xor(l, sh, 64);
-    }
-    if (lane < 16) st4(&s_o[w][4 * c16], o);
-    if (lane == 0) { s_m[w] = m; s_l[w] = l; }
-    __syncthreads();
-    if (tid >= HD) return;
-    float M = s_m[0];
-#pragma unroll
-    for (int k = 1; k < NW; ++k) M = fmaxf(M, s_m[k]);
-    float L = 0.f, O = 0.f;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-        const float wgt = s_m[k] == NEG_INF ? 0.f : vh_exp2(s_m[k] - M);      // (a wave without a chunk; M itself is -inf
-        L += s_l[k] * wgt;                                                    //  only for an empty split)
-        O += s_o[k][tid] * wgt;
-    }
-    float* pr = a.partial + ((int64_t)bh * a.n_tot + a.n_pb + split) * PART_LD;
-    pr[tid] = O;
-    if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
+    constexpr bool is16 = std::is_same<T, uint16_t>::value;   // (the roundings the two forms have always had: ring_range)
+    float M, L, O;
+    ring_range<T, 4, 2, false, is16, is16>(a.q + (int64_t)b * a.ldq + head * HD, a.ks + (int64_t)bh * a.S_suf * HD,
+                               a.vs + (int64_t)bh * a.S_suf * HD, a.S_suf, [&] {
+                                   int len = a.suffix_len[b] + a.len_bias;
+                                   // (the 16-bit form alone cuts the length at the allocation; kept as each form had it)
+                                   if constexpr (!std::is_same<T, float>::value) len = min(len, a.S_suf);
+                                   const int nchunks = (len + 31) >> 5;
+                                   const int cps = (nchunks + a.n_split - 1) / a.n_split;
+                                   const int c_begin = split * cps;
+                                   return KeyRange{len, c_begin, min(nchunks, c_begin + cps)};
+                               }, M, L, O);
+    if (tid < HD) write_record(a.partial + ((int64_t)bh * a.n_tot + a.n_pb + split) * PART_LD, tid, O, M, L);
 }
 
-__global__ __launch_bounds__(256) void attn_shared_kernel(SharedArgs a) { attn_shared_body<false>(a); }
+__global__ __launch_bounds__(256) void attn_shared_kernel(SharedArgs<float> a) { attn_shared_body<false>(a); }
 // several utterances' beams, each group over its own prompt (vh_attn_decode_shared_groups)
-__global__ __launch_bounds__(256) void attn_shared_groups_kernel(SharedArgs a) { attn_shared_body<true>(a); }
+__global__ __launch_bounds__(256) void attn_shared_groups_kernel(SharedArgs<float> a) { attn_shared_body<true>(a); }
+// 16-bit caches (vh_attn_decode_shared_kv16)
+__global__ __launch_bounds__(256) void attn_shared16_kernel(SharedArgs<uint16_t> a) { attn_shared_body<false>(a); }
 
 // out[b, head] = merge of the n_tot records of (b, head).  256 threads: one parallel pass over the (m, l) pairs gives the
 // weights and the denominator; thread group g = tid >> 6 then sums records g, g + 4, ... of column tid & 63 (independent
@@ -2081,7 +1901,7 @@ extern "C" int vh_attn_decode_shared(const float* q, int ldq, const float* kpref
                vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split_suffix));
     hipStream_t s = (hipStream_t)stream;
     const int prefix_wgs = (n_pb + 3) / 4 * n_heads;
-    SharedArgs a{q, ldq, kprefix, vprefix, prefix_len, prefix_S, ksuffix, vsuffix, suffix_len, len_bias, S_suf, n_split_suffix,
+    SharedArgs<float> a{q, ldq, kprefix, vprefix, prefix_len, prefix_S, ksuffix, vsuffix, suffix_len, len_bias, S_suf, n_split_suffix,
                  (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs, nullptr, 1, B};
     // (the events of vh_ar_decoder_profile_attn bracket this launch: the step's attention kernel in this form)
     hipExtLaunchKernelGGL(attn_shared_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s, g_attn_ev[0],
@@ -2125,7 +1945,7 @@ extern "C" int vh_attn_decode_shared_groups(const float* q, int ldq, const float
                vh_attn_decode_shared_groups_ws_bytes(B, n_heads, prefix_cap, n_split_suffix));
     hipStream_t s = (hipStream_t)stream;
     const int prefix_wgs = (n_pb + 3) / 4 * n_heads * n_groups;
-    SharedArgs a{q, ldq, kprefix, vprefix, prefix_cap, prefix_S, ksuffix, vsuffix, suffix_len, len_bias, S_suf, n_split_suffix,
+    SharedArgs<float> a{q, ldq, kprefix, vprefix, prefix_cap, prefix_S, ksuffix, vsuffix, suffix_len, len_bias, S_suf, n_split_suffix,
                  (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs, prefix_len, n_groups, beams};
     // (the events of vh_ar_decoder_profile_attn bracket this launch, as in the other forms)
     hipExtLaunchKernelGGL(attn_shared_groups_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s,
@@ -2134,133 +1954,6 @@ extern "C" int vh_attn_decode_shared_groups(const float* q, int ldq, const float
                        n_heads, n_pb, n_split_suffix, prefix_len, beams);
     VH_CHECK_LAUNCH("vh_attn_decode_shared_groups");
     return VH_OK;
-}
-
-// =============================================================================================
-// The same two-role launch over 16-bit caches (perf mode with a shared prompt): the prompt's K / V tiles are loaded ONCE as
-// 16-bit and widened to fp32 in registers, then go through the same fp32 MFMA score and output products with the beams as lanes
-// (q is not rounded: fp32 arithmetic on the rounded cache); the beams' own rows run the ring16 burst loop with key splits.
-// Records, merge launch and workspace are the fp32 form's.
-// =============================================================================================
-struct Shared16Args {
-    const float* q; int ldq;
-    const uint16_t* kp; const uint16_t* vp;      // prefix (1, h, prefix_S, 64), 16-bit
-    int prefix_len, prefix_S;
-    const uint16_t* ks; const uint16_t* vs;      // suffix (B, h, S_suf, 64), 16-bit
-    const int32_t* suffix_len; int len_bias;
-    int S_suf, n_split;
-    float* partial;
-    int n_heads, B, n_pb, n_tot, prefix_wgs;
-};
-
-__device__ __forceinline__ void shared16_prefix_role(const Shared16Args& a, int wg, int lane, int w) {
-    const int head = wg % a.n_heads, blk = (wg / a.n_heads) * 4 + w;
-    if (blk >= a.n_pb) return;                               // (wave-uniform; no barrier in this role)
-    const int r = lane & 31, hh = lane >> 5;
-    const uint16_t* kb = a.kp + (int64_t)head * a.prefix_S * HD;
-    const uint16_t* vb = a.vp + (int64_t)head * a.prefix_S * HD;
-    const int k0 = blk * 32;
-    const float qscale = 0.125f * LOG2E;
-    // K fragment (A operand): key k0 + r, d = 32 hh + j: 64 bytes = four 16-byte loads, widened; rows beyond the prompt repeat
-    // its last row (masked below)
-    f32x4 kf[8];
-    {
-        const uint16_t* kr = kb + (int64_t)min(k0 + r, a.prefix_len - 1) * HD + 32 * hh;
-        u32x4 kw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) kw[j] = *reinterpret_cast<const u32x4*>(kr + 8 * j);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            kf[2 * j] = f32x4{BF_LO(kw[j].x), BF_HI(kw[j].x), BF_LO(kw[j].y), BF_HI(kw[j].y)};
-            kf[2 * j + 1] = f32x4{BF_LO(kw[j].z), BF_HI(kw[j].z), BF_LO(kw[j].w), BF_HI(kw[j].w)};
-        }
-    }
-    // V^T operand values (the fp32 kernel's pairing of keys and accumulator registers), one 16-bit element per load: half the
-    // bytes of the fp32 form at the SAME 32 load instructions per lane (K above went from eight loads to four) — the first thing
-    // to look at in a kernel trace of this role
-    float vf[2][16];
-#pragma unroll
-    for (int x = 0; x < 16; ++x) {
-        const int key = min(k0 + (x & 3) + 8 * (x >> 2) + 4 * hh, a.prefix_len - 1);
-        vf[0][x] = BF_LO((uint32_t)vb[(int64_t)key * HD + r]);
-        vf[1][x] = BF_LO((uint32_t)vb[(int64_t)key * HD + 32 + r]);
-    }
-    const bool whole = k0 + 32 <= a.prefix_len;              // wave-uniform
-    for (int qb = 0; qb * 32 < a.B; ++qb) {
-        const int b = min(qb * 32 + r, a.B - 1);             // lanes beyond B repeat the last beam (never stored)
-        f32x16 s;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) s[e] = 0.f;
-        {
-            const float* qr = a.q + (int64_t)b * a.ldq + head * HD + 32 * hh;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const f32x4 qf = ld4(qr + 4 * j) * qscale;
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j].x, qf.x, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j].y, qf.y, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j].z, qf.z, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j].w, qf.w, s, 0, 0, 0);
-            }
-        }
-        // D reg x of lane (r = beam, hh): key k0 + (x & 3) + 8 (x >> 2) + 4 hh
-        float m = NEG_INF;
-#pragma unroll
-        for (int x = 0; x < 16; ++x) {
-            if (!whole && k0 + (x & 3) + 8 * (x >> 2) + 4 * hh >= a.prefix_len) s[x] = NEG_INF;
-            m = fmaxf(m, s[x]);
-        }
-        m = fmaxf(m, __shfl_xor(m, 32, 64));                 // the beam's other key half; finite: key k0 < prefix_len
-        float l = 0.f;
-#pragma unroll
-        for (int x = 0; x < 16; ++x) {
-            s[x] = vh_exp2(s[x] - m);
-            l += s[x];
-        }
-        l += __shfl_xor(l, 32, 64);
-        f32x16 o0, o1;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { o0[e] = 0.f; o1[e] = 0.f; }
-#pragma unroll
-        for (int x = 0; x < 16; ++x) {                       // O^T += V^T P^T: P^T is the B operand as it lies
-            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[0][x], s[x], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[1][x], s[x], o1, 0, 0, 0);
-        }
-        if (qb * 32 + r < a.B) {
-            float* pr = a.partial + (((int64_t)b * a.n_heads + head) * a.n_tot + blk) * PART_LD;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                st4(pr + 8 * g4 + 4 * hh, f32x4{o0[4 * g4], o0[4 * g4 + 1], o0[4 * g4 + 2], o0[4 * g4 + 3]});
-                st4(pr + 32 + 8 * g4 + 4 * hh, f32x4{o1[4 * g4], o1[4 * g4 + 1], o1[4 * g4 + 2], o1[4 * g4 + 3]});
-            }
-            if (hh == 0) { pr[HD] = m; pr[HD + 1] = l; }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void attn_shared16_kernel(Shared16Args a) {
-    constexpr int NW = 4;
-    __shared__ float s_m[NW], s_l[NW];
-    __shared__ __attribute__((aligned(16))) float s_o[NW][HD];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if ((int)blockIdx.x < a.prefix_wgs) {                    // workgroup-uniform
-        shared16_prefix_role(a, blockIdx.x, lane, w);
-        return;
-    }
-    // ---- suffix role: (beam, head) x key split over the beam's own rows (the ring16 burst loop)
-    const int unit = blockIdx.x - a.prefix_wgs;
-    const int split = unit % a.n_split, bh = unit / a.n_split;
-    const int b = bh / a.n_heads, head = bh - b * a.n_heads;
-    const int len = min(a.suffix_len[b] + a.len_bias, a.S_suf);
-    const int nchunks = (len + 31) >> 5;
-    const int cps = (nchunks + a.n_split - 1) / a.n_split;
-    const int c_begin = split * cps, c_end = min(nchunks, c_begin + cps);
-    float M, L, O;
-    ring16_range<NW, 2>(a.q + (int64_t)b * a.ldq + head * HD, a.ks + (int64_t)bh * a.S_suf * HD,
-                        a.vs + (int64_t)bh * a.S_suf * HD, len, c_begin, c_end, s_m, s_l, s_o, M, L, O);
-    if (tid >= HD) return;
-    float* pr = a.partial + ((int64_t)bh * a.n_tot + a.n_pb + split) * PART_LD;
-    pr[tid] = O;
-    if (tid == 0) { pr[HD] = M; pr[HD + 1] = L; }
 }
 
 extern "C" int vh_attn_decode_shared_kv16(const float* q, int ldq, const uint16_t* kprefix16, const uint16_t* vprefix16,
@@ -2289,8 +1982,8 @@ extern "C" int vh_attn_decode_shared_kv16(const float* q, int ldq, const uint16_
                vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split_suffix));
     hipStream_t s = (hipStream_t)stream;
     const int prefix_wgs = (n_pb + 3) / 4 * n_heads;
-    Shared16Args a{q, ldq, kprefix16, vprefix16, prefix_len, prefix_S, ksuffix16, vsuffix16, suffix_len, len_bias, S_suf,
-                   n_split_suffix, (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs};
+    SharedArgs<uint16_t> a{q, ldq, kprefix16, vprefix16, prefix_len, prefix_S, ksuffix16, vsuffix16, suffix_len, len_bias, S_suf,
+                           n_split_suffix, (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs, nullptr, 1, B};
     // (the events of vh_ar_decoder_profile_attn bracket this launch: the step's attention kernel in this form)
     hipExtLaunchKernelGGL(attn_shared16_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s, g_attn_ev[0],
                           g_attn_ev[1], 0, a);
