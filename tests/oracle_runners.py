@@ -424,3 +424,315 @@ def audit_sampled_rows(sd, cfg, text, rows, scores, prompt_len, max_new, top_k, 
                              f'midpoint by {rep["off"]:+.6f})')
         report.append(rep)
     return report
+
+
+# ---- training at every width and row count (tests/test_train_widths_cpu.py, tests/test_train_widths_gpu.py) ----------------
+# Whole models: (d_model, n_heads, dim_feedforward) of a two-layer model, and which models / NAR stages train at it.
+TRAIN_WIDTHS = {
+    'base': (768, 12, 3072),           # layernorm_bwd_kernel<4> with a masked last slot; the common size
+    'd640': (640, 10, 1296),           # dff % 32 != 0: the node-by-node stack (LinearFn, GeluFn, vh_colsum) at head width 64
+    'd896': (896, 14, 1792),           # <4> masked
+    'odd_heads': (576, 9, 1152),       # 64 * n_heads is no multiple of 128
+    'd1152': (1152, 18, 2304),         # <8> masked
+    'd1536': (1536, 24, 3072),         # <8> under AdaptiveLayerNorm; adaproj K = 1536
+    'd2048': (2048, 32, 2048),         # the upper bound of vh_layernorm_bwd / vh_adaproj_*
+    'beyond': (2112, 33, 256),         # refused
+}
+TRAIN_WIDTH_RUNS = [('base', 'ValleAR', None), ('base', 'ValleNAR', 3), ('d640', 'ValleAR', None), ('d896', 'ValleAR', None),
+                    ('odd_heads', 'ValleAR', None), ('odd_heads', 'ValleNAR', 2), ('d1152', 'ValleAR', None),
+                    ('d1536', 'ValleNAR', 5), ('d2048', 'ValleAR', None), ('d2048', 'ValleNAR', 1)]
+
+
+def train_width_inputs(case, model):
+    """(config kwargs, state dict, batch) of whole-model case `case`: two layers, dropout 0, synth.make_state_dict(rich=True);
+    AR: three rows of 5..12 text and 13..30 audio tokens (the size of cases.ar_train_inputs), NAR: three rows of 10 text
+    tokens and 36 frames (cases.nar_inputs' lengths)."""
+    from valle2_amd import synth
+    d, h, dff = TRAIN_WIDTHS[case]
+    kw = dict(d_model=d, n_heads=h, dim_feedforward=dff, num_layers=2, dropout=0.0,
+              norm='LayerNorm' if model == 'ValleAR' else 'AdaptiveLayerNorm')
+    cfg = C.cfg_of(kw)
+    sd = synth.make_state_dict(cfg, model, seed=300 + d, rich=True)
+    if model == 'ValleAR':
+        batch = synth.synth_ar_batch(cfg, 3, tok_range=(5, 12), code_range=(13, 30), seed=400 + d)
+    else:
+        batch = synth.synth_nar_batch(cfg, 3, n_tokens=10, n_frames=36, seed=400 + d)
+    return kw, sd, batch
+
+
+def oracle_training_loss(sd, cfg, batch, model, stage=None, dtype=torch.float64, grads=True):
+    """(loss, params) of the oracle's training loss with the state dict cast to `dtype`; grads=True differentiates it by torch
+    autograd (params[name].grad).  The oracle builds no floating-point constant of its own on this path (masks are bool, the
+    position tables come from the state dict), so the cast of the state dict is the whole of the float64 form."""
+    params = {k: v.to(dtype).clone().requires_grad_(grads and not k.endswith('.pe')) for k, v in sd.items()}
+    with torch.set_grad_enabled(grads):
+        loss = O.ar_training_loss(params, cfg, batch) if model == 'ValleAR' else O.nar_training_loss(params, cfg, batch, stage)
+        if grads:
+            loss.backward()
+    assert loss.dtype == dtype
+    return loss.detach(), params
+
+
+# Row kernels.  Every reference below is plain torch in `dtype`: float64 is what the GPU tests compare against, float32 is the
+# CPU companion's emulation of a kernel (the same arithmetic in the kernels' number format) — the measured error of the
+# emulation against float64 is what the tolerances of the sums over rows rest on, and with one `fault` planted it is what
+# the comparison helpers must reject.
+SUM_MARGIN = 4              # a sum over rows on the GPU may be off by this many times the fp32 emulation's own error
+
+
+def sum_rows(t):
+    """Sum over dim 0.  float32: one row added after the other in fp32 (the plain order, fixed whatever the thread count:
+    the error of a sum that promises no order, which is what the kernels' atomics give); float64: torch's sum."""
+    if t.dtype == torch.float64:
+        return t.sum(0)
+    acc = torch.zeros_like(t[0])
+    for r in range(t.shape[0]):
+        acc += t[r]
+    return acc
+
+
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def ln_inputs(rows, d, mean=0.3, dres=False):
+    """Inputs of test_train_gpu.test_layernorm_backward (2 * randn + mean), fp32."""
+    inp = dict(x=2 * torch.randn(rows, d, generator=_g(1)) + mean, gamma=1 + 0.1 * torch.randn(d, generator=_g(2)),
+               beta=0.1 * torch.randn(d, generator=_g(3)), scale=1 + 0.2 * torch.randn(d, generator=_g(4)),
+               shift=0.2 * torch.randn(d, generator=_g(5)), dy=torch.randn(rows, d, generator=_g(6)))
+    if dres:
+        inp['dres'] = torch.randn(rows, d, generator=_g(7))
+    return inp
+
+
+LN_WAVES = 2048             # waves of a vh_layernorm_bwd launch at >= 2048 rows (256 workgroups of 8): wave w owns rows w, w + 2048, ...
+
+
+def ln_reference(inp, ada, dtype=torch.float64, fault=None, eps=1e-5):
+    """y = s * (gamma * xhat + beta) + t and its backward under dy (+ dres added to dx, dcol = column sums of that dx), written
+    out from the definition.  fault (fp32 emulations of a wrong kernel):
+      'tail_unmasked'   the slot after the row's last 16-byte column group is read as data: the four floats that follow the
+                        row in memory enter the sum its mean is made of
+      'last_row'        rows >= LN_WAVES (a wave's second row) are never reached: dx stays as allocated (zero here), no sums
+      'stale_ahead'     a wave's second row is computed from the operands of its first (the look-ahead never refilled)."""
+    x, gamma, beta, dy = (inp[k].to(dtype) for k in ('x', 'gamma', 'beta', 'dy'))
+    s, t = (inp['scale'].to(dtype), inp['shift'].to(dtype)) if ada else (None, None)
+    dres = inp['dres'].to(dtype) if 'dres' in inp else None
+    rows, d = x.shape
+    if fault == 'stale_ahead':
+        x, dy = x.clone(), dy.clone()
+        x[LN_WAVES:], dy[LN_WAVES:] = x[:rows - LN_WAVES], dy[:rows - LN_WAVES]
+        if dres is not None:
+            dres = dres.clone()
+            dres[LN_WAVES:] = dres[:rows - LN_WAVES]
+    rsum = lambda m: m.sum(1, keepdim=True)                                                      # noqa: E731
+    mu = rsum(x) / d
+    if fault == 'tail_unmasked':
+        after = torch.cat([x.reshape(-1), x.new_zeros(4)]).unfold(0, d + 4, d)[:, d:]           # (rows, 4): what follows each row
+        mu = (rsum(x) + rsum(after)) / d
+    v = x - mu
+    rstd = (rsum(v * v) / d + eps).rsqrt()
+    xhat = v * rstd
+    u = gamma * xhat + beta
+    du = dy * s if ada else dy
+    g = du * gamma
+    m1, m2 = rsum(g) / d, rsum(g * xhat) / d
+    dx = (g - m1 - xhat * m2) * rstd
+    if dres is not None:
+        dx = dx + dres
+    keep = slice(0, LN_WAVES) if fault == 'last_row' else slice(None)
+    out = dict(y=s * u + t if ada else u, dgamma=sum_rows((du * xhat)[keep]), dbeta=sum_rows(du[keep]))
+    if ada:
+        out.update(dscale=sum_rows((dy * u)[keep]), dshift=sum_rows(dy[keep]))
+    if fault == 'last_row':
+        dx = dx.clone()
+        dx[LN_WAVES:] = 0
+    if dres is not None:
+        out['dcol'] = sum_rows(dx[keep])
+    out['dx'] = dx
+    return out
+
+
+LN_SUMS = ('dgamma', 'dbeta', 'dscale', 'dshift', 'dcol')
+
+
+def ce_inputs(rows, V, ld=None, amp=None):
+    """Logits (rows, V) of scale 2 as test_train_gpu.test_cross_entropy_forward_backward draws them — a column slice of a
+    (rows, ld) buffer when ld is given; amp: uniform in [-amp, amp] instead, every row holding both ends — and targets."""
+    buf = 2 * torch.randn(rows, ld or V, generator=_g(9))
+    if amp is not None:
+        buf = amp * (2 * torch.rand(rows, ld or V, generator=_g(9)) - 1)
+        buf[:, 0], buf[:, V - 1] = amp, -amp
+    return buf[:, :V], torch.randint(0, V, (rows,), generator=_g(10))
+
+
+def ce_reference(logits, target, upstream, dtype=torch.float64, fault=None):
+    """Mean cross entropy over the rows and d(upstream * loss) / d logits.  fault 'ld_for_V' (fp32 emulation): the row's
+    maximum and log-sum-exp run over the buffer's ld columns."""
+    rows, V = logits.shape
+    lg = logits.to(dtype)
+    wide = lg
+    if fault == 'ld_for_V':
+        wide = torch.as_strided(logits, (rows, logits.stride(0)), (logits.stride(0), 1)).to(dtype)
+    lse = torch.logsumexp(wide, dim=1)
+    per_row = lse - lg[torch.arange(rows), target]
+    dl = torch.exp(lg - lse[:, None])
+    dl[torch.arange(rows), target] -= 1
+    return dict(loss=sum_rows(per_row / rows), dlogits=dl * (upstream / rows))
+
+
+SOFTMAX_CASES = {       # (B, h, Tq, Tk, mode): the cases of vh_softmax_rows / vh_softmax_bwd
+    'full': (2, 2, 5, 5, 'full'), 'prefix_rows': (2, 3, 70, 70, 'prefix'), 'prefix_tq_lt_tk': (1, 2, 33, 97, 'prefix'),
+    'explicit_pad': (2, 2, 64, 129, 'explicit'), 'one_query': (3, 1, 1, 200, 'full'),
+}
+SOFTMAX_SCALE = 48 ** -0.5
+
+
+def softmax_inputs(name):
+    """Raw scores S and upstream dP (B, h, Tq, Tk) and the mask arguments of the case (CPU tensors: x_len / x_len_dev / kv_len
+    int32, mask / pad uint8).  Every row keeps a visible key: kv_len >= 1, x_len >= 1, the diagonal unmasked and unpadded."""
+    B, h, Tq, Tk, mode = SOFTMAX_CASES[name]
+    S = 7 * torch.randn(B, h, Tq, Tk, generator=_g(50))                    # q . k at head width 48: standard deviation 7
+    dP = torch.randn(B, h, Tq, Tk, generator=_g(51))
+    spec = {}
+    if name == 'prefix_rows':
+        spec = dict(x_len_dev=torch.tensor([20, 35], dtype=torch.int32), kv_len=torch.tensor([70, 61], dtype=torch.int32))
+    elif name == 'prefix_tq_lt_tk':
+        spec = dict(x_len=70, kv_len=torch.tensor([90], dtype=torch.int32))          # queries on both sides of the prefix's end
+    elif name == 'explicit_pad':
+        mask = torch.rand(Tq, Tk, generator=_g(52)) < 0.3
+        mask[torch.arange(Tq), Tk - Tq + torch.arange(Tq)] = False
+        pad = torch.zeros(B, Tk, dtype=torch.bool)
+        pad[1, 10:40] = True                                               # (the diagonal lies in columns 65 .. 128)
+        spec = dict(mask=mask.to(torch.uint8), pad=pad.to(torch.uint8))
+    elif name == 'one_query':
+        spec = dict(kv_len=torch.tensor([200, 1, 77], dtype=torch.int32))
+    return S, dP, mode, spec
+
+
+def softmax_visible(name, spec, fault=None):
+    """(B, 1, Tq, Tk) bool: the keys query i of batch row b sees — vh_attn_rows' rule (include/valle_hip.h), the query's
+    position being Tk - Tq + i.  fault 'no_qpos' (emulation): the position taken for i."""
+    B, h, Tq, Tk, mode = SOFTMAX_CASES[name]
+    j = torch.arange(Tk)[None, None, :]
+    i = torch.arange(Tq)[None, :, None]
+    if mode == 'explicit':
+        vis = ~spec['mask'].bool()[None] & ~spec['pad'].bool()[:, None, :]
+    else:
+        kvl = spec['kv_len'].long().clamp(max=Tk)[:, None, None] if 'kv_len' in spec else torch.full((B, 1, 1), Tk)
+        vis = (j < kvl).expand(B, Tq, Tk)
+        if mode == 'prefix':
+            xl = spec['x_len_dev'].long()[:, None, None] if 'x_len_dev' in spec else torch.full((B, 1, 1), spec['x_len'])
+            qpos = i if fault == 'no_qpos' else Tk - Tq + i
+            vis = vis & ((j < xl) | ((qpos >= xl) & (j <= qpos)))
+    return vis[:, None]
+
+
+def softmax_reference(name, dtype=torch.float64, fault=None):
+    """P = softmax(S * scale + mask) and dS = scale * P * (dP - sum(dP * P)) of the case."""
+    S, dP, mode, spec = softmax_inputs(name)
+    vis = softmax_visible(name, spec, fault)
+    assert bool(softmax_visible(name, spec).any(-1).all()), 'a row without a visible key'
+    P = torch.softmax((S.to(dtype) * SOFTMAX_SCALE).masked_fill(~vis, O.NEG_INF), dim=-1)
+    dPd = dP.to(dtype)
+    return dict(P=P, dS=SOFTMAX_SCALE * P * (dPd - (dPd * P).sum(-1, keepdim=True)))
+
+
+
+def embed_inputs(d, T, B=3, vocab=40, J=3):
+    """Ragged rows ending in a run of ONE id (test_train_gpu.test_embedding_backward_and_colsum): ids (B, T, J) int64 whose
+    column slices are what the kernels read, J tables, upstream gradient for t0 + T positions."""
+    tabs = [torch.randn(vocab, d, generator=_g(20 + j)) for j in range(J)]
+    ids = torch.randint(0, vocab, (B, T, J), generator=_g(34))
+    for b, n_real in enumerate((T, (T * 9) // 16, 1)[:B]):
+        ids[b, n_real:] = vocab - 1
+    return tabs, ids
+
+
+def embed_table_grads(ids, dy, vocab, dtype=torch.float64):
+    """d tables[j] = scatter-add of dy (B, T, d) over ids[..., j]: position after position in `dtype` (index_add_ walks the
+    index in order)."""
+    B, T, J = ids.shape
+    flat = dy.to(dtype).reshape(B * T, -1)
+    return [torch.zeros(vocab, flat.shape[1], dtype=dtype).index_add_(0, ids[..., j].reshape(-1), flat) for j in range(J)]
+
+
+COLSUM_CASES = [(1, 4, 4), (63, 260, 260), (65, 768, 1000), (2053, 2048, 2048)]      # (rows, cols, ld)
+
+
+def colsum_inputs(rows, cols, ld):
+    buf = torch.randn(rows, ld, generator=_g(60))
+    return buf[:, :cols], torch.randn(cols, generator=_g(61))          # x (a column slice), what `out` holds before the call
+
+
+def colsum_reference(x, out0, dtype=torch.float64):
+    return out0.to(dtype) + sum_rows(x.to(dtype).contiguous())
+
+
+def worst(got, ref):
+    """Largest absolute difference of `got` from the float64 reference."""
+    return float((got.detach().cpu().double() - ref.detach().double()).abs().max())
+
+
+def check_close(name, got, ref, atol=2e-5, rtol=1e-4):
+    """A per-element quantity against float64 with the tolerances of tests/test_train_gpu.py; the failure names it."""
+    got, ref = got.detach().cpu().double(), ref.detach().double()
+    assert got.shape == ref.shape, f'{name}: shape {tuple(got.shape)} vs {tuple(ref.shape)}'
+    bad = ~((got - ref).abs() <= atol + rtol * ref.abs())              # (not <=: a NaN fails)
+    assert not bool(bad.any()), f'{name}: {int(bad.sum())} of {bad.numel()} elements off, worst {worst(got, ref):.3e} (atol {atol:g} rtol {rtol:g})'
+
+
+def check_sum(name, got, ref, measured):
+    """A sum over rows against float64: at most SUM_MARGIN times the fp32 emulation's own measured error."""
+    err = worst(got, ref)
+    assert err <= SUM_MARGIN * measured, f'{name}: worst error {err:.3e} > {SUM_MARGIN} x {measured:.3e}'      # (a NaN fails)
+    return err
+
+
+def embed_reference(ids, dy, t0, vocab, dtype=torch.float64):
+    """Table gradients of the embedding cases: t0 = 0, the J tables under dy (EmbedSumPeFn); t0 > 0, EmbedConcatFn's two parts —
+    table 0 over the first t0 positions of ids[..., 0], then the J tables over all T positions at row offset t0."""
+    grads = embed_table_grads(ids, dy[:, t0:], vocab, dtype)
+    if t0:
+        first = embed_table_grads(ids[:, :t0, :1], dy[:, :t0], vocab, dtype)[0]
+        grads[0] = grads[0] + first if dtype == torch.float64 else grads[0].add_(first)
+    return grads
+
+
+def _collect(checks):
+    """Run every check, then fail once, naming each quantity that failed (the CPU companion asserts on the names)."""
+    failed = []
+    for name, fn in checks:
+        try:
+            fn()
+        except AssertionError as e:
+            failed.append((name, str(e)))
+    assert not failed, 'failed: ' + ', '.join(n for n, _ in failed) + ' | ' + ' | '.join(m for _, m in failed)
+
+
+def check_ln(got, ref, measured):
+    """LayerNorm backward results {dx, dgamma, dbeta[, dscale, dshift][, dcol]} against the float64 reference."""
+    checks = [('dx', lambda: check_close('dx', got['dx'], ref['dx']))]
+    checks += [(q, lambda q=q: check_sum(q, got[q], ref[q], measured[q])) for q in measured]
+    if 'dcol' in measured:
+        checks.append(('dcol_of_dx', lambda: check_sum('dcol against the columns of the dx written', got['dcol'],
+                                                       got['dx'].detach().cpu().double().sum(0), measured['dcol'])))
+    _collect(checks)
+
+
+def check_ce(loss, dlogits, ref, rows):
+    """Cross entropy.  The loss is a mean over rows: each row's term to test_train_gpu's rtol 1e-6 + atol 1e-6, plus the sum
+    of `rows` non-negative fp32 terms in an order nobody fixes (a wave's rows, its workgroup, then one atomic per workgroup):
+    the rounding errors of n additions, each at most 2^-24 of the running sum, add up like a random walk — sqrt(n) * 2^-24 *
+    the sum (Higham, Accuracy and Stability of Numerical Algorithms, section 4.2's rule of thumb: the worst-case n * u holds
+    for no more than sqrt(n) * u in practice).  One scalar's measured fp32 error says nothing (at 8229 rows the plain fp32 sum
+    happens to land 2e-8 from the float64 one), so this bound is worked out, not measured.  A row skipped moves the loss by
+    1 / rows of itself: 20 times the allowance at 8229 rows.  dlogits per element at 1e-7 + 1e-4."""
+    def loss_ok():
+        err, tol = worst(loss, ref['loss']), 1e-6 + (1e-6 + rows ** 0.5 * 2.0 ** -24) * float(ref['loss'].abs())
+        assert err <= tol, f'loss: error {err:.3e} > {tol:.3e}'
+    _collect([('loss', loss_ok), ('dlogits', lambda: check_close('dlogits', dlogits, ref['dlogits'], atol=1e-7, rtol=1e-4))])
+
+
+def check_softmax(P, dS, ref):
+    _collect([('P', lambda: check_close('P', P, ref['P'])), ('dS', lambda: check_close('dS', dS, ref['dS']))])

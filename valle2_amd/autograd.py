@@ -661,9 +661,18 @@ def _stack_transposes(transformer):
 LAYER_OUTPUT_HOOK = None
 
 
+MAX_TRAIN_D_MODEL = 2048       # vh_layernorm_bwd and vh_adaproj_fwd / _bwd hold a row in registers: 8 float4 per lane
+
+
 def transformer_train(transformer, x, B, T, spec, embedding=None):
     layers = list(transformer.layers)
     cfg = transformer.hparams
+    if cfg.d_model > MAX_TRAIN_D_MODEL:
+        # refused HERE, before a graph exists: the forward kernels take d_model up to 4096, so the loss would come out and
+        # the backward would stop at the top layer's LayerNorm — after the head's and that layer's FeedForward gradients
+        # had been written (into a FlatAdamW's flat buffer, claimed for the step)
+        raise _lib.VhError(f'training serves d_model <= {MAX_TRAIN_D_MODEL} (the LayerNorm backward, vh_layernorm_bwd), '
+                           f'got d_model={cfg.d_model}')
     fused = (ATTENTION_BACKWARD == 'flash' and cfg.dim_feedforward % 32 == 0 and cfg.d_model % 32 == 0 and
              cfg.d_model == cfg.n_heads * HEAD_DIM)      # (another head width: node by node on the general kernels)
     if not fused:
