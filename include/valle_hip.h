@@ -520,7 +520,9 @@ typedef struct {
     /* perf mode of the decode step, second half (round 6; with vh_ar_decoder_desc.kv_bf16): h16 copies (vh_h16_format) of the four
      * matrices a step streams — wqkv_f16 (3d, d) and w1_f16 (dff, d) of the FOLDED weights above, wo16 (d, d), w2_16 (d, dff).
      * All four non-NULL: the step's QKV, out-projection and FeedForward launches read them (half the weight bytes; fp32
-     * accumulators, fp32 rows, c1 / c2 / biases fp32); any NULL: the fp32 matrices, as before. */
+     * accumulators, fp32 rows, c1 / c2 / biases fp32); any NULL: the fp32 matrices, as before.  A caller that sets them should
+     * point qkv_c1 / w1_c1 at the row sums of the ROUNDED matrices (sum_k wqkv_f16[n,k], sum_k w1_f16[n,k]): with the sums of the
+     * fp32 fold the epilogue leaves rstd * mean * (rowsum(Wf16) - c1), which grows with a row's |mean| / std. */
     const uint16_t *wqkv_f16, *wo16, *w1_f16, *w2_16;
 } vh_layer;
 

@@ -337,8 +337,9 @@ def _forced_logits64(sd, cfg, text, codes_rows):
     for r, c in enumerate(codes_rows):
         codes[r, :len(c)] = c
     text = text.cpu().long()
-    batch = {'tokens': text[None].repeat(len(codes_rows), 1), 'tokens_lens': torch.full((len(codes_rows),), len(text)),
-             'codes': codes, 'codes_lens': lens}
+    if text.dim() == 1:                                        # (2-D: a text of its own per row, equal lengths)
+        text = text[None].repeat(len(codes_rows), 1)
+    batch = {'tokens': text, 'tokens_lens': torch.full((len(codes_rows),), text.shape[1]), 'codes': codes, 'codes_lens': lens}
     with torch.no_grad():
         return O.ar_logits(sd64, cfg, batch).permute(0, 2, 1)
 
@@ -424,6 +425,239 @@ def audit_sampled_rows(sd, cfg, text, rows, scores, prompt_len, max_new, top_k, 
                              f'midpoint by {rep["off"]:+.6f})')
         report.append(rep)
     return report
+
+
+# ---- the decode step over h16 weights (VALLE2_DECODE_W16) against a float64 mirror -----------------------------------------
+# (tests/test_decode_w16_cpu.py, tests/test_decode_w16_gpu.py)
+W16_ATOL, W16_RTOL = 2e-4, 1e-4     # the project's summation-order bound (tests/test_perf_mode_beams_gpu.py)
+W16_POWER = 5                       # the mirror stands at least this many tolerances from the unrounded oracle
+W16_STEPS = 7                       # forced tokens: the logits of step 0 are the prompt pass's, steps 1..6 are six decode steps
+W16_FREE_STEPS = 24
+W16_MAX_ROWS = 64
+W16_MODEL_SEED = 77
+# model -> (d_model, n_heads, dim_feedforward, text ids, prompt frames, head scale): contexts (text + BOS + prompt) of 20, 27, 33
+# and 40 positions.  The scale brings the oracle's logit standard deviation at the prompts' ends to about 2.2 (as drawn:
+# 0.160, 0.229, 0.362 and 0.631; float64, on the CPU).  'd128s32' is d128 with a dim_feedforward that takes 32-column slices.
+W16_MODELS = {
+    'd128': (128, 2, 528, 9, 10, 13.8),        # dim_feedforward % 32 != 0: slices of 16
+    'd256': (256, 4, 1024, 14, 12, 9.7),
+    'd512': (512, 8, 2048, 16, 16, 6.1),
+    'd1024': (1024, 16, 2048, 20, 19, 3.5),
+    'd128s32': (128, 2, 544, 9, 10, 13.5),     # ffn_decode_kernel<128, 32>: no model of the four reaches it
+}
+
+
+def w16_model_tol(h16):
+    """What perf-mode logits may differ from the unrounded reference's: MODEL_TOL of tests/test_bf16_gpu.py."""
+    return 1.5e-2 if h16 == torch.float16 else 5e-2
+
+
+W16_FAULTS = ('swap_halves', 'no_residual', 'w2_shift8', 'eos_row_zero', 'c1_shift', 'k_late')
+
+
+def w16_inputs(model):
+    """(config kwargs, state dict, texts (64, T), firsts (64, F), forced (W16_STEPS,)) of w16 model `model`: two layers,
+    LayerNorm, synth.make_state_dict(rich=True), the head scaled (asserted by the callers on the oracle's logits at the prompts'
+    ends: standard deviation 1.5 .. 3).  Every row draws a text and a prompt of its own; a case of B rows takes the first B."""
+    from valle2_amd import synth
+    d, h, dff, T, F, scale = W16_MODELS[model]
+    kw = dict(d_model=d, n_heads=h, dim_feedforward=dff, num_layers=2, dropout=0.0, norm='LayerNorm', top_k=1, tok_p=1.0,
+              max_audio_len=W16_FREE_STEPS)
+    cfg = C.cfg_of(kw)
+    sd = synth.make_state_dict(cfg, 'ValleAR', seed=W16_MODEL_SEED, rich=True)
+    sd['proj.weight'] = sd['proj.weight'] * scale
+    gen = _g(7000 + d)
+    texts = torch.randint(0, cfg.vocab_size, (W16_MAX_ROWS, T), generator=gen)
+    firsts = torch.randint(0, cfg.num_audio_tokens, (W16_MAX_ROWS, F), generator=gen)
+    forced = torch.randint(0, cfg.num_audio_tokens, (W16_STEPS,), generator=gen)
+    assert len({tuple(r.tolist()) for r in texts}) == W16_MAX_ROWS and len({tuple(r.tolist()) for r in firsts}) == W16_MAX_ROWS
+    assert 20 <= T + F + 1 <= 40
+    return kw, sd, texts, firsts, forced
+
+
+def w16_check_std(logits0, what=''):
+    """The head's scale, as audit_inputs asserts it: the logits at every prompt's end have a standard deviation of 1.5 .. 3."""
+    std = logits0.double().std(-1)
+    assert 1.5 <= float(std.min()) and float(std.max()) <= 3.0, f'inputs drifted: {what} logit std {float(std.min()):.3f} .. {float(std.max()):.3f}'
+    return std
+
+
+def w16_oracle_logits(sd, cfg, texts, firsts, forced):
+    """The unrounded float64 oracle's logits (B, len(forced), V + 1) at the steps of a forced decode: step t is read at audio
+    position prompt_len - 1 + t of rows [BOS, prompt, forced[:-1]]."""
+    bos = torch.tensor([cfg.num_audio_tokens + 1])
+    pl = firsts.shape[1] + 1
+    rows = [torch.cat([bos, f.long(), forced[:-1].long()]) for f in firsts]
+    return _forced_logits64(sd, cfg, texts, rows)[:, pl - 1:pl - 1 + len(forced)]
+
+
+def w16_distance(a, ref):
+    """max |a - ref| / (atol + rtol |ref|): above 1, torch.testing.assert_close(a, ref, atol=W16_ATOL, rtol=W16_RTOL) fails."""
+    a, ref = a.detach().cpu().double(), ref.detach().cpu().double()
+    return float(((a - ref).abs() / (W16_ATOL + W16_RTOL * ref.abs())).max())
+
+
+class W16Mirror:
+    """What a perf_mode='kv' decode with h16 weights computes, restated in float64 from the state dict alone.
+
+    Prompt pass: the float64 oracle with full-precision weights (O.transformer, use_cache=True); its K/V rounded once to h16.
+    A step (include/valle_hip.h, "LayerNorm folded into the weights"): Wf = W * gamma as ONE fp32 multiply, rounded to h16;
+    c1 = sum_k Wf16[n,k] from the ROUNDED matrix (engine.decode_weights16; c1='fold': from the unrounded fold, as the route was
+    first built — what the row-offset case of tests/test_decode_w16_cpu.py measures) and c2 = sum_k beta[k] W[n,k] + b[n] from
+    the unrounded fold (float64 sums rounded to fp32);
+    the products rstd * (x Wf16^T - mean * c1) + c2 in float64; the new K/V rows rounded to h16 before they are attended; Wo,
+    W2 and the head rounded to h16; exact-erf GELU; q and the residual stream never rounded.
+
+    h16: torch.float16 | torch.bfloat16, or torch.float64 for "nothing rounded" (the fold in float64 too: the oracle itself).
+    weights16=False: the matrices stay fp32 and only K/V are rounded — the fp32-weight perf_mode='kv' decoder.
+    fault: one of W16_FAULTS planted (what the GPU comparison must be able to see).
+    x_offset=(row, c): c added to every element of that row's step input (the residual stream keeps it; LayerNorm's mean is c
+    off): `self.offset_ratio` is then the smallest |mean| / std over that row's LayerNorm inputs."""
+
+    def __init__(self, sd, cfg, texts, firsts, h16, weights16=True, fault=None, x_offset=None, c1='rounded'):
+        assert (fault is None or fault in W16_FAULTS) and c1 in ('rounded', 'fold'), (fault, c1)
+        self.c1_rounded = c1 == 'rounded'
+        self.cfg, self.h16, self.exact, self.fault, self.x_offset = cfg, h16, h16 == torch.float64, fault, x_offset
+        self.w16 = weights16 and not self.exact
+        self.sd = {k: v.double() for k, v in sd.items()}
+        self.sd32 = sd
+        self.offset_ratio = float('inf')
+        texts, firsts = torch.as_tensor(texts).cpu().long(), torch.as_tensor(firsts).cpu().long()
+        B, self.T = texts.shape
+        self.pl = firsts.shape[1] + 1
+        s = self.sd
+        codes0 = torch.cat([torch.full((B, 1), cfg.num_audio_tokens + 1), firsts], dim=1)
+        tok = O.add_position(O.embed(s['tokens_emb.word_embeddings.weight'], texts), s['tokens_position_emb.pe'])
+        aud = O.add_position(O.embed(s['audio_emb.word_embeddings.weight'], codes0), s['audio_position_emb.pe'])
+        with torch.no_grad():
+            y, kv = O.transformer(s, 'transformer.', torch.cat([tok, aud], dim=1), cfg, attn_mask=O.build_attn_mask(self.T, self.pl),
+                                  use_cache=True)
+        self.logits0 = y[:, -1] @ s['proj.weight'].T                     # the prompt pass's head: full precision
+        self.kv = [[self._round(k), self._round(v)] for k, v in kv]
+        self.k_prev = [None] * cfg.num_layers                            # fault 'k_late'
+        self.n_steps = 0
+        self.layers = [self._layer_tables(i) for i in range(cfg.num_layers)]
+        self.proj = self._matrix(s['proj.weight'], sd['proj.weight'])
+        if fault == 'eos_row_zero':
+            self.proj = self.proj.clone()
+            self.proj[cfg.num_audio_tokens] = 0
+
+    def _round(self, t):
+        return t if self.exact else t.to(self.h16).double()
+
+    def _matrix(self, w64, w32):
+        return w32.float().to(self.h16).double() if self.w16 else w64
+
+    def _fold(self, W, gamma, beta, bias):
+        """(Wf as the step reads it, c1, c2) of `vh_ln_fold` + `decode_weights16`."""
+        s64 = lambda k: self.sd[k]                                                                    # noqa: E731
+        if self.exact:
+            Wf = s64(W) * s64(gamma)
+            Wq = Wf
+        else:
+            Wf32 = self.sd32[W].float() * self.sd32[gamma].float()
+            Wf = Wf32.double()
+            Wq = Wf32.to(self.h16).double() if self.w16 else Wf
+        c1 = (Wq if self.c1_rounded else Wf).sum(1)
+        c2 = (s64(W) * s64(beta)).sum(1) + (s64(bias) if bias is not None else 0)
+        if not self.exact:
+            c1, c2 = c1.float().double(), c2.float().double()
+        if self.fault == 'c1_shift':
+            c1 = torch.cat([c1[:1], c1[:-1]])
+        return Wq, c1, c2
+
+    def _layer_tables(self, i):
+        p = f'transformer.layers.{i}.'
+        qkv = self._fold(p + 'self_attn.qkv.weight', p + 'norm1.weight', p + 'norm1.bias', None)
+        w1 = self._fold(p + 'ffn.linear_1.weight', p + 'norm2.weight', p + 'norm2.bias', p + 'ffn.linear_1.bias')
+        if self.fault == 'swap_halves':
+            Wq = qkv[0]
+            qkv = (Wq.view(Wq.shape[0], -1, 2).flip(-1).reshape(Wq.shape),) + qkv[1:]
+        wo = self._matrix(self.sd[p + 'self_attn.out.weight'], self.sd32[p + 'self_attn.out.weight'])
+        w2 = self._matrix(self.sd[p + 'ffn.linear_2.weight'], self.sd32[p + 'ffn.linear_2.weight'])
+        if self.fault == 'w2_shift8':
+            w2 = w2.clone()
+            w2[:, 8:16] = w2[:, 16:24]
+        return dict(qkv=qkv, w1=w1, wo=wo, bo=self.sd[p + 'self_attn.out.bias'], w2=w2, b2=self.sd[p + 'ffn.linear_2.bias'])
+
+    def _folded_linear(self, x, tab, row_stats):
+        Wq, c1, c2 = tab
+        mean = x.mean(-1, keepdim=True)
+        var = ((x - mean) ** 2).mean(-1, keepdim=True)
+        if row_stats is not None:
+            self.offset_ratio = min(self.offset_ratio, float(mean[row_stats].abs() / var[row_stats].sqrt()))
+        return (var + 1e-5).rsqrt() * (x @ Wq.T - mean * c1) + c2
+
+    def step(self, tokens):
+        """One decode step: `tokens` (B,) int64 (or one id for every row) are appended at the next audio position; returns the
+        logits (B, V + 1) that follow them."""
+        cfg, s = self.cfg, self.sd
+        B, h = self.logits0.shape[0], cfg.n_heads
+        tokens = torch.as_tensor(tokens).long().reshape(-1).expand(B)
+        pos = self.pl + self.n_steps
+        x = s['audio_emb.word_embeddings.weight'][tokens] + s['audio_position_emb.pe'][pos, 0]
+        row = None
+        if self.x_offset is not None:
+            row = self.x_offset[0]
+            x = x.clone()
+            x[row] += self.x_offset[1]
+        d = x.shape[1]
+        hd = d // h
+        for i, L in enumerate(self.layers):
+            q, k, v = self._folded_linear(x, L['qkv'], row).chunk(3, dim=-1)
+            k, v = (self._round(t).view(B, h, 1, hd) for t in (k, v))
+            K, V = self.kv[i]
+            k_seen = k
+            if self.fault == 'k_late':                                   # this step's row lands one position on: the keys end
+                k_seen = self.k_prev[i] if self.k_prev[i] is not None else torch.zeros_like(k)   # with what was there before
+                self.k_prev[i] = k
+            K_att = torch.cat([K, k_seen], dim=2)
+            self.kv[i] = [torch.cat([K, k_seen], dim=2), torch.cat([V, v], dim=2)]
+            V = self.kv[i][1]
+            sc = (q.view(B, h, 1, hd) @ K_att.transpose(-1, -2)) / math.sqrt(hd)
+            attn = (torch.softmax(sc, dim=-1) @ V).reshape(B, d)
+            o = attn @ L['wo'].T + L['bo']
+            x = o if self.fault == 'no_residual' else x + o
+            hid = torch.nn.functional.gelu(self._folded_linear(x, L['w1'], row))
+            x = x + hid @ L['w2'].T + L['b2']
+        self.n_steps += 1
+        return x @ self.proj.T
+
+
+def w16_mirror_logits(sd, cfg, texts, firsts, forced, keep, h16, fault=None, weights16=True, x_offset=None, trace=None,
+                      c1='rounded'):
+    """Logits (B, len(keep), V + 1) of the W16Mirror teacher-forced as generation._decode_forced does it: forced[t] is appended
+    after step t for every row, whatever the head said; the logits of step 0 are the prompt pass's.  trace (a dict) receives
+    'offset_ratio'."""
+    forced = torch.as_tensor(forced).cpu().long()
+    with torch.no_grad():
+        m = W16Mirror(sd, cfg, texts, firsts, h16, weights16=weights16, fault=fault, x_offset=x_offset, c1=c1)
+        out = {0: m.logits0}
+        for t in range(1, max(keep) + 1):
+            out[t] = m.step(forced[t - 1])
+    if trace is not None:
+        trace['offset_ratio'] = m.offset_ratio
+    return torch.stack([out[t] for t in keep], dim=1)
+
+
+def w16_mirror_greedy(sd, cfg, texts, firsts, steps, h16):
+    """(tokens, top-2 margins, top logits), each (B, steps), of the W16Mirror decoding greedily: a row that has drawn EOS keeps
+    drawing it (valle_ar.py:166), so its tokens count up to and including the first EOS."""
+    eos = cfg.num_audio_tokens
+    with torch.no_grad():
+        m = W16Mirror(sd, cfg, texts, firsts, h16)
+        logits, toks, margins, tops = m.logits0, [], [], []
+        for t in range(steps):
+            top2 = torch.topk(logits, 2, dim=-1)
+            tok = top2.indices[:, 0]
+            if toks:
+                tok = torch.where(toks[-1] == eos, torch.full_like(tok, eos), tok)
+            toks.append(tok)
+            margins.append(top2.values[:, 0] - top2.values[:, 1])
+            tops.append(top2.values[:, 0])
+            if t + 1 < steps:
+                logits = m.step(tok)
+    return torch.stack(toks, dim=1), torch.stack(margins, dim=1), torch.stack(tops, dim=1)
 
 
 # ---- training at every width and row count (tests/test_train_widths_cpu.py, tests/test_train_widths_gpu.py) ----------------

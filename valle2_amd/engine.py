@@ -269,9 +269,13 @@ DECODE_W16 = os.environ.get('VALLE2_DECODE_W16', '0') == '1'
 
 
 def decode_weights16(transformer, folded):
-    """Per layer (Wqkv∘γ1, Wo, W1∘γ2, W2) as h16 for the PERF-MODE decode step (the second half of SURVEY section 7's perf mode:
-    16-bit storage of what a step streams, fp32 accumulate — the folded matrices are narrowed AFTER the fold, so the
-    epilogue's c1 / c2 stay the fp32 sums of the fold).  Built once per weight set, beside the folded weights."""
+    """Per layer (Wqkv∘γ1, Wo, W1∘γ2, W2, c1 of Wqkv∘γ1, c1 of W1∘γ2) for the PERF-MODE decode step (the second half of SURVEY
+    section 7's perf mode: 16-bit storage of what a step streams, fp32 accumulate): the four matrices as h16 — the folded ones
+    narrowed AFTER the fold — and the epilogue's c1 of the two folded ones summed over the ROUNDED matrix, so that
+    rstd * (x Wf16^T - mean * c1) is LayerNorm(x) Wf16^T exactly.  With the c1 of the unrounded fold the epilogue leaves
+    rstd * mean * (rowsum(Wf16) - c1): nothing for a centred row, 2e-2 on the logits of a row whose mean is 20 standard
+    deviations (tests/test_decode_w16_cpu.py).  c2 stays the fp32 sum of the fold.  Built once per weight set, beside the
+    folded weights."""
     layers = list(transformer.layers)
     key = (_WEIGHTS_EPOCH, id(folded)) + tuple((t.data_ptr(), t._version) for l in layers
                                                for t in (l.self_attn.out.weight, l.ffn.linear_2.weight))
@@ -279,8 +283,11 @@ def decode_weights16(transformer, folded):
     if cached is not None and cached[0] == key:
         return cached[1]
     with torch.no_grad(), torch.inference_mode(False):
-        out = [(kernels.to_bf16(folded[i][0][0]), kernels.to_bf16(l.self_attn.out.weight.detach()),
-                kernels.to_bf16(folded[i][1][0]), kernels.to_bf16(l.ffn.linear_2.weight.detach())) for i, l in enumerate(layers)]
+        out = []
+        for i, l in enumerate(layers):                # (the row sums: once per weight set, in float64 — nothing a step runs)
+            wq, w1 = kernels.to_bf16(folded[i][0][0]), kernels.to_bf16(folded[i][1][0])
+            out.append((wq, kernels.to_bf16(l.self_attn.out.weight.detach()), w1, kernels.to_bf16(l.ffn.linear_2.weight.detach()),
+                        wq.double().sum(1).float().contiguous(), w1.double().sum(1).float().contiguous()))
     _derived(transformer)['decode16'] = (key, out, folded)       # (the folded list is kept alive: its id is part of the key)
     return out
 
@@ -727,9 +734,10 @@ class ArDecoder(StepSampler):
         self._w16 = self._proj16 = None
         if self.kv_bf16 and DECODE_W16 and self.ffn_ws is not None and d in (128, 256, 512, 1024) and cfg.dim_feedforward % 16 == 0:
             self._w16 = decode_weights16(model.transformer, self._folded)
-            for i, (wq, wo, w1, w2) in enumerate(self._w16):
+            for i, (wq, wo, w1, w2, c1q, c1w) in enumerate(self._w16):
                 self._table[i].wqkv_f16, self._table[i].wo16 = ptr(wq), ptr(wo)
                 self._table[i].w1_f16, self._table[i].w2_16 = ptr(w1), ptr(w2)
+                self._table[i].qkv_c1, self._table[i].w1_c1 = ptr(c1q), ptr(c1w)     # (this decoder's table: the sums of the h16 matrices)
             with torch.inference_mode(False):
                 self._proj16 = kernels.to_bf16(model.proj.weight.detach()) if d % 8 == 0 else None
         self.w16 = self._w16 is not None
