@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 134            /* 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 135            /* 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -483,7 +483,9 @@ int vh_head_greedy(const float* x, int ldx, const float* proj_w, float* logits, 
  * always keeps the largest), torch.multinomial and the log-prob gather; then the bookkeeping of
  * vh_greedy_step plus sum_logprobs[b] += logprob while row b has not finished (valle_ar.py:167).
  * Randomness is a counter-based generator keyed on (seed, row, audio_pos[b]) — replaying a captured
- * graph draws fresh numbers; the stream is NOT torch's, so parity is distributional.  V <= 2048 (wider rows: vh_sample_step_wide). */
+ * graph draws fresh numbers; the stream is NOT torch's, so parity is distributional.  V <= 2048 (wider rows: vh_sample_step_wide).
+ * One filter and one seed for every row of the launch, the row's index b as the generator's `row`; a seed, key and filter PER
+ * ROW: vh_sample_step_rows below. */
 int vh_sample_step(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
                    float temperature, uint64_t seed, int64_t* codes, int64_t codes_stride,
                    int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
@@ -503,6 +505,39 @@ int vh_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k,
                         int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                         const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
                         float* x_next, int B, int d, void* stream);
+
+/* ---- K12 (stochastic) with PER-ROW sampling: every row's seed, draw key and filter from device memory ----------
+ * One record per row, indexed as logits / codes / audio_pos are.  32 bytes, 16-byte aligned (two 16-byte loads per
+ * workgroup): seed at byte 0, key at 8, top_k at 12, top_p at 16, temperature at 20, 8 reserved bytes (write zeros).
+ *   seed         the row's own seed: the draw at audio position p is uniform01(seed, key, p) — nothing of the launch (its
+ *                scalar seed, the decoder's seed_dev, the row's index in the launch) enters it;
+ *   key          the `row` of the counter-based generator: the beam index WITHIN the request, so the beams of one request
+ *                draw different numbers from one seed and the same numbers wherever the request's rows stand;
+ *   top_k        as vh_sample_step's (<= 0 keeps all).  top_k == 1 is vh_greedy_step's token: the largest logit, the lowest
+ *                index on ties (compared as values: -0.0 == +0.0), log-probability exactly 0, whatever top_p and temperature say;
+ *   top_p        as vh_sample_step's;
+ *   temperature  > 0 (NOT checked: the records live on the device); the kernel divides 1.0f by it in fp32, as the host does
+ *                for vh_sample_step, so a record that holds a call's values filters exactly as that call.
+ * The caller may rewrite records between launches (stream-ordered); a captured graph holds the pointer, not the values. */
+typedef struct {
+    uint64_t seed;
+    uint32_t key;
+    int32_t top_k;
+    float top_p;
+    float temperature;
+    uint32_t reserved[2];
+} vh_row_sampling;
+
+/* vh_sample_step / vh_sample_step_wide with rs[b] in place of (top_k, top_p, temperature, seed) and of the row index as
+ * the draw key; everything else as there (V <= 2048 / V <= VH_SAMPLE_MAX_V).  rs: device array of B records, not NULL. */
+int vh_sample_step_rows(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs, int64_t* codes,
+                        int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                        const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
+                        float* x_next, int B, int d, void* stream);
+int vh_sample_step_wide_rows(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs, int64_t* codes,
+                             int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                             const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
+                             float* x_next, int B, int d, void* stream);
 
 /* ---- composite: one AR decode step / hipGraph replay ----------------------------------------
  * The 5 launches per layer of one decode step (LN1+QKV+append, decode attention, out-proj+
@@ -547,7 +582,7 @@ typedef struct {
     int64_t *codes;                   /* (B, codes_stride) growing code sequence */
     int64_t codes_stride;
     /* sampling (valle/config.py:48-51): top_k == 1 → vh_greedy_step, else vh_sample_step (V <= 2048) or
-     * vh_sample_step_wide (V <= VH_SAMPLE_MAX_V; a wider V is refused when the decoder is created) */
+     * vh_sample_step_wide (V <= VH_SAMPLE_MAX_V; a wider V is refused when the decoder is created); per row: row_sampling below */
     int top_k;
     float top_p, temperature;
     uint64_t seed;
@@ -589,6 +624,11 @@ typedef struct {
      * n_split) bytes.  fp32 caches at head width 64 only: kv_bf16 and other head widths are refused. */
     int n_groups, beams_per_group, prefix_cap;
     const int32_t *prefix_lens;
+    /* optional: per-row sampling, a device array of B vh_row_sampling records (16-byte aligned) read by every step.  With it
+     * the step samples through vh_sample_step_rows / vh_sample_step_wide_rows whatever top_k says (a record's top_k == 1 is that
+     * row's greedy token); top_k, top_p, temperature, seed and seed_dev above are not read, V <= VH_SAMPLE_MAX_V.  Refused with
+     * head_ws (the fused greedy head has no sampler behind it).  NULL: the forms above. */
+    const vh_row_sampling *row_sampling;
 } vh_ar_decoder_desc;
 
 typedef struct vh_ar_decoder vh_ar_decoder;

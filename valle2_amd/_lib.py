@@ -32,6 +32,12 @@ class VhDropoutSpec(C.Structure):
 c_dropp = C.POINTER(VhDropoutSpec)
 
 
+class VhRowSampling(C.Structure):
+    """include/valle_hip.h vh_row_sampling: one row's seed, draw key and filter (32 bytes)."""
+    _fields_ = [('seed', C.c_uint64), ('key', C.c_uint32), ('top_k', C.c_int32), ('top_p', C.c_float),
+                ('temperature', C.c_float), ('reserved', C.c_uint32 * 2)]
+
+
 class VhLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         'ln1_g', 'ln1_b', 'wqkv', 'wo', 'bo', 'ln2_g', 'ln2_b', 'w1', 'b1', 'w2', 'b2',
@@ -56,6 +62,7 @@ class VhArDecoderDesc(C.Structure):
         ('prefix_len', C.c_int), ('prefix_S', C.c_int), ('attn_partial_bytes', C.c_size_t),
         ('head_ws', C.c_void_p), ('head_ws_bytes', C.c_size_t), ('seed_dev', C.c_void_p), ('proj_w16', C.c_void_p),
         ('n_groups', C.c_int), ('beams_per_group', C.c_int), ('prefix_cap', C.c_int), ('prefix_lens', C.c_void_p),
+        ('row_sampling', C.c_void_p),
     ]
 
 
@@ -185,6 +192,11 @@ SIGNATURES = {
     'vh_sample_step_wide': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64,
                                       c_i64p, C.c_int64, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p,
                                       c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    # seed, draw key and filter per row (ABI 135)
+    'vh_sample_step_rows': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64p, C.c_int64, c_i32p, c_i32p,
+                                      c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    'vh_sample_step_wide_rows': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64p, C.c_int64, c_i32p, c_i32p,
+                                           c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
     'vh_categorical_rows': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint32,
                                       c_i64p, C.c_int64, c_f32p, C.c_void_p]),
     'vh_adamw_ws_bytes': (C.c_size_t, []),

@@ -162,8 +162,9 @@ def synthesize(ar, nar, prompt_tokens: Tensor, prompt, target_tokens: Tensor, co
 
 @torch.inference_mode()
 def synthesize_many(ar, nar, items, codec=None, greedy_nar: bool = False):
-    """`synthesize` for several utterances at once: items = [(prompt_tokens, prompt, target_tokens), ...] with `prompt` as in
-    `synthesize`.  AR: ValleAR.generate_many (one grouped decode, every utterance's beams over its own prompt K/V); NAR: one
+    """`synthesize` for several utterances at once: items = [(prompt_tokens, prompt, target_tokens[, sampling]), ...] with
+    `prompt` as in `synthesize`; the optional fourth element is the utterance's valle2_amd.Sampling, handed to the AR model only
+    (the NAR stage's draws stay keyed on its packed rows: greedy_nar=True is its reproducible form).  AR: ValleAR.generate_many (one grouped decode, every utterance's beams over its own prompt K/V); NAR: one
     ragged ValleNAR.generate_batch over all utterances.  Returns a list, per utterance what `synthesize` returns."""
     return _synthesize_list(ar, nar, items, codec, greedy_nar, lambda utts: ar.generate_many(utts))
 
@@ -172,25 +173,25 @@ def synthesize_many(ar, nar, items, codec=None, greedy_nar: bool = False):
 def synthesize_queued(ar, nar, items, codec=None, greedy_nar: bool = False, *, slots=None):
     """`synthesize_many` with the AR side on ValleAR.generate_queued: `slots` utterances decode at once and a finished one
     hands its rows to the next waiting one (slots=None: as many as one launch holds).  Same arguments otherwise, same result
-    for a greedy AR model; a sampled one draws per slot (see generate_queued)."""
+    for a greedy AR model and for items that carry a Sampling; a sampled one without draws per slot (see generate_queued)."""
     return _synthesize_list(ar, nar, items, codec, greedy_nar, lambda utts: ar.generate_queued(utts, slots=slots))
 
 
 def _synthesize_list(ar, nar, items, codec, greedy_nar, ar_generate):
     cfg = ar.config
     utts = []
-    for prompt_tokens, prompt, target_tokens in items:
+    for prompt_tokens, prompt, target_tokens, *sampling in items:
         if prompt.dtype.is_floating_point:
             if codec is None:
                 raise ValueError('synthesize_many: a waveform prompt needs a codec to encode it')
             prompt = codec.encode(prompt)
-        utts.append((prompt_tokens, to_prompt_codes(prompt, cfg), target_tokens))                 # codes (T, Q)
+        utts.append((prompt_tokens, to_prompt_codes(prompt, cfg), target_tokens, *sampling))     # codes (T, Q)
     firsts = ar_generate(utts)                                                          # per utterance (Ty,) first codebook
     for i, first in enumerate(firsts):
         if first.numel() == 0:
             raise RuntimeError(f'synthesize: the AR model emitted EOS at its first step (no frames to refine) for utterance {i}')
     dev = firsts[0].device
-    codes = nar.generate_batch([torch.cat([pt.to(dev), tt.to(dev)]) for pt, _, tt in utts], [pc.to(dev) for _, pc, _ in utts],
+    codes = nar.generate_batch([torch.cat([pt.to(dev), tt.to(dev)]) for pt, _, tt, *_ in utts], [pc.to(dev) for _, pc, *_ in utts],
                                firsts, greedy=greedy_nar)
     outs = [from_generated(c, cfg) for c in codes]                                      # (Q, Ty) each
     if codec is None:

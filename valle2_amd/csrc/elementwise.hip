@@ -405,14 +405,39 @@ __device__ __forceinline__ uint32_t okey(float x) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// Per-row sampling (rs != NULL): the block of row b takes its seed, the `row` key of its draws and its filter from rs[b]
+// (block-uniform: one block serves one row); the scalar seed and *seed_dev are not added.  1 / temperature is the host's
+// fp32 division, so a record holding the call's values filters as the call does.  top_k == 1 is the arg-max with the lowest
+// index on ties and a log-probability of exactly 0 (greedy_step_kernel's token): the scores stay unscaled (a scale could
+// merge neighbouring logits into a tie), zeros of either sign become +0.0 (greedy_step_kernel compares values, for which
+// -0.0 == +0.0; the radix keys would order them), top_p is off and only the first survivor in index order is kept.
+#define ROW_SAMPLING_LOAD(rec)                                            \
+    do {                                                                  \
+        const vh_row_sampling r_ = (rec);                                 \
+        seed = r_.seed;                                                   \
+        draw_key = r_.key;                                                \
+        top_k = r_.top_k;                                                 \
+        top_p = r_.top_p;                                                 \
+        inv_temp = 1.0f / r_.temperature;                                 \
+        greedy = top_k == 1;                                              \
+        if (greedy) { top_p = 1.0f; inv_temp = 1.0f; }                    \
+    } while (0)
+
 __global__ __launch_bounds__(256) void sample_step_kernel(
     const float* __restrict__ logits, int ldl, int V, int eos, int top_k, float top_p, float inv_temp,
     uint64_t seed, int64_t* __restrict__ codes, int64_t codes_stride, int32_t* __restrict__ eos_count,
     const int32_t* __restrict__ pos_base, float* __restrict__ sum_logprobs,
     const float* __restrict__ audio_emb, const float* __restrict__ pe, int32_t* __restrict__ audio_pos,
-    int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, int npow2, const uint64_t* __restrict__ seed_dev) {
-    // a captured graph freezes `seed`; a decoder that outlives one generate() keeps the call's seed in device memory instead
-    if (seed_dev) seed += *seed_dev;
+    int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, int npow2, const uint64_t* __restrict__ seed_dev,
+    const vh_row_sampling* __restrict__ rs) {
+    uint32_t draw_key = blockIdx.x;   // the `row` of uniform01: the launch's row index, or the request's own key
+    bool greedy = false;
+    if (rs) {
+        ROW_SAMPLING_LOAD(rs[blockIdx.x]);
+    } else if (seed_dev) {
+        // a captured graph freezes `seed`; a decoder that outlives one generate() keeps the call's seed in device memory instead
+        seed += *seed_dev;
+    }
     __shared__ float s_val[SAMPLE_MAXV];
     __shared__ int s_idx[SAMPLE_MAXV];
     __shared__ int s_hist[256];
@@ -434,7 +459,8 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     if (fast) {
         float vmax = -INFINITY;
         for (int i = tid; i < V; i += 256) {
-            const float x = lr[i] * inv_temp;
+            float x = lr[i] * inv_temp;
+            if (greedy) x += 0.0f;                      // -0.0 -> +0.0: the keys then order the scores as a float compare does
             s_val[i] = x;
             vmax = fmaxf(vmax, x);
         }
@@ -490,7 +516,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
         __syncthreads();
         int base = incl - mine;
         for (int ww = 0; ww < wv; ++ww) base += s_hist[ww];
-        const int n_keep = s_hist[0] + s_hist[1] + s_hist[2] + s_hist[3];
+        const int n_keep = greedy ? 1 : s_hist[0] + s_hist[1] + s_hist[2] + s_hist[3];   // (greedy: the lowest index of the ties)
         __syncthreads();                                 // s_hist / s_val are re-used below
         // compact (value, index); the survivor count is small (top_k plus ties) but may be anything <= V
         float kv[8];
@@ -505,7 +531,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
             float total = 0.f;
             for (int j0 = 0; j0 < n_keep; j0 += 64) total += (j0 + lane < n_keep) ? expf(s_val[j0 + lane] - m) : 0.f;
             total = wave_sum(total);
-            const float u = uniform01(seed, (uint32_t)b, (uint32_t)pos) * total;
+            const float u = uniform01(seed, draw_key, (uint32_t)pos) * total;
             float run = 0.f;
             int pick = n_keep - 1;
             bool found = false;
@@ -558,6 +584,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
                 const float kth = s_val[min(top_k, V) - 1];
                 n_keep = min(top_k, V);
                 while (n_keep < V && s_val[n_keep] >= kth) ++n_keep;         // ties kept
+                if (greedy) n_keep = 1;                                      // (V == 1: the only row top_k == 1 brings here)
             }
             const float m = s_val[0];
             float total = 0.f;
@@ -575,7 +602,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
                 total = 0.f;
                 for (int i = 0; i < n_keep; ++i) total += expf(s_val[i] - m);
             }
-            const float u = uniform01(seed, (uint32_t)b, (uint32_t)pos) * total;
+            const float u = uniform01(seed, draw_key, (uint32_t)pos) * total;
             float acc = 0.f;
             int pick = n_keep - 1;
             for (int i = 0; i < n_keep; ++i) {
@@ -589,6 +616,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
         pick_tok = s_sel[2];
         pick_logprob = s_red[4];
     }
+    if (greedy) pick_logprob = 0.f;
     if (tid == 0) {
         int64_t* row = codes + (int64_t)b * codes_stride;
         int tok = pick_tok;
@@ -613,9 +641,10 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     }
 }
 
-// vh_sample_step with the seed = seed + *seed_dev (seed_dev may be NULL): the decoder plan's form (plan.hip)
+// vh_sample_step with the seed = seed + *seed_dev (seed_dev may be NULL), or with per-row records (rs != NULL: top_k, top_p,
+// temperature, seed and seed_dev are not read): the decoder plan's form (plan.hip)
 int vh_internal_sample_step(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
-                            float temperature, uint64_t seed, const uint64_t* seed_dev, int64_t* codes, int64_t codes_stride,
+                            float temperature, uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs, int64_t* codes, int64_t codes_stride,
                             int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                             const float* audio_emb, const float* pe, int32_t* audio_pos,
                             int32_t* cache_len, float* x_next, int B, int d, void* stream) {
@@ -623,14 +652,15 @@ int vh_internal_sample_step(const float* logits, int ldl, int V, int eos, int to
                VH_EINVAL, "vh_sample_step: null pointer");
     VH_REQUIRE(B > 0 && V > 0 && V <= SAMPLE_MAXV && ldl >= V && d > 0 && d % 4 == 0, VH_EINVAL,
                "vh_sample_step: bad dims B=%d V=%d (<= %d) ldl=%d d=%d", B, V, SAMPLE_MAXV, ldl, d);
-    VH_REQUIRE(temperature > 0.f, VH_EINVAL, "vh_sample_step: temperature must be positive");
+    VH_REQUIRE(rs || temperature > 0.f, VH_EINVAL, "vh_sample_step: temperature must be positive");
+    VH_REQUIRE(vh_aligned16(rs), VH_EALIGN, "vh_sample_step: the per-row sampling records must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(audio_emb) && vh_aligned16(pe) && vh_aligned16(x_next), VH_EALIGN,
                "vh_sample_step: audio_emb/pe/x_next must be 16-byte aligned");
     int npow2 = 2;
     while (npow2 < V) npow2 <<= 1;
     hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
-                       eos, top_k, top_p, 1.0f / temperature, seed, codes, codes_stride, eos_count,
-                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, npow2, seed_dev);
+                       eos, top_k, top_p, rs ? 1.0f : 1.0f / temperature, seed, codes, codes_stride, eos_count,
+                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, npow2, seed_dev, rs);
     VH_CHECK_LAUNCH("vh_sample_step");
     return VH_OK;
 }
@@ -640,8 +670,17 @@ extern "C" int vh_sample_step(const float* logits, int ldl, int V, int eos, int 
                               int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                               const float* audio_emb, const float* pe, int32_t* audio_pos,
                               int32_t* cache_len, float* x_next, int B, int d, void* stream) {
-    return vh_internal_sample_step(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, codes, codes_stride, eos_count,
+    return vh_internal_sample_step(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, nullptr, codes, codes_stride, eos_count,
                                    pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
+}
+
+extern "C" int vh_sample_step_rows(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs, int64_t* codes,
+                                  int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                                  const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
+                                  float* x_next, int B, int d, void* stream) {
+    VH_REQUIRE(rs, VH_EINVAL, "vh_sample_step_rows: null sampling records (vh_sample_step takes one filter for every row)");
+    return vh_internal_sample_step(logits, ldl, V, eos, 0, 1.f, 1.f, 0, nullptr, rs, codes, codes_stride, eos_count, pos_base, sum_logprobs,
+                                  audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -724,8 +763,15 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
     uint64_t seed, int64_t* __restrict__ codes, int64_t codes_stride, int32_t* __restrict__ eos_count,
     const int32_t* __restrict__ pos_base, float* __restrict__ sum_logprobs,
     const float* __restrict__ audio_emb, const float* __restrict__ pe, int32_t* __restrict__ audio_pos,
-    int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, const uint64_t* __restrict__ seed_dev) {
-    if (seed_dev) seed += *seed_dev;
+    int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, const uint64_t* __restrict__ seed_dev,
+    const vh_row_sampling* __restrict__ rs) {
+    uint32_t draw_key = blockIdx.x;
+    bool greedy = false;
+    if (rs) {
+        ROW_SAMPLING_LOAD(rs[blockIdx.x]);
+    } else if (seed_dev) {
+        seed += *seed_dev;
+    }
     __shared__ float s_val[VH_SAMPLE_MAX_V];
     __shared__ int s_idx[VH_SAMPLE_MAX_V];
     __shared__ int s_hist[256];
@@ -742,7 +788,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
     // 1. scores and their maximum
     float vmax = -INFINITY;
     for (int i = tid; i < V; i += WIDE_THREADS) {
-        const float x = lr[i] * inv_temp;
+        float x = lr[i] * inv_temp;
+        if (greedy) x += 0.0f;                          // -0.0 -> +0.0, as in the narrow kernel
         s_val[i] = x;
         vmax = fmaxf(vmax, x);
     }
@@ -829,7 +876,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
         at += __popcll(bal);
     }
     __syncthreads();
-    const float u01 = uniform01(seed, (uint32_t)b, (uint32_t)pos);
+    if (greedy) n = 1;                                 // slot 0: the lowest index of the ties for the maximum
+    const float u01 = uniform01(seed, draw_key, (uint32_t)pos);
 
     if (top_k > 0 && top_k < V && top_p == 1.0f) {
         // fast path: the draw over the survivors in index order
@@ -880,7 +928,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
     }
     const int slot = s_sel[2];
     const int pick_tok = s_idx[slot];
-    const float pick_logprob = (s_val[slot] - m) - logf(s_tot);
+    const float pick_logprob = greedy ? 0.f : (s_val[slot] - m) - logf(s_tot);
 
     if (tid == 0) {
         int64_t* row = codes + (int64_t)b * codes_stride;
@@ -906,9 +954,10 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
     }
 }
 
-// vh_sample_step_wide with the seed = seed + *seed_dev (seed_dev may be NULL): the decoder plan's form (plan.hip)
+// vh_sample_step_wide with the seed = seed + *seed_dev (seed_dev may be NULL), or with per-row records (rs != NULL: top_k, top_p,
+// temperature, seed and seed_dev are not read): the decoder plan's form (plan.hip)
 int vh_internal_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
-                                 float temperature, uint64_t seed, const uint64_t* seed_dev, int64_t* codes,
+                                 float temperature, uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs, int64_t* codes,
                                  int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                                  const float* audio_emb, const float* pe, int32_t* audio_pos,
                                  int32_t* cache_len, float* x_next, int B, int d, void* stream) {
@@ -916,12 +965,13 @@ int vh_internal_sample_step_wide(const float* logits, int ldl, int V, int eos, i
                VH_EINVAL, "vh_sample_step_wide: null pointer");
     VH_REQUIRE(B > 0 && V > 0 && V <= VH_SAMPLE_MAX_V && ldl >= V && d > 0 && d % 4 == 0, VH_EINVAL,
                "vh_sample_step_wide: bad dims B=%d V=%d (<= %d) ldl=%d d=%d", B, V, VH_SAMPLE_MAX_V, ldl, d);
-    VH_REQUIRE(temperature > 0.f, VH_EINVAL, "vh_sample_step_wide: temperature must be positive");
+    VH_REQUIRE(rs || temperature > 0.f, VH_EINVAL, "vh_sample_step_wide: temperature must be positive");
+    VH_REQUIRE(vh_aligned16(rs), VH_EALIGN, "vh_sample_step_wide: the per-row sampling records must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(audio_emb) && vh_aligned16(pe) && vh_aligned16(x_next), VH_EALIGN,
                "vh_sample_step_wide: audio_emb/pe/x_next must be 16-byte aligned");
     hipLaunchKernelGGL(sample_step_wide_kernel, dim3(B), dim3(WIDE_THREADS), 0, (hipStream_t)stream, logits, ldl, V,
-                       eos, top_k, top_p, 1.0f / temperature, seed, codes, codes_stride, eos_count,
-                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, seed_dev);
+                       eos, top_k, top_p, rs ? 1.0f : 1.0f / temperature, seed, codes, codes_stride, eos_count,
+                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, seed_dev, rs);
     VH_CHECK_LAUNCH("vh_sample_step_wide");
     return VH_OK;
 }
@@ -931,9 +981,18 @@ extern "C" int vh_sample_step_wide(const float* logits, int ldl, int V, int eos,
                                    int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                                    const float* audio_emb, const float* pe, int32_t* audio_pos,
                                    int32_t* cache_len, float* x_next, int B, int d, void* stream) {
-    return vh_internal_sample_step_wide(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, codes, codes_stride,
+    return vh_internal_sample_step_wide(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, nullptr, codes, codes_stride,
                                         eos_count, pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d,
                                         stream);
+}
+
+extern "C" int vh_sample_step_wide_rows(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs, int64_t* codes,
+                                       int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                                       const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
+                                       float* x_next, int B, int d, void* stream) {
+    VH_REQUIRE(rs, VH_EINVAL, "vh_sample_step_wide_rows: null sampling records (vh_sample_step_wide takes one filter for every row)");
+    return vh_internal_sample_step_wide(logits, ldl, V, eos, 0, 1.f, 1.f, 0, nullptr, rs, codes, codes_stride, eos_count, pos_base, sum_logprobs,
+                                       audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
 }
 
 

@@ -146,10 +146,18 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
             VH_REQUIRE(d->layers[i].kprefix && d->layers[i].vprefix, VH_EINVAL,
                        "vh_ar_decoder: grouped shared prompts need kprefix / vprefix in every layer (layer %d)", i);
     }
-    VH_REQUIRE(d->top_k == 1 || d->temperature > 0.f, VH_EINVAL,
+    VH_REQUIRE(d->top_k == 1 || d->row_sampling || d->temperature > 0.f, VH_EINVAL,
                "vh_ar_decoder: sampling (top_k=%d) needs temperature > 0", d->top_k);
-    VH_REQUIRE(d->top_k == 1 || d->V <= VH_SAMPLE_MAX_V, VH_EUNSUPPORTED,
-               "vh_ar_decoder: sampling (top_k=%d) serves V <= %d (VH_SAMPLE_MAX_V), got V=%d", d->top_k, VH_SAMPLE_MAX_V, d->V);
+    VH_REQUIRE((d->top_k == 1 && !d->row_sampling) || d->V <= VH_SAMPLE_MAX_V, VH_EUNSUPPORTED,
+               "vh_ar_decoder: sampling (top_k=%d%s) serves V <= %d (VH_SAMPLE_MAX_V), got V=%d", d->top_k,
+               d->row_sampling ? ", row_sampling" : "", VH_SAMPLE_MAX_V, d->V);
+    if (d->row_sampling) {
+        // the fused greedy head has no sampler behind it: a row of the records could not sample
+        VH_REQUIRE(!d->head_ws, VH_EUNSUPPORTED,
+                   "vh_ar_decoder: row_sampling with head_ws: per-row sampling runs the sampler on every row, head_ws (head + "
+                   "greedy step in one launch) has none — set one or the other");
+        VH_REQUIRE(vh_aligned16(d->row_sampling), VH_EALIGN, "vh_ar_decoder: row_sampling must be 16-byte aligned");
+    }
     if (d->head_ws) {
         VH_REQUIRE(d->top_k == 1 && d->B <= 64 && d->d_model <= 1024, VH_EUNSUPPORTED,
                    "vh_ar_decoder: head_ws (head + greedy step in one launch) is for top_k == 1, B <= 64, d_model <= 1024");
@@ -194,12 +202,12 @@ int vh_internal_ffn_decode_w16(const float* x, int ldx, const uint16_t* w1f16, c
                                const uint16_t* w2_16, const float* b2, float* out, int ldo, int M, int d_model, int dff,
                                float ln_eps, void* workspace, size_t workspace_bytes, void* stream);                  // ffn.hip
 int vh_internal_sample_step(const float* logits, int ldl, int V, int eos, int top_k, float top_p, float temperature, uint64_t seed,
-                            const uint64_t* seed_dev, int64_t* codes, int64_t codes_stride, int32_t* eos_count,
+                            const uint64_t* seed_dev, const vh_row_sampling* rs, int64_t* codes, int64_t codes_stride, int32_t* eos_count,
                             const int32_t* pos_base, float* sum_logprobs, const float* audio_emb, const float* pe,
                             int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d, void* stream);   // elementwise.hip
 int vh_internal_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k, float top_p, float temperature,
-                                 uint64_t seed, const uint64_t* seed_dev, int64_t* codes, int64_t codes_stride,
-                                 int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs, const float* audio_emb,
+                                 uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs, int64_t* codes,
+                                 int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs, const float* audio_emb,
                                  const float* pe, int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d,
                                  void* stream);   // elementwise.hip
 
@@ -340,16 +348,16 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
     else
         TRY(vh_linear(d.x, D, d.proj_w, nullptr, nullptr, 0, d.logits, dec->ldl, B, d.V, D, VH_ACT_NONE,
                       nullptr, nullptr, nullptr, nullptr, 0.f, s));
-    if (d.top_k == 1)
+    if (d.top_k == 1 && !d.row_sampling)
         TRY(vh_greedy_step(d.logits, dec->ldl, d.V, d.eos, d.codes, d.codes_stride, d.eos_count,
                            d.pos_base, d.audio_emb, d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
     else if (d.V > 2048)              // wider than vh_sample_step's LDS row (decoder_check bounds V by VH_SAMPLE_MAX_V)
         TRY(vh_internal_sample_step_wide(d.logits, dec->ldl, d.V, d.eos, d.top_k, d.top_p, d.temperature, d.seed, d.seed_dev,
-                                         d.codes, d.codes_stride, d.eos_count, d.pos_base, d.sum_logprobs, d.audio_emb,
+                                         d.row_sampling, d.codes, d.codes_stride, d.eos_count, d.pos_base, d.sum_logprobs, d.audio_emb,
                                          d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
     else
         TRY(vh_internal_sample_step(d.logits, dec->ldl, d.V, d.eos, d.top_k, d.top_p, d.temperature, d.seed, d.seed_dev,
-                                    d.codes, d.codes_stride, d.eos_count, d.pos_base, d.sum_logprobs, d.audio_emb,
+                                    d.row_sampling, d.codes, d.codes_stride, d.eos_count, d.pos_base, d.sum_logprobs, d.audio_emb,
                                     d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
     return VH_OK;
 }

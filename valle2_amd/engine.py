@@ -590,13 +590,23 @@ def _capture_stream(device_index):
     return st
 
 
+def _check_row_sampling(rs, batch):
+    if rs is not None and (rs.dtype != torch.uint8 or tuple(rs.shape) != (batch, kernels.ROW_SAMPLING_BYTES) or not rs.is_cuda
+                           or not rs.is_contiguous()):
+        raise _lib.VhError(f'row_sampling must be a contiguous uint8 device tensor ({batch}, {kernels.ROW_SAMPLING_BYTES})')
+    return rs
+
+
 class StepSampler:
     """Head + sampling step on the last hidden row of a full forward (valle_ar.py:158-171: logits, top-k / top-p / greedy
     draw, EOS bookkeeping, token append) with the decode state on the device — what ArDecoder.sample_from does, without
     the native decoder behind it: the recompute path of ValleAR.generate_batch (use_kv_cache=False, or a head width the
     decoder is not built for) samples through this."""
 
-    def __init__(self, model, batch, codes, cache_len, audio_pos, pos_base, seed=0):
+    def __init__(self, model, batch, codes, cache_len, audio_pos, pos_base, seed=0, row_sampling=None):
+        """row_sampling: a uint8 device tensor (batch, kernels.ROW_SAMPLING_BYTES) of vh_row_sampling records, or None.  With
+        it every row samples from its own record (seed, draw key, filter) and the config's top_k, tok_p, temperature and
+        `seed` are not read; the caller owns the tensor and may rewrite it between steps."""
         cfg = model.config
         dev = codes.device
         self.B, self.V, self.d = batch, cfg.num_audio_tokens + 1, cfg.d_model
@@ -606,6 +616,7 @@ class StepSampler:
         self.eos_count = torch.zeros(codes.shape[1] + 1, device=dev, dtype=torch.int32)
         self.sum_logprobs = torch.zeros(batch, device=dev, dtype=torch.float32)
         self.sampling = (int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature), int(seed))
+        self.row_sampling = _check_row_sampling(row_sampling, batch)
         self.codes, self.cache_len, self.audio_pos, self.pos_base = codes, cache_len, audio_pos, pos_base
         self._keep = (model.proj.weight.detach(), model.audio_emb.weight.detach(), model.audio_position_emb.pe)
         self.n_split, self.ffn_ws, self.kv_bf16, self.head_ws = 0, None, False, None
@@ -614,11 +625,16 @@ class StepSampler:
         """Head + first sample on the last hidden rows of a prompt pass (the tail of step 0), for the decode rows `rows`:
         the one Python call site of the sample kernels.  cache_len stands in for the rows' own counter (generate_queued's
         refill: the first sample appends no K/V row, and vh_decode_group_reset left cache_len where the first step appends).
-        The sampler keys its draws on the row index within what it is handed."""
+        Without row sampling the sampler keys its draws on the row index within what it is handed; with it, on the rows'
+        own records."""
         m = self._keep
         cache_len = self.cache_len[rows] if cache_len is None else cache_len
         kernels.linear(hidden_last, m[0], out=self.logits[rows, : self.V])
-        if self.sampling[0] == 1:
+        if self.row_sampling is not None:
+            kernels.sample_step(self.logits[rows], self.V, self.eos, 0, 1.0, 1.0, 0, self.codes[rows], self.eos_count,
+                                self.sum_logprobs[rows], m[1], m[2], self.audio_pos[rows], cache_len, self.x[rows],
+                                pos_base=self.pos_base[rows], rs=self.row_sampling[rows])
+        elif self.sampling[0] == 1:
             kernels.greedy_step(self.logits[rows], self.V, self.eos, self.codes[rows], self.eos_count, m[1], m[2],
                                 self.audio_pos[rows], cache_len, self.x[rows], pos_base=self.pos_base[rows])
         else:
@@ -641,7 +657,7 @@ class ArDecoder(StepSampler):
 
     def __init__(self, model, batch, s_max, codes, cache: KVCache, cache_len, audio_pos, pos_base,
                  n_split=None, use_graph=True, seed=0, prefix: KVCache | None = None, prefix_len=0,
-                 prefix_lens=None, prefix_cap=0, beams=1):
+                 prefix_lens=None, prefix_cap=0, beams=1, row_sampling=None):
         """prefix / prefix_len: SHARED-PROMPT decoding (the beams of ONE utterance, valle_ar.py:135-138): `prefix` is a
         one-row cache holding the prompt's K/V (its first prefix_len rows), `cache` then holds only the generated rows of
         every beam (s_max = its capacity) and cache_len counts those.  A 16-bit `cache` is perf mode; it takes key splits
@@ -650,7 +666,10 @@ class ArDecoder(StepSampler):
         prefix_lens / prefix_cap / beams: GROUPED shared prompts (several utterances, each replicated over `beams` rows):
         `prefix` is then a G-row cache, G = batch // beams, prefix_lens the int32 device tensor (G) of the prompts' lengths
         — read by every step, so the caller rewrites it between calls — and prefix_cap (<= prefix.s_max) bounds them.  fp32
-        caches only; prefix_len is not used."""
+        caches only; prefix_len is not used.
+
+        row_sampling: as StepSampler's; the captured steps read the records through the pointer, so rewriting the tensor
+        between replays re-keys the rows."""
         cfg = model.config
         dev = cache.buf.device
         d, dff, V = cfg.d_model, cfg.dim_feedforward, cfg.num_audio_tokens + 1
@@ -706,7 +725,8 @@ class ArDecoder(StepSampler):
         self.sampling = (int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature), int(seed))
         # the sampling seed lives in device memory (desc.seed = 0 + *seed_dev): a captured graph would freeze a by-value
         # seed, and this decoder may serve many generate() calls (`reset`)
-        self.seed_dev = torch.tensor([int(seed)], dtype=torch.int64).to(dev) if self.sampling[0] != 1 else None
+        self.row_sampling = _check_row_sampling(row_sampling, batch)
+        self.seed_dev = torch.tensor([int(seed)], dtype=torch.int64).to(dev) if self.sampling[0] != 1 and row_sampling is None else None
         self.codes, self.cache, self.cache_len, self.audio_pos = codes, cache, cache_len, audio_pos
         self.pos_base = pos_base
         # (above 1024 the folded GEMMs are one-row-tile kernels: more than 16 rows run as row groups that each stream the
@@ -727,7 +747,7 @@ class ArDecoder(StepSampler):
         self.ffn_ws = torch.empty(ffn_bytes // 4, **f32) if ffn_bytes else None
         # opt-in (VALLE2_HEAD_FUSED=1): head + greedy step as one launch (vh_head_greedy; DESIGN.md 3.20 has the A/B)
         self.head_ws = None
-        if os.environ.get('VALLE2_HEAD_FUSED') == '1' and self.sampling[0] == 1 and batch <= 64 and d in (128, 256, 512, 1024):
+        if os.environ.get('VALLE2_HEAD_FUSED') == '1' and self.sampling[0] == 1 and row_sampling is None and batch <= 64 and d in (128, 256, 512, 1024):
             self.head_ws = kernels.head_greedy_ws(batch, V, dev)
         self._table = layer_table(model.transformer, cache, self._folded)
         # perf mode, second half: the step's four matrices (and the head) as h16 — half the weight bytes per launch
@@ -763,7 +783,8 @@ class ArDecoder(StepSampler):
             n_groups=prefix.batch if self.grouped else 0, beams_per_group=self.beams if self.grouped else 0,
             prefix_cap=self.prefix_cap if self.grouped else 0, prefix_lens=ptr(prefix_lens) if self.grouped else None,
             attn_partial_bytes=self.partial.numel() * 4 if self.partial is not None else 0,
-            head_ws=ptr(self.head_ws), head_ws_bytes=self.head_ws.numel() * 4 if self.head_ws is not None else 0)
+            head_ws=ptr(self.head_ws), head_ws_bytes=self.head_ws.numel() * 4 if self.head_ws is not None else 0,
+            row_sampling=ptr(self.row_sampling))
         self._desc = desc
         self._h = _lib.lib().vh_ar_decoder_create(C.byref(desc))
         if not self._h:

@@ -11,6 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib, kernels
+from . import sampling as _sampling
 from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, QueueSchedule, StepSampler,
                      cached_decode_supported, ffn_fused_width, group_prefix_cap, grouped_prompts_fit, perf_forward_supported,
                      queue_steps_cap, transformer_forward, transformer_forward_bf16)
@@ -50,6 +51,15 @@ def _check_grouped_decoder(entry, cfg, beams, needs):
         raise ValueError(f'{entry}: beams={beams} with use_kv_cache={cfg.use_kv_cache}, d_model={cfg.d_model}, '
                          f'n_heads={cfg.n_heads}: {needs} the cached decoder at head width '
                          f'{kernels.HEAD_DIM} (d_model <= {MAX_DECODE_D_MODEL})')
+
+
+def check_sampling(sampling, n, forced=None):
+    """The refusals of generate_batch(sampling=...): one Sampling per utterance or none at all, and no teacher forcing.
+    Returns the list, or None for a call without row sampling."""
+    sampling = _sampling.check_list('generate_batch', sampling, n)
+    if sampling is not None and forced is not None:
+        raise ValueError('generate_batch: sampling with forced: teacher forcing appends the given tokens, nothing is drawn')
+    return sampling
 
 
 def check_beams(cfg, beams, shared_prompt=False, perf_mode=False, forced=None):
@@ -136,6 +146,7 @@ class DecodePlan:
     use_graph: bool
     queued: bool          # the plan of generate_queued
     slot_eligible: bool   # the decoder may survive the call in a slot of the model
+    row_sampling: bool = False   # every utterance carries its own Sampling: the sampler reads per-row records, not the config
 
 
 def _caches(kind, cfg, G, B, s0, s_max, cap, max_new, perf_mode):
@@ -161,11 +172,11 @@ def _caches(kind, cfg, G, B, s0, s_max, cap, max_new, perf_mode):
 
 
 def plan_decode(cfg, txs, pls, *, max_new, beams=1, shared_prompt=False, perf_mode=False, use_graph=True, by_hand=False,
-                queued=False, cap=None, pos_limits=None):
+                queued=False, cap=None, pos_limits=None, row_sampling=False):
     """The DecodePlan of a call over utterances of text lengths `txs` and prompt lengths `pls` (BOS included).  by_hand:
     profile_attn or forced, the forms that drive the decoder themselves.  queued: generate_queued's rows (GROUPED whatever
     `beams`, `cap` given: of the longest prompt of the whole list, max_new: its steps cap).  pos_limits: (audio, text) rows
-    of the positional tables."""
+    of the positional tables.  row_sampling: the utterances carry a Sampling each."""
     G, B = len(txs), len(txs) * beams
     other_width = cfg.d_model != cfg.n_heads * kernels.HEAD_DIM
     hd_cached = other_width and cached_decode_supported(cfg)
@@ -197,7 +208,8 @@ def plan_decode(cfg, txs, pls, *, max_new, beams=1, shared_prompt=False, perf_mo
         use_graph=bool(use_graph), queued=queued,
         # (perf_mode='kv' with rows of their own narrows into a fresh cache per call: no slot; over a shared prompt it narrows
         # into the slot's 16-bit prefix)
-        slot_eligible=not (no_cache or by_hand or (bool(perf_mode) and not prefill_bf16 and kind != SHARED)))
+        slot_eligible=not (no_cache or by_hand or (bool(perf_mode) and not prefill_bf16 and kind != SHARED)),
+        row_sampling=bool(row_sampling))
 
 
 def slot_key(plan, cfg, device, weights):
@@ -211,7 +223,7 @@ def slot_key(plan, cfg, device, weights):
             plan.codes_width, plan.max_new, (plan.G, plan.beams, plan.cap) if grouped else None,
             int(cfg.max_audio_len) if plan.queued else None, plan.prefill_bf16, bool(plan.perf_mode), plan.use_graph,
             int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature), str(device), _lib.TUNING_EPOCH,
-            tuple(os.environ.get(k) for k in _DECODER_ENV), weights)
+            tuple(os.environ.get(k) for k in _DECODER_ENV), weights) + (('row_sampling',) if plan.row_sampling else ())
 
 
 def weights_key(model):
@@ -231,21 +243,26 @@ class DecodeState:
     def __init__(self):
         self.codes = self.cache_len = self.audio_pos = self.pos_base = self.group_len = None
         self.poll_dev = self.poll_host = self.first_len = None            # generate_queued only
+        self.row_sampling = None                                          # (B, 32) uint8: vh_row_sampling records of a call with Sampling
         self.cache = self.prefix = self.dec = None
         self.reused = self.busy = False
         self.uses = 0
 
-    def arm(self, model, plan):
+    def arm(self, model, plan, sampling=None):
         """Ready for a call of `plan`: allocates on first use, refills in place where an earlier call left its buffers and
         decoder.  The small host-to-device copies and the decoder's reset go up BEFORE the prompt pass is enqueued (a copy
-        behind it would hold the host until the pass has finished).  Returns the call's sampling seed."""
+        behind it would hold the host until the pass has finished).  sampling: one Sampling per utterance (plan.row_sampling)
+        — row g * beams + j gets (seed_g, j, top_k_g, tok_p_g, temperature_g) and nothing is drawn from torch's generator.
+        Returns the call's sampling seed (0 with row sampling)."""
         cfg, dev = model.config, model.device
         i32 = dict(dtype=torch.int32)
         host = {'cache_len': torch.tensor(plan.cache_len0, **i32), 'audio_pos': torch.tensor(plan.row_pls, **i32)}
         if plan.kind == GROUPED:
             host['group_len'] = torch.tensor(plan.ctx, **i32)     # the prompts' lengths, where the (captured) decode steps read them
         # sampling seed drawn from torch's generator, so torch.manual_seed() makes a run repeatable
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if cfg.top_k != 1 else 0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if cfg.top_k != 1 and not plan.row_sampling else 0
+        if plan.row_sampling:
+            host['row_sampling'] = kernels.pack_row_sampling([r for s in sampling for r in s.records(cfg, plan.beams)])
         self.reused = self.dec is not None
         if self.reused:
             self.codes.fill_(model.eos_token)
@@ -271,11 +288,12 @@ class DecodeState:
     def decoder(self, model, plan, seed):
         """The call's decoder, built over the armed buffers AFTER the prompt pass is enqueued (host work the pass hides)."""
         if self.dec is None and plan.kind == RECOMPUTE_GENERAL:
-            self.dec = StepSampler(model, plan.B, self.codes, self.cache_len, self.audio_pos, self.pos_base, seed=seed)
+            self.dec = StepSampler(model, plan.B, self.codes, self.cache_len, self.audio_pos, self.pos_base, seed=seed,
+                                   row_sampling=self.row_sampling)
         elif self.dec is None:
             self.dec = ArDecoder(model, plan.B, self.cache.s_max, self.codes, self.cache, self.cache_len, self.audio_pos,
                                  self.pos_base, use_graph=plan.use_graph and not plan.no_cache, seed=seed, prefix=self.prefix,
-                                 prefix_len=plan.s0,
+                                 prefix_len=plan.s0, row_sampling=self.row_sampling,
                                  **(dict(prefix_lens=self.group_len, prefix_cap=plan.cap, beams=plan.beams) if plan.kind == GROUPED else {}))
         return self.dec
 
@@ -329,10 +347,11 @@ def release_decoders(model):
 
 # ---- utterances in, best beams out ----------------------------------------------------------------------------------------
 def unpack_utterances(utterances):
-    """[(prompt_tokens, prompt_codes, target_tokens | None), ...] -> (texts, firsts): per utterance the text ids the model
-    reads (prompt text, then the target's) and the first codebook of its prompt (valle_ar.py:107-121)."""
+    """[(prompt_tokens, prompt_codes, target_tokens | None[, sampling]), ...] -> (texts, firsts): per utterance the text ids
+    the model reads (prompt text, then the target's) and the first codebook of its prompt (valle_ar.py:107-121).  The optional
+    fourth element is the utterance's Sampling (sampling.of_utterances reads it)."""
     texts, firsts = [], []
-    for prompt_tokens, prompt_codes, target_tokens in utterances:
+    for prompt_tokens, prompt_codes, target_tokens, *_ in utterances:
         assert prompt_tokens.dim() == 1, 'Prompt tokens should be 1D tensor.'
         assert prompt_codes.dim() == 2, 'Prompt codes should be 2D tensor.'
         if target_tokens is not None:
@@ -464,7 +483,7 @@ def _decode_cached(plan, dec, done):
     return done, None
 
 
-def _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode, beams=1):
+def _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode, beams=1, sampling=None):
     """More rows than one decode launch serves (64: 4 MFMA row tiles): consecutive groups of 64 rows; rows are
     independent, so the result is what one pass would give.  beams > 1: consecutive chunks of whole utterances, 64 // beams
     of them per launch."""
@@ -473,7 +492,8 @@ def _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode
     per = MAX_DECODE_ROWS // beams
     for r0 in range(0, len(texts), per):
         parts.append(model.generate_batch(texts[r0:r0 + per], first_codes[r0:r0 + per],
-                                          max_new=max_new, use_graph=use_graph, perf_mode=perf_mode, beams=beams))
+                                          max_new=max_new, use_graph=use_graph, perf_mode=perf_mode, beams=beams,
+                                          sampling=None if sampling is None else sampling[r0:r0 + per]))
         stats.append(model.last_generate_stats)
     width = max(p.shape[1] for p in parts)
     out = torch.full((B, width), model.eos_token, device=dev, dtype=torch.int64)
@@ -491,7 +511,7 @@ def _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode
 
 
 def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, perf_mode, forced, keep_logits, shared_prompt,
-                   beams):
+                   beams, sampling=None):
     """ValleAR.generate_batch on the device (its docstring says what the arguments mean)."""
     model._require_layernorm()
     cfg, dev = model.config, model.device
@@ -499,22 +519,26 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
     if G == 0 or len(first_codes) != G:
         raise ValueError('generate_batch: texts and first_codes must be non-empty lists of equal length')
     check_beams(cfg, beams, shared_prompt, perf_mode, forced)
+    sampling = check_sampling(sampling, G, forced)
     by_hand = forced is not None or bool(profile_attn)
     check_forms(cfg, perf_mode, by_hand, shared_prompt)
     max_new = cfg.max_audio_len if max_new is None else max_new
     if beams > 1 and G * beams > MAX_DECODE_ROWS:
-        return _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode, beams=beams)
+        return _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode, beams=beams, sampling=sampling)
     if G > MAX_DECODE_ROWS:
         if shared_prompt or forced is not None:
             raise ValueError(f'shared_prompt / forced serve at most {MAX_DECODE_ROWS} rows')
-        return _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode)
+        return _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode, sampling=sampling)
     plan = plan_decode(cfg, [int(t.shape[0]) for t in texts], [int(c.shape[0]) + 1 for c in first_codes],   # BOS + prompt
                        max_new=max_new, beams=beams, shared_prompt=bool(shared_prompt), perf_mode=perf_mode, use_graph=use_graph,
-                       by_hand=by_hand, pos_limits=(model.audio_position_emb.pe.shape[0], model.tokens_position_emb.pe.shape[0]))
+                       by_hand=by_hand, pos_limits=(model.audio_position_emb.pe.shape[0], model.tokens_position_emb.pe.shape[0]),
+                       row_sampling=sampling is not None)
     if not plan.fits:
         # beyond the 256 records one merge serves: the same rows, each with its own prompt pass and K/V
         out = model.generate_batch([t for t in texts for _ in range(beams)], [c for c in first_codes for _ in range(beams)],
-                                   max_new=max_new, use_graph=use_graph, profile_attn=profile_attn)
+                                   max_new=max_new, use_graph=use_graph, profile_attn=profile_attn,
+                                   # (the replicated records: beam j of an utterance keeps key j)
+                                   sampling=None if sampling is None else [r for s in sampling for r in _sampling.beam_rows(s, beams)])
         model.last_generate_stats.update(groups=G, beams=beams, grouped_shared=False)
         return out
     B = plan.B
@@ -532,7 +556,7 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
         if plan.kind == SHARED and (any(t is not texts[0] and not torch.equal(t, texts[0]) for t in texts[1:])
                                     or any(c is not first_codes[0] and not torch.equal(c, first_codes[0]) for c in first_codes[1:])):
             raise ValueError('shared_prompt: every row must carry the same text and prompt ids')
-        seed = state.arm(model, plan)
+        seed = state.arm(model, plan, sampling)
         t_host1 = time.perf_counter()
         last, fwd, text_ids = prompt_pass(model, plan, state, texts, first_codes)
         t_host2 = time.perf_counter()
@@ -569,7 +593,7 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
             'logits': kept, 'prefill_ms': marks[0].elapsed_time(marks[1]), 'decode_ms': marks[1].elapsed_time(marks[2]),
             'attn_mean_ms': attn_ms, 'attn_floor_ms': attn_floor_ms, 'attn_kernel_ms': attn_kernel_ms, 's0': plan.s0,
             'prompt_lens': plan.row_pls, 'groups': G, 'beams': beams, 'grouped_shared': plan.kind == GROUPED,
-            'sum_logprobs': dec.sum_logprobs.clone(),
+            'sum_logprobs': dec.sum_logprobs.clone(), 'sampling': 'rows' if plan.row_sampling else 'call',
             # host time this call spent OUTSIDE enqueueing the prompt pass and the replays and waiting for them: set-up of
             # the call's state + building / capturing the decoder (nothing on a reused slot) + the tail after the last step
             # has finished
@@ -591,6 +615,7 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
     check_queued(model.config, beams, slots)
     cfg, dev, d = model.config, model.device, model.config.d_model
     texts, firsts = unpack_utterances(utterances)
+    sampling = _sampling.of_utterances('generate_queued', utterances)
     n = len(texts)
     if n == 0:
         raise ValueError('generate_queued: utterances must be a non-empty list')
@@ -602,7 +627,7 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
     # the rows the call starts with; the capacity of the longest prompt of the CALL: any refill fits.  Every row may run
     # whole polls up to the one that covers max_new before the host rewinds or re-arms it
     plan = plan_decode(cfg, txs[:slots], pls[:slots], max_new=queue_steps_cap(max_new, poll), beams=beams, use_graph=use_graph,
-                       queued=True, cap=group_prefix_cap(max(ctx)))
+                       queued=True, cap=group_prefix_cap(max(ctx)), row_sampling=sampling is not None)
     if not plan.fits:
         out = model.generate_many(utterances, beams=beams)
         model.last_generate_stats.update(queued=False)
@@ -618,7 +643,11 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
         marks[0].record()
         texts = [kernels.ids_to_device(t, dev, cfg.vocab_size, 'text ids') for t in texts]
         firsts = [kernels.ids_to_device(c, dev, cfg.num_audio_tokens, 'prompt codes').contiguous() for c in firsts]
-        seed = state.arm(model, plan)
+        seed = state.arm(model, plan, sampling and sampling[:slots])
+        # the records of the utterances that wait: a refill copies its own over the group's, device to device
+        waiting = None
+        if sampling is not None and n > slots:
+            waiting = _lib.to_device_async(kernels.pack_row_sampling([r for s in sampling[slots:] for r in s.records(cfg, beams)]), dev)
         last, _, _ = prompt_pass(model, plan, state, texts[:slots], firsts[:slots])
         dec = state.decoder(model, plan, seed)
         codes, cache_len, audio_pos, pos_base, group_len = state.codes, state.cache_len, state.audio_pos, state.pos_base, state.group_len
@@ -627,7 +656,7 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
         dec.sample_from(last)
         del last
         marks[1].record()
-        sampled = cfg.top_k != 1
+        sampled = cfg.top_k != 1 or plan.row_sampling
         sched = QueueSchedule(n, slots)
         saved, at_cap = {}, {}
         scratch = None
@@ -692,6 +721,10 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
                     scratch = ForwardScratch(max(ctx), d, cfg.dim_feedforward, dev)
                 transformer_forward(model.transformer, x, prefix.group_view(g), mode=kernels.MASK_PREFIX,
                                     scratch=scratch.fit(ctx[nxt]), x_len=txs[nxt])
+                if waiting is not None:
+                    # the group's rows take the new utterance's seed, keys 0 .. beams - 1 and filter: a stream-ordered write
+                    # between replays (the captured steps hold the pointer), before the first sample reads them
+                    state.row_sampling[rows].copy_(waiting[(nxt - slots) * beams:(nxt - slots + 1) * beams])
                 # (first_len stands in for cache_len: the first sample appends no K/V row, and vh_decode_group_reset left
                 # cache_len where the first step appends)
                 dec.sample_from(x[:, -1].expand(beams, d).contiguous(), rows, state.first_len)
@@ -708,7 +741,8 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
             'rows': [saved[u][0] for u in range(n)], 'grouped_shared': True,
             'decoder_reused': state.reused, 'slot_uses': state.uses if state.busy else 0,
             'n_split': dec.n_split, 'prefill_ms': marks[0].elapsed_time(marks[1]),
-            'decode_ms': marks[1].elapsed_time(done_mark), 'poll_gap_ms': gap_s * 1e3, 'kv_cache': True}
+            'decode_ms': marks[1].elapsed_time(done_mark), 'poll_gap_ms': gap_s * 1e3, 'kv_cache': True,
+            'sampling': 'rows' if plan.row_sampling else 'call'}
         ok = True
         return [best_beam_tokens(model, *saved[u], pls[u]) for u in range(n)]
     finally:

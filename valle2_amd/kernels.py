@@ -683,19 +683,46 @@ def head_greedy(x, proj_w, logits, V, eos, codes, eos_count, audio_emb, pe, audi
 
 
 def sample_step(logits, V, eos, top_k, top_p, temperature, seed, codes, eos_count, sum_logprobs, audio_emb,
-                pe, audio_pos, cache_len, x_next, pos_base=None, wide=None):
+                pe, audio_pos, cache_len, x_next, pos_base=None, wide=None, rs=None):
     """The stochastic decode step: `vh_sample_step` up to V = SAMPLE_NARROW_V, `vh_sample_step_wide` above it (up to
-    SAMPLE_MAX_V).  wide=True / False forces one kernel (tests compare the two at V <= 2048)."""
+    SAMPLE_MAX_V).  wide=True / False forces one kernel (tests compare the two at V <= 2048).  rs: a uint8 device tensor
+    (B, ROW_SAMPLING_BYTES) of vh_row_sampling records (`pack_row_sampling`) — every row's seed, draw key and filter come
+    from its record (`vh_sample_step_rows` / `vh_sample_step_wide_rows`) and top_k, top_p, temperature and seed are not read."""
     B = logits.shape[0]
     d = x_next.shape[1]
     if wide is None:
         wide = V > SAMPLE_NARROW_V
     name = 'vh_sample_step_wide' if wide else 'vh_sample_step'
+    if rs is not None:
+        if rs.dtype != torch.uint8 or tuple(rs.shape) != (B, ROW_SAMPLING_BYTES) or not rs.is_cuda:
+            raise _lib.VhError(f'sample_step: rs must be a uint8 device tensor ({B}, {ROW_SAMPLING_BYTES}), got {tuple(rs.shape)} {rs.dtype}')
+        name += '_rows'
+        check(getattr(_lib.lib(), name)(
+            logits.data_ptr(), logits.stride(0), V, eos, ptr(rs), ptr(codes), codes.stride(0), ptr(eos_count), ptr(pos_base),
+            ptr(sum_logprobs), ptr(audio_emb), ptr(pe), ptr(audio_pos), ptr(cache_len), ptr(_f32(x_next, 'x_next')),
+            B, d, stream()), name)
+        return
     check(getattr(_lib.lib(), name)(
         logits.data_ptr(), logits.stride(0), V, eos, int(top_k), float(top_p), float(temperature),
         int(seed) & (2 ** 64 - 1), ptr(codes), codes.stride(0), ptr(eos_count), ptr(pos_base),
         ptr(sum_logprobs), ptr(audio_emb), ptr(pe), ptr(audio_pos), ptr(cache_len), ptr(_f32(x_next, 'x_next')),
         B, d, stream()), name)
+
+
+ROW_SAMPLING_BYTES = 32   # sizeof(vh_row_sampling)
+_ROW_SAMPLING_DTYPE = [('seed', '<u8'), ('key', '<u4'), ('top_k', '<i4'), ('top_p', '<f4'), ('temperature', '<f4'),
+                       ('reserved', '<u4', (2,))]
+
+
+def pack_row_sampling(records):
+    """[(seed, key, top_k, top_p, temperature), ...] -> a HOST uint8 tensor (n, ROW_SAMPLING_BYTES) in the layout of
+    vh_row_sampling (include/valle_hip.h), one record per decode row."""
+    import numpy as np
+    arr = np.zeros(len(records), dtype=np.dtype(_ROW_SAMPLING_DTYPE))
+    assert arr.dtype.itemsize == ROW_SAMPLING_BYTES
+    for i, (seed, key, top_k, top_p, temperature) in enumerate(records):
+        arr[i] = (int(seed), int(key), int(top_k), float(top_p), float(temperature), (0, 0))
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(records), ROW_SAMPLING_BYTES).copy())
 
 
 POLL_NONE = -(1 << 30)            # vh_decode_groups_poll: a maximum over no rows

@@ -1,0 +1,102 @@
+"""Per-request sampling: what one utterance of a generate call asks of the sampler (seed, top-k, top-p, temperature), and
+the records the sample kernels read it from (include/valle_hip.h, vh_row_sampling).  Pure Python, no device."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import NamedTuple
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _is_real(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+@dataclass(frozen=True)
+class Sampling:
+    """The sampling of ONE utterance: Sampling(seed, top_k=None, tok_p=None, temperature=None); None is the config's value.
+
+    With it the utterance's draws are a function of (seed, beam index within the utterance, audio position) and its filter
+    is its own: the same in generate(), generate_batch(beams=n) at any group index, generate_many and generate_queued at any
+    slot, started or refilled, whatever else the call decodes.  top_k == 1 is greedy decoding for this utterance (the largest
+    logit, the lowest index on ties, scores exactly 0); top_k == 0 keeps the whole vocabulary.  Ranges (ValueError): seed an
+    int in [0, 2**64), top_k an int >= 0, 0 < tok_p <= 1, temperature > 0."""
+    seed: int
+    top_k: int | None = None
+    tok_p: float | None = None
+    temperature: float | None = None
+
+    def __post_init__(self):
+        if not _is_int(self.seed) or not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f'Sampling: seed={self.seed!r} (an int in [0, 2**64))')
+        if self.top_k is not None and (not _is_int(self.top_k) or not 0 <= self.top_k < 2 ** 31):
+            raise ValueError(f'Sampling: top_k={self.top_k!r} (an int >= 0; 0 keeps the whole vocabulary, 1 is greedy)')
+        if self.tok_p is not None and (not _is_real(self.tok_p) or not 0.0 < self.tok_p <= 1.0):
+            raise ValueError(f'Sampling: tok_p={self.tok_p!r} (0 < tok_p <= 1)')
+        if self.temperature is not None and (not _is_real(self.temperature) or not self.temperature > 0.0):
+            raise ValueError(f'Sampling: temperature={self.temperature!r} (a finite number > 0)')
+
+    def resolved(self, cfg):
+        """(top_k, tok_p, temperature) with the config's values where this holds None."""
+        top_k = int(cfg.top_k) if self.top_k is None else self.top_k
+        tok_p = float(cfg.tok_p) if self.tok_p is None else float(self.tok_p)
+        temperature = float(cfg.temperature) if self.temperature is None else float(self.temperature)
+        if not temperature > 0.0:
+            raise ValueError(f'Sampling: the config\'s temperature={temperature!r} must be > 0')
+        return max(top_k, 0), tok_p, temperature
+
+    def records(self, cfg, beams, first_key=0):
+        """The (seed, key, top_k, top_p, temperature) of this utterance's `beams` rows (kernels.pack_row_sampling): beam j
+        carries key first_key + j."""
+        return [(self.seed, first_key + j) + self.resolved(cfg) for j in range(beams)]
+
+
+class KeyedRows(NamedTuple):
+    """Internal: rows of a request handed over as utterances of their own, keyed from `first_key` on (generate() and the
+    independent-rows fallback pass one utterance's beams as single rows: row j carries beam j).  Not part of the public
+    interface: callers pass Sampling."""
+    request: Sampling
+    first_key: int
+
+    def records(self, cfg, beams):
+        return self.request.records(cfg, beams, self.first_key)
+
+
+def beam_rows(request, beams, first_key=0):
+    """[KeyedRows] for the `beams` rows of `request` (a Sampling or a KeyedRows), one entry per row."""
+    if isinstance(request, KeyedRows):
+        request, first_key = request.request, request.first_key + first_key
+    return [KeyedRows(request, first_key + j) for j in range(beams)]
+
+
+def check_list(entry, sampling, n, what='utterance'):
+    """None when no entry of `sampling` (None, or a list of n) is a Sampling, the list when every one is; a mix is a
+    ValueError naming the first without one."""
+    if sampling is None:
+        return None
+    sampling = list(sampling)
+    if len(sampling) != n:
+        raise ValueError(f'{entry}: sampling holds {len(sampling)} entries for {n} {what}s (one Sampling each)')
+    for i, s in enumerate(sampling):
+        if s is not None and not isinstance(s, (Sampling, KeyedRows)):
+            raise ValueError(f'{entry}: sampling of {what} {i} is {type(s).__name__}, not a valle2_amd.Sampling')
+    if all(s is None for s in sampling):
+        return None
+    for i, s in enumerate(sampling):
+        if s is None:
+            raise ValueError(f'{entry}: {what} {i} carries no Sampling and others do: either every {what} of a call '
+                             'carries one or none does')
+    return sampling
+
+
+def of_utterances(entry, utterances):
+    """check_list over the optional fourth element of [(prompt_tokens, prompt_codes, target_tokens[, sampling]), ...]."""
+    utterances = list(utterances)
+    for i, u in enumerate(utterances):
+        if len(u) not in (3, 4):
+            raise ValueError(f'{entry}: utterance {i} has {len(u)} elements: (prompt_tokens, prompt_codes, target_tokens) '
+                             'with an optional Sampling as the fourth')
+    return check_list(entry, [u[3] if len(u) == 4 else None for u in utterances], len(utterances))

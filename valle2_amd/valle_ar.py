@@ -18,6 +18,7 @@ import torch.nn as nn
 from torch import optim
 
 from . import _lib, dropout, generation, kernels
+from . import sampling as _sampling
 from .engine import KVCache, shared_prompt_fits, transformer_forward, transformer_forward_bf16
 from .generation import DECODER_SLOTS, EOS_POLL, MAX_DECODE_ROWS, SHARED_PROMPT  # noqa: F401  (tools import them from here)
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device
@@ -39,9 +40,26 @@ def _beams_refused_early(fn):
 
     @functools.wraps(fn)
     def wrapper(self, *args, **kwargs):
-        if kwargs.get('beams', 1) != 1:
+        if kwargs.get('beams', 1) != 1 or kwargs.get('sampling') is not None:
             a = sig.bind(self, *args, **kwargs).arguments
-            generation.check_beams(self.config, a['beams'], a.get('shared_prompt', False), a.get('perf_mode', False), a.get('forced'))
+            generation.check_beams(self.config, a.get('beams', 1), a.get('shared_prompt', False), a.get('perf_mode', False), a.get('forced'))
+            generation.check_sampling(a.get('sampling'), len(a['texts']), a.get('forced'))
+        return fn(self, *args, **kwargs)
+    return wrapper
+
+
+def _sampling_refused_early(fn):
+    """generate(sampling=...) and the utterance lists of generate_many: what is wrong with the Sampling entries is said
+    before anything touches a device."""
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        a = sig.bind(self, *args, **kwargs).arguments
+        if 'utterances' in a:
+            _sampling.of_utterances(fn.__name__, a['utterances'])
+        elif a.get('sampling') is not None and not isinstance(a['sampling'], _sampling.Sampling):
+            raise ValueError(f'{fn.__name__}: sampling is {type(a["sampling"]).__name__}, not a valle2_amd.Sampling')
         return fn(self, *args, **kwargs)
     return wrapper
 
@@ -165,15 +183,21 @@ class ValleAR(_Base):
         return loss
 
     # ------------------------------------------------------------------------------------
+    @_sampling_refused_early
     @_on_device
     @torch.inference_mode()
-    def generate(self, prompt_tokens, prompt_codes, target_tokens=None, *, perf_mode=False):
+    def generate(self, prompt_tokens, prompt_codes, target_tokens=None, *, perf_mode=False, sampling=None):
         """valle_ar.py:92-180 — one utterance replicated over `num_beams` rows; returns the 1-D
         int64 first-codebook tokens of the best beam with EOS stripped.
 
         perf_mode (keyword-only, default off; True or 'kv' as in `generate_batch`): the decode steps stream a 16-bit K/V
         cache — with the shared prompt below, the prompt's K/V are read once per step AND at half the bytes.  Off, this runs
         exactly what it always ran.
+
+        sampling (keyword-only, a valle2_amd.Sampling): the request's own seed and filter — beam j draws from (seed, j, audio
+        position), whatever torch's generator holds, and the same draws come out of generate_batch(beams=n), generate_many
+        and generate_queued for an utterance that carries the same Sampling.  None: the config's filter and a seed from
+        torch's generator, as always.
 
         The beams share one prompt, so (SHARED_PROMPT, default on) the prompt pass runs for ONE row and its K/V are read
         once per decode step for all beams (`generate_batch(..., shared_prompt=True)`); the beams themselves — their
@@ -184,19 +208,23 @@ class ValleAR(_Base):
         # (a prompt beyond the shared kernel's record bound — 7680 keys at 4 beams x 8 heads — decodes as independent rows)
         shared = shared and shared_prompt_fits(beams, self.config.n_heads, int(text.shape[0]) + int(prompt_codes.shape[0]) + 1)   # + BOS
         rows = self.generate_batch([text] * beams, [first] * beams, shared_prompt=shared and beams <= MAX_DECODE_ROWS,
-                                   perf_mode=perf_mode)
+                                   perf_mode=perf_mode,
+                                   sampling=None if sampling is None else _sampling.beam_rows(sampling, beams))
         return generation.best_beam_tokens(self, rows, self.last_generate_stats['sum_logprobs'], prompt_codes.shape[0] + 1)
 
+    @_sampling_refused_early
     @_on_device
     @torch.inference_mode()
     def generate_many(self, utterances, *, beams=None):
         """`generate()` for several utterances in one decode: utterances = [(prompt_tokens, prompt_codes, target_tokens |
         None), ...], each replicated over `beams` rows (default config.num_beams) that share its prompt's K/V
         (`generate_batch(..., beams=n)`).  Returns a list of 1-D int64 tensors, per utterance what generate() returns: the
-        best beam by get_best_beam over that utterance's rows and scores, prompt cut, EOS stripped."""
+        best beam by get_best_beam over that utterance's rows and scores, prompt cut, EOS stripped.  An utterance may carry
+        its Sampling as a fourth element (every utterance of the call, or none): its draws and filter are then its own, the
+        same at any place in the list."""
         beams = self.config.num_beams if beams is None else int(beams)
         texts, firsts = generation.unpack_utterances(utterances)
-        rows = self.generate_batch(texts, firsts, beams=beams)
+        rows = self.generate_batch(texts, firsts, beams=beams, sampling=_sampling.of_utterances('generate_many', utterances))
         stats = self.last_generate_stats
         return [generation.best_beam_tokens(self, rows[g * beams:(g + 1) * beams],
                                             stats['sum_logprobs'][g * beams:(g + 1) * beams].to(rows.device), stats['prompt_lens'][g * beams])
@@ -213,18 +241,23 @@ class ValleAR(_Base):
         head width 64, use_kv_cache=True, d_model <= 4096, greedy and sampled.  A longest prompt whose capacity is beyond the
         256 records of the grouped merge falls back to generate_many (`last_generate_stats['queued']` is False).
 
-        Greedy tokens do not depend on the schedule.  SAMPLED tokens do: the sampler keys its draws on (seed, row index it is
-        given, position), the decode steps hand it the decoder's rows and a refill's first sample the group's rows 0 .. beams
-        - 1, so an utterance's draws depend on the slot it lands in and on whether it started the call or refilled a slot
-        (the same list, slots and seed give the same output).
+        Greedy tokens do not depend on the schedule.  Neither do the SAMPLED tokens of utterances that carry a Sampling as
+        their fourth element (every utterance of the call, or none): their draws are keyed on (the utterance's seed, the beam
+        within it, the audio position) and their filter is their own — a refill rewrites its group's records before its
+        first sample — so an utterance decodes the same in any slot, started or refilled, and as generate_many and
+        generate() decode it.  WITHOUT a Sampling the sampler keys its draws on (the call's seed, the row index it is given,
+        position): the decode steps hand it the decoder's rows and a refill's first sample the group's rows 0 .. beams - 1, so
+        an utterance's draws then depend on the slot it lands in and on whether it started the call or refilled a slot (the
+        same list, slots and seed give the same output).
 
-        `last_generate_stats`: queued, slots, refills, polls, steps (decode steps replayed), parked_group_steps, max_cache_len
+        `last_generate_stats`: sampling ('rows' with Sampling, else 'call'), queued, slots, refills, polls, steps (decode steps replayed), parked_group_steps, max_cache_len
         / max_audio_pos (largest values any row reached) beside s_suf / codes_width (what they must stay within), intervals
         ((slot, start poll, end poll) per utterance), sum_logprobs and prompt_lens per row in utterance order, rows (per
         utterance in input order, the saved (beams, length) int64 tokens its best beam was chosen from: BOS + prompt + what was
         generated, cut at max_audio_len; a call that fell back to generate_many records none)."""
         beams = self.config.num_beams if beams is None else beams
         generation.check_queued(self.config, beams, slots)
+        _sampling.of_utterances('generate_queued', utterances)
         return self._generate_queued(utterances, beams, slots)
 
     @_on_device
@@ -241,7 +274,7 @@ class ValleAR(_Base):
     @_on_device
     @torch.inference_mode()
     def generate_batch(self, texts, first_codes, max_new=None, use_graph=True, profile_attn=False, perf_mode=False,
-                       forced=None, keep_logits=(), shared_prompt=False, *, beams=1):
+                       forced=None, keep_logits=(), shared_prompt=False, *, beams=1, sampling=None):
         """Batched greedy decoding of B independent rows (extension; `generate` is built on it).
         texts[b]: 1-D int64 text ids; first_codes[b]: 1-D int64 first-codebook prompt (no BOS).
         Rows may differ in text and prompt length.  Returns codes (B, max_prompt_len + n_new) int64
@@ -271,9 +304,13 @@ class ValleAR(_Base):
         beams (vh_attn_decode_shared_groups); the result and `last_generate_stats` are laid out as for G * n independent rows
         (`prompt_lens`, `sum_logprobs` per row) plus `groups`, `beams` and `grouped_shared` (False when a prompt beyond the
         kernel's record bound sent the call down the independent-rows path).  More than 64 rows decode in consecutive chunks
-        of whole utterances.  fp32 cached decoder at head width 64 only: shared_prompt, perf_mode and forced are refused."""
+        of whole utterances.  fp32 cached decoder at head width 64 only: shared_prompt, perf_mode and forced are refused.
+        sampling (keyword-only): a list with one valle2_amd.Sampling per entry of texts (every entry or None).  Row g * beams +
+        j then draws from (sampling[g].seed, j, audio position) through sampling[g]'s own top_k / tok_p / temperature (None:
+        the config's) — on every kind of decode, graph or eager — and no seed is drawn from torch's generator;
+        `last_generate_stats['sampling']` is 'rows' ('call' without).  Refused with forced."""
         return generation.generate_batch(self, texts, first_codes, max_new, use_graph, profile_attn, perf_mode, forced, keep_logits,
-                                         shared_prompt, beams)
+                                         shared_prompt, beams, sampling)
 
     def configure_optimizers(self):
         """valle_ar.py:182-194"""
