@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 135            /* 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 136            /* 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -712,6 +712,27 @@ int vh_adaproj_bwd(const vh_adaproj_item* items, int n, const float* emb, const 
 int vh_categorical_rows(const float* logits, int ld, int V, int rows, float temperature, int greedy,
                         uint64_t seed, uint32_t stream_id, int64_t* tokens, int64_t tokens_stride,
                         float* logprob, void* stream);
+
+/* vh_categorical_rows keyed on the REQUEST, not on the row's place in the launch (ABI 136).  Packed row r belongs to request
+ * g = row_request[r] and is its frame t = row_key[r] (int32 device arrays of `rows` entries); rq = requests[g] is one of
+ * n_requests vh_row_sampling records in device memory (16-byte aligned):
+ *   the draw      u = uniform01(rq.seed, t, stream_id): the generator of the other samplers, keyed on the frame index inside
+ *                 the request — which rows share the launch, their order and their count do not enter;
+ *   the scale     rq.top_k == 1: the arg-max over the unscaled logits, the lowest index on ties, log-probability exactly 0;
+ *                 otherwise 1.0f / rq.temperature, the fp32 division vh_sample_step_rows does.  rq.temperature > 0 is NOT
+ *                 checked: the records live on the device;
+ *   not read      rq.key, rq.top_p and any other value of rq.top_k (the reference's NAR stage has no filter, valle_nar.py:160);
+ *   the token     goes to tokens[g * request_stride + t * key_stride] (element strides >= 1): codebook n of a (B, Ty_max, Q)
+ *                 codes tensor is tokens = codes + n, request_stride = Ty_max * Q, key_stride = Q, n_keys = Ty_max;
+ *   guards        a row with g outside [0, n_requests) or t outside [0, n_keys) reads no record and writes nothing.
+ * The arithmetic of a row is vh_categorical_rows': one request with row_key[r] = r draws that launch's tokens and
+ * log-probabilities bit for bit.  logprob (rows floats, indexed by packed row, may be NULL).  rows == 0 is VH_OK. */
+int vh_categorical_rows_keyed(const float* logits, int ld, int V, int rows,
+                              const vh_row_sampling* requests, int n_requests,
+                              const int32_t* row_request, const int32_t* row_key, int n_keys,
+                              uint32_t stream_id,
+                              int64_t* tokens, int64_t request_stride, int64_t key_stride,
+                              float* logprob /* rows, may be NULL */, void* stream);
 
 /* ---- optimizer step over one flat fp32 buffer ------------------------------------------------
  * replaces optim.AdamW(fused) (valle/models/valle_ar.py:182-194), the global-norm clip

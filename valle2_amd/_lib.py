@@ -199,6 +199,9 @@ SIGNATURES = {
                                            c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
     'vh_categorical_rows': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint32,
                                       c_i64p, C.c_int64, c_f32p, C.c_void_p]),
+    # the NAR stage sampler keyed on (request, frame) (ABI 136)
+    'vh_categorical_rows_keyed': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_i32p, c_i32p, C.c_int,
+                                            C.c_uint32, c_i64p, C.c_int64, C.c_int64, c_f32p, C.c_void_p]),
     'vh_adamw_ws_bytes': (C.c_size_t, []),
     'vh_adamw_flat': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p,

@@ -164,7 +164,8 @@ def synthesize(ar, nar, prompt_tokens: Tensor, prompt, target_tokens: Tensor, co
 def synthesize_many(ar, nar, items, codec=None, greedy_nar: bool = False):
     """`synthesize` for several utterances at once: items = [(prompt_tokens, prompt, target_tokens[, sampling]), ...] with
     `prompt` as in `synthesize`; the optional fourth element is the utterance's valle2_amd.Sampling, handed to the AR model only
-    (the NAR stage's draws stay keyed on its packed rows: greedy_nar=True is its reproducible form).  AR: ValleAR.generate_many (one grouped decode, every utterance's beams over its own prompt K/V); NAR: one
+    (the NAR stage's draws stay keyed on its packed rows: greedy_nar=True is its reproducible form, `synthesize_requests` the
+    entry that hands the Sampling to both stages).  AR: ValleAR.generate_many (one grouped decode, every utterance's beams over its own prompt K/V); NAR: one
     ragged ValleNAR.generate_batch over all utterances.  Returns a list, per utterance what `synthesize` returns."""
     return _synthesize_list(ar, nar, items, codec, greedy_nar, lambda utts: ar.generate_many(utts))
 
@@ -177,7 +178,29 @@ def synthesize_queued(ar, nar, items, codec=None, greedy_nar: bool = False, *, s
     return _synthesize_list(ar, nar, items, codec, greedy_nar, lambda utts: ar.generate_queued(utts, slots=slots))
 
 
-def _synthesize_list(ar, nar, items, codec, greedy_nar, ar_generate):
+@torch.inference_mode()
+def synthesize_requests(ar, nar, items, codec=None, *, queued=False, slots=None):
+    """`synthesize_many` for requests that pin their sampling: items = [(prompt_tokens, prompt, target_tokens, sampling), ...]
+    with a valle2_amd.Sampling in EVERY item (ValueError naming the first item without one).  The Sampling goes to both
+    stages — AR: ValleAR.generate_many, or generate_queued(slots=slots) when `queued`; NAR: ValleNAR.generate_batch(sampling=
+    [...]) — and the result is what `synthesize_many` returns.
+
+    An item's codes are a function of the item alone: not of the other items, their order, `queued`, `slots` or
+    torch.manual_seed.  The limit: the draw of every token is fixed by (seed, beam or frame, position or stage) and never
+    changes, but it is taken against the request's own fp32 logits, and those can differ in their last bits with the GEMM
+    kernel the batch size selects (M <= 64 rows take the skinny kernels, more rows the tiles, with split-K at K >= 1024);
+    a token changes only where such a difference moves a cumulative boundary across the draw."""
+    from .sampling import Sampling
+    items = list(items)
+    for i, item in enumerate(items):
+        if len(item) != 4 or not isinstance(item[3], Sampling):
+            raise ValueError(f'synthesize_requests: item {i} carries no valle2_amd.Sampling: every item is (prompt_tokens, '
+                             'prompt, target_tokens, Sampling)')
+    ar_generate = (lambda utts: ar.generate_queued(utts, slots=slots)) if queued else (lambda utts: ar.generate_many(utts))
+    return _synthesize_list(ar, nar, items, codec, False, ar_generate, nar_sampling=[item[3] for item in items])
+
+
+def _synthesize_list(ar, nar, items, codec, greedy_nar, ar_generate, nar_sampling=None):
     cfg = ar.config
     utts = []
     for prompt_tokens, prompt, target_tokens, *sampling in items:
@@ -191,8 +214,9 @@ def _synthesize_list(ar, nar, items, codec, greedy_nar, ar_generate):
         if first.numel() == 0:
             raise RuntimeError(f'synthesize: the AR model emitted EOS at its first step (no frames to refine) for utterance {i}')
     dev = firsts[0].device
+    nar_kw = dict(greedy=greedy_nar) if nar_sampling is None else dict(sampling=nar_sampling)
     codes = nar.generate_batch([torch.cat([pt.to(dev), tt.to(dev)]) for pt, _, tt, *_ in utts], [pc.to(dev) for _, pc, *_ in utts],
-                               firsts, greedy=greedy_nar)
+                               firsts, **nar_kw)
     outs = [from_generated(c, cfg) for c in codes]                                      # (Q, Ty) each
     if codec is None:
         return outs

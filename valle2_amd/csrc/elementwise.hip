@@ -1004,13 +1004,10 @@ extern "C" int vh_sample_step_wide_rows(const float* logits, int ldl, int V, int
 //   u = uniform(seed, row, stream_id) * total picks the lane whose range holds the draw, and that lane walks
 //   its range (inverse CDF in index order).  Also returns log p(token) (tests; optional).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void categorical_rows_kernel(
-    const float* __restrict__ logits, int ld, int V, int rows, float inv_temp, int greedy, uint64_t seed,
-    uint32_t stream_id, int64_t* __restrict__ tokens, int64_t tokens_stride, float* __restrict__ logprob) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* lr = logits + (int64_t)row * ld;
+// One row of either launch below, by its wave: `lr` the row's logits, u01 its uniform, `token` / `lp` (may be NULL) where
+// lane 0 (greedy) or the owner lane stores.
+__device__ __forceinline__ void categorical_row(const float* __restrict__ lr, int V, int lane, float inv_temp, bool greedy,
+                                                float u01, int64_t* __restrict__ token, float* __restrict__ lp) {
     const int chunk = (V + 63) / 64;
     const int i0 = min(V, lane * chunk), i1 = min(V, i0 + chunk);
     float m = -INFINITY;
@@ -1027,8 +1024,8 @@ __global__ __launch_bounds__(256) void categorical_rows_kernel(
         for (int o = 32; o >= 1; o >>= 1) cand = min(cand, __shfl_xor(cand, o));
         if (lane == 0) {
             // a row of NaN / -inf only has no maximum: emit the last valid id, never V (outside every table)
-            tokens[(int64_t)row * tokens_stride] = min(cand, V - 1);
-            if (logprob) logprob[row] = 0.f;
+            *token = min(cand, V - 1);
+            if (lp) *lp = 0.f;
         }
         return;
     }
@@ -1041,7 +1038,7 @@ __global__ __launch_bounds__(256) void categorical_rows_kernel(
         if (lane >= o) incl += up;
     }
     const float total = __shfl(incl, 63);
-    const float u = uniform01(seed, (uint32_t)row, stream_id) * total;
+    const float u = u01 * total;
     // the first lane whose inclusive sum exceeds u holds the draw (a lane with an empty range never does
     // unless every later lane is empty too: the last non-empty lane is the fallback for u == total rounding)
     const unsigned long long hit = __ballot(incl > u && i1 > i0);
@@ -1054,9 +1051,19 @@ __global__ __launch_bounds__(256) void categorical_rows_kernel(
             acc += expf(lr[i] * inv_temp - wm);
             if (acc > u) { pick = i; break; }
         }
-        tokens[(int64_t)row * tokens_stride] = pick;
-        if (logprob) logprob[row] = (lr[pick] * inv_temp - wm) - logf(total);
+        *token = pick;
+        if (lp) *lp = (lr[pick] * inv_temp - wm) - logf(total);
     }
+}
+
+__global__ __launch_bounds__(256) void categorical_rows_kernel(
+    const float* __restrict__ logits, int ld, int V, int rows, float inv_temp, int greedy, uint64_t seed,
+    uint32_t stream_id, int64_t* __restrict__ tokens, int64_t tokens_stride, float* __restrict__ logprob) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    categorical_row(logits + (int64_t)row * ld, V, lane, inv_temp, greedy != 0, uniform01(seed, (uint32_t)row, stream_id),
+                    tokens + (int64_t)row * tokens_stride, logprob ? logprob + row : nullptr);
 }
 
 extern "C" int vh_categorical_rows(const float* logits, int ld, int V, int rows, float temperature, int greedy,
@@ -1071,6 +1078,51 @@ extern "C" int vh_categorical_rows(const float* logits, int ld, int V, int rows,
                        V, rows, greedy ? 1.0f : 1.0f / temperature, greedy, seed, stream_id, tokens, tokens_stride,
                        logprob);
     VH_CHECK_LAUNCH("vh_categorical_rows");
+    return VH_OK;
+}
+
+// The same draw keyed on the REQUEST: packed row r belongs to request g = row_request[r] and is its frame t = row_key[r];
+// seed, temperature and greediness (top_k == 1) come from requests[g], the uniform is uniform01(seed, t, stream_id) and the
+// token lands at tokens[g * request_stride + t * key_stride] — nothing of the row's place in the launch enters.  g and t are
+// the same for every lane of the wave (read through the first lane, so the record is a wave-uniform load); a row whose g or
+// t is out of range reads no record and stores nothing.  1 / temperature is the fp32 division of ROW_SAMPLING_LOAD.
+__global__ __launch_bounds__(256) void categorical_rows_keyed_kernel(
+    const float* __restrict__ logits, int ld, int V, int rows, const vh_row_sampling* __restrict__ requests, int n_requests,
+    const int32_t* __restrict__ row_request, const int32_t* __restrict__ row_key, int n_keys, uint32_t stream_id,
+    int64_t* __restrict__ tokens, int64_t request_stride, int64_t key_stride, float* __restrict__ logprob) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int g = __builtin_amdgcn_readfirstlane(row_request[row]);
+    const int t = __builtin_amdgcn_readfirstlane(row_key[row]);
+    if (g < 0 || g >= n_requests || t < 0 || t >= n_keys) return;
+    const vh_row_sampling rq = requests[g];
+    const bool greedy = rq.top_k == 1;
+    categorical_row(logits + (int64_t)row * ld, V, lane, greedy ? 1.0f : 1.0f / rq.temperature, greedy,
+                    uniform01(rq.seed, (uint32_t)t, stream_id), tokens + (int64_t)g * request_stride + (int64_t)t * key_stride,
+                    logprob ? logprob + row : nullptr);
+}
+
+extern "C" int vh_categorical_rows_keyed(const float* logits, int ld, int V, int rows, const vh_row_sampling* requests,
+                                         int n_requests, const int32_t* row_request, const int32_t* row_key, int n_keys,
+                                         uint32_t stream_id, int64_t* tokens, int64_t request_stride, int64_t key_stride,
+                                         float* logprob, void* stream) {
+    VH_REQUIRE(logits, VH_EINVAL, "vh_categorical_rows_keyed: null logits");
+    VH_REQUIRE(requests, VH_EINVAL, "vh_categorical_rows_keyed: null requests (vh_categorical_rows takes one seed for every row)");
+    VH_REQUIRE(row_request && row_key, VH_EINVAL, "vh_categorical_rows_keyed: null row_request / row_key");
+    VH_REQUIRE(tokens, VH_EINVAL, "vh_categorical_rows_keyed: null tokens");
+    VH_REQUIRE(V > 0 && ld >= V && rows >= 0, VH_EINVAL, "vh_categorical_rows_keyed: bad dims rows=%d V=%d ld=%d", rows, V, ld);
+    VH_REQUIRE(n_requests >= 1 && n_keys >= 1, VH_EINVAL, "vh_categorical_rows_keyed: n_requests=%d n_keys=%d must be >= 1",
+               n_requests, n_keys);
+    VH_REQUIRE(request_stride >= 1 && key_stride >= 1, VH_EINVAL,
+               "vh_categorical_rows_keyed: request_stride=%lld key_stride=%lld must be >= 1", (long long)request_stride,
+               (long long)key_stride);
+    VH_REQUIRE(vh_aligned16(requests), VH_EALIGN, "vh_categorical_rows_keyed: requests must be 16-byte aligned");
+    if (rows == 0) return VH_OK;
+    hipLaunchKernelGGL(categorical_rows_keyed_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, ld,
+                       V, rows, requests, n_requests, row_request, row_key, n_keys, stream_id, tokens, request_stride,
+                       key_stride, logprob);
+    VH_CHECK_LAUNCH("vh_categorical_rows_keyed");
     return VH_OK;
 }
 

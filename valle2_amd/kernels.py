@@ -919,6 +919,34 @@ def categorical_rows(logits, tokens, temperature=1.0, greedy=False, seed=0, stre
     return tokens
 
 
+def categorical_rows_keyed(logits, tokens, requests, row_request, row_key, stream_id, logprob=None):
+    """`vh_categorical_rows_keyed`: packed row r of logits (R, V) is frame row_key[r] of request row_request[r]; its draw is
+    uniform01(seed of the request, frame, stream_id) under the request's temperature (its top_k == 1: the arg-max) and its
+    token goes to tokens[request, frame].  tokens: an int64 device view (n_requests, n_keys) with any strides (a codebook
+    column of the codes tensor); requests: the uint8 (n_requests, ROW_SAMPLING_BYTES) device tensor of `pack_row_sampling`;
+    row_request / row_key: int32 device tensors of R entries."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < 1:
+        raise _lib.VhError(f'categorical_rows_keyed: logits {tuple(logits.shape)} must be (R, V) rows with unit stride')
+    R, V = logits.shape
+    if tokens.dtype != torch.int64 or tokens.dim() != 2 or not tokens.is_cuda or 0 in tokens.shape:
+        raise _lib.VhError(f'categorical_rows_keyed: tokens must be an int64 device view (n_requests, n_keys), got '
+                           f'{tuple(tokens.shape)} {tokens.dtype}')
+    n_requests, n_keys = tokens.shape
+    if requests.dtype != torch.uint8 or tuple(requests.shape) != (n_requests, ROW_SAMPLING_BYTES) or not requests.is_cuda:
+        raise _lib.VhError(f'categorical_rows_keyed: requests must be a uint8 device tensor ({n_requests}, '
+                           f'{ROW_SAMPLING_BYTES}), got {tuple(requests.shape)} {requests.dtype}')
+    if logprob is not None and (logprob.dtype != torch.float32 or logprob.numel() != R or not logprob.is_contiguous()):
+        raise _lib.VhError('categorical_rows_keyed: logprob must be a contiguous fp32 device tensor of R entries')
+    if R == 0:
+        return tokens
+    check(_lib.lib().vh_categorical_rows_keyed(
+        _dev_f32(logits, 'logits'), logits.stride(0) if R > 1 else V, V, R, ptr(requests), n_requests,
+        _i32_dev(row_request, R, 'categorical_rows_keyed: row_request'), _i32_dev(row_key, R, 'categorical_rows_keyed: row_key'),
+        n_keys, int(stream_id) & 0xFFFFFFFF, tokens.data_ptr(), tokens.stride(0) if n_requests > 1 else 1,
+        tokens.stride(1) if n_keys > 1 else 1, ptr(logprob), stream()), 'vh_categorical_rows_keyed')
+    return tokens
+
+
 def gemm(a, b, out, a_kmajor=False, b_kmajor=False):
     """out = op(a) @ op(b) through vh_gemm_batched.  a, b, out are 2-D (rows, cols) or 4-D
     (batch, heads, rows, cols) tensors / views with unit stride in the last dimension:

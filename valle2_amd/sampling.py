@@ -15,6 +15,13 @@ def _is_real(v):
     return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
 
 
+# The NAR stage n draws on stream NAR_STREAM | n.  The generator's third argument is an audio position (< 5000) in the AR
+# stage and the stream here, its second the beam index there and the frame index here: with the high bit set a request's AR
+# draw (seed, beam j, position p) and its NAR draw (seed, frame t, stage n) never share a uniform (without it (j, p) == (t, n)
+# would).
+NAR_STREAM = 0x80000000
+
+
 @dataclass(frozen=True)
 class Sampling:
     """The sampling of ONE utterance: Sampling(seed, top_k=None, tok_p=None, temperature=None); None is the config's value.
@@ -22,7 +29,9 @@ class Sampling:
     With it the utterance's draws are a function of (seed, beam index within the utterance, audio position) and its filter
     is its own: the same in generate(), generate_batch(beams=n) at any group index, generate_many and generate_queued at any
     slot, started or refilled, whatever else the call decodes.  top_k == 1 is greedy decoding for this utterance (the largest
-    logit, the lowest index on ties, scores exactly 0); top_k == 0 keeps the whole vocabulary.  Ranges (ValueError): seed an
+    logit, the lowest index on ties, scores exactly 0); top_k == 0 keeps the whole vocabulary.  The NAR stage
+    (ValleNAR.generate_batch(sampling=...)) takes the seed, the temperature and top_k == 1 from it: frame t of codebook n
+    draws uniform01(seed, t, NAR_STREAM | n), whatever else the call refines.  Ranges (ValueError): seed an
     int in [0, 2**64), top_k an int >= 0, 0 < tok_p <= 1, temperature > 0."""
     seed: int
     top_k: int | None = None
@@ -52,6 +61,16 @@ class Sampling:
         """The (seed, key, top_k, top_p, temperature) of this utterance's `beams` rows (kernels.pack_row_sampling): beam j
         carries key first_key + j."""
         return [(self.seed, first_key + j) + self.resolved(cfg) for j in range(beams)]
+
+    def nar_record(self, cfg):
+        """The (seed, key, top_k, top_p, temperature) record the NAR stage sampler reads for this request
+        (vh_categorical_rows_keyed): its seed, its temperature (the config's where this holds None), and top_k 1 only where its
+        OWN top_k is 1 — the reference's NAR stage draws from the whole vocabulary (valle_nar.py:160), so the config's top_k,
+        a request's other top_k values and tok_p do not filter it; the key is the frame's and travels with the row."""
+        temperature = float(cfg.temperature) if self.temperature is None else float(self.temperature)
+        if not temperature > 0.0:
+            raise ValueError(f'Sampling: the config\'s temperature={temperature!r} must be > 0')
+        return (self.seed, 0, 1 if self.top_k == 1 else 0, 1.0, temperature)
 
 
 class KeyedRows(NamedTuple):

@@ -8,15 +8,45 @@ AdaLN conditioned on stage_embs[n-1], full attention, head proj_layers[n-1].
 """
 from __future__ import annotations
 
+import functools
+import inspect
 import random
 
 import torch
 import torch.nn as nn
 
 from . import _lib, dropout, kernels
+from . import sampling as _sampling
 from .engine import ForwardScratch, ForwardScratch16, KVCache, head16, transformer_forward, transformer_forward_bf16
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device
 from .valle_ar import _Base
+
+
+def _sampling_refused_early(fn):
+    """generate(sampling=...) / generate_batch(sampling=[...]): what is wrong with the Sampling entries is said before
+    anything touches a device (the wrappers below move the call to the HIP device first)."""
+    sig = inspect.signature(fn)
+    name = fn.__name__
+
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        if kwargs.get('sampling') is not None:
+            a = sig.bind(self, *args, **kwargs).arguments
+            given = a['sampling']
+            if 'texts' not in a:                                       # generate: one Sampling
+                given = [given]
+            elif not isinstance(given, (list, tuple)):
+                raise ValueError(f'{name}: sampling is {type(given).__name__}, not a list with one valle2_amd.Sampling per utterance')
+            for i, s in enumerate(given):
+                if s is not None and not isinstance(s, _sampling.Sampling):
+                    raise ValueError(f'{name}: sampling{f" of utterance {i}" if "texts" in a else ""} is {type(s).__name__}, '
+                                     'not a valle2_amd.Sampling')
+            if a.get('seed') is not None:
+                raise ValueError(f'{name}: sampling together with seed= (every Sampling carries its own seed)')
+            for s in _sampling.check_list(name, given, len(a['texts']) if 'texts' in a else 1) or ():
+                s.nar_record(self.config)                              # the config's temperature, where the request has none
+        return fn(self, *args, **kwargs)
+    return wrapper
 
 
 class ValleNAR(_Base):
@@ -171,19 +201,24 @@ class ValleNAR(_Base):
         scheduler = optim.lr_scheduler.CosineAnnealingWarmRestarts(optimizer, self.config.lr_warmup)
         return {'optimizer': optimizer, 'lr_scheduler': scheduler}
 
+    @_sampling_refused_early
     @_on_device
     @torch.inference_mode()
     def generate(self, prompt_tokens, prompt_codes, target_tokens, target_codes_first_layer,
-                 greedy: bool = False):
+                 greedy: bool = False, *, sampling=None):
         """valle_nar.py:107-165 (intended algorithm) → codes (Ty, Q) int64.  The reference samples
         from Categorical(logits / temperature) (:160); greedy=True takes the arg-max instead,
-        which is what the parity tests pin.  One utterance of `generate_batch`."""
+        which is what the parity tests pin.  One utterance of `generate_batch`.
+        sampling (keyword-only, a valle2_amd.Sampling): the request's own seed and temperature, see `generate_batch`."""
         text = torch.cat([prompt_tokens, target_tokens], dim=0)
-        return self.generate_batch([text], [prompt_codes], [target_codes_first_layer], greedy=greedy)[0]
+        return self.generate_batch([text], [prompt_codes], [target_codes_first_layer], greedy=greedy,
+                                   sampling=None if sampling is None else [sampling])[0]
 
+    @_sampling_refused_early
     @_on_device
     @torch.inference_mode()
-    def generate_batch(self, texts, prompt_codes, first_layers, greedy: bool = False, seed=None, perf_mode: bool = False):
+    def generate_batch(self, texts, prompt_codes, first_layers, greedy: bool = False, seed=None, perf_mode: bool = False, *,
+                       sampling=None):
         """Batched NAR decoding of B independent utterances (extension; `generate` is built on it).
         texts[b]: 1-D int64 text ids (prompt + target text); prompt_codes[b]: (Tc_b, Q) int64 acoustic
         prompt; first_layers[b]: (Ty_b,) int64 first-codebook codes of the target (the AR model's
@@ -196,7 +231,14 @@ class ValleNAR(_Base):
         once, and codebook n is drawn on the device by `vh_categorical_rows` (Categorical(logits /
         temperature), or the arg-max when greedy).
         perf_mode=True: the seven stack forwards on the bf16 matrix cores (see `stage_logits`); the drawn codes are then not
-        guaranteed to be the parity path's."""
+        guaranteed to be the parity path's.
+        sampling (keyword-only): a list with one valle2_amd.Sampling per utterance (every entry or None).  Frame t of codebook
+        n of utterance b is then drawn from uniform01(sampling[b].seed, t, NAR_STREAM | n) at sampling[b]'s temperature (None:
+        the config's), or is the arg-max where sampling[b].top_k == 1 (its other top_k values and tok_p are not read: this
+        stage has no filter) — by `vh_categorical_rows_keyed`, straight into the codes tensor.  Nothing is drawn from torch's
+        generator and nothing of the draw depends on the other utterances, their order or their lengths; a token can differ
+        between two calls only where the utterance's own logits do.  greedy=True makes every request greedy; refused with
+        seed= (ValueError)."""
         dev = self._dev()
         cfg = self.config
         q, d = cfg.num_quantizers, cfg.d_model
@@ -241,9 +283,19 @@ class ValleNAR(_Base):
         scratch = (ForwardScratch16 if perf_mode else ForwardScratch)(B * total, d, cfg.dim_feedforward, dev)
         forward = transformer_forward_bf16 if perf_mode else transformer_forward
         x = torch.empty_like(base)
-        if seed is None:       # drawn from torch's generator, so torch.manual_seed() makes a run repeatable
-            seed = 0 if greedy else int(torch.randint(0, 2 ** 62, (1,)).item())
-        toks = torch.empty(starts[-1], device=dev, dtype=torch.int64)
+        sampling = _sampling.check_list('generate_batch', sampling, B)
+        if sampling is not None:
+            # one record per utterance and the (utterance, frame) of every packed row, once per call
+            records = [s.nar_record(cfg) for s in sampling]
+            if greedy:
+                records = [(sd, key, 1, top_p, temperature) for sd, key, _, top_p, temperature in records]
+            requests = _lib.to_device_async(kernels.pack_row_sampling(records), dev)
+            row_request = i32([b for b in range(B) for _ in range(tys[b])])
+            row_key = i32([t for b in range(B) for t in range(tys[b])])
+        else:
+            if seed is None:       # drawn from torch's generator, so torch.manual_seed() makes a run repeatable
+                seed = 0 if greedy else int(torch.randint(0, 2 ** 62, (1,)).item())
+            toks = torch.empty(starts[-1], device=dev, dtype=torch.int64)
         for n in range(1, q):
             x.copy_(base)
             kernels.embed_sum_pe(out, self._tables(n), pe_a, 0, x, lens=ty_d, row_pos0=tc_d, row_t0=t0_target,
@@ -252,6 +304,9 @@ class ValleNAR(_Base):
                     embedding=self.stage_embs[n - 1].weight, scratch=scratch)                # (cached AdaLN table per stage)
             z = x.view(B * total, d).index_select(0, idx)                      # target frames of every row
             logits = self._head(z, n, perf_mode)
+            if sampling is not None:
+                kernels.categorical_rows_keyed(logits, out[:, :, n], requests, row_request, row_key, _sampling.NAR_STREAM | n)
+                continue
             kernels.categorical_rows(logits, toks, temperature=cfg.temperature, greedy=greedy, seed=seed,
                                      stream_id=n)
             out[:, :, n][valid] = toks                                          # packed row-major -> (B, ty_max)
