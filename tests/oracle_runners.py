@@ -970,3 +970,218 @@ def check_ce(loss, dlogits, ref, rows):
 
 def check_softmax(P, dS, ref):
     _collect([('P', lambda: check_close('P', P, ref['P'])), ('dS', lambda: check_close('dS', dS, ref['dS']))])
+
+
+# ---- many-row attention on every mask geometry (tests/test_attn_geometry_cpu.py, tests/test_attn_geometry_gpu.py) -----------
+# name -> (B, h, Tq, Tk, mode).  What a case is for stands beside it; the per-row lengths are in ATTN_GEOMETRY_LENGTHS.  Block
+# sizes of the kernels under test: 32-key tiles and 32-query waves, 64-key tiles (attn16), 128-query blocks, key chunks of
+# attn_chunk_keys(T, n) <= 256 keys (the fused backward).  Tq < Tk cases are forward only (the backward is Tq == Tk).
+ATTN_GEOMETRY_CASES = {
+    'prefix_small': (4, 2, 100, 100, 'prefix'),      # T <= 128: one query block, one chunk; x_len 0, 1, T and above T
+    'prefix_mid': (4, 2, 200, 200, 'prefix'),        # 129 .. 256: one chunk of 224 keys; kv_len ==, just above and below x_len
+    'prefix_long': (4, 2, 600, 600, 'prefix'),       # > 512: three chunks of 224 (the last holds 152), five query blocks (88), a
+                                                     # last tile of 24; the prefix ends on a chunk edge (224), inside chunks
+    'prefix_512': (4, 2, 512, 512, 'prefix'),        # a multiple of 256: two full chunks, the prefix end on their edge; kv_len > Tk
+    'prefix_scalar': (2, 1, 300, 300, 'prefix'),     # the host-side x_len (no x_len_dev) on a 32-key wave edge
+    'full_small': (4, 2, 100, 100, 'full'),          # attn_bwd_fused_kernel<4> (one chunk of 128 keys); kv_len = 1
+    'full_mid': (4, 2, 200, 200, 'full'),            # one chunk of 224 (<8>) or two of 128 (<4>)
+    'full_long': (4, 2, 600, 600, 'full'),           # three to five chunks; kv_len > Tk, chunks that are all padding
+    'full_512': (3, 1, 512, 512, 'full'),
+    'explicit_shared': (2, 2, 300, 300, 'explicit'),         # one (Tq, Tk) mask + pad, forward and backward
+    'explicit_bmask': (3, 2, 70, 150, 'explicit'),           # a (B, Tq, Tk) mask + pad: vh_attn_rows_bmask, forward only
+    'prefix_tq_lt_tk': (4, 2, 150, 400, 'prefix'),           # q_off = 250 (no multiple of 32): queries on both sides of the prefix end
+    'full_tq_lt_tk': (2, 2, 70, 333, 'full'),
+    'empty_row_full': (3, 2, 300, 300, 'full'),              # a batch row with kv_len = 0 beside ordinary rows, slab path
+    'empty_row_prefix': (4, 2, 300, 300, 'prefix'),
+    'empty_row_small': (3, 2, 100, 100, 'prefix'),           # ... and where one chunk writes dQ itself (no slab, no reduce)
+}
+ATTN_GEOMETRY_LENGTHS = {       # per batch row: x_len_dev (prefix cases; an int = the host-side x_len) and kv_len
+    'prefix_small': dict(x_len_dev=[0, 1, 100, 133], kv_len=[100, 1, 64, 33]),
+    'prefix_mid': dict(x_len_dev=[31, 32, 33, 129], kv_len=[200, 32, 34, 128]),
+    'prefix_long': dict(x_len_dev=[224, 257, 255, 127], kv_len=[600, 511, 256, 129]),
+    'prefix_512': dict(x_len_dev=[256, 512, 64, 65], kv_len=[512, 257, 63, 700]),
+    'prefix_scalar': dict(x_len=128, kv_len=[300, 127]),
+    'full_small': dict(kv_len=[100, 1, 31, 65]),
+    'full_mid': dict(kv_len=[200, 127, 128, 129]),
+    'full_long': dict(kv_len=[900, 255, 449, 32]),
+    'full_512': dict(kv_len=[512, 511, 385]),
+    'explicit_shared': {}, 'explicit_bmask': {},
+    'prefix_tq_lt_tk': dict(x_len_dev=[300, 285, 100, 401], kv_len=[400, 399, 320, 383]),
+    'full_tq_lt_tk': dict(kv_len=[333, 193]),
+    'empty_row_full': dict(kv_len=[300, 0, 191]),
+    'empty_row_prefix': dict(x_len_dev=[63, 50, 128, 290], kv_len=[300, 0, 257, 192]),
+    'empty_row_small': dict(x_len_dev=[40, 40, 96], kv_len=[100, 0, 97]),
+}
+ATTN_EMPTY_ROWS = {'empty_row_full': [1], 'empty_row_prefix': [1], 'empty_row_small': [1]}          # batch rows without a key (kv_len = 0)
+ATTN_QUANTITIES = ('out', 'lse2', 'dq', 'dk', 'dv')
+# (atol, rtol) per quantity: out from tests/test_kernels_gpu.py::test_attn_rows, the gradients from tests/test_train_gpu.py::
+# test_attn_rows_bwd_vs_torch_autograd; lse2 has SUM_MARGIN times the fp32 emulation's measured error instead (the GPU file)
+ATTN_TOL = {'out': (3e-5, 0.0), 'dq': (6e-5, 1e-4), 'dk': (6e-5, 1e-4), 'dv': (6e-5, 1e-4)}
+ATTN_Q16_PRESCALE = 0.125 * 1.4426950408889634          # kernels.Q16_PRESCALE: what attn_rows_bf16 expects q multiplied by
+ATTN_FAULTS = {       # fault -> (the case that must reject it, the quantities it must show on)
+    'x_len_of_row0': ('prefix_mid', ('out', 'lse2', 'dq', 'dk', 'dv')),
+    'causal_lt': ('prefix_long', ('out', 'lse2', 'dq', 'dk', 'dv')),
+    'qpos_gt': ('prefix_long', ('out', 'lse2', 'dq', 'dk', 'dv')),
+    'no_q_off': ('prefix_tq_lt_tk', ('out', 'lse2')),
+    'kv_unclamped_pad_ignored': ('explicit_shared', ('out', 'lse2', 'dq', 'dk', 'dv')),
+    'mask_of_row0': ('explicit_bmask', ('out', 'lse2')),
+    'diag_tile_unmasked': ('prefix_long', ('out', 'lse2', 'dq', 'dk', 'dv')),
+    'tile_skipped_by_first_query': ('prefix_tq_lt_tk', ('out', 'lse2')),
+    'dq_chunk_lost': ('prefix_long', ('dq',)),
+    'dq_chunk_extra': ('prefix_long', ('dq',)),
+}
+
+
+def attn_chunk_keys(T, n_chunks=None):
+    """Keys per chunk of the fused backward when T keys are cut into n_chunks (default: the fewest, ceil(T / 256)): equal
+    chunks of whole 32-key wave blocks (vh_attn_rows_bwd_ws)."""
+    n = n_chunks or -(-T // 256)
+    return (-(-T // n) + 31) // 32 * 32
+
+
+def attn_geometry_inputs(name):
+    """(q (B, h, Tq, 64), k, v (B, h, Tk, 64), dout (B, h, Tq, 64), mode, spec) of the case: seeded randn, so q . k / 8 has
+    unit variance; spec holds the mask arguments as CPU tensors (x_len int / x_len_dev, kv_len int32; mask, pad uint8).  Every
+    query keeps a visible key (kv_len >= 1; explicit: key 0 is never masked or padded) except the rows of ATTN_EMPTY_ROWS."""
+    B, h, Tq, Tk, mode = ATTN_GEOMETRY_CASES[name]
+    seed = 700 + 10 * list(ATTN_GEOMETRY_CASES).index(name)
+    q, dout = (torch.randn(B, h, Tq, 64, generator=_g(seed + i)) for i in (0, 3))
+    k, v = (torch.randn(B, h, Tk, 64, generator=_g(seed + i)) for i in (1, 2))
+    spec = {key: (val if isinstance(val, int) else torch.tensor(val, dtype=torch.int32))
+            for key, val in ATTN_GEOMETRY_LENGTHS[name].items()}
+    if mode == 'explicit':
+        per_row = name == 'explicit_bmask'
+        mask = torch.rand((B, Tq, Tk) if per_row else (Tq, Tk), generator=_g(seed + 4)) < 0.3
+        mask[..., 0] = False
+        pad = torch.zeros(B, Tk, dtype=torch.bool)
+        pad[1, 10:40] = True
+        pad[1, Tk - 37:] = True
+        pad[B - 1, 1:Tk:3] = True
+        spec = dict(mask=mask.to(torch.uint8), pad=pad.to(torch.uint8))
+    return q, k, v, dout, mode, spec
+
+
+def attn_visible(name, spec, fault=None):
+    """(B, Tq, Tk) bool: the keys query i of batch row b sees, written from the three lines of include/valle_hip.h
+    (vh_attn_rows), the query's position being Tk - Tq + i.  fault: the visibility a wrong kernel would apply —
+      'x_len_of_row0'   x_len_dev[0] for every batch row          'causal_lt'  key < qpos for key <= qpos
+      'qpos_gt'         qpos > xl for qpos >= xl                   'no_q_off'   the query's position taken as i
+      'kv_unclamped_pad_ignored'  explicit mode without pad        'mask_of_row0'  the mask's batch stride taken as 0
+      'diag_tile_unmasked'  a wave (32 queries) takes a 32-key tile without the element mask when the tile's FIRST key, not
+                        its last, is at or before the wave's first query (and the tile lies below kv_len, the wave past xl)
+      'tile_skipped_by_first_query'  a wave skips the tiles that lie beyond its FIRST query, not its last."""
+    B, h, Tq, Tk, mode = ATTN_GEOMETRY_CASES[name]
+    q_off = Tk - Tq
+    j = torch.arange(Tk)[None, None, :]
+    i = torch.arange(Tq)[None, :, None]
+    if mode == 'explicit':
+        mask = spec['mask'].bool()
+        mask = mask[None].expand(B, Tq, Tk) if mask.dim() == 2 else mask
+        if fault == 'mask_of_row0':
+            mask = mask[:1].expand(B, Tq, Tk)
+        pad = torch.zeros_like(spec['pad']) if fault == 'kv_unclamped_pad_ignored' else spec['pad']
+        return ~mask & ~pad.bool()[:, None, :]
+    kvl = spec['kv_len'].long().clamp(max=Tk)
+    vis = (j < kvl[:, None, None]).expand(B, Tq, Tk)
+    if mode == 'full':
+        return vis.clone()
+    xl = spec['x_len_dev'].long() if 'x_len_dev' in spec else torch.full((B,), spec['x_len'])
+    if fault == 'x_len_of_row0':
+        xl = xl[:1].expand(B)
+    x = xl[:, None, None]
+    qpos = i if fault == 'no_q_off' else q_off + i
+    past = qpos > x if fault == 'qpos_gt' else qpos >= x
+    causal = j < qpos if fault == 'causal_lt' else j <= qpos
+    vis = (vis & ((j < x) | (past & causal))).clone()
+    if fault in ('diag_tile_unmasked', 'tile_skipped_by_first_query'):
+        for b in range(B):
+            for w0 in range(0, Tq, 32):                      # a wave's queries w0 .. w0 + 31, positions from wpos_min on
+                wpos_min = q_off + w0
+                for k0 in range(0, Tk, 32):
+                    if fault == 'diag_tile_unmasked':
+                        if k0 + 32 <= int(kvl[b]) and wpos_min >= int(xl[b]) and k0 <= wpos_min:
+                            vis[b, w0:w0 + 32, k0:k0 + 32] = True
+                    elif not (k0 < int(xl[b]) or (wpos_min >= int(xl[b]) and k0 <= wpos_min)):
+                        vis[b, w0:w0 + 32, k0:k0 + 32] = False
+    return vis
+
+
+def attn_geometry_reference(name, dtype=torch.float64, fault=None, h16=None):
+    """out, lse2 (B, h, Tq) and — where Tq == Tk — dq, dk, dv of the case, written out from the definition in `dtype`
+    (float64: what the GPU tests compare against; float32: the emulation of a kernel):
+      P = softmax(q k^T / 8 + mask), lse2 = logsumexp / ln 2, out = P v, dV = P^T dO, dS = P o (dP - rowsum(dO o out)),
+      dQ = dS k / 8, dK = dS^T q / 8.
+    A batch row without a key (ATTN_EMPTY_ROWS) has P = 0: zero gradients; its out / lse2 are not compared.  h16: q (scaled
+    by ATTN_Q16_PRESCALE first, as vh_linear_qkv_bf16 leaves it), k and v rounded to that 16-bit format before anything else.
+    fault: one of attn_visible's, or in the chunk bookkeeping of the fused backward at the fewest chunks —
+      'dq_chunk_lost'   dQ leaves out every key chunk that starts at or after x_len, whatever the query
+      'dq_chunk_extra'  dQ adds a slab of ones for every chunk the fused kernel never wrote for the query (a chunk of
+                        padding; under the prefix mask a chunk starting at or after x_len and after the query)."""
+    q, k, v, dout, mode, spec = attn_geometry_inputs(name)
+    B, h, Tq, Tk, _ = ATTN_GEOMETRY_CASES[name]
+    if h16 is not None:
+        q = (q * ATTN_Q16_PRESCALE).to(h16).double() / ATTN_Q16_PRESCALE
+        k, v = k.to(h16), v.to(h16)
+    q, k, v, dout = (t.to(dtype) for t in (q, k, v, dout))
+    chunk_fault = fault in ('dq_chunk_lost', 'dq_chunk_extra')
+    vis = attn_visible(name, spec, None if chunk_fault else fault)[:, None]
+    s = (q @ k.transpose(-1, -2) / 8).masked_fill(~vis, O.NEG_INF)
+    lse = torch.logsumexp(s, dim=-1)
+    P = torch.where(vis.any(-1, keepdim=True), torch.exp(s - lse[..., None]), torch.zeros((), dtype=dtype))
+    out = P @ v
+    res = dict(out=out, lse2=lse / math.log(2.0))
+    if Tq != Tk:
+        return res
+    dP = dout @ v.transpose(-1, -2)
+    dS = P * (dP - (dout * out).sum(-1, keepdim=True))
+    res.update(dv=P.transpose(-1, -2) @ dout, dk=dS.transpose(-1, -2) @ q / 8)
+    dS_q = dS
+    if chunk_fault:
+        ck = attn_chunk_keys(Tk)
+        kb0 = (torch.arange(Tk) // ck * ck)[None, :]                          # first key of the chunk a key lies in
+        xl = spec['x_len_dev'].long() if 'x_len_dev' in spec else torch.full((B,), spec.get('x_len', Tk))
+        if fault == 'dq_chunk_lost':
+            dS_q = dS * (kb0 < xl[:, None])[:, None, None, :].to(dtype)
+    res['dq'] = dS_q @ k / 8
+    if fault == 'dq_chunk_extra':
+        kvl = spec['kv_len'].long().clamp(max=Tk)
+        qi = torch.arange(Tq)[None, :]
+        for c0 in range(0, Tk, ck):
+            unwritten = (c0 >= kvl)[:, None] | ((c0 >= xl)[:, None] & (qi < c0) if mode == 'prefix' else False)
+            res['dq'] = res['dq'] + 0.125 * unwritten[:, None, :, None].to(dtype)
+    return res
+
+
+def attn_kept_rows(name):
+    """Batch rows whose out / lse2 are compared (all but ATTN_EMPTY_ROWS)."""
+    return [b for b in range(ATTN_GEOMETRY_CASES[name][0]) if b not in ATTN_EMPTY_ROWS.get(name, [])]
+
+
+def attn_miss(quantity, got, ref, lse2_measured=None):
+    """How far `got` is from the float64 reference, in units of the tolerance the GPU file applies to the quantity: the largest
+    |got - ref| / (atol + rtol |ref|) (lse2: / (SUM_MARGIN x the fp32 emulation's measured error)).  <= 1 passes; NaN -> inf."""
+    got, ref = got.detach().cpu().double(), ref.detach().double()
+    assert got.shape == ref.shape, f'{quantity}: shape {tuple(got.shape)} vs {tuple(ref.shape)}'
+    if quantity == 'lse2':
+        tol = torch.full_like(ref, SUM_MARGIN * lse2_measured)
+    else:
+        tol = ATTN_TOL[quantity][0] + ATTN_TOL[quantity][1] * ref.abs()
+    ratio = ((got - ref).abs() / tol)
+    return float(torch.nan_to_num(ratio, nan=float('inf')).max()) if ratio.numel() else 0.0
+
+
+def check_attn(name, got, ref, lse2_measured, quantities=None):
+    """The quantities of `got` (same layout as the reference's) against float64; out / lse2 on attn_kept_rows only, and the
+    gradients of a row without a key exactly zero.  Fails once, naming every quantity that failed."""
+    kept = attn_kept_rows(name)
+
+    def one(qn):
+        g_, r_ = got[qn], ref[qn]
+        if qn in ('out', 'lse2'):
+            g_, r_ = g_[kept], r_[kept]
+        else:
+            for b in ATTN_EMPTY_ROWS.get(name, []):
+                assert float(g_[b].abs().max()) == 0.0, f'{qn}: row {b} has no key, its gradient must be exactly zero'
+        m = attn_miss(qn, g_, r_, lse2_measured)
+        assert m <= 1.0, f'{qn}: {m:.3g} x the tolerance (worst error {worst(g_, r_):.3e})'
+    _collect([(qn, lambda qn=qn: one(qn)) for qn in (quantities or ATTN_QUANTITIES) if qn in ref and qn in got])

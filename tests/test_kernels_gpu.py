@@ -270,6 +270,29 @@ def test_linear_fused_layernorm(K, M, ada):
     close(K.linear(a.to(DEV), w.to(DEV), ln=ln), ref, atol=5e-5)
 
 
+@pytest.mark.parametrize('M', [17, 20, 48, 64])
+def test_linear_in_place_residual_off_the_fast_path(K, M):
+    """K % 128 != 0 at 17 .. 64 rows: the generic skinny kernel (no row groups) used to be launched with the row groups'
+    gridDim.z, so several workgroups wrote every column block — and with out == residual (the FeedForward's second product at
+    dim_feedforward = 528, the prompt pass of a 20-token prompt) one that read the residual after another one's store added it
+    twice, now and then.  Every repetition must give the reference's result, bit for bit the same."""
+    N, K_ = 128, 528
+    a = torch.randn(M, K_, generator=g(70))
+    w = torch.randn(N, K_, generator=g(71)) / math.sqrt(K_)
+    bias = torch.randn(N, generator=g(72))
+    x = torch.randn(M, N, generator=g(73))
+    ref = (x.double() + a.double() @ w.double().T + bias.double()).float()
+    ad, wd, bd, xd = a.to(DEV), w.to(DEV), bias.to(DEV), x.to(DEV)
+    first = None
+    for rep in range(20):
+        out = xd.clone()
+        K.linear(ad, wd, bd, residual=out, out=out)
+        got = out.cpu()
+        close(got, ref)
+        first = got if first is None else first
+        assert torch.equal(got, first), rep
+
+
 @pytest.mark.parametrize('M,N,K_,act', [(3, 96, 128, 0), (32, 2048, 512, 1), (32, 1536, 512, 0), (64, 64, 1024, 1),
                                         (17, 512, 256, 0)])
 def test_linear_folded_layernorm(K, M, N, K_, act):

@@ -478,7 +478,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmArgs a, int tiles
     // that are never stored — and a K tail (K % 32 = 16) is clamped here and zeroed when the slab is
     // written to LDS.
     auto gload1 = [&](int i, int k0) {           // one A row + one W row of the K slab at k0
-        const int kk = k0 + skq < a.k_len ? k0 : 0;  // K % 4 == 0 is guaranteed by the host check
+        // K % 4 == 0 is guaranteed by the host check.  A quad beyond the K range reads the row's FIRST quad instead (the value is
+        // zeroed in lstore): with k0 alone clamped to 0 it read columns skq .. skq + 3 of the first slab, which at K < 32 (K = 16)
+        // lie past the row — for the last row of A and of W up to 60 bytes past the end of the matrix
+        const int kk = k0 + skq < a.k_len ? k0 : -skq;
         ra[i] = ld4(pa[i] + kk);
         rw[i] = ld4(pw[i] + kk);
     };
@@ -1623,6 +1626,11 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
         } else {
         // ---- generic guarded kernel for every other K (multiple of 16)
         if (a.w16) { vh_set_error("%s: no 16-bit-weight form of this shape (K=%d)", name, a.K); return VH_EUNSUPPORTED; }
+        // this kernel has no row groups: every workgroup of a column group computes ALL rows.  With the gridDim.z of the row
+        // groups left in place, M = 17 .. 64 launched two to eight workgroups per column group that each wrote the whole
+        // column block — and with out == residual (the FeedForward's second product in place, K = dim_feedforward % 128 != 0)
+        // a workgroup that read the residual after another one's store added it twice.
+        grid.z = 1;
 #define SK(MT, NW, CH, LN) \
     hipLaunchKernelGGL((gemm_skinny_kernel<MT, NW, EPI, CH, LN>), grid, dim3(NW * 64), 0, s, a, ln)
         if (has_ln) {
