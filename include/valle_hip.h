@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 136            /* 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 137            /* 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -287,6 +287,24 @@ int vh_attn_rows_lse(const float* q, int ldq, const float* kcache, const float* 
                      int ldo, int B, int n_heads, int Tq, int Tk, int S_max, int mode, int x_len,
                      const int32_t* x_len_dev, const int32_t* kv_len, const uint8_t* mask,
                      const uint8_t* pad, float* lse2, void* stream);
+
+/* vh_attn_rows over the SEGMENTS of one packed row stream, VH_MASK_FULL only: a ragged batch with no padding rows.
+ * Utterance s owns rows seg_start[s] .. seg_start[s] + seg_len[s] - 1 of q (M, ldq), of out (M, ldo) and of ONE K/V stream
+ * per head, kcache / vcache (1, h, S_max >= M, 64), M = the sum of the lengths: query row seg_start[s] + i attends keys seg_start[s] + j, j < seg_len[s],
+ * of the same cache and nothing else.  One workgroup = the 128 queries from blocks[2 i + 1] on of segment blocks[2 i] x one
+ * head, over that segment's keys in 32-key tiles counted from the segment's key 0 — vh_attn_rows' tile order, and its
+ * arithmetic, for that utterance alone (B = 1, Tq = Tk = seg_len[s]): the same bits.  K/V rows past a segment's end are
+ * clamped to its last row and masked; query rows past it are neither loaded nor stored.  Workgroups run in table order:
+ * list the blocks of the longest segment first (they visit the most tiles).
+ * seg_start, seg_len (n_seg) and blocks (n_blocks pairs) are DEVICE int32 arrays the host cannot check: the caller vouches
+ * that the segments are disjoint and inside [0, M), that every block names a segment < n_seg and a first query
+ * 0 <= q0 < seg_len, and that the blocks cover every query once (a query no block covers keeps its old `out` row).  Inside
+ * such segments no row of another segment is read as a visible key and no row at or beyond M is touched.  (A block naming
+ * no segment is skipped and a segment reaching past S_max is cut there, so the caches are never overrun; q and out have
+ * no such guard.) */
+int vh_attn_rows_packed(const float* q, int ldq, const float* kcache, const float* vcache, float* out, int ldo,
+                        int n_heads, int S_max, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
+                        const int32_t* blocks, int n_blocks, void* stream);
 
 /* ---- backward of vh_attn_rows (training, Tq == Tk == T): dQ, dK, dV without materialising P -----
  * replaces the autograd backward of F.scaled_dot_product_attention (valle/models/modules.py:167) in
@@ -845,6 +863,13 @@ typedef struct {
     const float *x_in;
 } vh_forward_desc;
 int vh_transformer_forward(const vh_forward_desc* desc, void* stream);
+/* vh_transformer_forward over packed rows (the NAR stage of a ragged batch): desc->B = 1, desc->T = the sum of the segment
+ * lengths, desc->mode = VH_MASK_FULL, kv_len / x_len_dev / mask / pad NULL (anything else is refused: VH_EINVAL for B,
+ * VH_EUNSUPPORTED for the mask fields); x (T, d) holds utterance s at rows seg_start[s] .. + seg_len[s] - 1 and every layer's
+ * K/V lands at the same rows of its (1, h, S_max, 64) cache.  The launches of vh_transformer_forward with
+ * vh_attn_rows_packed for vh_attn_rows; the segment and block arrays are its arguments, under its contract. */
+int vh_transformer_forward_packed(const vh_forward_desc* desc, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
+                                  const int32_t* blocks, int n_blocks, void* stream);
 
 /* ---- perf mode of the MFMA-bound legs: bf16 operands, fp32 accumulate (opt-in; never the parity path) ------------
  * SURVEY.md section 7's "perf mode" for the prompt pass (valle/models/valle_ar.py:141-158 at kv_cache=None) and the NAR

@@ -238,6 +238,10 @@ SIGNATURES = {
                                   C.c_int64, C.c_int, c_f32p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'vh_transformer_forward': (C.c_int, [C.POINTER(VhForwardDesc), C.c_void_p]),
+    # NAR decoding over packed rows (ABI 137)
+    'vh_attn_rows_packed': (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
+                                      c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_void_p]),
+    'vh_transformer_forward_packed': (C.c_int, [C.POINTER(VhForwardDesc), c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_void_p]),
     'vh_h16_format': (C.c_int, []),
     'vh_to_bf16': (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     'vh_layernorm_bf16': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_float,

@@ -7,6 +7,8 @@
 //                       MFMA's B operand, and the O rescale is lane-local.  K/V tiles of 32 keys
 //                       are register-staged into double-buffered LDS.  Masks are analytic
 //                       (prefix-LM / full / key length), never materialised.   MFMA-bound.
+//  attn_rows_packed_kernel : the same body (attn_rows_body.inc) over the SEGMENTS of one packed row
+//                       stream under the full mask: a ragged NAR batch with no padding rows.
 //  attn_decode_kernel : one query row per (batch, head) against the whole cache — the dominant
 //                       kernel of AR decoding.  Pure HBM streaming: every K/V byte is read once
 //                       with 16-B loads, 1 KiB per wave-instruction, 16 KiB in flight per wave;
@@ -616,180 +618,19 @@ struct RowsArgs {
     int64_t mask_bstride;   // explicit mode: elements between the masks of consecutive batch rows (0: one (Tq,Tk) mask for all)
 };
 
-__global__ __launch_bounds__(256, 2) void attn_rows_kernel(RowsArgs a) {
-    // [buf][K|V][key][KLD]; reused at the end as the [128][KLD] output transpose buffer
-    __shared__ __attribute__((aligned(16))) float lds[2 * 2 * KT * KLD];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    // 1-D grid, heaviest query blocks first: under the causal/prefix mask the last query block of
-    // a head visits up to 4x the key tiles of the first, and with only ~4 workgroups per CU slot a
-    // heavy block dispatched late becomes the tail.  id % (B*h) is the (b,head), so workgroups that
-    // share an XCD (ids b, b+8, ...) still see every query block: no XCD gets only heavy ones.
-    const int n_bh = gridDim.x / a.n_qblocks;
-    const int bh = blockIdx.x % n_bh, b = bh / a.n_heads, head = bh - b * a.n_heads;
-    const int q0 = (a.n_qblocks - 1 - (int)(blockIdx.x / n_bh)) * QB;
-    const int q_off = a.Tk - a.Tq;
-    const int kvl = a.kv_len ? min(a.kv_len[b], a.Tk) : a.Tk;
-    const int xl = a.x_len_dev ? a.x_len_dev[b] : a.x_len;
+// The segments of vh_attn_rows_packed: utterance s owns rows seg_start[s] .. seg_start[s] + seg_len[s] - 1 of ONE (M, ·) q / out
+// and of one (1, h, S_max, 64) K/V stream; blocks[2 i], blocks[2 i + 1] = (segment, first query inside it) of workgroup row i.
+struct PackedSegs {
+    const int32_t* seg_start; const int32_t* seg_len; const int32_t* blocks;
+    int n_seg, n_rows;            // n_rows: the cache's S_max — no segment row at or beyond it is touched
+};
 
-    // number of key tiles this block has to visit
-    const int last_pos = q_off + min(q0 + QB, a.Tq) - 1;
-    int kmax = kvl;
-    if (a.mode == VH_MASK_PREFIX) kmax = min(kvl, max(xl, last_pos >= xl ? last_pos + 1 : 0));
-    if (a.mode == VH_MASK_EXPLICIT) kmax = a.Tk;
-    const int n_tiles = (kmax + KT - 1) / KT;
-
-    // Q fragment (B operand of Sᵀ = K·Qᵀ): lane holds Q[qi][8t+4h+j], pre-scaled
-    const int qi = q0 + w * 32 + r;            // this lane's query row
-    const int qpos = q_off + qi;               // its key position
-    const float qscale = 0.125f * LOG2E;
-    f32x4 qf[8];
-    {
-        const float* qp = a.q + ((int64_t)b * a.Tq + qi) * a.ldq + head * HD + 4 * h;
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-            qf[t] = qi < a.Tq ? ld4(qp + 8 * t) * qscale : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-
-    const float* kb = a.kc + (int64_t)bh * a.S_max * HD;
-    const float* vb = a.vc + (int64_t)bh * a.S_max * HD;
-    const int skey = tid >> 4, squad = (tid & 15) * 4;  // staging: 2 keys per thread per operand
-    f32x4 rk[2], rv[2];
-    // Keys beyond Tk are clamped to the last written row (rows < Tk were all written by this forward's QKV GEMM):
-    // their scores are masked to -inf, so their (finite) values meet p = 0.  Address = wave-uniform head base +
-    // one 32-bit per-lane byte offset: no 64-bit vector arithmetic in the loop (VALU slots are MFMA slots).
-    auto gload = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const uint32_t off = (uint32_t)(min(k0 + skey + 16 * i, a.Tk - 1) * HD + squad) * 4u;
-            rk[i] = ld4((const float*)((const char*)kb + off));
-            rv[i] = ld4((const float*)((const char*)vb + off));
-        }
-    };
-    auto lstore = [&](int buf) {
-        float* kd = lds + buf * (2 * KT * KLD);
-        float* vd = kd + KT * KLD;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            st4(kd + (skey + 16 * i) * KLD + squad, rk[i]);
-            st4(vd + (skey + 16 * i) * KLD + squad, rv[i]);
-        }
-    };
-
-    f32x16 O0, O1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { O0[e] = 0.f; O1[e] = 0.f; }
-    float m = NEG_INF, l = 0.f;
-
-    // positions covered by this wave's 32 queries (for tile skipping / fast path)
-    const int wpos_min = q_off + q0 + w * 32, wpos_max = wpos_min + 31;
-
-    if (n_tiles > 0) {
-        gload(0);
-        lstore(0);
-    }
-    __syncthreads();
-    for (int kt = 0; kt < n_tiles; ++kt) {
-        const int cur = kt & 1, k0 = kt * KT;
-        if (kt + 1 < n_tiles) gload(k0 + KT);
-
-        bool any = k0 < kvl, all = k0 + KT <= kvl;
-        if (a.mode == VH_MASK_PREFIX) {
-            any = any && (k0 < xl || (wpos_max >= xl && k0 <= wpos_max));
-            all = all && (k0 + KT <= xl || (wpos_min >= xl && k0 + KT - 1 <= wpos_min));
-        } else if (a.mode == VH_MASK_EXPLICIT) {
-            any = true; all = false;
-        }
-        if (any) {
-            const float* ks = lds + cur * (2 * KT * KLD);
-            const float* vs = ks + KT * KLD;
-            // ---- Sᵀ[key][q] = sum_d K[key][d] Q[q][d]
-            f32x16 S;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const f32x4 kf = ld4(ks + r * KLD + 8 * t + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)        // the first product starts from the constant-zero C operand
-                    S = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j], qf[t][j], (t | j) ? S : f32x16{}, 0, 0, 0);
-            }
-            // ---- mask: reg e ↔ key k0 + (e&3) + 8(e>>2) + 4h ; lane ↔ query qi
-            if (!all) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int key = k0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                    bool vis;
-                    if (a.mode == VH_MASK_EXPLICIT) {
-                        vis = key < a.Tk && qi < a.Tq && !a.mask[b * a.mask_bstride + (int64_t)qi * a.Tk + key] &&
-                              !(a.pad && a.pad[(int64_t)b * a.Tk + key]);
-                    } else {
-                        vis = key < kvl;
-                        if (a.mode == VH_MASK_PREFIX) vis = vis && (key < xl || (qpos >= xl && key <= qpos));
-                    }
-                    if (!vis) S[e] = NEG_INF;
-                }
-            }
-            // ---- online softmax (per lane = per query; the other 16 keys sit in lane^32)
-            float tmax = S[0];
-#pragma unroll
-            for (int e = 1; e < 16; ++e) tmax = fmaxf(tmax, S[e]);
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float m_new = fmaxf(m, tmax);
-            const float m_use = m_new == NEG_INF ? 0.f : m_new;  // fully masked so far: p = 0
-            const float alpha = vh_exp2(m - m_use);
-            // subtract and sum two scores per instruction (v_pk_add_f32); the exponentials stay scalar
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            f32x2 psum2 = {0.f, 0.f};
-            const f32x2 nm2 = {-m_use, -m_use};
-#pragma unroll
-            for (int e = 0; e < 16; e += 2) {
-                f32x2 d = f32x2{S[e], S[e + 1]} + nm2;
-                d.x = vh_exp2(d.x);
-                d.y = vh_exp2(d.y);
-                psum2 += d;
-                S[e] = d.x;
-                S[e + 1] = d.y;
-            }
-            const float psum = psum2.x + psum2.y;
-            l = l * alpha + psum;
-            m = m_new;
-            if (__any(alpha != 1.0f)) {                // no query of this wave raised its maximum: nothing to rescale
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { O0[e] *= alpha; O1[e] *= alpha; }
-            }
-            // ---- Oᵀ[d][q] += sum_key V[key][d] P[key][q]; k-step e covers keys (e,h=0),(e,h=1)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float* vrow = vs + ((e & 3) + 8 * (e >> 2) + 4 * h) * KLD + r;
-                O0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[0], S[e], O0, 0, 0, 0);
-                O1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[32], S[e], O1, 0, 0, 0);
-            }
-        }
-        if (kt + 1 < n_tiles) lstore(cur ^ 1);
-        __syncthreads();
-    }
-
-    // ---- normalise, transpose through LDS, store coalesced rows
-    const float ltot = l + __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / ltot;  // fully masked row → 0/0 = NaN, as SDPA gives
-    if (a.lse2 && h == 0 && qi < a.Tq) a.lse2[(int64_t)bh * a.Tq + qi] = m + log2f(ltot);
-    float* ob = lds;                // [128][KLD]; all K/V reads finished at the last barrier
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-        // regs 4g4..4g4+3 ↔ d = 8*g4 + 4h + {0..3} (+32 for O1)
-        f32x4 v0 = {O0[4 * g4], O0[4 * g4 + 1], O0[4 * g4 + 2], O0[4 * g4 + 3]};
-        f32x4 v1 = {O1[4 * g4], O1[4 * g4 + 1], O1[4 * g4 + 2], O1[4 * g4 + 3]};
-        st4(ob + (w * 32 + r) * KLD + 8 * g4 + 4 * h, v0 * inv);
-        st4(ob + (w * 32 + r) * KLD + 32 + 8 * g4 + 4 * h, v1 * inv);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int row = skey + 16 * i;
-        if (q0 + row < a.Tq)
-            st4(a.out + ((int64_t)b * a.Tq + q0 + row) * a.ldo + head * HD + squad,
-                ld4(ob + row * KLD + squad));
-    }
-}
+#define ATTN_ROWS_PACKED 0
+#include "attn_rows_body.inc"       // attn_rows_kernel(RowsArgs)
+#undef ATTN_ROWS_PACKED
+#define ATTN_ROWS_PACKED 1
+#include "attn_rows_body.inc"       // attn_rows_packed_kernel(RowsArgs, PackedSegs)
+#undef ATTN_ROWS_PACKED
 
 static int attn_rows_launch(const float* q, int ldq, const float* kcache, const float* vcache,
                             float* out, int ldo, int B, int n_heads, int Tq, int Tk, int S_max,
@@ -840,6 +681,30 @@ extern "C" int vh_attn_rows_lse(const float* q, int ldq, const float* kcache, co
     VH_REQUIRE(lse2, VH_EINVAL, "vh_attn_rows_lse: null lse2");
     return attn_rows_launch(q, ldq, kcache, vcache, out, ldo, B, n_heads, Tq, Tk, S_max, mode, x_len,
                             x_len_dev, kv_len, mask, pad, lse2, stream);
+}
+
+extern "C" int vh_attn_rows_packed(const float* q, int ldq, const float* kcache, const float* vcache, float* out, int ldo,
+                                   int n_heads, int S_max, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
+                                   const int32_t* blocks, int n_blocks, void* stream) {
+    VH_REQUIRE(q && kcache && vcache && out, VH_EINVAL, "vh_attn_rows_packed: null pointer (q, kcache, vcache or out)");
+    VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL, "vh_attn_rows_packed: null pointer (seg_start, seg_len or blocks)");
+    VH_REQUIRE(n_heads > 0 && S_max >= 1, VH_EINVAL, "vh_attn_rows_packed: bad dims n_heads=%d S_max=%d", n_heads, S_max);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_packed: n_seg=%d", n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_attn_rows_packed: n_blocks=%d", n_blocks);
+    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD, VH_EINVAL, "vh_attn_rows_packed: ldq=%d", ldq);
+    VH_REQUIRE(ldo % 4 == 0 && ldo >= n_heads * HD, VH_EINVAL, "vh_attn_rows_packed: ldo=%d", ldo);
+    VH_REQUIRE(vh_aligned16(q), VH_EALIGN, "vh_attn_rows_packed: q must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(out), VH_EALIGN, "vh_attn_rows_packed: out must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(kcache) && vh_aligned16(vcache), VH_EALIGN,
+               "vh_attn_rows_packed: kcache and vcache must be 16-byte aligned");
+    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED, "vh_attn_rows_packed: n_blocks=%d x n_heads=%d workgroups",
+               n_blocks, n_heads);
+    RowsArgs a{q, ldq, kcache, vcache, out, ldo, n_heads, 0, 0, S_max, VH_MASK_FULL, 0,
+               nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0};
+    PackedSegs ps{seg_start, seg_len, blocks, n_seg, S_max};
+    hipLaunchKernelGGL(attn_rows_packed_kernel, dim3(n_blocks * n_heads), dim3(256), 0, (hipStream_t)stream, a, ps);
+    VH_CHECK_LAUNCH("vh_attn_rows_packed");
+    return VH_OK;
 }
 
 // =============================================================================================

@@ -445,14 +445,14 @@ extern "C" int vh_ar_decoder_profile_attn(vh_ar_decoder* dec, int n_steps, void*
 // ---------------------------------------------------------------------------------------------
 // full-sequence forward (prefill / NAR stage / training forward)
 // ---------------------------------------------------------------------------------------------
-extern "C" int vh_transformer_forward(const vh_forward_desc* f, void* stream) {
-    VH_REQUIRE(f && f->layers && f->x && f->xn && f->q && f->attn && f->hidden, VH_EINVAL,
-               "vh_transformer_forward: null pointer in desc");
-    VH_REQUIRE(f->B > 0 && f->T > 0 && f->n_layers > 0 && f->S_max >= f->T, VH_EINVAL,
-               "vh_transformer_forward: bad dims B=%d T=%d L=%d S_max=%d", f->B, f->T, f->n_layers,
-               f->S_max);
-    VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM, VH_EUNSUPPORTED,
-               "vh_transformer_forward: d_model=%d != n_heads=%d x 64", f->d_model, f->n_heads);
+// the segments of a packed forward (vh_transformer_forward_packed); null: the padded (B, T) layout
+struct packed_rows {
+    const int32_t *seg_start, *seg_len, *blocks;
+    int n_seg, n_blocks;
+};
+
+// the layers of both forwards: the same launches in the same order, the packed one with vh_attn_rows_packed for vh_attn_rows
+static int forward_layers(const vh_forward_desc* f, const packed_rows* pk, void* stream) {
     const int B = f->B, T = f->T, D = f->d_model, M = B * T;
     for (int i = 0; i < f->n_layers; ++i) {
         const vh_layer& L = f->layers[i];
@@ -462,8 +462,12 @@ extern "C" int vh_transformer_forward(const vh_forward_desc* f, void* stream) {
                          stream));
         TRY(vh_linear_qkv(f->xn, D, L.wqkv, f->q, D, L.kcache, L.vcache, nullptr, B, T, D, f->n_heads,
                           f->S_max, nullptr, nullptr, nullptr, nullptr, 0.f, stream));
-        TRY(vh_attn_rows(f->q, D, L.kcache, L.vcache, f->attn, D, B, f->n_heads, T, T, f->S_max,
-                         f->mode, f->x_len, f->x_len_dev, f->kv_len, f->mask, f->pad, stream));
+        if (pk)
+            TRY(vh_attn_rows_packed(f->q, D, L.kcache, L.vcache, f->attn, D, f->n_heads, f->S_max, pk->seg_start, pk->seg_len,
+                                    pk->n_seg, pk->blocks, pk->n_blocks, stream));
+        else
+            TRY(vh_attn_rows(f->q, D, L.kcache, L.vcache, f->attn, D, B, f->n_heads, T, T, f->S_max,
+                             f->mode, f->x_len, f->x_len_dev, f->kv_len, f->mask, f->pad, stream));
         TRY(vh_linear_ws(f->attn, D, L.wo, L.bo, src, D, f->x, D, M, D, D, VH_ACT_NONE, f->gemm_ws,
                          f->gemm_ws_bytes, stream));
         TRY(vh_layernorm(f->x, L.ln2_g, L.ln2_b, ada ? ada + 2 * D : nullptr, ada ? ada + 3 * D : nullptr,
@@ -474,4 +478,48 @@ extern "C" int vh_transformer_forward(const vh_forward_desc* f, void* stream) {
                          f->gemm_ws_bytes, stream));
     }
     return VH_OK;
+}
+
+extern "C" int vh_transformer_forward(const vh_forward_desc* f, void* stream) {
+    VH_REQUIRE(f && f->layers && f->x && f->xn && f->q && f->attn && f->hidden, VH_EINVAL,
+               "vh_transformer_forward: null pointer in desc");
+    VH_REQUIRE(f->B > 0 && f->T > 0 && f->n_layers > 0 && f->S_max >= f->T, VH_EINVAL,
+               "vh_transformer_forward: bad dims B=%d T=%d L=%d S_max=%d", f->B, f->T, f->n_layers,
+               f->S_max);
+    VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM, VH_EUNSUPPORTED,
+               "vh_transformer_forward: d_model=%d != n_heads=%d x 64", f->d_model, f->n_heads);
+    return forward_layers(f, nullptr, stream);
+}
+
+extern "C" int vh_transformer_forward_packed(const vh_forward_desc* f, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
+                                             const int32_t* blocks, int n_blocks, void* stream) {
+    VH_REQUIRE(f && f->layers && f->x && f->xn && f->q && f->attn && f->hidden, VH_EINVAL,
+               "vh_transformer_forward_packed: null pointer in desc");
+    VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL,
+               "vh_transformer_forward_packed: null pointer (seg_start, seg_len or blocks)");
+    VH_REQUIRE(f->B == 1, VH_EINVAL, "vh_transformer_forward_packed: B=%d (the packed rows are ONE row stream: B = 1, T = the sum "
+               "of the segment lengths)", f->B);
+    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "vh_transformer_forward_packed: bad dims T=%d L=%d", f->T, f->n_layers);
+    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "vh_transformer_forward_packed: S_max=%d < T=%d", f->S_max, f->T);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_transformer_forward_packed: n_seg=%d", n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_transformer_forward_packed: n_blocks=%d", n_blocks);
+    VH_REQUIRE(f->mode == VH_MASK_FULL, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed: mode=%d (segments attend under the full mask only)", f->mode);
+    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed: kv_len is set (a segment's length is its key length)");
+    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed: x_len_dev is set (no prefix mask over segments)");
+    VH_REQUIRE(!f->mask, VH_EUNSUPPORTED, "vh_transformer_forward_packed: mask is set (no explicit mask over segments)");
+    VH_REQUIRE(!f->pad, VH_EUNSUPPORTED, "vh_transformer_forward_packed: pad is set (packed rows have no padding)");
+    VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed: d_model=%d != n_heads=%d x 64", f->d_model, f->n_heads);
+    // what vh_attn_rows_packed would refuse inside layer 0, said before anything is launched
+    VH_REQUIRE(vh_aligned16(f->q), VH_EALIGN, "vh_transformer_forward_packed: q must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(f->attn), VH_EALIGN, "vh_transformer_forward_packed: attn must be 16-byte aligned");
+    for (int i = 0; i < f->n_layers; ++i) {
+        VH_REQUIRE(f->layers[i].kcache && f->layers[i].vcache, VH_EINVAL,
+                   "vh_transformer_forward_packed: null kcache / vcache (layer %d)", i);
+        VH_REQUIRE(vh_aligned16(f->layers[i].kcache) && vh_aligned16(f->layers[i].vcache), VH_EALIGN,
+                   "vh_transformer_forward_packed: kcache and vcache must be 16-byte aligned (layer %d)", i);
+    }
+    const packed_rows pk{seg_start, seg_len, blocks, n_seg, n_blocks};
+    return forward_layers(f, &pk, stream);
 }

@@ -402,6 +402,75 @@ def transformer_forward(transformer, x, cache: KVCache, *, mode, x_len=0, x_len_
     return x
 
 
+PACK_QUERY_BLOCK = 128            # queries one workgroup of vh_attn_rows_packed takes (attention.hip QB)
+
+
+def pack_plan(lengths):
+    """The packed layout of a ragged batch (pure Python, no device): utterance b's `lengths[b]` rows sit at rows
+    starts[b] .. starts[b] + lengths[b] - 1 of one (M, d) buffer, no gaps.  Returns (starts, M, blocks): starts the exclusive
+    prefix sum, M the sum, blocks the (segment, first query) of every 128-query block of every segment — each query once —
+    with the blocks of the LONGEST segment first (they visit the most key tiles; ties keep the batch order)."""
+    lengths = [int(n) for n in lengths]
+    if not lengths:
+        raise ValueError('pack_plan: no lengths')
+    if min(lengths) < 1:
+        raise ValueError(f'pack_plan: every length must be >= 1, got {min(lengths)}')
+    starts, m = [], 0
+    for n in lengths:
+        starts.append(m)
+        m += n
+    order = sorted(range(len(lengths)), key=lambda s: -lengths[s])
+    blocks = [(s, q0) for s in order for q0 in range(0, lengths[s], PACK_QUERY_BLOCK)]
+    return starts, m, blocks
+
+
+class PackedRows:
+    """`pack_plan(lengths)` as device int32 tensors, built once per call: what `kernels.attn_rows_packed` and
+    `transformer_forward_packed` take."""
+
+    def __init__(self, lengths, device):
+        self.lengths = [int(n) for n in lengths]
+        self.starts, self.rows, blocks = pack_plan(self.lengths)
+        self.n_seg, self.n_blocks = len(self.lengths), len(blocks)
+        i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), device)   # noqa: E731
+        self.seg_start, self.seg_len, self.blocks = i32(self.starts), i32(self.lengths), i32(blocks)
+
+
+def transformer_forward_packed(transformer, x, cache: KVCache, rows: PackedRows, embedding=None, scratch=None):
+    """`transformer_forward(mode=MASK_FULL)` of a ragged batch over PACKED rows: x (M, d) holds utterance b at rows
+    rows.starts[b] .. + rows.lengths[b] - 1 and is updated in place; each utterance attends its own rows only
+    (`vh_attn_rows_packed`), every other launch is the row-wise one over M rows.  `cache`: a one-row KVCache of s_max >= M;
+    each layer's K/V land at the packed rows.  Returns x."""
+    cfg = transformer.hparams
+    if x.dim() != 2:
+        raise _lib.VhError(f'transformer_forward_packed: x must be (M, d), got {tuple(x.shape)}')
+    M, d = x.shape
+    if not x.is_contiguous():
+        raise _lib.VhError('x must be contiguous')
+    if d != cfg.n_heads * HEAD_DIM:
+        raise _lib.VhError(f'transformer_forward_packed: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
+    if M != rows.rows:
+        raise _lib.VhError(f'transformer_forward_packed: x has {M} rows, the packed rows {rows.rows}')
+    if cache is None or cache.batch != 1 or cache.s_max < M or cache.n_layers != cfg.num_layers or cache.bf16:
+        raise _lib.VhError('KV cache does not fit this forward')
+    scratch = scratch or ForwardScratch(M, d, cfg.dim_feedforward, x.device)
+    table = layer_table(transformer, cache)
+    ada = None
+    if cfg.norm != 'LayerNorm':
+        if embedding is None:
+            raise TypeError('AdaptiveLayerNorm needs `embedding` (reference: Linear(None) TypeError)')
+        ada = adaln_table(transformer, embedding)
+    desc = VhForwardDesc(
+        B=1, T=M, d_model=d, n_heads=cfg.n_heads, dff=cfg.dim_feedforward, n_layers=cfg.num_layers,
+        S_max=cache.s_max, mode=kernels.MASK_FULL, x_len=0, ln_eps=1e-5, layers=table, ada=ptr(ada),
+        x=ptr(x), xn=ptr(scratch.xn), q=ptr(scratch.q), attn=ptr(scratch.attn),
+        hidden=ptr(scratch.hidden), gemm_ws=ptr(scratch.ws), gemm_ws_bytes=scratch.ws_bytes)
+    check(_lib.lib().vh_transformer_forward_packed(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg,
+                                                   ptr(rows.blocks), rows.n_blocks, stream()),
+          'vh_transformer_forward_packed')
+    return x
+
+
 def _transformer_forward_generic(transformer, x, *, mode, x_len, x_len_dev, kv_len, mask, pad, embedding, x_in, cache=None):
     """`transformer_forward` for a head width other than 64 (valle/models/modules.py:109-111 allows any divisor of d_model;
     every configuration of the path and of the reference's tests has 64, which is what the flash kernels and the native

@@ -38,6 +38,8 @@ def embed_sum_pe(ids, tables, pe, pos0, out, out_t0=0, lens=None, row_pos0=None,
     lens / row_pos0 / row_t0: device int32 (B) — valid ids per row and per-row overrides of pos0 / out_t0 (a ragged
     batch in one launch); with them the caller vouches, through `max_pos` (largest position + 1 any row reaches) and
     its own layout, that positions stay inside the table and rows inside `out`.
+    out (rows, d) with row_t0: the PACKED form — row t of batch row b goes to out[row_t0[b] + t], no batch stride (the
+    rows of a ragged batch back to back in one buffer).
     drop: a dropout.spec — the dropout after the position add (modules.py:80), field row = the row's index in `out`."""
     if ids.dtype != torch.int64:
         raise _lib.VhError('ids must be int64')
@@ -50,7 +52,11 @@ def embed_sum_pe(ids, tables, pe, pos0, out, out_t0=0, lens=None, row_pos0=None,
     if n > J and J != 1:
         raise _lib.VhError(f'{n} tables but ids has {J} codebooks')
     d = tables[0].shape[1]
-    if out.dim() != 3 or out.shape[0] != B or out.shape[2] != d or (row_t0 is None and out_t0 + T > out.shape[1]):
+    packed = out.dim() == 2 and row_t0 is not None
+    if packed:
+        if out.shape[1] != d or not out.is_contiguous():
+            raise _lib.VhError(f'packed out {tuple(out.shape)} must be contiguous (rows, {d})')
+    elif out.dim() != 3 or out.shape[0] != B or out.shape[2] != d or (row_t0 is None and out_t0 + T > out.shape[1]):
         raise _lib.VhError(f'out shape {tuple(out.shape)} does not fit B={B} T={T} d={d} t0={out_t0}')
     if row_pos0 is not None or row_t0 is not None:
         for t_ in (row_pos0, row_t0, lens):
@@ -70,7 +76,7 @@ def embed_sum_pe(ids, tables, pe, pos0, out, out_t0=0, lens=None, row_pos0=None,
     vocab = (C.c_int32 * n)(*[int(t.shape[0]) for t in tables])    # ids are range-checked in the kernel
     check(_lib.lib().vh_embed_sum_pe(
         ids.data_ptr(), ids.stride(0), ids.stride(1), ids.stride(2), arr, vocab, n,
-        ptr(_f32(pe, 'pe')), pos0, ptr(lens), ptr(_f32(out, 'out')), out.stride(0), out_t0,
+        ptr(_f32(pe, 'pe')), pos0, ptr(lens), ptr(_f32(out, 'out')), 0 if packed else out.stride(0), out_t0,
         B, T, d, ptr(_lib.err_flag(out.device)), ptr(row_pos0), ptr(row_t0), _drop_ref(drop), stream()),
         'vh_embed_sum_pe')
     return out
@@ -303,6 +309,22 @@ def attn_rows(q, kcache, vcache, out, B, n_heads, Tq, Tk, mode, x_len=0, x_len_d
         _dev_f32(q, 'q'), q.stride(0), ptr(kcache), ptr(vcache), _dev_f32(out, 'out'), out.stride(0), B,
         n_heads, Tq, Tk, S_max, mode, x_len, ptr(x_len_dev), ptr(kv_len), ptr(mask), ptr(pad),
         stream()), 'vh_attn_rows')
+    return out
+
+
+def attn_rows_packed(q, kcache, vcache, out, n_heads, rows):
+    """Full-mask attention of every segment of `rows` (an engine.PackedRows) over its own rows of ONE K/V stream: q / out
+    (M, ·) with heads at columns head*64, kcache / vcache (1, n_heads, S_max >= M, 64) — `attn_rows` of each utterance alone,
+    in one launch and with no padding rows (vh_attn_rows_packed)."""
+    S_max = kcache.shape[2]
+    M = rows.rows
+    if tuple(kcache.shape) != (1, n_heads, S_max, HEAD_DIM) or kcache.shape != vcache.shape or M > S_max:
+        raise _lib.VhError(f'attn_rows_packed: cache {tuple(kcache.shape)} M={M}')
+    if q.shape[0] != M or out.shape[0] != M:
+        raise _lib.VhError('attn_rows_packed: q/out rows')
+    check(_lib.lib().vh_attn_rows_packed(
+        _dev_f32(q, 'q'), q.stride(0), ptr(kcache), ptr(vcache), _dev_f32(out, 'out'), out.stride(0), n_heads, S_max,
+        ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()), 'vh_attn_rows_packed')
     return out
 
 

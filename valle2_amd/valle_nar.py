@@ -17,7 +17,8 @@ import torch.nn as nn
 
 from . import _lib, dropout, kernels
 from . import sampling as _sampling
-from .engine import ForwardScratch, ForwardScratch16, KVCache, head16, transformer_forward, transformer_forward_bf16
+from .engine import (ForwardScratch, ForwardScratch16, KVCache, PackedRows, head16, transformer_forward, transformer_forward_bf16,
+                     transformer_forward_packed)
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device
 from .valle_ar import _Base
 
@@ -45,6 +46,18 @@ def _sampling_refused_early(fn):
                 raise ValueError(f'{name}: sampling together with seed= (every Sampling carries its own seed)')
             for s in _sampling.check_list(name, given, len(a['texts']) if 'texts' in a else 1) or ():
                 s.nar_record(self.config)                              # the config's temperature, where the request has none
+        return fn(self, *args, **kwargs)
+    return wrapper
+
+
+def _packed_width_refused_early(fn):
+    """generate_packed: a head width the packed attention is not built for is said before anything touches a device."""
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        cfg = self.config
+        if cfg.d_model != cfg.n_heads * kernels.HEAD_DIM:
+            raise ValueError(f'{fn.__name__}: head width {cfg.d_model // cfg.n_heads} (d_model={cfg.d_model} / n_heads={cfg.n_heads}): '
+                             'the packed attention serves width 64 only — generate_batch serves the others')
         return fn(self, *args, **kwargs)
     return wrapper
 
@@ -214,6 +227,24 @@ class ValleNAR(_Base):
         return self.generate_batch([text], [prompt_codes], [target_codes_first_layer], greedy=greedy,
                                    sampling=None if sampling is None else [sampling])[0]
 
+    def _ragged_inputs(self, name, dev, texts, prompt_codes, first_layers):
+        """The input checks of `generate_batch` / `generate_packed`: the three id lists on the device and their lengths."""
+        cfg = self.config
+        B = len(texts)
+        if B == 0 or len(prompt_codes) != B or len(first_layers) != B:
+            raise ValueError(f'{name}: texts, prompt_codes and first_layers must be non-empty lists of equal length')
+        texts = [kernels.ids_to_device(t, dev, cfg.vocab_size, 'text ids') for t in texts]
+        pcs = [kernels.ids_to_device(c, dev, cfg.num_audio_tokens, 'prompt codes') for c in prompt_codes]
+        firsts = [kernels.ids_to_device(f, dev, cfg.num_audio_tokens, 'first-layer codes') for f in first_layers]
+        for t, c, f in zip(texts, pcs, firsts):
+            if t.dim() != 1 or c.dim() != 2 or c.shape[1] != cfg.num_quantizers or f.dim() != 1:
+                raise ValueError(f'{name}: expected text (Tx,), prompt codes (Tc, Q), first layer (Ty,)')
+        txs, tcs, tys = [t.shape[0] for t in texts], [c.shape[0] for c in pcs], [f.shape[0] for f in firsts]
+        if max(tc + ty for tc, ty in zip(tcs, tys)) > self.audio_position_emb.pe.shape[0] or \
+                max(txs) > self.tokens_position_emb.pe.shape[0]:
+            raise _lib.VhError('sequence exceeds the positional table (max_len 5000)')
+        return texts, pcs, firsts, txs, tcs, tys
+
     @_sampling_refused_early
     @_on_device
     @torch.inference_mode()
@@ -243,20 +274,10 @@ class ValleNAR(_Base):
         cfg = self.config
         q, d = cfg.num_quantizers, cfg.d_model
         B = len(texts)
-        if B == 0 or len(prompt_codes) != B or len(first_layers) != B:
-            raise ValueError('generate_batch: texts, prompt_codes and first_layers must be non-empty lists of equal length')
-        texts = [kernels.ids_to_device(t, dev, cfg.vocab_size, 'text ids') for t in texts]
-        pcs = [kernels.ids_to_device(c, dev, cfg.num_audio_tokens, 'prompt codes') for c in prompt_codes]
-        firsts = [kernels.ids_to_device(f, dev, cfg.num_audio_tokens, 'first-layer codes') for f in first_layers]
-        for t, c, f in zip(texts, pcs, firsts):
-            if t.dim() != 1 or c.dim() != 2 or c.shape[1] != q or f.dim() != 1:
-                raise ValueError('generate_batch: expected text (Tx,), prompt codes (Tc, Q), first layer (Ty,)')
-        txs, tcs, tys = [t.shape[0] for t in texts], [c.shape[0] for c in pcs], [f.shape[0] for f in firsts]
+        texts, pcs, firsts, txs, tcs, tys = self._ragged_inputs('generate_batch', dev, texts, prompt_codes, first_layers)
         lens = [a + b + c for a, b, c in zip(txs, tcs, tys)]
         total = max(lens)
         pe_a, pe_t = self.audio_position_emb.pe, self.tokens_position_emb.pe
-        if max(tc + ty for tc, ty in zip(tcs, tys)) > pe_a.shape[0] or max(txs) > pe_t.shape[0]:
-            raise _lib.VhError('sequence exceeds the positional table (max_len 5000)')
         ty_max = max(tys)
         pad = torch.nn.utils.rnn.pad_sequence                      # index plumbing: ragged id lists -> padded id tensors
         i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), dev)   # noqa: E731
@@ -304,6 +325,84 @@ class ValleNAR(_Base):
                     embedding=self.stage_embs[n - 1].weight, scratch=scratch)                # (cached AdaLN table per stage)
             z = x.view(B * total, d).index_select(0, idx)                      # target frames of every row
             logits = self._head(z, n, perf_mode)
+            if sampling is not None:
+                kernels.categorical_rows_keyed(logits, out[:, :, n], requests, row_request, row_key, _sampling.NAR_STREAM | n)
+                continue
+            kernels.categorical_rows(logits, toks, temperature=cfg.temperature, greedy=greedy, seed=seed,
+                                     stream_id=n)
+            out[:, :, n][valid] = toks                                          # packed row-major -> (B, ty_max)
+        _lib.raise_device_errors(dev)
+        return [out[b, :tys[b]].clone() for b in range(B)]
+
+    @_packed_width_refused_early
+    @_sampling_refused_early
+    @_on_device
+    @torch.inference_mode()
+    def generate_packed(self, texts, prompt_codes, first_layers, greedy: bool = False, seed=None, *, sampling=None):
+        """`generate_batch` computed over PACKED rows: same inputs, checks, return value and sampling semantics (see there),
+        fp32 only (no perf_mode), head width 64 only (ValueError otherwise, before any device work).
+
+        The B utterances lie back to back in ONE (M, d) buffer, M = sum of the row lengths, utterance b —
+        [text_b | prompt_b | target_b] — at rows start_b .. start_b + len_b - 1 (`engine.pack_plan`); there is no padding
+        row.  LayerNorm, the GEMMs and the K/V append run over the M rows as one sequence; the attention runs each
+        utterance over its own rows (`vh_attn_rows_packed`), so a ragged batch computes sum(len_b) rows and
+        sum(len_b^2) scores where generate_batch computes B max(len) and max(len) sum(len_b).  The packed logits rows keep
+        generate_batch's order, utterance by utterance and frame by frame: the draws are keyed as there.  The GEMMs see
+        another row count than the padded form's, so logits agree with it to summation order, not to the bit; a greedy
+        token can differ where the two leading logits are closer than that."""
+        dev = self._dev()
+        cfg = self.config
+        q, d = cfg.num_quantizers, cfg.d_model
+        B = len(texts)
+        texts, pcs, firsts, txs, tcs, tys = self._ragged_inputs('generate_packed', dev, texts, prompt_codes, first_layers)
+        rows = PackedRows([a + b + c for a, b, c in zip(txs, tcs, tys)], dev)
+        M = rows.rows
+        pe_a, pe_t = self.audio_position_emb.pe, self.tokens_position_emb.pe
+        ty_max = max(tys)
+        pad = torch.nn.utils.rnn.pad_sequence                      # index plumbing: ragged id lists -> padded id tensors
+        i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), dev)   # noqa: E731
+        out = torch.zeros(B, ty_max, q, device=dev, dtype=torch.int64)
+        out[:, :, 0] = pad(firsts, batch_first=True)
+        tx_d, tc_d, ty_d = i32(txs), i32(tcs), i32(tys)
+        t0_prompt = i32([s + a for s, a in zip(rows.starts, txs)])
+        t0_target = i32([s + a + c for s, a, c in zip(rows.starts, txs, tcs)])
+        valid = torch.arange(ty_max, device=dev)[None, :] < ty_d[:, None]          # (B, ty_max) target frames that exist
+        # text and acoustic-prompt embeddings, once per call and ONE launch each for the whole batch: row_t0 places
+        # utterance b's rows at its packed start (every row of `base` but the target frames' is written here)
+        base = torch.empty(M, d, device=dev, dtype=torch.float32)
+        kernels.embed_sum_pe(pad(texts, batch_first=True), [self.tokens_emb.weight.detach()], pe_t, 0, base, lens=tx_d,
+                             row_t0=rows.seg_start, max_pos=max(txs))
+        if max(tcs):
+            kernels.embed_sum_pe(pad(pcs, batch_first=True), self._tables(q), pe_a, 0, base, lens=tc_d, row_t0=t0_prompt,
+                                 max_pos=max(tcs))
+        # packed row of every target frame, and where each utterance's run starts in the packed logits
+        idx = torch.cat([torch.arange(tys[b], device=dev) + (rows.starts[b] + txs[b] + tcs[b]) for b in range(B)])
+        starts = [0]
+        for ty in tys:
+            starts.append(starts[-1] + ty)
+        cache = KVCache(cfg.num_layers, 1, cfg.n_heads, M, dev)
+        scratch = ForwardScratch(M, d, cfg.dim_feedforward, dev)
+        x = torch.empty_like(base)
+        sampling = _sampling.check_list('generate_packed', sampling, B)
+        if sampling is not None:
+            records = [s.nar_record(cfg) for s in sampling]
+            if greedy:
+                records = [(sd, key, 1, top_p, temperature) for sd, key, _, top_p, temperature in records]
+            requests = _lib.to_device_async(kernels.pack_row_sampling(records), dev)
+            row_request = i32([b for b in range(B) for _ in range(tys[b])])
+            row_key = i32([t for b in range(B) for t in range(tys[b])])
+        else:
+            if seed is None:       # drawn from torch's generator, so torch.manual_seed() makes a run repeatable
+                seed = 0 if greedy else int(torch.randint(0, 2 ** 62, (1,)).item())
+            toks = torch.empty(starts[-1], device=dev, dtype=torch.int64)
+        for n in range(1, q):
+            x.copy_(base)
+            kernels.embed_sum_pe(out, self._tables(n), pe_a, 0, x, lens=ty_d, row_pos0=tc_d, row_t0=t0_target,
+                                 max_pos=max(tc + ty for tc, ty in zip(tcs, tys)))
+            transformer_forward_packed(self.transformer, x, cache, rows, embedding=self.stage_embs[n - 1].weight,
+                                       scratch=scratch)
+            z = x.index_select(0, idx)                                          # target frames of every utterance
+            logits = self._head(z, n, False)
             if sampling is not None:
                 kernels.categorical_rows_keyed(logits, out[:, :, n], requests, row_request, row_key, _sampling.NAR_STREAM | n)
                 continue
