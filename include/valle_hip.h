@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 137            /* 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 138            /* 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -234,6 +234,42 @@ int vh_linear_qkv_hd(const float* A, int lda, const float* Wqkv, float* q_out, i
 int vh_linear_qkv_folded_hd(const float* A, int lda, const float* Wf, const float* c1, const float* c2, float* q_out, int ldq,
                             float* kcache, float* vcache, const int32_t* cache_len, int B, int T, int d_model, int n_heads,
                             int S_max, float ln_eps, int head_dim, void* stream);
+
+/* ---- which compiled form a decode GEMM takes (ABI 138; read-only, launches nothing, touches no GPU state) ------------
+ * vh_linear_form runs the named entry point's own argument checks and its dispatch plan for a shape, with the current
+ * vh_set_tuning knobs, and returns what that entry point would return for well-formed pointers: VH_OK and the form in *out,
+ * or the entry's refusal code with vh_last_error() set to the entry's own message (*out is zeroed).
+ *   entry               asks                                                         M, N, K, T
+ *   VH_ENTRY_LINEAR     vh_linear (ln_kind NONE / GAMMA), vh_linear_folded (FOLDED)  as the entry's; T ignored
+ *   VH_ENTRY_QKV        vh_linear_qkv / vh_linear_qkv_folded                         M = B*T rows, K = d_model, N = 3 K
+ *   VH_ENTRY_QKV_HD     vh_linear_qkv_hd / vh_linear_qkv_folded_hd                   the same (any valid head width)
+ *   VH_ENTRY_QKV_KV16   vh_linear_qkv_folded_kv16 (FOLDED only; T == 1)              the same
+ *   VH_ENTRY_LINEAR_WS  vh_linear_ws with a workspace of vh_linear_ws_bytes          as the entry's: the GEMM launch (the
+ *                                                                                    split-K reduce and a tail split's extra slices are not described)
+ *   VH_ENTRY_HEAD_GREEDY vh_head_greedy                                              M = B, N = V, K = d_model
+ * w16 != 0 asks for the 16-bit-weight form the decoder of perf mode uses (VH_ENTRY_LINEAR without LayerNorm and
+ * VH_ENTRY_QKV_KV16).  A combination no entry point has (an unknown entry, M % T != 0, N != 3 K for the QKV entries, w16
+ * elsewhere) is VH_EINVAL.
+ * out: family (VH_FORM_*; VH_FORM_NONE when M == 0), the template tuple of the kernel (gemm_skinny_fast<mt, nw, epi, pw, ln,
+ * nj, w16>; gemm_skinny_kernel<mt, nw, epi, pw, ln>; gemm_head_greedy_kernel<pw>; the tile kernels are <epi>), the launch
+ * grid and block and the rows per row group (0: none).
+ * vh_linear_form_row(i, out) lists the compiled skinny forms, i = 0, 1, ...: the tuple and in out->epis the set of epilogues
+ * (bit e = epilogue e) row i is built for; VH_EINVAL past the last row.  Every form vh_linear_form returns for a skinny
+ * family is one of these rows. */
+enum { VH_LN_NONE = 0, VH_LN_GAMMA = 1, VH_LN_FOLDED = 2 };
+enum { VH_ENTRY_LINEAR = 0, VH_ENTRY_QKV = 1, VH_ENTRY_QKV_HD = 2, VH_ENTRY_QKV_KV16 = 3, VH_ENTRY_LINEAR_WS = 4,
+       VH_ENTRY_HEAD_GREEDY = 5 };
+enum { VH_FORM_NONE = 0, VH_FORM_SKINNY_FAST = 1, VH_FORM_SKINNY_GENERIC = 2, VH_FORM_TILE_DMA = 3, VH_FORM_TILE_REG = 4,
+       VH_FORM_HEAD_GREEDY = 5 };
+typedef struct vh_linear_form_info {
+    int family;
+    int mt, nw, epi, pw, ln, nj, w16;
+    unsigned grid[3], block;
+    int rg_rows;
+    unsigned epis;                /* vh_linear_form: 1 << epi; vh_linear_form_row: every epilogue the row is built for */
+} vh_linear_form_info;
+int vh_linear_form(int entry, int M, int N, int K, int T, int ln_kind, int w16, vh_linear_form_info* out);
+int vh_linear_form_row(int i, vh_linear_form_info* out);
 
 /* ---- prompt pass at a head width other than 64: K / V of the QKV projection into the cache --------------------------
  * qkv (B*T, ld) holds [Q | K | V] column blocks of d = n_heads * head_dim columns (the projection the prompt's attention

@@ -104,6 +104,36 @@ int main() {
     REFUSED(vh_ffn_decode(P, 128, P, P, P, P, nullptr, P, 128, 4, 192, 512, 1e-5f, P, 1 << 20, S));
     REFUSED(vh_ffn_decode(P, 128, P, P, P, P, nullptr, P, 128, 4, 128, 512, 1e-5f, P, 16, S));      // workspace too small
     REFUSED(vh_ffn_decode(P, 128, P, P, P, P, nullptr, P, 128, 65, 128, 512, 1e-5f, P, 1 << 24, S));
+    // ---- which form a decode GEMM takes: the entry points' own checks and plan, nothing launched ----------------------
+    vh_linear_form_info fi;
+    REFUSED(vh_linear_form(VH_ENTRY_LINEAR, 4, 64, 128, 1, VH_LN_NONE, 0, nullptr));
+    REFUSED(vh_linear_form(-1, 4, 64, 128, 1, VH_LN_NONE, 0, &fi));
+    REFUSED(vh_linear_form(VH_ENTRY_QKV, 3, 384, 128, 2, VH_LN_NONE, 0, &fi));                    // M % T != 0
+    REFUSED(vh_linear_form(VH_ENTRY_QKV_KV16, 4, 384, 128, 1, VH_LN_GAMMA, 0, &fi));
+    REFUSED(vh_linear_form(VH_ENTRY_LINEAR, 4, 64, 384, 1, VH_LN_FOLDED, 0, &fi));                // vh_linear_folded's refusal
+    REFUSED(vh_linear_form(VH_ENTRY_QKV_KV16, 4, 3 * 640, 640, 1, VH_LN_FOLDED, 1, &fi));         // no 16-bit-weight form at 640
+    REFUSED(vh_linear_form(VH_ENTRY_HEAD_GREEDY, 4, 1025, 640, 1, VH_LN_NONE, 0, &fi));
+    EXPECT(vh_linear_form(VH_ENTRY_LINEAR, 0, 64, 128, 1, VH_LN_NONE, 0, &fi) == VH_OK && fi.family == VH_FORM_NONE, "0 rows: no form");
+    EXPECT(vh_linear_form(VH_ENTRY_LINEAR, 33, 1040, 896, 1, VH_LN_FOLDED, 0, &fi) == VH_OK && fi.family == VH_FORM_SKINNY_FAST && fi.mt == 1 &&
+               fi.pw == 7 && fi.ln == 3 && fi.rg_rows == 16 && fi.grid[0] == 65 && fi.grid[2] == 3 && fi.block == 512,
+           "folded 896 above 32 rows: row groups");
+    for (int entry = VH_ENTRY_LINEAR; entry <= VH_ENTRY_HEAD_GREEDY; ++entry)
+        for (int K : {16, 128, 640, 1024, 2048, 4096})
+            for (int M : {1, 17, 64, 65, 129})
+                for (int ln = VH_LN_NONE; ln <= VH_LN_FOLDED; ++ln)
+                    for (int w16 = 0; w16 < 2; ++w16) {
+                        const int qkv = entry >= VH_ENTRY_QKV && entry <= VH_ENTRY_QKV_KV16;
+                        const int rc = vh_linear_form(entry, M, qkv ? 3 * K : 1040, K, 1, ln, w16, &fi);
+                        EXPECT(rc == VH_OK ? fi.family != VH_FORM_NONE && fi.block > 0 && fi.grid[0] > 0 : vh_last_error()[0] != 0, "form or reason");
+                    }
+    int n_rows = 0;
+    while (vh_linear_form_row(n_rows, &fi) == VH_OK) {
+        EXPECT(fi.epis != 0 && fi.block == 64u * fi.nw, "table row");
+        ++n_rows;
+    }
+    EXPECT(n_rows > 0, "compiled forms listed");
+    REFUSED(vh_linear_form_row(-1, &fi));
+    REFUSED(vh_linear_form_row(0, nullptr));
     // ---- attention -------------------------------------------------------------------------------------------------
     REFUSED(vh_attn_rows(nullptr, 128, P, P, P, 128, 1, 2, 4, 4, 8, VH_MASK_FULL, 0, nullptr, nullptr, nullptr, nullptr, S));
     REFUSED(vh_attn_rows(P, 128, P, P, P, 128, 1, 2, 9, 9, 8, VH_MASK_FULL, 0, nullptr, nullptr, nullptr, nullptr, S));      // Tk > S_max

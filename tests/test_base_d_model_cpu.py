@@ -174,11 +174,14 @@ def test_decoder_check_reaches_the_same_verdicts_at_768_as_at_512(L):
 
 
 def test_python_gates_keep_the_old_widths():
-    """VALLE2_HEAD_FUSED and VALLE2_DECODE_W16 have no kernels at the new widths: their gates name the old four."""
-    import inspect
+    """VALLE2_HEAD_FUSED and VALLE2_DECODE_W16 have no kernels at the new widths: their gates (queries of the library's dispatch
+    plan) are false there and true at the old four."""
     from valle2_amd import engine
-    src = inspect.getsource(engine.ArDecoder.__init__)
-    assert src.count('d in (128, 256, 512, 1024)') == 2
+    for d in (640, 768, 896):
+        assert engine.head_fused_shape(8, 1025, d) is False and engine.w16_width(d) is False
+    for d in (128, 256, 512, 1024):
+        assert engine.head_fused_shape(8, 1025, d) is True and engine.head_fused_shape(64, 1025, d) is True and engine.w16_width(d) is True
+        assert engine.head_fused_shape(65, 1025, d) is False
     assert engine.BASE_FOLD_WIDTHS == (640, 768, 896)
 
 

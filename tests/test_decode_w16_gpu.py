@@ -12,7 +12,7 @@ with the plain epilogue, ffn_decode_kernel<D, SW, W16>) against a float64 mirror
 (c) free-running greedy and sampled decodes, graph and eager; the fp16 prompt pass in front of it.
 (d) the fallbacks: a width without h16 kernels, no perf mode, a decoder slot built without the variable.
 
-Template instantiations reached (read from gemm.hip launch_gemm and ffn.hip ffn_plan; M rows, mt = ceil(M / 16)):
+Template instantiations reached (gemm.hip gemm_plan — tests/golden/gemm_decode_forms.txt lists them per shape — and ffn.hip ffn_plan; M rows, mt = ceil(M / 16)):
   gemm_skinny_fast<MT, 8, EPI_QKV16, PW, LN, NJ, true>, (PW, NJ at LN 2) = (1, 2) d128, (2, 4) d256, (4, 8) d512, (4, 16) d1024:
     LN 3, MT 1, NJ 1   every case without a knob: one tile (M <= 16) and row groups of 8 (d128; d256 to 40 rows) or 16
                        (VH_TUNE_ROW_GROUPS 3: 16 everywhere); d512 and d1024 share <1, 8, EPI_QKV16, 4, 3, 1, true>
@@ -29,7 +29,7 @@ Template instantiations reached (read from gemm.hip launch_gemm and ffn.hip ffn_
     <512, 16> / <512, 32>   d512 up to 16 rows / from 17 rows; both with 8 and 16 rows per workgroup under the knobs at 24 rows
     <1024, 16>         every d1024 case;  <1024, 32> is never dispatched (ffn_plan: slices of 16 at d_model 1024)
   Not dispatched for h16 weights at all: LN 1 (the unfolded LayerNorm), NW 16 (K > 1024), PW 5..7 (640 / 768 / 896), EPI_QKV,
-  EPI_QKV_HD, EPI_PARTIAL, EPI_HEAD — launch_gemm refuses them, and engine.ArDecoder's gate keeps those shapes on fp32 weights."""
+  EPI_QKV_HD, EPI_PARTIAL, EPI_HEAD — gemm_plan refuses them, and engine.ArDecoder's gate keeps those shapes on fp32 weights."""
 import contextlib
 import functools
 

@@ -238,6 +238,69 @@ def test_linear_dispatch_sweep(K, seed):
         close(out, ref, atol=6e-5)
 
 
+def _first_shape_of_each_form():
+    """From tests/golden/gemm_decode_forms.txt: for every distinct (kernel form) a fp32-weight entry point without LayerNorm
+    reaches, the first (knobs, entry, M, N, K, T) of the file that reaches it."""
+    import re
+    from pathlib import Path
+    text = (Path(__file__).resolve().parent / 'golden' / 'gemm_decode_forms.txt').read_text().splitlines()
+    names = {m.group(1): m.group(2) for m in (re.match(r'(F\d+) (\S+) ', ln) for ln in text) if m}
+    first, knobs = {}, None
+    for ln in text:
+        m = re.match(r'\[knobs ROW_GROUPS=(\d) LN_STATS=(\d) TILE_DMA=(\d)\]', ln)
+        if m:
+            knobs = tuple(map(int, m.groups()))
+            continue
+        m = re.match(r'(linear|linear_ws|qkv|qkv_hd) N=(\d+) K=(\d+) T=(\d+): (.*)', ln)
+        if knobs is None or not m:
+            continue
+        for group in m.group(5).split():
+            rows, token = group.split('=')
+            if token[0] == 'F':
+                first.setdefault(names[token.split('/')[0]], (knobs, m.group(1), int(rows.split(',')[0]), int(m.group(2)), int(m.group(3)),
+                                                              int(m.group(4))))
+    return [pytest.param(*shape, id=f'{form}-{shape[1]}-M{shape[2]}-N{shape[3]}-K{shape[4]}-T{shape[5]}') for form, shape in first.items()]
+
+
+@pytest.mark.parametrize('knobs,entry,M,N,K_,T', _first_shape_of_each_form())
+def test_every_dispatched_form_without_layernorm_is_integer_exact(K, knobs, entry, M, N, K_, T):
+    """The launcher maps a plan's tuple to template arguments: a row of the table wired to the wrong instantiation computes a
+    wrong (or partial) product.  Every form of the pinned dispatch table that needs no LayerNorm and takes fp32 weights, at the
+    first shape that reaches it, on the small-integer operands of test_linear_dispatch_sweep: sums exact in fp32, so the
+    result is torch's bit for bit (the h16-weight and LayerNorm forms: test_decode_w16_gpu, test_base_d_model_gpu,
+    test_wide_d_model_gpu, test_decode_any_head_dim_gpu)."""
+    from valle2_amd import _lib
+    a = torch.randint(-2, 3, (M, K_), generator=g(7)).float()
+    w = torch.randint(-2, 3, (N, K_), generator=g(57)).float()
+    ref = a @ w.T
+    ad, wd = a.to(DEV), w.to(DEV)
+    lib = _lib.lib()
+    try:
+        for knob, v in zip((2, 9, 4), knobs):               # VH_TUNE_ROW_GROUPS, VH_TUNE_LN_STATS, VH_TUNE_TILE_DMA
+            lib.vh_set_tuning(knob, v)
+        if entry == 'linear':
+            assert torch.equal(K.linear(ad, wd).cpu(), ref)
+        elif entry == 'linear_ws':
+            assert torch.equal(K.linear_ws(ad, wd).cpu(), ref)
+        else:
+            B, hd = M // T, 64 if entry == 'qkv' else 32
+            h = K_ // hd
+            kc = torch.zeros(B, h, T + 1, hd, device=DEV)
+            vc = torch.zeros_like(kc)
+            q = torch.full((M, K_), float('nan'), device=DEV)
+            if entry == 'qkv':
+                K.linear_qkv(ad, wd, q, kc, vc, B, T, h)
+            else:
+                K.linear_qkv_hd(ad, wd, q, kc, vc, h, torch.zeros(B, dtype=torch.int32, device=DEV))
+            assert torch.equal(q.cpu(), ref[:, :K_])
+            for cache, cols in ((kc, ref[:, K_:2 * K_]), (vc, ref[:, 2 * K_:])):
+                assert torch.equal(cache[:, :, :T].cpu(), cols.view(B, T, h, hd).transpose(1, 2))
+                assert int(cache[:, :, T:].abs().sum()) == 0
+    finally:
+        for knob in (2, 9, 4):
+            lib.vh_set_tuning(knob, 0)
+
+
 @pytest.mark.parametrize('M', [7, 32, 200])
 @pytest.mark.parametrize('act', [0, 1])
 def test_linear_epilogues(K, M, act):

@@ -195,7 +195,7 @@ def compile_ffn_asm():
 # d_model 640 / 768 / 896 (PW = d / 128): per EPI (plain, QKV, QKV16) the fragment-statistics form and the row-resident forms at
 # MT 1 / 2 / 4 with NJ = d / 64; the fused FeedForward at 16 and 32 hidden columns per workgroup.  fp32 weights only.
 BASE_FOLD_PW = (5, 6, 7)
-# (MT = 4 at PW = 7 would spill: launch_gemm does not build it and serves those row counts as row groups)
+# (MT = 4 at PW = 7 would spill: gemm.hip FORM_TABLE has no such row and gemm_plan serves those row counts as row groups)
 BASE_FOLD_GEMMS = [(mt, epi, pw, ln, nj) for epi in (0, 1, 3) for pw in BASE_FOLD_PW
                    for mt, ln, nj in [(1, 3, 1), (1, 2, 2 * pw), (2, 2, 2 * pw), (4, 2, 2 * pw)] if (mt, pw) != (4, 7)]
 BASE_FOLD_FFNS = [(128 * pw, sw) for pw in BASE_FOLD_PW for sw in (16, 32)]

@@ -94,6 +94,16 @@ class VhForward16Desc(C.Structure):
     ]
 
 
+class VhLinearFormInfo(C.Structure):
+    """include/valle_hip.h vh_linear_form_info: the compiled form of a decode GEMM (family, template tuple, launch geometry)."""
+    _fields_ = [('family', C.c_int), ('mt', C.c_int), ('nw', C.c_int), ('epi', C.c_int), ('pw', C.c_int), ('ln', C.c_int),
+                ('nj', C.c_int), ('w16', C.c_int), ('grid', C.c_uint * 3), ('block', C.c_uint), ('rg_rows', C.c_int),
+                ('epis', C.c_uint)]
+
+
+LN_NONE, LN_GAMMA, LN_FOLDED = 0, 1, 2                                                        # VH_LN_*
+ENTRY_LINEAR, ENTRY_QKV, ENTRY_QKV_HD, ENTRY_QKV_KV16, ENTRY_LINEAR_WS, ENTRY_HEAD_GREEDY = range(6)   # VH_ENTRY_*
+
 # name → (restype, argtypes); must list every symbol include/valle_hip.h declares
 SIGNATURES = {
     'vh_version': (C.c_int, []),
@@ -242,6 +252,9 @@ SIGNATURES = {
     'vh_attn_rows_packed': (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                       c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_void_p]),
     'vh_transformer_forward_packed': (C.c_int, [C.POINTER(VhForwardDesc), c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_void_p]),
+    # which compiled form a decode GEMM takes (ABI 138)
+    'vh_linear_form': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(VhLinearFormInfo)]),
+    'vh_linear_form_row': (C.c_int, [C.c_int, C.POINTER(VhLinearFormInfo)]),
     'vh_h16_format': (C.c_int, []),
     'vh_to_bf16': (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     'vh_layernorm_bf16': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_float,
@@ -283,6 +296,19 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
 
 
 TUNING_EPOCH = 0
+
+
+def linear_form(entry, M, N, K, T=1, ln_kind=LN_NONE, w16=False):
+    """vh_linear_form: the form the library's `entry` takes for the shape, or None where it refuses it (vh_last_error says
+    why).  Needs no GPU: nothing is launched."""
+    global _host_lib
+    if _host_lib is None:
+        _host_lib = load_library()
+    info = VhLinearFormInfo()
+    return info if _host_lib.vh_linear_form(entry, M, N, K, T, ln_kind, int(w16), C.byref(info)) == 0 else None
+
+
+_host_lib = None
 
 
 def h16_dtype():

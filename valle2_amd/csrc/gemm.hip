@@ -21,7 +21,9 @@
 //   16x16x4 : A[i=l&15][k=l>>4], B[k=l>>4][j=l&15]; D reg r: row i=4(l>>4)+r,          col j=l&15
 // The k index of a product is only summed over, so each lane feeds 4 consecutive k (one float4)
 // per operand and the 4 MFMAs of a group consume element j of both operands: same k on both sides.
+#include <cstdarg>
 #include <type_traits>
+#include <utility>
 
 #include "vh_common.h"
 
@@ -1420,11 +1422,6 @@ extern "C" size_t vh_linear_ex_ws_bytes(int M, int N, int K) {
     return split ? (size_t)(tiles - n_whole) * split * TM * TN * sizeof(float) : 0;
 }
 
-// K of the wide folded-LayerNorm form (gemm_skinny_fast<1, 16, .., PW, 3, 1>): 256 PW passes, PW in 5..8, one or two passes
-static bool folded_wide_k(int K) {
-    return K > 1024 && K <= 4096 && K % (K <= 2048 ? 256 : 512) == 0;
-}
-
 static int splitk_plan(int M, int N, int K) {
     // number of K slices (0 = do not split)
     if (M > 64) {
@@ -1478,182 +1475,208 @@ static int check_gemm(const char* name, const GemmArgs& a, const LnFuse& ln) {
 
 #define SKINNY_ARGS(g) (g).A, (g).W, (g).lda, (g).K, (g).k_len, (g).M, (g).N
 
-template <int EPI>
-static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hipStream_t s, float* tail_ws = nullptr,
-                       size_t tail_ws_bytes = 0) {
-    if (a.M == 0) return VH_OK;
-    const bool train_epi = a.aux != nullptr || a.colsum != nullptr || a.act >= VH_ACT_GELU_BWD || a.drop.thresh != 0;   // tile-kernel epilogues only
-    if (a.M <= 64 && !train_epi) {
-        const int mt = (a.M + 15) / 16;
-        dim3 grid((a.N + 15) / 16);
-        const bool wide = a.K > 1024;
-        const bool has_ln = ln.gamma != nullptr || ln.c1 != nullptr;
-        const bool fold = ln.c1 != nullptr;
-        // one workgroup per (16 columns, 16 rows) instead of (16 columns, all rows): see the kernel
-        // (the folded LayerNorm at K > 1024 is a one-row-tile kernel: every K of its set takes row groups)
-        // (folded K = 896 above 32 rows: the row-resident MT = 4 form would spill, so those row counts take row groups whatever the knob says)
-        const bool no_mt4 = fold && a.K == 896 && mt >= 3;
-        const bool rowgroups = (vh_tuning(VH_TUNE_ROW_GROUPS) != 2 || no_mt4) && mt >= 2 && (!wide || a.K % 2048 == 0 || fold) &&
-                               EPI != EPI_PARTIAL && (!IS_QKV(EPI) || a.T == 1);
-        GemmArgs ag = a;                  // groups of 16 rows, or of 8 while that keeps the grid within the CUs
-        if (rowgroups) {
-            ag.rg_rows = (vh_tuning(VH_TUNE_ROW_GROUPS) != 3 && (int)grid.x * ((a.M + 7) / 8) <= 256) ? 8 : 16;
-            grid.z = (a.M + ag.rg_rows - 1) / ag.rg_rows;
-        }
-        // ---- compact fast path: K = 16*NW*PW*passes
-#define SF(MT, NW, PW, LN, NJ)                                                                                                   \
-    do {                                                                                                                        \
-        if constexpr ((EPI == EPI_PLAIN && (LN) == 0 && (NW) == 8) || (EPI == EPI_QKV16 && (LN) >= 2)) {                          \
-            if (ag.w16) {                                                                                                       \
-                hipLaunchKernelGGL((gemm_skinny_fast<MT, NW, EPI, PW, LN, NJ, true>), grid, dim3(NW * 64), 0, s, SKINNY_ARGS(ag), ag, ln); \
-                break;                                                                                                          \
-            }                                                                                                                   \
-        }                                                                                                                       \
-        if (ag.w16) { vh_set_error("%s: no 16-bit-weight form of this shape", name); return VH_EUNSUPPORTED; }                   \
-        hipLaunchKernelGGL((gemm_skinny_fast<MT, NW, EPI, PW, LN, NJ>), grid, dim3(NW * 64), 0, s, SKINNY_ARGS(ag), ag, ln);        \
-    } while (0)
-#define SF_MT(NW, PW, LN, NJ)                                                  \
-    do {                                                                       \
-        if (rowgroups) SF(1, NW, PW, LN, NJ);                                  \
-        else if (mt == 1) SF(1, NW, PW, LN, NJ);                               \
-        else if (mt == 2) SF(2, NW, PW, LN, NJ);                               \
-        else SF(4, NW, PW, LN, NJ);                                            \
-        VH_CHECK_LAUNCH(name);                                                 \
-        return VH_OK;                                                          \
-    } while (0)
-        // K in {640, 768, 896} = 128 PW, PW in 5..7: the folded forms at eight waves and ONE pass, fp32 weights only (no 16-bit-weight
-        // instantiation).  768 could also run PW 3 x 2 passes; the compiled counts decide: one pass holds 109 (LN = 3) / 250 (LN = 2,
-        // MT = 4) VGPRs, the two-pass form some 30 / 80 fewer, both without scratch and both one 512-thread workgroup per CU (256
-        // registers a wave), so the form with one memory round trip is taken.  PW = 7 at MT = 4 (xf alone is 112 registers) needs
-        // 80-88 bytes of scratch at 256 VGPRs: that pair is not built — more than 32 rows at K = 896 run as row groups (no_mt4
-        // above), and a QKV product with T > 1 of that size is refused (tools/check_isa.py check_base_folded).
-#define SFB(MT, PW, LN, NJ)                                                                                                      \
-    do {                                                                                                                        \
-        if (ag.w16) { vh_set_error("%s: no 16-bit-weight form of the folded LayerNorm at K=%d", name, a.K); return VH_EUNSUPPORTED; } \
-        hipLaunchKernelGGL((gemm_skinny_fast<MT, 8, EPI, PW, LN, NJ>), grid, dim3(512), 0, s, SKINNY_ARGS(ag), ag, ln);            \
-    } while (0)
-#define SFB_MT(PW, NJ)                                                         \
-    do {                                                                       \
-        if (rowgroups || mt == 1) SFB(1, PW, 2, NJ);                           \
-        else if (mt == 2) SFB(2, PW, 2, NJ);                                   \
-        else if constexpr ((PW) == 7) {                                        \
-            vh_set_error("%s: folded LayerNorm at K=%d serves more than 32 rows as row groups only (T == 1): the four-row-tile form " \
-                         "does not fit the register file", name, a.K);         \
-            return VH_EUNSUPPORTED;                                            \
-        } else SFB(4, PW, 2, NJ);                                              \
-        VH_CHECK_LAUNCH(name);                                                 \
-        return VH_OK;                                                          \
-    } while (0)
-        if (fold && wide) {
-            // K = 256 PW passes with PW in 5..8 and one pass (1280 .. 2048) or two (2560, 3072, 3584, 4096): folded_wide_k,
-            // which check_folded enforced — any other K would make the pass loop read past the rows: 16 waves,
-            // passes, statistics from the fragments — one row tile per workgroup, more than 16 rows as row groups
-            if constexpr (EPI == EPI_PLAIN || EPI == EPI_QKV) {
-                if (a.w16) { vh_set_error("%s: no 16-bit-weight form of the folded LayerNorm at K=%d", name, a.K); return VH_EUNSUPPORTED; }
-                if (mt >= 2 && !rowgroups) {
-                    vh_set_error("%s: folded LayerNorm at K=%d serves more than 16 rows as row groups (T == 1, row groups enabled)",
-                                 name, a.K);
-                    return VH_EUNSUPPORTED;
-                }
-                const int passes = a.K <= 2048 ? 1 : 2, pw = a.K / (256 * passes);
-                if (!folded_wide_k(a.K) || pw < 5 || pw > 8 || 256 * pw * passes != a.K) {
-                    vh_set_error("%s: folded LayerNorm has no wide form for K=%d", name, a.K);
-                    return VH_EUNSUPPORTED;
-                }
-#define SFW(PW) hipLaunchKernelGGL((gemm_skinny_fast<1, 16, EPI, PW, 3, 1>), grid, dim3(1024), 0, s, SKINNY_ARGS(ag), ag, ln)
-                if (pw == 5) SFW(5); else if (pw == 6) SFW(6); else if (pw == 7) SFW(7); else SFW(8);
-#undef SFW
-                VH_CHECK_LAUNCH(name);
-                return VH_OK;
-            } else {
-                vh_set_error("%s: folded LayerNorm at K=%d serves the fp32 forms (vh_linear_folded, vh_linear_qkv_folded)", name, a.K);
-                return VH_EUNSUPPORTED;
-            }
-        }
-        if (has_ln) {  // K <= 1024 (check_gemm); statistics need K = 64*NJ
-            if (fold && (rowgroups || mt == 1) && vh_tuning(VH_TUNE_LN_STATS) != 1) {   // statistics from the fragments
-#define SF3(NW, PW) do { SF(1, NW, PW, 3, 1); VH_CHECK_LAUNCH(name); return VH_OK; } while (0)
-                if (a.K == 128) SF3(8, 1);
-                if (a.K == 256) SF3(8, 2);
-                if (a.K == 512) SF3(8, 4);
-                if (a.K == 1024) SF3(8, 4);
-#undef SF3
-                if constexpr (EPI != EPI_QKV_HD) {          // K = 128 PW, PW in 5..7, one pass
-#define SFB3(PW) do { SFB(1, PW, 3, 1); VH_CHECK_LAUNCH(name); return VH_OK; } while (0)
-                    if (a.K == 640) SFB3(5);
-                    if (a.K == 768) SFB3(6);
-                    if (a.K == 896) SFB3(7);
-#undef SFB3
-                }
-            }
-            if (fold) {
-                if (a.K == 128) SF_MT(8, 1, 2, 2);
-                if (a.K == 256) SF_MT(8, 2, 2, 4);
-                if (a.K == 512) SF_MT(8, 4, 2, 8);
-                if (a.K == 1024) SF_MT(8, 4, 2, 16);
-                if constexpr (EPI != EPI_QKV_HD) {          // the row-resident forms of 640 / 768 / 896 (NJ = K / 64)
-                    if (a.K == 640) SFB_MT(5, 10);
-                    if (a.K == 768) SFB_MT(6, 12);
-                    if (a.K == 896) SFB_MT(7, 14);
-                }
-                vh_set_error("%s: folded LayerNorm needs K in {128,256,512,640,768,896,1024} at head width 64, {128,256,512,1024} at "
-                             "any other (K=%d)", name, a.K);
-                return VH_EUNSUPPORTED;
-            }
-            if (a.K == 128) SF_MT(8, 1, 1, 2);
-            if (a.K == 256) SF_MT(8, 2, 1, 4);
-            if (a.K == 512) SF_MT(8, 4, 1, 8);
-            if (a.K == 1024) SF_MT(8, 4, 1, 16);
-        } else if (!wide) {
-            if (a.K % 512 == 0) SF_MT(8, 4, 0, 1);
-            if (a.K % 256 == 0) SF_MT(8, 2, 0, 1);
-            if (a.K % 128 == 0) SF_MT(8, 1, 0, 1);
-        } else {
-            if (a.K % 2048 == 0 && (mt <= 2 || rowgroups)) {
-                if (mt == 1 || rowgroups) SF(1, 16, 8, 0, 1); else SF(2, 16, 8, 0, 1);
-                VH_CHECK_LAUNCH(name);
-                return VH_OK;
-            }
-            if (a.K % 1024 == 0) SF_MT(16, 4, 0, 1);
-        }
-#undef SF_MT
-#undef SF
-#undef SFB_MT
-#undef SFB
-        if constexpr (EPI == EPI_QKV16) {
-            vh_set_error("%s: bf16 K/V append needs the folded LayerNorm shapes (K in {128,256,512,640,768,896,1024})", name);
-            return VH_EUNSUPPORTED;
-        } else {
-        // ---- generic guarded kernel for every other K (multiple of 16)
-        if (a.w16) { vh_set_error("%s: no 16-bit-weight form of this shape (K=%d)", name, a.K); return VH_EUNSUPPORTED; }
-        // this kernel has no row groups: every workgroup of a column group computes ALL rows.  With the gridDim.z of the row
-        // groups left in place, M = 17 .. 64 launched two to eight workgroups per column group that each wrote the whole
-        // column block — and with out == residual (the FeedForward's second product in place, K = dim_feedforward % 128 != 0)
-        // a workgroup that read the residual after another one's store added it twice.
-        grid.z = 1;
-#define SK(MT, NW, CH, LN) \
-    hipLaunchKernelGGL((gemm_skinny_kernel<MT, NW, EPI, CH, LN>), grid, dim3(NW * 64), 0, s, a, ln)
-        if (has_ln) {
-            if (mt == 1) SK(1, 8, 4, true); else if (mt == 2) SK(2, 8, 4, true); else SK(4, 8, 4, true);
-        } else if (wide) {
-            if (mt == 1) SK(1, 16, 8, false); else if (mt == 2) SK(2, 16, 8, false); else SK(4, 16, 4, false);
-        } else {
-            if (mt == 1) SK(1, 8, 4, false); else if (mt == 2) SK(2, 8, 4, false); else SK(4, 8, 4, false);
-        }
-#undef SK
-        }
-    } else if constexpr (EPI == EPI_QKV16) {
-        vh_set_error("%s: bf16 K/V append is the decode path (M <= 64)", name);
-        return VH_EUNSUPPORTED;
-    } else if constexpr (EPI == EPI_QKV_HD) {
-        vh_set_error("%s: the K/V append at a runtime head width is the decode path (M <= 64)", name);
-        return VH_EUNSUPPORTED;
-    } else {
-        if (a.w16) { vh_set_error("%s: 16-bit weights are the decode step's form (M <= 64)", name); return VH_EUNSUPPORTED; }
-        const int tm = (a.M + TM - 1) / TM, tn = (a.N + TN - 1) / TN;
+// ---- the plan: which compiled form serves a shape, or why none does.  Pure: no HIP call, no global, no data pointer ----
+enum { LN_NONE = VH_LN_NONE, LN_GAMMA = VH_LN_GAMMA, LN_FOLDED = VH_LN_FOLDED };
+enum { FAM_NONE = VH_FORM_NONE /* M == 0: nothing to launch */, FAST = VH_FORM_SKINNY_FAST, GENERIC = VH_FORM_SKINNY_GENERIC,
+       TILE_DMA = VH_FORM_TILE_DMA, TILE_REG = VH_FORM_TILE_REG, HEAD_GREEDY = VH_FORM_HEAD_GREEDY };
+struct GemmShape { int epi, M, N, K, k_len, T, ln, w16, train_epi; };
+struct GemmKnobs { int row_groups, ln_stats, tile_dma; };     // VH_TUNE_ROW_GROUPS, VH_TUNE_LN_STATS, VH_TUNE_TILE_DMA
+struct GemmForm {
+    int family, epi;
+    int mt, nw, pw, ln, nj, w16;     // template tuple of the skinny kernels (pw is CH and ln is 0 / 1 for the generic one)
+    unsigned gx, gy, gz, block;      // tile kernels: gx counts the output tiles (a tail split adds its slices at the launch)
+    int rg_rows;
+    char msg[512];                   // the refusal's text; untouched on success
+};
+
+__attribute__((format(printf, 2, 3))) static int refuse(GemmForm& f, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(f.msg, sizeof f.msg, fmt, ap);
+    va_end(ap);
+    return VH_EUNSUPPORTED;
+}
+static void form_reset(GemmForm& f, int epi) {     // nothing to launch, grid (1, 1, 1), no message
+    f.family = FAM_NONE; f.epi = epi; f.mt = f.nw = f.pw = f.ln = f.nj = f.w16 = 0;
+    f.gx = f.gy = f.gz = 1; f.block = 0; f.rg_rows = 0; f.msg[0] = 0;
+}
+static int skinny(GemmForm& f, int family, int mt, int nw, int pw, int ln, int nj, int w16) {
+    f.family = family; f.mt = mt; f.nw = nw; f.pw = pw; f.ln = ln; f.nj = nj; f.w16 = w16; f.block = nw * 64;
+    return VH_OK;
+}
+// rows per row group: 16, or 8 while that keeps the grid within the CUs
+static int row_group_rows(unsigned gx, int M, bool allow8) { return (allow8 && (int)gx * ((M + 7) / 8) <= 256) ? 8 : 16; }
+
+// K of the folded-LayerNorm forms: waves, PW and the NJ of the row-resident statistics (LN = 2).  false: no folded form
+static bool folded_geom(int K, int* nw, int* pw, int* nj) {
+    *nw = 8; *nj = K / 64; *pw = K == 1024 ? 4 : K / 128;          // 1024: two passes of 512
+    if (K == 128 || K == 256 || K == 512 || K == 640 || K == 768 || K == 896 || K == 1024) return true;
+    // wide (gemm_skinny_fast<1, 16, .., PW, 3, 1>): 256 PW a pass, PW in 5..8, one pass (1280 .. 2048) or two (2560 .. 4096) —
+    // any other K would make the pass loop read past the rows
+    const int pass = K <= 2048 ? 256 : 512;
+    *nw = 16; *nj = 1; *pw = K / pass;
+    return K > 1024 && K <= 4096 && K % pass == 0;
+}
+
+static int gemm_plan(const char* name, const GemmShape& p, const GemmKnobs& kn, GemmForm& f) {
+    const int EPI = p.epi, M = p.M, K = p.K;
+    form_reset(f, EPI);
+    if (p.w16 && EPI == EPI_PLAIN && !(M <= 64 && K % 128 == 0 && K <= 1024))
+        return refuse(f, "vh_linear (16-bit weights): M=%d K=%d (decode rows, K a multiple of 128 up to 1024)", M, K);
+    if (M <= 0) return VH_OK;
+    if (M > 64 || p.train_epi) {                   // the tile kernels (the training epilogues exist only there)
+        if (EPI == EPI_QKV16) return refuse(f, "%s: bf16 K/V append is the decode path (M <= 64)", name);
+        if (EPI == EPI_QKV_HD) return refuse(f, "%s: the K/V append at a runtime head width is the decode path (M <= 64)", name);
+        if (p.w16) return refuse(f, "%s: 16-bit weights are the decode step's form (M <= 64)", name);
         // The LDS-DMA kernel needs whole 32-wide K slabs; a ragged K goes to the register-staged kernel.
-        if (a.k_len % TK == 0 && vh_tuning(VH_TUNE_TILE_DMA) != 1) {
-            TailSplit ts{tm * tn, 1, a.K, nullptr};
+        f.family = (p.k_len % TK == 0 && kn.tile_dma != 1) ? TILE_DMA : TILE_REG;
+        f.gx = ((M + TM - 1) / TM) * ((p.N + TN - 1) / TN);
+        if (EPI == EPI_PARTIAL) f.gy = K / p.k_len;          // K slices in gridDim.y
+        f.block = 256;
+        return VH_OK;
+    }
+    const int mt = (M + 15) / 16, mt_all = mt == 3 ? 4 : mt;
+    const bool wide = K > 1024, fold = p.ln == LN_FOLDED;
+    f.gx = (p.N + 15) / 16;
+    if (EPI == EPI_PARTIAL) {                      // a K slice per gridDim.y: 4 waves x 4 k-steps of 16 = 256 k per pass
+        f.gy = K / p.k_len;
+        return skinny(f, FAST, mt_all, 4, 4, 0, 1, 0);
+    }
+    // one workgroup per (16 columns, 16 rows) instead of (16 columns, all rows): see the kernel
+    // (the folded LayerNorm at K > 1024 is a one-row-tile kernel: every K of its set takes row groups)
+    // (folded K = 896 above 32 rows: the row-resident MT = 4 form would spill, so those row counts take row groups whatever the knob says)
+    const bool no_mt4 = fold && K == 896 && mt >= 3;
+    const bool rowgroups = (kn.row_groups != 2 || no_mt4) && mt >= 2 && (!wide || K % 2048 == 0 || fold) && (!IS_QKV(EPI) || p.T == 1);
+    if (rowgroups) {
+        f.rg_rows = row_group_rows(f.gx, M, kn.row_groups != 3);
+        f.gz = (M + f.rg_rows - 1) / f.rg_rows;
+    }
+    const int mt_res = rowgroups ? 1 : mt_all;     // row tiles one workgroup keeps
+    int nw = 8, pw = 0, nj = 1;
+    if (fold && wide) {                            // 16 waves, statistics from the fragments — one row tile per workgroup
+        if (EPI != EPI_PLAIN && EPI != EPI_QKV)
+            return refuse(f, "%s: folded LayerNorm at K=%d serves the fp32 forms (vh_linear_folded, vh_linear_qkv_folded)", name, K);
+        if (p.w16) return refuse(f, "%s: no 16-bit-weight form of the folded LayerNorm at K=%d", name, K);
+        if (mt_res != 1) return refuse(f, "%s: folded LayerNorm at K=%d serves more than 16 rows as row groups (T == 1, row groups enabled)", name, K);
+        if (!folded_geom(K, &nw, &pw, &nj)) return refuse(f, "%s: folded LayerNorm has no wide form for K=%d", name, K);
+        return skinny(f, FAST, 1, 16, pw, 3, 1, 0);
+    }
+    if (fold) {
+        const bool known = folded_geom(K, &nw, &pw, &nj), base = pw >= 5;      // base: K in {640, 768, 896} = 128 PW at head width 64
+        if (!known || (base && EPI == EPI_QKV_HD))
+            return refuse(f, "%s: folded LayerNorm needs K in {128,256,512,640,768,896,1024} at head width 64, {128,256,512,1024} at any other (K=%d)", name, K);
+        // K in {640, 768, 896}: eight waves and ONE pass (109 VGPRs at LN = 3, 250 at LN = 2 / MT = 4, no scratch: one memory round
+        // trip beats 768 = PW 3 x 2 passes), fp32 weights only.  PW = 7 at MT = 4 (xf alone is 112 registers) needs 80-88 bytes of
+        // scratch at 256 VGPRs: that pair is not built — more than 32 rows at K = 896 run as row groups (no_mt4 above), and a QKV
+        // product with T > 1 of that size is refused (tools/check_isa.py check_base_folded).
+        if (pw == 7 && mt_res == 4)
+            return refuse(f, "%s: folded LayerNorm at K=%d serves more than 32 rows as row groups only (T == 1): the four-row-tile form does not fit the register file", name, K);
+        if (p.w16 && base) return refuse(f, "%s: no 16-bit-weight form of the folded LayerNorm at K=%d", name, K);
+        if (p.w16 && EPI != EPI_QKV16) return refuse(f, "%s: no 16-bit-weight form of this shape", name);
+        if (mt_res == 1 && kn.ln_stats != 1) return skinny(f, FAST, 1, 8, pw, 3, 1, p.w16);       // statistics from the fragments
+        return skinny(f, FAST, mt_res, 8, pw, 2, nj, p.w16);                                       // row-resident, NJ = K / 64
+    }
+    // ---- compact fast path: K = 16*NW*PW*passes
+    if (p.ln == LN_GAMMA) {                        // statistics need K = 64*NJ
+        if (K == 128 || K == 256 || K == 512 || K == 1024) { pw = K == 1024 ? 4 : K / 128; nj = K / 64; }
+    } else if (!wide) {
+        pw = K % 512 == 0 ? 4 : K % 256 == 0 ? 2 : K % 128 == 0 ? 1 : 0;
+    } else if (K % 2048 == 0 && mt_res <= 2) {
+        nw = 16; pw = 8;
+    } else if (K % 1024 == 0) {
+        nw = 16; pw = 4;
+    }
+    if (pw && p.w16 && !(EPI == EPI_PLAIN && p.ln == LN_NONE && nw == 8)) return refuse(f, "%s: no 16-bit-weight form of this shape", name);
+    if (pw) return skinny(f, FAST, mt_res, nw, pw, p.ln == LN_GAMMA, nj, p.w16);
+    // ---- generic guarded kernel for every other K (multiple of 16)
+    if (EPI == EPI_QKV16) return refuse(f, "%s: bf16 K/V append needs the folded LayerNorm shapes (K in {128,256,512,640,768,896,1024})", name);
+    if (p.w16) return refuse(f, "%s: no 16-bit-weight form of this shape (K=%d)", name, K);
+    // this kernel has no row groups: every workgroup of a column group computes ALL rows, so a gridDim.z above 1 would write each
+    // column block several times (and with out == residual add the residual more than once)
+    f.gz = 1; f.rg_rows = 0;
+    if (p.ln != LN_NONE) return skinny(f, GENERIC, mt_all, 8, 4, 1, 0, 0);
+    return skinny(f, GENERIC, mt_all, wide ? 16 : 8, wide && mt_all != 4 ? 8 : 4, 0, 0, 0);
+}
+
+// ---- the compiled forms of the skinny kernels, one row per template tuple, and the epilogues each is built for.
+// A new width is a rule in gemm_plan, a row here and a line in tests/golden/gemm_decode_forms.txt.
+struct FormRow { int family, mt, nw, pw, ln, nj, w16; unsigned epis; };
+constexpr unsigned E_PLAIN = 1u << EPI_PLAIN, E_PARTIAL = 1u << EPI_PARTIAL, E_QKV16 = 1u << EPI_QKV16,
+                   E_HD64 = E_PLAIN | 1u << EPI_QKV /* head width 64 */, E_FP32 = E_HD64 | 1u << EPI_QKV_HD, E_FOLD = E_FP32 | E_QKV16;
+#define MT1(fam, ...) {fam, 1, __VA_ARGS__}
+#define MT12(fam, ...) {fam, 1, __VA_ARGS__}, {fam, 2, __VA_ARGS__}
+#define MT124(fam, ...) {fam, 1, __VA_ARGS__}, {fam, 2, __VA_ARGS__}, {fam, 4, __VA_ARGS__}
+constexpr FormRow FORM_TABLE[] = {
+    //         NW PW LN NJ W16 epilogues
+    // no LayerNorm: K % 512 / 256 / 128 == 0 up to 1024 (h16 weights for vh_linear only); K % 2048 == 0 (up to 32 resident rows)
+    // and K % 1024 == 0 above; one K slice of vh_linear_ws
+    MT124(FAST, 8, 4, 0, 1, 0, E_FP32), MT124(FAST, 8, 2, 0, 1, 0, E_FP32), MT124(FAST, 8, 1, 0, 1, 0, E_FP32),
+    MT124(FAST, 8, 4, 0, 1, 1, E_PLAIN), MT124(FAST, 8, 2, 0, 1, 1, E_PLAIN), MT124(FAST, 8, 1, 0, 1, 1, E_PLAIN),
+    MT12(FAST, 16, 8, 0, 1, 0, E_FP32), MT124(FAST, 16, 4, 0, 1, 0, E_FP32), MT124(FAST, 4, 4, 0, 1, 0, E_PARTIAL),
+    // LayerNorm in the operand load, K in {128, 256, 512, 1024}
+    MT124(FAST, 8, 1, 1, 2, 0, E_FP32), MT124(FAST, 8, 2, 1, 4, 0, E_FP32), MT124(FAST, 8, 4, 1, 8, 0, E_FP32), MT124(FAST, 8, 4, 1, 16, 0, E_FP32),
+    // folded LayerNorm, row-resident statistics: K in {128, 256, 512, 1024} (the bf16 K/V append also with h16 weights) and
+    // K in {640, 768, 896} at head width 64 (PW = 7 at MT = 4 does not fit the register file)
+    MT124(FAST, 8, 1, 2, 2, 0, E_FOLD), MT124(FAST, 8, 2, 2, 4, 0, E_FOLD), MT124(FAST, 8, 4, 2, 8, 0, E_FOLD), MT124(FAST, 8, 4, 2, 16, 0, E_FOLD),
+    MT124(FAST, 8, 1, 2, 2, 1, E_QKV16), MT124(FAST, 8, 2, 2, 4, 1, E_QKV16), MT124(FAST, 8, 4, 2, 8, 1, E_QKV16), MT124(FAST, 8, 4, 2, 16, 1, E_QKV16),
+    MT124(FAST, 8, 5, 2, 10, 0, E_HD64 | E_QKV16), MT124(FAST, 8, 6, 2, 12, 0, E_HD64 | E_QKV16), MT12(FAST, 8, 7, 2, 14, 0, E_HD64 | E_QKV16),
+    // folded LayerNorm, statistics from the fragments (one row tile): PW 4 serves K = 512 and, in two passes, 1024; 16 waves and
+    // 256 PW a pass at 1024 < K <= 4096
+    MT1(FAST, 8, 1, 3, 1, 0, E_FOLD), MT1(FAST, 8, 2, 3, 1, 0, E_FOLD), MT1(FAST, 8, 4, 3, 1, 0, E_FOLD),
+    MT1(FAST, 8, 1, 3, 1, 1, E_QKV16), MT1(FAST, 8, 2, 3, 1, 1, E_QKV16), MT1(FAST, 8, 4, 3, 1, 1, E_QKV16),
+    MT1(FAST, 8, 5, 3, 1, 0, E_HD64 | E_QKV16), MT1(FAST, 8, 6, 3, 1, 0, E_HD64 | E_QKV16), MT1(FAST, 8, 7, 3, 1, 0, E_HD64 | E_QKV16),
+    MT1(FAST, 16, 5, 3, 1, 0, E_HD64), MT1(FAST, 16, 6, 3, 1, 0, E_HD64), MT1(FAST, 16, 7, 3, 1, 0, E_HD64), MT1(FAST, 16, 8, 3, 1, 0, E_HD64),
+    // the guarded kernel for every other K: NW, CH, LN
+    MT124(GENERIC, 8, 4, 0, 0, 0, E_FP32), MT124(GENERIC, 8, 4, 1, 0, 0, E_FP32), MT12(GENERIC, 16, 8, 0, 0, 0, E_FP32),
+    {GENERIC, 4, 16, 4, 0, 0, 0, E_FP32},
+};
+#undef MT1
+#undef MT12
+#undef MT124
+constexpr int FORM_ROWS = sizeof(FORM_TABLE) / sizeof(FORM_TABLE[0]);
+constexpr uint32_t form_key(int family, int mt, int nw, int pw, int ln, int nj, int w16) {
+    return (uint32_t)(family | mt << 3 | nw << 6 | pw << 11 | ln << 15 | nj << 17 | w16 << 22);
+}
+
+template <int EPI, int I>      // row I of the table, where it is built for EPI and is the form asked for
+static bool launch_row(uint32_t key, dim3 grid, hipStream_t s, const GemmArgs& a, const LnFuse& ln) {
+    constexpr FormRow R = FORM_TABLE[I];
+    if constexpr ((R.epis >> EPI) & 1u) {
+        if (key != form_key(R.family, R.mt, R.nw, R.pw, R.ln, R.nj, R.w16)) return false;
+        if constexpr (R.family == FAST)
+            hipLaunchKernelGGL((gemm_skinny_fast<R.mt, R.nw, EPI, R.pw, R.ln, R.nj, R.w16 != 0>), grid, dim3(R.nw * 64), 0, s, SKINNY_ARGS(a), a, ln);
+        else
+            hipLaunchKernelGGL((gemm_skinny_kernel<R.mt, R.nw, EPI, R.pw, R.ln != 0>), grid, dim3(R.nw * 64), 0, s, a, ln);
+        return true;
+    }
+    return false;
+}
+template <int EPI, int... I>
+static bool launch_rows(std::integer_sequence<int, I...>, uint32_t key, dim3 grid, hipStream_t s, const GemmArgs& a, const LnFuse& ln) {
+    return (launch_row<EPI, I>(key, grid, s, a, ln) || ...);
+}
+
+// vh_linear_form: the entry points run as they are, and the launcher hands the form over instead of launching it
+static thread_local GemmForm* t_form_query = nullptr;
+
+template <int EPI>
+static int launch_form(const char* name, const GemmForm& f, const GemmArgs& a, const LnFuse& ln, hipStream_t s, float* tail_ws,
+                       size_t tail_ws_bytes) {
+    if (t_form_query) *t_form_query = f;
+    if (t_form_query || f.family == FAM_NONE) return VH_OK;
+    if (f.family == FAST || f.family == GENERIC) {
+        GemmArgs ag = a;
+        ag.rg_rows = f.rg_rows;
+        const uint32_t key = form_key(f.family, f.mt, f.nw, f.pw, f.ln, f.nj, f.w16);
+        VH_REQUIRE(launch_rows<EPI>(std::make_integer_sequence<int, FORM_ROWS>{}, key, dim3(f.gx, f.gy, f.gz), s, ag, ln), VH_EUNSUPPORTED,
+                   "%s: internal: no compiled form <family %d, MT %d, NW %d, EPI %d, PW %d, LN %d, NJ %d, W16 %d>", name, f.family, f.mt, f.nw, EPI,
+                   f.pw, f.ln, f.nj, f.w16);
+    } else if constexpr (EPI == EPI_QKV16 || EPI == EPI_QKV_HD) {
+        VH_REQUIRE(false, VH_EUNSUPPORTED, "%s: internal: no tile kernel with epilogue %d", name, EPI);
+    } else {
+        const int tn = (a.N + TN - 1) / TN, tm = (int)f.gx / tn;
+        if (f.family == TILE_DMA) {
+            TailSplit ts{tm * tn, 1, a.k_len, nullptr};
             if constexpr (EPI == EPI_PLAIN) {
                 int n_whole;
                 const int split = tail_ws ? tail_plan(a.M, a.N, a.K, &n_whole) : 0;
@@ -1661,19 +1684,31 @@ static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hi
                     ts = TailSplit{n_whole, split, a.K / split, tail_ws};
             }
             const int tail = tm * tn - ts.n_whole;
+            const dim3 grid(ts.n_whole + tail * ts.split, f.gy);
             if (EPI == EPI_PLAIN && a.drop.thresh)
-                hipLaunchKernelGGL((gemm_tile_dma_kernel<EPI, EPI == EPI_PLAIN>), dim3(ts.n_whole + tail * ts.split), dim3(256), 0,
-                                   s, a, tm, tn, ts);
+                hipLaunchKernelGGL((gemm_tile_dma_kernel<EPI, EPI == EPI_PLAIN>), grid, dim3(256), 0, s, a, tm, tn, ts);
             else
-                hipLaunchKernelGGL((gemm_tile_dma_kernel<EPI>), dim3(ts.n_whole + tail * ts.split), dim3(256), 0, s, a, tm, tn,
-                                   ts);
+                hipLaunchKernelGGL((gemm_tile_dma_kernel<EPI>), grid, dim3(256), 0, s, a, tm, tn, ts);
             if (tail) hipLaunchKernelGGL(tile_tail_fixup_kernel, dim3(tail * 4), dim3(256), 0, s, a, ts, tn);
         } else {
-            hipLaunchKernelGGL((gemm_tile_kernel<EPI>), dim3(tm * tn), dim3(256), 0, s, a, tm, tn);
+            hipLaunchKernelGGL((gemm_tile_kernel<EPI>), dim3(tm * tn, f.gy), dim3(256), 0, s, a, tm, tn);
         }
     }
     VH_CHECK_LAUNCH(name);
     return VH_OK;
+}
+
+static GemmKnobs current_knobs() { return GemmKnobs{vh_tuning(VH_TUNE_ROW_GROUPS), vh_tuning(VH_TUNE_LN_STATS), vh_tuning(VH_TUNE_TILE_DMA)}; }
+
+template <int EPI>
+static int launch_gemm(const char* name, const GemmArgs& a, const LnFuse& ln, hipStream_t s, float* tail_ws = nullptr,
+                       size_t tail_ws_bytes = 0) {
+    const bool train_epi = a.aux != nullptr || a.colsum != nullptr || a.act >= VH_ACT_GELU_BWD || a.drop.thresh != 0;
+    const GemmShape shape{EPI, a.M, a.N, a.K, a.k_len, a.T, ln.c1 ? LN_FOLDED : ln.gamma ? LN_GAMMA : LN_NONE, a.w16, train_epi};
+    GemmForm f;
+    const int rc = gemm_plan(name, shape, current_knobs(), f);
+    VH_REQUIRE(rc == VH_OK, rc, "%s", f.msg);
+    return launch_form<EPI>(name, f, a, ln, s, tail_ws, tail_ws_bytes);
 }
 
 extern "C" int vh_linear(const float* A, int lda, const float* W, const float* bias,
@@ -1781,9 +1816,8 @@ extern "C" int vh_ln_fold(const float* W, const float* gamma, const float* beta,
 
 static int check_folded(const char* name, const GemmArgs& a, const LnFuse& ln) {
     VH_REQUIRE(ln.c1 && ln.c2, VH_EINVAL, "%s: null c1/c2", name);
-    const bool k_ok = a.K == 128 || a.K == 256 || a.K == 512 || a.K == 640 || a.K == 768 || a.K == 896 || a.K == 1024 ||
-                      folded_wide_k(a.K);
-    VH_REQUIRE(a.M <= 64 && a.N % 16 == 0 && k_ok, VH_EUNSUPPORTED,
+    int nw, pw, nj;
+    VH_REQUIRE(a.M <= 64 && a.N % 16 == 0 && folded_geom(a.K, &nw, &pw, &nj), VH_EUNSUPPORTED,
                "%s: folded LayerNorm is the decode path: M <= 64, N %% 16 == 0, K in {128,256,512,640,768,896,1024} or a multiple of 256 "
                "up to 2048 / of 512 up to 4096 (M=%d N=%d K=%d)", name, a.M, a.N, a.K);
     VH_REQUIRE(vh_aligned16(ln.c1) && vh_aligned16(ln.c2), VH_EALIGN, "%s: c1/c2 must be 16-byte aligned", name);
@@ -1797,6 +1831,21 @@ extern "C" size_t vh_head_greedy_ws_bytes(int B, int V) {
     return HEAD_WS_COUNTERS * sizeof(int) + (size_t)B * ((V + 15) / 16) * sizeof(uint64_t);
 }
 
+// the head's form: gemm_head_greedy_kernel<PW> over 16-column blocks; EPI_HEAD is MT = 1 only, so more than 16 rows always run as
+// row groups of 8 or 16 (VH_TUNE_ROW_GROUPS is not read)
+static int head_plan(int B, int V, int d, GemmForm& f) {
+    form_reset(f, EPI_HEAD);
+    if (!(B <= 64 && (d == 128 || d == 256 || d == 512 || d == 1024)))
+        return refuse(f, "vh_head_greedy: B <= 64 rows and d_model in {128, 256, 512, 1024} (B=%d d=%d); use vh_linear + vh_greedy_step", B, d);
+    skinny(f, HEAD_GREEDY, 1, 8, d % 512 == 0 ? 4 : d / 128, 0, 1, 0);
+    f.gx = (V + 15) / 16;
+    if (B > 16) {
+        f.rg_rows = row_group_rows(f.gx, B, true);
+        f.gz = (B + f.rg_rows - 1) / f.rg_rows;
+    }
+    return VH_OK;
+}
+
 extern "C" int vh_head_greedy(const float* x, int ldx, const float* proj_w, float* logits, int ldl, int V, int eos,
                               int64_t* codes, int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base,
                               const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len, float* x_next,
@@ -1805,9 +1854,9 @@ extern "C" int vh_head_greedy(const float* x, int ldx, const float* proj_w, floa
                VH_EINVAL, "vh_head_greedy: null pointer");
     VH_REQUIRE(B > 0 && V > 0 && ldl >= V && ldx >= d && ldx % 4 == 0, VH_EINVAL,
                "vh_head_greedy: bad dims B=%d V=%d ldl=%d d=%d ldx=%d", B, V, ldl, d, ldx);
-    VH_REQUIRE(B <= 64 && (d == 128 || d == 256 || d == 512 || d == 1024), VH_EUNSUPPORTED,
-               "vh_head_greedy: B <= 64 rows and d_model in {128, 256, 512, 1024} (B=%d d=%d); use vh_linear + vh_greedy_step",
-               B, d);
+    GemmForm f;
+    const int shape_rc = head_plan(B, V, d, f);
+    VH_REQUIRE(shape_rc == VH_OK, shape_rc, "%s", f.msg);
     VH_REQUIRE(vh_aligned16(x) && vh_aligned16(proj_w) && vh_aligned16(audio_emb) && vh_aligned16(pe) && vh_aligned16(x_next) &&
                    vh_aligned16(workspace),
                VH_EALIGN, "vh_head_greedy: x/proj_w/audio_emb/pe/x_next and the workspace must be 16-byte aligned");
@@ -1815,19 +1864,18 @@ extern "C" int vh_head_greedy(const float* x, int ldx, const float* proj_w, floa
                workspace_bytes, vh_head_greedy_ws_bytes(B, V));
     GemmArgs a{};
     a.A = x; a.lda = ldx; a.W = proj_w; a.out = logits; a.ldo = ldl; a.M = B; a.N = V; a.K = d; a.act = VH_ACT_NONE; a.k_len = d;
-    dim3 grid((V + 15) / 16);
-    if (B > 16) {                          // row groups as launch_gemm chooses them: 8 rows while the grid stays within the CUs
-        a.rg_rows = ((int)grid.x * ((B + 7) / 8) <= 256) ? 8 : 16;
-        grid.z = (B + a.rg_rows - 1) / a.rg_rows;
-    }
+    a.rg_rows = f.rg_rows;
+    const dim3 grid(f.gx, f.gy, f.gz);
+    if (t_form_query) *t_form_query = f;
+    if (t_form_query) return VH_OK;
     HeadStep hs{};
     hs.counters = (int*)workspace;
     hs.cand = (uint64_t*)((char*)workspace + HEAD_WS_COUNTERS * sizeof(int));
     hs.V = V; hs.eos = eos; hs.codes = codes; hs.codes_stride = codes_stride; hs.eos_count = eos_count; hs.pos_base = pos_base;
     hs.audio_emb = audio_emb; hs.pe = pe; hs.audio_pos = audio_pos; hs.cache_len = cache_len; hs.x_next = x_next; hs.d = d;
     hipStream_t s = (hipStream_t)stream;
-    if (d % 512 == 0) hipLaunchKernelGGL(gemm_head_greedy_kernel<4>, grid, dim3(512), 0, s, SKINNY_ARGS(a), a, hs);
-    else if (d == 256) hipLaunchKernelGGL(gemm_head_greedy_kernel<2>, grid, dim3(512), 0, s, SKINNY_ARGS(a), a, hs);
+    if (f.pw == 4) hipLaunchKernelGGL(gemm_head_greedy_kernel<4>, grid, dim3(512), 0, s, SKINNY_ARGS(a), a, hs);
+    else if (f.pw == 2) hipLaunchKernelGGL(gemm_head_greedy_kernel<2>, grid, dim3(512), 0, s, SKINNY_ARGS(a), a, hs);
     else hipLaunchKernelGGL(gemm_head_greedy_kernel<1>, grid, dim3(512), 0, s, SKINNY_ARGS(a), a, hs);
     VH_CHECK_LAUNCH("vh_head_greedy");
     return VH_OK;
@@ -1941,11 +1989,15 @@ int vh_internal_linear_w16(const float* A, int lda, const uint16_t* W16, const f
     a.A = A; a.lda = lda; a.W = reinterpret_cast<const float*>(W16); a.bias = bias; a.res = residual; a.ldr = ldr; a.out = out;
     a.ldo = ldo; a.M = M; a.N = N; a.K = K; a.act = VH_ACT_NONE; a.k_len = K; a.w16 = 1;
     LnFuse ln{};
-    VH_REQUIRE(M <= 64 && K % 128 == 0 && K <= 1024 && ldo >= N && (!residual || ldr >= N), VH_EUNSUPPORTED,
-               "vh_linear (16-bit weights): M=%d K=%d (decode rows, K a multiple of 128 up to 1024)", M, K);
+    GemmForm f;                            // the shape gate is the plan's, and it comes before the pointer checks
+    const int shape_rc = gemm_plan("vh_linear_w16", GemmShape{EPI_PLAIN, M, N, K, K, 0, LN_NONE, 1, 0}, current_knobs(), f);
+    if (shape_rc || ldo < N || (residual && ldr < N)) {
+        vh_set_error("vh_linear (16-bit weights): M=%d K=%d (decode rows, K a multiple of 128 up to 1024)", M, K);
+        return VH_EUNSUPPORTED;
+    }
     VH_REQUIRE(((uintptr_t)W16 & 7u) == 0, VH_EALIGN, "vh_linear (16-bit weights): W must be 8-byte aligned");
     if (int rc = check_gemm("vh_linear_w16", a, ln)) return rc;
-    return launch_gemm<EPI_PLAIN>("vh_linear_w16", a, ln, (hipStream_t)stream);
+    return launch_form<EPI_PLAIN>("vh_linear_w16", f, a, ln, (hipStream_t)stream, nullptr, 0);
 }
 
 int vh_internal_linear_qkv_folded_kv16_w16(const float* A, int lda, const uint16_t* Wf16, const float* c1, const float* c2,
@@ -1997,13 +2049,10 @@ extern "C" int vh_linear_ws(const float* A, int lda, const float* W, const float
                    (!residual || ldr % 4 == 0),
                VH_EALIGN, "vh_linear_ws: out/bias/residual alignment");
     hipStream_t s = (hipStream_t)stream;
-    if (M > 64) {                                 // tile kernel, K slices in gridDim.y
-        const int tm = (M + TM - 1) / TM, tn = (N + TN - 1) / TN;
-        if (part.k_len % TK == 0 && vh_tuning(VH_TUNE_TILE_DMA) != 1)
-            hipLaunchKernelGGL((gemm_tile_dma_kernel<EPI_PARTIAL>), dim3(tm * tn, splits), dim3(256), 0, s, part, tm, tn,
-                               TailSplit{tm * tn, 1, part.k_len, nullptr});
-        else
-            hipLaunchKernelGGL((gemm_tile_kernel<EPI_PARTIAL>), dim3(tm * tn, splits), dim3(256), 0, s, part, tm, tn);
+    // the slices: a tile kernel (M > 64) or gemm_skinny_fast<MT, 4, EPI_PARTIAL, 4, 0, 1>, K slices in gridDim.y
+    if (int rc = launch_gemm<EPI_PARTIAL>("vh_linear_ws", part, none, s)) return rc;
+    if (t_form_query) return VH_OK;
+    if (M > 64) {
         const int items_t = M * (lds_ / 4);
         const int rbt = 256;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((items_t + rbt - 1) / rbt), dim3(rbt), 0, s,
@@ -2011,18 +2060,77 @@ extern "C" int vh_linear_ws(const float* A, int lda, const float* W, const float
         VH_CHECK_LAUNCH("vh_linear_ws");
         return VH_OK;
     }
-    dim3 grid((N + 15) / 16, splits);
-    const int mt = (M + 15) / 16;
-    // each slice: 4 waves x 4 k-steps of 16 = 256 k per pass
-    if (mt == 1) hipLaunchKernelGGL((gemm_skinny_fast<1, 4, EPI_PARTIAL, 4, 0, 1>), grid, dim3(256), 0, s, SKINNY_ARGS(part), part, none);
-    else if (mt == 2) hipLaunchKernelGGL((gemm_skinny_fast<2, 4, EPI_PARTIAL, 4, 0, 1>), grid, dim3(256), 0, s, SKINNY_ARGS(part), part, none);
-    else hipLaunchKernelGGL((gemm_skinny_fast<4, 4, EPI_PARTIAL, 4, 0, 1>), grid, dim3(256), 0, s, SKINNY_ARGS(part), part, none);
     const int items = M * (lds_ / 4);
     // small workgroups: the slabs (splits x 64 KB) are pulled through as many CUs as possible
     const int rb = vh_tuning(VH_TUNE_REDUCE_BLOCK) > 0 ? vh_tuning(VH_TUNE_REDUCE_BLOCK) : 128;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((items + rb - 1) / rb), dim3(rb), 0, s,
                        (const float*)slabs, splits, fin, lds_);
     VH_CHECK_LAUNCH("vh_linear_ws");
+    return VH_OK;
+}
+
+// ---- which form a shape takes: the entry point itself runs, on operands that are never touched, up to its launch ----
+static void form_info(vh_linear_form_info* out, const GemmForm& f) {
+    *out = vh_linear_form_info{f.family, f.mt, f.nw, f.epi, f.pw, f.ln, f.nj, f.w16, {f.gx, f.gy, f.gz}, f.block, f.rg_rows, 1u << f.epi};
+}
+
+extern "C" int vh_linear_form(int entry, int M, int N, int K, int T, int ln_kind, int w16, vh_linear_form_info* out) {
+    VH_REQUIRE(out, VH_EINVAL, "vh_linear_form: null pointer");
+    *out = vh_linear_form_info{};
+    const bool qkv = entry == VH_ENTRY_QKV || entry == VH_ENTRY_QKV_HD || entry == VH_ENTRY_QKV_KV16;
+    VH_REQUIRE(entry >= VH_ENTRY_LINEAR && entry <= VH_ENTRY_HEAD_GREEDY && ln_kind >= VH_LN_NONE && ln_kind <= VH_LN_FOLDED, VH_EINVAL,
+               "vh_linear_form: entry=%d ln_kind=%d", entry, ln_kind);
+    VH_REQUIRE(!qkv || (T > 0 && M >= 0 && M % T == 0 && N == 3 * K), VH_EINVAL,
+               "vh_linear_form: a QKV entry takes M = B*T rows and N = 3 K (M=%d T=%d N=%d K=%d)", M, T, N, K);
+    VH_REQUIRE((entry != VH_ENTRY_QKV_KV16 || (ln_kind == VH_LN_FOLDED && T == 1)) &&
+                   ((entry != VH_ENTRY_LINEAR_WS && entry != VH_ENTRY_HEAD_GREEDY) || ln_kind == VH_LN_NONE),
+               VH_EINVAL, "vh_linear_form: entry %d has no LayerNorm kind %d at T=%d", entry, ln_kind, T);
+    VH_REQUIRE(!w16 || (entry == VH_ENTRY_LINEAR && ln_kind == VH_LN_NONE) || entry == VH_ENTRY_QKV_KV16, VH_EINVAL,
+               "vh_linear_form: entry %d has no 16-bit-weight form with LayerNorm kind %d", entry, ln_kind);
+    alignas(16) static float operand[4];          // every pointer argument: non-null, 16-byte aligned, never dereferenced
+    float* const P = operand;
+    uint16_t* const H = reinterpret_cast<uint16_t*>(operand);
+    int32_t* const I = reinterpret_cast<int32_t*>(operand);
+    const float* const g = ln_kind == VH_LN_GAMMA ? P : nullptr;
+    const int B = qkv ? M / T : M, ldn = (N + 3) / 4 * 4, ldk = (K + 3) / 4 * 4;
+    GemmForm f;
+    form_reset(f, 0);
+    t_form_query = &f;
+    int rc;
+    switch (entry) {
+    case VH_ENTRY_LINEAR:
+        rc = w16 ? vh_internal_linear_w16(P, ldk, H, nullptr, nullptr, 0, P, ldn, M, N, K, nullptr)
+             : ln_kind == VH_LN_FOLDED ? vh_linear_folded(P, ldk, P, P, P, nullptr, 0, P, ldn, M, N, K, VH_ACT_NONE, 1e-5f, nullptr)
+                                       : vh_linear(P, ldk, P, nullptr, nullptr, 0, P, ldn, M, N, K, VH_ACT_NONE, g, g, nullptr, nullptr, 1e-5f, nullptr);
+        break;
+    case VH_ENTRY_QKV:
+        rc = ln_kind == VH_LN_FOLDED ? vh_linear_qkv_folded(P, ldk, P, P, P, P, K, P, P, I, B, T, K, K / VH_HEAD_DIM, T, 1e-5f, nullptr)
+                                     : vh_linear_qkv(P, ldk, P, P, K, P, P, I, B, T, K, K / VH_HEAD_DIM, T, g, g, nullptr, nullptr, 1e-5f, nullptr);
+        break;
+    case VH_ENTRY_QKV_HD:                          // head width 4: every d_model the entry can take has such a split
+        rc = ln_kind == VH_LN_FOLDED ? vh_linear_qkv_folded_hd(P, ldk, P, P, P, P, K, P, P, I, B, T, K, K / 4, 1, 1e-5f, 4, nullptr)
+                                     : vh_linear_qkv_hd(P, ldk, P, P, K, P, P, I, B, T, K, K / 4, 1, g, g, nullptr, nullptr, 1e-5f, 4, nullptr);
+        break;
+    case VH_ENTRY_QKV_KV16:
+        rc = w16 ? vh_internal_linear_qkv_folded_kv16_w16(P, ldk, H, P, P, P, K, H, H, I, B, K, K / VH_HEAD_DIM, 1, 1e-5f, nullptr)
+                 : vh_linear_qkv_folded_kv16(P, ldk, P, P, P, P, K, H, H, I, B, K, K / VH_HEAD_DIM, 1, 1e-5f, nullptr);
+        break;
+    case VH_ENTRY_LINEAR_WS:
+        rc = vh_linear_ws(P, ldk, P, nullptr, nullptr, 0, P, ldn, M, N, K, VH_ACT_NONE, P, SIZE_MAX, nullptr);
+        break;
+    default:
+        rc = vh_head_greedy(P, ldk, P, P, ldn, N, 0, reinterpret_cast<int64_t*>(operand), 1, I, I, P, P, I, I, P, M, K, P, SIZE_MAX, nullptr);
+        break;
+    }
+    t_form_query = nullptr;
+    if (rc == VH_OK) form_info(out, f);
+    return rc;
+}
+
+extern "C" int vh_linear_form_row(int i, vh_linear_form_info* out) {
+    VH_REQUIRE(out && i >= 0 && i < FORM_ROWS, VH_EINVAL, "vh_linear_form_row: row %d of %d", i, FORM_ROWS);
+    const FormRow& r = FORM_TABLE[i];
+    *out = vh_linear_form_info{r.family, r.mt, r.nw, -1, r.pw, r.ln, r.nj, r.w16, {0, 0, 0}, (unsigned)r.nw * 64, 0, r.epis};
     return VH_OK;
 }
 

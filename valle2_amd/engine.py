@@ -140,9 +140,19 @@ def ffn_fused_width(d: int) -> bool:
 
 
 def folded_width(d: int) -> bool:
-    """K of the folded-LayerNorm decode GEMMs (gemm.hip check_folded): the four narrow shapes, 640 / 768 / 896, or 256 PW passes with PW in 5..8 and one or
-    two passes — a multiple of 256 from 1280 to 2048, of 512 from 2560 to 4096 (16 waves, statistics from the operand fragments)."""
-    return d in (128, 256, 512, 1024) or d in BASE_FOLD_WIDTHS or (1024 < d <= MAX_DECODE_D_MODEL and d % (256 if d <= 2048 else 512) == 0)
+    """K of the folded-LayerNorm decode GEMMs, as the library's dispatch plan has them (gemm.hip gemm_plan): the four narrow shapes, 640 / 768 / 896, or 256 PW
+    passes with PW in 5..8 and one or two passes — a multiple of 256 from 1280 to 2048, of 512 from 2560 to 4096."""
+    return _lib.linear_form(_lib.ENTRY_LINEAR, 1, 16, d, ln_kind=_lib.LN_FOLDED) is not None
+
+
+def head_fused_shape(batch: int, V: int, d: int) -> bool:
+    """Rows and d_model vh_head_greedy (head + greedy step in one launch) has a kernel for."""
+    return _lib.linear_form(_lib.ENTRY_HEAD_GREEDY, batch, V, d) is not None
+
+
+def w16_width(d: int) -> bool:
+    """d_model at which the decode step's QKV product has a 16-bit-weight form (vh_linear_qkv_folded_kv16 with h16 weights)."""
+    return _lib.linear_form(_lib.ENTRY_QKV_KV16, 1, 3 * d, d, ln_kind=_lib.LN_FOLDED, w16=True) is not None
 
 
 def folded_layer_norms(transformer):
@@ -816,12 +826,12 @@ class ArDecoder(StepSampler):
         self.ffn_ws = torch.empty(ffn_bytes // 4, **f32) if ffn_bytes else None
         # opt-in (VALLE2_HEAD_FUSED=1): head + greedy step as one launch (vh_head_greedy; DESIGN.md 3.20 has the A/B)
         self.head_ws = None
-        if os.environ.get('VALLE2_HEAD_FUSED') == '1' and self.sampling[0] == 1 and row_sampling is None and batch <= 64 and d in (128, 256, 512, 1024):
+        if os.environ.get('VALLE2_HEAD_FUSED') == '1' and self.sampling[0] == 1 and row_sampling is None and head_fused_shape(batch, V, d):
             self.head_ws = kernels.head_greedy_ws(batch, V, dev)
         self._table = layer_table(model.transformer, cache, self._folded)
         # perf mode, second half: the step's four matrices (and the head) as h16 — half the weight bytes per launch
         self._w16 = self._proj16 = None
-        if self.kv_bf16 and DECODE_W16 and self.ffn_ws is not None and d in (128, 256, 512, 1024) and cfg.dim_feedforward % 16 == 0:
+        if self.kv_bf16 and DECODE_W16 and self.ffn_ws is not None and w16_width(d) and cfg.dim_feedforward % 16 == 0:
             self._w16 = decode_weights16(model.transformer, self._folded)
             for i, (wq, wo, w1, w2, c1q, c1w) in enumerate(self._w16):
                 self._table[i].wqkv_f16, self._table[i].wo16 = ptr(wq), ptr(wo)
