@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 138            /* 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 139            /* 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -466,6 +466,42 @@ int vh_attn_decode_shared_kv16(const float* q, int ldq, const uint16_t* kprefix1
                                int prefix_S, const uint16_t* ksuffix16, const uint16_t* vsuffix16, float* out, int ldo,
                                const int32_t* suffix_len, int len_bias, int B, int n_heads, int S_suf, int n_split_suffix,
                                void* partial, size_t partial_bytes, void* stream);
+
+/* ---- which kernels a decode-attention call launches (ABI 139; read-only, launches nothing, touches no GPU state) ------
+ * vh_attn_decode_form runs the named entry point's own argument check and its dispatch plan, with the current vh_set_tuning
+ * knobs, as for a call with valid 16-byte-aligned pointers, ldq = ldo = n_heads * head_dim and len_bias = 1, and returns
+ * what that entry point would return: VH_OK and the form in *out, or the entry's refusal code with vh_last_error() set to
+ * the entry's own message (*out is zeroed).
+ *   entry: VH_ATTN_ENTRY_* names one of the seven vh_attn_decode* functions; head_dim is read by VH_ATTN_ENTRY_HD only (the
+ *   others are width 64); prefix is prefix_len (SHARED, SHARED_KV16) or prefix_cap (SHARED_GROUPS) and prefix_S the rows of the
+ *   prefix cache; beams is read by SHARED_GROUPS only; S_max is the capacity of the rows' own cache (S_suf of the shared
+ *   forms); ws_bytes is the partial_bytes argument (VH_ATTN_ENTRY_DECODE, whose signature has none, ignores it).
+ * out: the kernel (VH_ATTN_K_*) with its template arguments (nw waves and d register sets of the width-64 kernels; lk lanes
+ * per key and nv slots per lane of the hd kernel; 0 where the kernel has none), grid and block; whether the split records
+ * are combined inside the launch and the byte offset of its ticket words in the workspace; the second launch (VH_ATTN_2ND_*)
+ * with grid and block; records per (row, head), floats per record and the workspace bytes the form needs.
+ * vh_attn_decode_form_row(i, out) lists the compiled first kernels, i = 0, 1, ...: kernel, nw, d, lk, nv (the rest zero);
+ * VH_EINVAL past the last row.  Every form vh_attn_decode_form returns is one of these rows. */
+enum { VH_ATTN_ENTRY_DECODE = 0, VH_ATTN_ENTRY_KV16 = 1, VH_ATTN_ENTRY_KV16_SPLIT = 2, VH_ATTN_ENTRY_SHARED = 3,
+       VH_ATTN_ENTRY_SHARED_GROUPS = 4, VH_ATTN_ENTRY_SHARED_KV16 = 5, VH_ATTN_ENTRY_HD = 6 };
+enum { VH_ATTN_K_NONE = 0, VH_ATTN_K_BURST = 1, VH_ATTN_K_RING = 2, VH_ATTN_K_RING16 = 3, VH_ATTN_K_RING16_SPLIT = 4,
+       VH_ATTN_K_HD = 5, VH_ATTN_K_SHARED = 6, VH_ATTN_K_SHARED_GROUPS = 7, VH_ATTN_K_SHARED16 = 8 };
+enum { VH_ATTN_2ND_NONE = 0, VH_ATTN_2ND_COMBINE = 1, VH_ATTN_2ND_HD_COMBINE = 2, VH_ATTN_2ND_MERGE = 3,
+       VH_ATTN_2ND_MERGE_GROUPS = 4 };
+typedef struct vh_attn_decode_form_info {
+    int kernel;                   /* VH_ATTN_K_* */
+    int nw, d, lk, nv;
+    unsigned grid[3], block;
+    int fused_combine;            /* the last workgroup of a (row, head) to arrive adds the split records */
+    size_t ticket_offset;         /* fused_combine: where the ticket words start in the workspace */
+    int second;                   /* VH_ATTN_2ND_* */
+    unsigned second_grid, second_block;
+    int records, record_floats;   /* per (row, head); 0 records: no workspace */
+    size_t ws_bytes;
+} vh_attn_decode_form_info;
+int vh_attn_decode_form(int entry, int B, int n_heads, int head_dim, int S_max, int n_split, int prefix, int prefix_S,
+                        int beams, size_t ws_bytes, vh_attn_decode_form_info* out);
+int vh_attn_decode_form_row(int i, vh_attn_decode_form_info* out);
 
 /* ---- K12/K13: greedy sampling + decode-state update + next-token embedding ------------------
  * replaces topk_sampling(top_k=1) (valle/models/utils.py:46-68: argmax, lowest index on ties),

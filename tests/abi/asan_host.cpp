@@ -162,6 +162,34 @@ int main() {
     REFUSED(vh_kv_to_bf16(nullptr, W16, 1, 1, 4, 4, S));
     REFUSED(vh_kv_to_bf16(P, W16, 1, 8, 4, 4, S));                                                 // rows > S
     REFUSED(vh_attn_decode_kv16(nullptr, 128, P16, P16, P, 128, I32, 1, 1, 2, 8, S));
+    // ---- which kernels a decode-attention call launches: the entry points' own check and plan, nothing launched ---------
+    vh_attn_decode_form_info ai;
+    REFUSED(vh_attn_decode_form(VH_ATTN_ENTRY_DECODE, 4, 8, 64, 64, 1, 0, 0, 1, 0, nullptr));
+    REFUSED(vh_attn_decode_form(-1, 4, 8, 64, 64, 1, 0, 0, 1, 0, &ai));
+    REFUSED(vh_attn_decode_form(VH_ATTN_ENTRY_HD + 1, 4, 8, 64, 64, 1, 0, 0, 1, 0, &ai));
+    EXPECT(vh_attn_decode_form(VH_ATTN_ENTRY_DECODE, 32, 8, 64, 64, 4, 0, 0, 1, 0, &ai) == VH_OK && ai.kernel == VH_ATTN_K_BURST && ai.nw == 4 &&
+               ai.grid[0] == 4 && ai.grid[1] == 256 && ai.block == 256 && ai.second == VH_ATTN_2ND_COMBINE && ai.second_grid == 256 &&
+               ai.ws_bytes == vh_attn_decode_ws_bytes(32, 8, 4),
+           "32 x 8 x 4 = 1024 workgroups: four waves, second launch");
+    for (int entry = VH_ATTN_ENTRY_DECODE; entry <= VH_ATTN_ENTRY_HD; ++entry)
+        for (int B : {0, 1, 4, 33, 64, 65})
+            for (int h : {0, 1, 8, 16})
+                for (int ns : {0, 1, 2, 8, 16, 17, 64, 65})
+                    for (int prefix : {0, 1, 100, 7681, 8192})
+                        for (int hd : {12, 16, 64, 132, 256, 260})
+                            for (size_t bytes : {(size_t)0, (size_t)1 << 40}) {
+                                const int rc = vh_attn_decode_form(entry, B, h, hd, 64, ns, prefix, 8192, B % 4 ? 1 : 4, bytes, &ai);
+                                EXPECT(rc == VH_OK ? ai.kernel != VH_ATTN_K_NONE && ai.block > 0 && ai.grid[0] > 0 && (entry == VH_ATTN_ENTRY_DECODE || ai.ws_bytes <= bytes)
+                                                   : vh_last_error()[0] != 0 && ai.kernel == VH_ATTN_K_NONE, "form or reason");
+                            }
+    int n_kernels = 0;
+    while (vh_attn_decode_form_row(n_kernels, &ai) == VH_OK) {
+        EXPECT(ai.kernel != VH_ATTN_K_NONE && ai.block == 0, "kernel row");
+        ++n_kernels;
+    }
+    EXPECT(n_kernels > 0, "compiled kernels listed");
+    REFUSED(vh_attn_decode_form_row(-1, &ai));
+    REFUSED(vh_attn_decode_form_row(0, nullptr));
     // ---- sampling --------------------------------------------------------------------------------------------------
     REFUSED(vh_greedy_step(nullptr, 8, 8, 7, I64, 4, I32, nullptr, P, P, I32, I32, P, 1, 64, S));
     REFUSED(vh_greedy_step(P, 4, 8, 7, I64, 4, I32, nullptr, P, P, I32, I32, P, 1, 64, S));       // ldl < V

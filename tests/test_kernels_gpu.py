@@ -576,9 +576,30 @@ def test_attn_rows_peaked_softmax(K):
     close(out, ref, atol=1e-4, rtol=1e-4)
 
 
+# (the last three: B h n_split = 1024 workgroups, where the four-wave burst kernel takes over — unsplit, two splits combined
+# inside the launch, four splits combined by the second launch)
 @pytest.mark.parametrize('B,h,S,n_split', [(4, 2, 37, 1), (32, 8, 300, 1), (2, 2, 1000, 4),
-                                           (3, 16, 65, 2), (1, 1, 1, 1), (2, 2, 31, 3)])
+                                           (3, 16, 65, 2), (1, 1, 1, 1), (2, 2, 31, 3),
+                                           (64, 16, 70, 1), (64, 8, 70, 2), (32, 8, 70, 4)])
 def test_attn_decode(K, B, h, S, n_split):
+    _attn_decode_case(K, B, h, S, n_split)
+
+
+@pytest.mark.parametrize('waves', [4, 8, 16])
+def test_attn_decode_waves_knob(K, waves):
+    """VH_TUNE_DECODE_WAVES picks the burst kernel's waves per workgroup (eight waves are launched by the knob alone)."""
+    from valle2_amd import _lib
+    lib = _lib.lib()
+    lib.vh_set_tuning(1, waves)
+    try:
+        _attn_decode_case(K, 4, 2, 37, 1)
+        _attn_decode_case(K, 3, 16, 65, 2)
+        _attn_decode_case(K, 2, 2, 300, 4)
+    finally:
+        lib.vh_set_tuning(1, 0)
+
+
+def _attn_decode_case(K, B, h, S, n_split):
     d = 64 * h
     S_max = S + 40
     q = torch.randn(B, d, generator=g(50))

@@ -104,6 +104,18 @@ class VhLinearFormInfo(C.Structure):
 LN_NONE, LN_GAMMA, LN_FOLDED = 0, 1, 2                                                        # VH_LN_*
 ENTRY_LINEAR, ENTRY_QKV, ENTRY_QKV_HD, ENTRY_QKV_KV16, ENTRY_LINEAR_WS, ENTRY_HEAD_GREEDY = range(6)   # VH_ENTRY_*
 
+
+class VhAttnDecodeFormInfo(C.Structure):
+    """include/valle_hip.h vh_attn_decode_form_info: the kernels a decode-attention call launches and the workspace it needs."""
+    _fields_ = [('kernel', C.c_int), ('nw', C.c_int), ('d', C.c_int), ('lk', C.c_int), ('nv', C.c_int), ('grid', C.c_uint * 3),
+                ('block', C.c_uint), ('fused_combine', C.c_int), ('ticket_offset', C.c_size_t), ('second', C.c_int),
+                ('second_grid', C.c_uint), ('second_block', C.c_uint), ('records', C.c_int), ('record_floats', C.c_int),
+                ('ws_bytes', C.c_size_t)]
+
+
+(ATTN_ENTRY_DECODE, ATTN_ENTRY_KV16, ATTN_ENTRY_KV16_SPLIT, ATTN_ENTRY_SHARED, ATTN_ENTRY_SHARED_GROUPS, ATTN_ENTRY_SHARED_KV16,
+ ATTN_ENTRY_HD) = range(7)                                                                    # VH_ATTN_ENTRY_*
+
 # name → (restype, argtypes); must list every symbol include/valle_hip.h declares
 SIGNATURES = {
     'vh_version': (C.c_int, []),
@@ -255,6 +267,9 @@ SIGNATURES = {
     # which compiled form a decode GEMM takes (ABI 138)
     'vh_linear_form': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(VhLinearFormInfo)]),
     'vh_linear_form_row': (C.c_int, [C.c_int, C.POINTER(VhLinearFormInfo)]),
+    # which kernels a decode-attention call launches (ABI 139)
+    'vh_attn_decode_form': (C.c_int, [C.c_int] * 9 + [C.c_size_t, C.POINTER(VhAttnDecodeFormInfo)]),
+    'vh_attn_decode_form_row': (C.c_int, [C.c_int, C.POINTER(VhAttnDecodeFormInfo)]),
     'vh_h16_format': (C.c_int, []),
     'vh_to_bf16': (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     'vh_layernorm_bf16': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_float,
@@ -306,6 +321,18 @@ def linear_form(entry, M, N, K, T=1, ln_kind=LN_NONE, w16=False):
         _host_lib = load_library()
     info = VhLinearFormInfo()
     return info if _host_lib.vh_linear_form(entry, M, N, K, T, ln_kind, int(w16), C.byref(info)) == 0 else None
+
+
+def attn_decode_form(entry, B, n_heads, n_split, *, head_dim=64, S_max=1, prefix=0, prefix_S=None, beams=1, ws_bytes=2 ** 62):
+    """vh_attn_decode_form: the kernels the library's decode-attention `entry` launches for the shape, or None where it refuses
+    it (vh_last_error says why).  The workspace is taken as large enough unless ws_bytes says otherwise.  Needs no GPU."""
+    global _host_lib
+    if _host_lib is None:
+        _host_lib = load_library()
+    info = VhAttnDecodeFormInfo()
+    rc = _host_lib.vh_attn_decode_form(entry, B, n_heads, head_dim, S_max, n_split, prefix, prefix if prefix_S is None else prefix_S,
+                                       beams, ws_bytes, C.byref(info))
+    return info if rc == 0 else None
 
 
 _host_lib = None

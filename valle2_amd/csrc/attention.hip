@@ -467,137 +467,14 @@ extern "C" int vh_kv_to_bf16(const float* src, uint16_t* dst, int n_streams, int
     return VH_OK;
 }
 
-static thread_local hipEvent_t g_attn_ev[2] = {nullptr, nullptr};
-void vh_internal_attn_decode_events(hipEvent_t start, hipEvent_t stop) { g_attn_ev[0] = start; g_attn_ev[1] = stop; }
-
-static void launch_ring16(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, float* out, int ldo,
-                          const int32_t* cache_len, int len_bias, int B, int n_heads, int S_max, void* stream) {
-#define AD16(NW, D)                                                                                                  \
-    hipExtLaunchKernelGGL((attn_decode_ring16_kernel<NW, D>), dim3(1, B * n_heads), dim3(NW * 64), 0, (hipStream_t)stream, \
-                          g_attn_ev[0], g_attn_ev[1], 0, q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, n_heads, \
-                          S_max)
-    // ring shape (waves x register sets of 32 keys): 8 x 2 as the fp32 kernel; 16 x 1, 16 x 2, 8 x 3, 8 x 4 and 4 x 4
-    // measured within 3 % of it (461-477 us per decode step, profiles/r3_ab_decode_perf_mode.log)
-    AD16(8, 2);
-#undef AD16
-}
-
-extern "C" int vh_attn_decode_kv16(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16,
-                                   float* out, int ldo, const int32_t* cache_len, int len_bias, int B, int n_heads,
-                                   int S_max, void* stream) {
-    VH_REQUIRE(q && kcache16 && vcache16 && out && cache_len, VH_EINVAL, "vh_attn_decode_kv16: null pointer");
-    VH_REQUIRE(B > 0 && n_heads > 0 && S_max > 0 && (len_bias == 0 || len_bias == 1), VH_EINVAL,
-               "vh_attn_decode_kv16: bad dims B=%d h=%d S_max=%d len_bias=%d", B, n_heads, S_max, len_bias);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL, "vh_attn_decode_kv16: ldq=%d ldo=%d",
-               ldq, ldo);
-    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kcache16) && vh_aligned16(vcache16), VH_EALIGN,
-               "vh_attn_decode_kv16: pointers must be 16-byte aligned");
-    launch_ring16(q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, B, n_heads, S_max, stream);
-    VH_CHECK_LAUNCH("vh_attn_decode_kv16");
-    return VH_OK;
-}
-
-extern "C" size_t vh_attn_decode_ws_bytes(int B, int n_heads, int n_split);
-
-extern "C" int vh_attn_decode_kv16_split(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16,
-                                         float* out, int ldo, const int32_t* cache_len, int len_bias, int B, int n_heads,
-                                         int S_max, int n_split, void* partial, size_t partial_bytes, void* stream) {
-    VH_REQUIRE(q && kcache16 && vcache16 && out && cache_len, VH_EINVAL, "vh_attn_decode_kv16_split: null pointer");
-    VH_REQUIRE(B > 0 && n_heads > 0 && S_max > 0 && (len_bias == 0 || len_bias == 1), VH_EINVAL,
-               "vh_attn_decode_kv16_split: bad dims B=%d h=%d S_max=%d len_bias=%d", B, n_heads, S_max, len_bias);
-    VH_REQUIRE(n_split >= 1 && n_split <= 16, VH_EINVAL, "vh_attn_decode_kv16_split: n_split=%d (1..16)", n_split);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL,
-               "vh_attn_decode_kv16_split: ldq=%d ldo=%d", ldq, ldo);
-    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kcache16) && vh_aligned16(vcache16) && vh_aligned16(partial), VH_EALIGN,
-               "vh_attn_decode_kv16_split: pointers must be 16-byte aligned");
-    if (n_split == 1) {                                   // the launch of vh_attn_decode_kv16, bit for bit
-        launch_ring16(q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, B, n_heads, S_max, stream);
-        VH_CHECK_LAUNCH("vh_attn_decode_kv16_split");
-        return VH_OK;
-    }
-    VH_REQUIRE(partial && partial_bytes >= vh_attn_decode_ws_bytes(B, n_heads, n_split), VH_EINVAL,
-               "vh_attn_decode_kv16_split: n_split=%d needs a workspace of %zu bytes (got %zu)", n_split,
-               vh_attn_decode_ws_bytes(B, n_heads, n_split), partial ? partial_bytes : (size_t)0);
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(n_split, B * n_heads);
-    // few workgroups -> 8 waves each (the ring16 shape: a (row, head, split) may own a CU); many -> 4 waves, several per CU.
-    // The threshold is the fp32 launch's rule (vh_attn_decode: `big`), taken over as it stands: NOT measured for the 16-bit stream.
-#define AD16S(NW)                                                                                                       \
-    hipExtLaunchKernelGGL((attn_decode_ring16_split_kernel<NW, 2>), grid, dim3(NW * 64), 0, s, g_attn_ev[0], g_attn_ev[1], 0, q, \
-                          ldq, kcache16, vcache16, cache_len, len_bias, n_heads, S_max, n_split, (float*)partial)
-    if ((int64_t)B * n_heads * n_split < 1024) AD16S(8); else AD16S(4);
-#undef AD16S
-    // records added in split order by the combine launch of the fp32 form: deterministic
-    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * n_heads), dim3(64), 0, s, (const float*)partial, out, ldo, n_heads,
-                       n_split);
-    VH_CHECK_LAUNCH("vh_attn_decode_kv16_split");
-    return VH_OK;
-}
-
-// workspace of a key-split launch: [B h][n_split] partial records, then B h ticket words (one per (b, head), padded to 16 B)
-static size_t decode_records_bytes(int B, int n_heads, int n_split) {
-    return (size_t)B * n_heads * n_split * PART_LD * sizeof(float);
-}
-extern "C" size_t vh_attn_decode_ws_bytes(int B, int n_heads, int n_split) {
-    if (n_split <= 1) return 0;
-    return decode_records_bytes(B, n_heads, n_split) + ((size_t)B * n_heads * sizeof(unsigned) + 15) / 16 * 16;
-}
-
-
-extern "C" int vh_attn_decode(const float* q, int ldq, const float* kcache, const float* vcache,
-                              float* out, int ldo, const int32_t* cache_len, int len_bias, int B,
-                              int n_heads, int S_max, int n_split, void* partial, void* stream) {
-    VH_REQUIRE(q && kcache && vcache && out && cache_len, VH_EINVAL, "vh_attn_decode: null pointer");
-    VH_REQUIRE(B > 0 && n_heads > 0 && S_max > 0 && n_split >= 1 && n_split <= 64, VH_EINVAL,
-               "vh_attn_decode: bad dims B=%d h=%d S_max=%d n_split=%d", B, n_heads, S_max, n_split);
-    VH_REQUIRE(len_bias == 0 || len_bias == 1, VH_EINVAL, "vh_attn_decode: len_bias=%d", len_bias);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL,
-               "vh_attn_decode: ldq=%d ldo=%d", ldq, ldo);
-    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kcache) && vh_aligned16(vcache), VH_EALIGN,
-               "vh_attn_decode: pointers must be 16-byte aligned");
-    VH_REQUIRE(n_split == 1 || partial, VH_EINVAL, "vh_attn_decode: n_split>1 needs a workspace");
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(n_split, B * n_heads);
-    // few workgroups → 16 waves each (one (b,head) can own a whole CU); many → 4 waves each
-    const bool big = (int64_t)B * n_heads * n_split < 1024;
-    // g_attn_ev (set only by vh_ar_decoder_profile_attn): start/stop events attached to the kernel's own dispatch
-    // packet (hipExtLaunchKernelGGL), i.e. the kernel's begin/end timestamps rather than a marker bracket.
-#define AD(KERN, ...)                                                                              \
-    hipExtLaunchKernelGGL((KERN<__VA_ARGS__>), grid, dim3(waves * 64), 0, s, g_attn_ev[0], g_attn_ev[1], 0, q, ldq, \
-                          kcache, vcache, out, ldo, cache_len, len_bias, n_heads, S_max, n_split, (float*)partial, arrived)
-    // default: one (b, head) per CU and no key split -> the ring kernel (8 waves x 2 register sets of 32 keys, speculative
-    // start: 605.9 vs 615.2 us per decode step, profiles/r2_ab_decode_ring.log); otherwise — key splits, more (b, head)
-    // pairs than CUs — the burst kernel.  VH_TUNE_DECODE_VARIANT = 1 forces the burst kernel (A/B); the other ring
-    // shapes round 2 measured (8x3, 16x1, 12x2, 16x2x16-key, 8x4x16-key; profiles/r2_attn_ab.log) were slower and are gone.
-    const int variant = vh_tuning(VH_TUNE_DECODE_VARIANT);
-    const int nw = vh_tuning(VH_TUNE_DECODE_WAVES);
-    // key splits: combined by a second launch (default) or by the last workgroup to arrive (VH_TUNE_DECODE_COMBINE = 1).
-    // Measured on generate() at the reference defaults (4 beams, 8 splits, 12L/512d; profiles/r4_ab_default_generate_combine.log):
-    // second launch 364.6 us per step; in-launch with an agent-scope release + acquire 609.7 (the release writes back the
-    // L2); in-launch with write-through stores and agent-scope loads, no fences, 377.6 — the hand-off (drain, ticket,
-    // dependent loads from beyond the L2) still costs 1 us per layer more than the 1.75 us dependent-launch floor it saves.
-    // the split records are combined by the last arriver of a (row, head) inside this launch (knob 1), or by a second launch
-    // (knob 2); default: inside at TWO splits (configs[4], 8 rows x 16 heads: 1483.5 vs 1496.6 us per step at context 2.7 k, 1027.2 vs
-    // 1028.3 at 0.6 k, profiles/r6_ab_config5_combine.log), the second launch at more (4 beams x 8 heads, 8 splits: DESIGN 3.1)
-    const int combine_knob = vh_tuning(VH_TUNE_DECODE_COMBINE);
-    const bool fused_combine = n_split > 1 && (combine_knob == 1 || (combine_knob == 0 && n_split == 2));
-    unsigned* arrived = fused_combine ? (unsigned*)((char*)partial + decode_records_bytes(B, n_heads, n_split)) : nullptr;
-    if (variant != 1 && big && n_split == 1 && nw == 0) {
-        const int waves = 8;
-        hipExtLaunchKernelGGL((attn_decode_ring_kernel<8, 2>), grid, dim3(waves * 64), 0, s, g_attn_ev[0], g_attn_ev[1], 0, q,
-                              ldq, kcache, vcache, out, ldo, cache_len, len_bias, n_heads, S_max);
-    } else {
-        const int waves = nw ? nw : (big ? 16 : 4);
-        if (waves == 16) AD(attn_decode_kernel, 16); else if (waves == 8) AD(attn_decode_kernel, 8);
-        else AD(attn_decode_kernel, 4);
-    }
-#undef AD
-    if (n_split > 1 && !fused_combine)
-        hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * n_heads), dim3(64), 0, s,
-                           (const float*)partial, out, ldo, n_heads, n_split);
-    VH_CHECK_LAUNCH("vh_attn_decode");
-    return VH_OK;
-}
+// The single-query kernels above are instantiated here, in this order, and so lie in the code object where they always have:
+// the launcher that names them (attn_launch) is at the end of the file, behind the backward kernels.  (Instantiated from there
+// they moved behind attn_bwd_fused_kernel and bench.py read 0.35 % lower in three alternating runs, 49216 against 49388
+// tokens/s; in this order the .text section is the same bytes as before the launcher moved and the runs agree.)
+[[maybe_unused]] static const void* const ATTN_DECODE_KERNEL_ORDER[] = {
+    (const void*)attn_decode_ring16_kernel<8, 2>, (const void*)attn_decode_ring16_split_kernel<8, 2>,
+    (const void*)attn_decode_ring16_split_kernel<4, 2>, (const void*)attn_decode_ring_kernel<8, 2>,
+    (const void*)attn_decode_kernel<16>, (const void*)attn_decode_kernel<8>, (const void*)attn_decode_kernel<4>};
 
 // =============================================================================================
 // many-row attention
@@ -1738,122 +1615,370 @@ __global__ __launch_bounds__(256) void attn_records_merge_groups_kernel(const fl
     records_merge_body(partial, out, ldo, n_heads, n_first + n_split, n_pb + n_split, n_first);
 }
 
+// =============================================================================================
+// decode attention, host side: one call record (vh_common.h), one check, one plan, one launcher.  The seven vh_attn_decode*
+// entry points and the decoder (plan.hip) fill a DecodeAttnCall; vh_attn_decode_form asks the same check and plan and
+// launches nothing (tests/golden/attn_decode_forms.txt pins what they answer).
+// =============================================================================================
+#define ATTN_MAX_RECORDS 256   // records of a (row, head) one merge launch serves (records_merge_body: one thread per record)
+
+typedef vh_attn_decode_form_info AttnForm;
+struct AttnKnobs { int variant, waves, combine; };   // VH_TUNE_DECODE_VARIANT, _WAVES, _COMBINE
+
+int vh_internal_attn_hd_record_floats(int hd);                                                          // attention_hd.hip
+bool vh_internal_attn_decode_hd_launch(const AttnForm& f, const DecodeAttnCall& c, hipEvent_t start, hipEvent_t stop);   // attention_hd.hip
+
+// start / stop events attached to the first kernel's own dispatch packet (hipExtLaunchKernelGGL), i.e. the kernel's begin /
+// end timestamps rather than a marker bracket; set only by vh_ar_decoder_profile_attn
+static thread_local hipEvent_t g_attn_ev[2] = {nullptr, nullptr};
+void vh_internal_attn_decode_events(hipEvent_t start, hipEvent_t stop) { g_attn_ev[0] = start; g_attn_ev[1] = stop; }
+
+// split records per (row, head): a shared prompt leaves one per 32-key block of the prefix (of the prefix CAPACITY with groups)
+// and one per suffix split; without one a key split leaves one per split, and an unsplit call none
+static int attn_records(const DecodeAttnCall& c) {
+    return c.prefix_kind ? (c.prefix + 31) / 32 + c.n_split : c.n_split > 1 ? c.n_split : 0;
+}
+static int attn_record_floats(const DecodeAttnCall& c) { return c.any_width ? vh_internal_attn_hd_record_floats(c.head_dim) : PART_LD; }
+// workspace: [B h][records] records; the width-64 key splits then keep B h ticket words (one per (b, head), padded to 16 B),
+// whichever way this call combines its records
+static size_t attn_records_bytes(const DecodeAttnCall& c) {
+    return (size_t)c.B * c.n_heads * attn_records(c) * attn_record_floats(c) * sizeof(float);
+}
+static size_t attn_ws_bytes(const DecodeAttnCall& c) {
+    const size_t rec = attn_records_bytes(c);
+    const bool tickets = rec && !c.prefix_kind && !c.any_width;
+    return rec + (tickets ? ((size_t)c.B * c.n_heads * sizeof(unsigned) + 15) / 16 * 16 : 0);
+}
+
+int vh_internal_attn_decode_check(const DecodeAttnCall& c, bool pointers) {
+    const bool prefix = c.prefix_kind != ATTN_PREFIX_NONE, groups = c.prefix_kind == ATTN_PREFIX_GROUPS;
+    VH_REQUIRE(!c.any_width || (c.head_dim % 4 == 0 && c.head_dim >= 16 && c.head_dim <= VH_HEAD_DIM_MAX), VH_EUNSUPPORTED,
+               "%s: head_dim=%d (served: multiples of 4 from 16 to %d)", c.name, c.head_dim, VH_HEAD_DIM_MAX);
+    // a shared prompt always leaves records: its workspace is one of the pointers
+    VH_REQUIRE(!pointers || (c.q && c.k && c.v && c.out && c.len && (!prefix || (c.kprefix && c.vprefix && c.ws)) &&
+                             (!groups || c.group_len)), VH_EINVAL, "%s: null pointer", c.name);
+    VH_REQUIRE(c.B > 0 && c.n_heads > 0 && c.S_max > 0, VH_EINVAL, "%s: bad dims B=%d h=%d S_max=%d", c.name, c.B, c.n_heads, c.S_max);
+    // the rows of a shared prompt are the columns of one score tile (two passes of 32)
+    VH_REQUIRE(!prefix || (c.B <= 64 && c.prefix > 0 && c.prefix <= c.prefix_S), VH_EINVAL,
+               "%s: bad dims B=%d (1..64 rows over a shared prompt) %s=%d/%d", c.name, c.B, groups ? "prefix_cap" : "prefix", c.prefix,
+               c.prefix_S);
+    const int max_split = c.kv16 ? 16 : 64;
+    VH_REQUIRE(c.n_split >= 1 && c.n_split <= max_split, VH_EINVAL, "%s: n_split=%d (1..%d)", c.name, c.n_split, max_split);
+    VH_REQUIRE(!groups || (c.beams >= 1 && c.B % c.beams == 0), VH_EINVAL,
+               "%s: B=%d is not a multiple of beams=%d (the rows of a group)", c.name, c.B, c.beams);
+    VH_REQUIRE(!prefix || attn_records(c) <= ATTN_MAX_RECORDS, VH_EUNSUPPORTED,
+               "%s: %d prefix blocks + %d splits exceed the %d records one merge serves", c.name, attn_records(c) - c.n_split,
+               c.n_split, ATTN_MAX_RECORDS);
+    VH_REQUIRE(c.len_bias == 0 || c.len_bias == 1, VH_EINVAL, "%s: len_bias=%d", c.name, c.len_bias);
+    const int width = c.n_heads * c.head_dim;
+    VH_REQUIRE(c.ldq % 4 == 0 && c.ldq >= width && c.ldo >= width, VH_EINVAL, "%s: ldq=%d ldo=%d", c.name, c.ldq, c.ldo);
+    // (the fp32 forms without a shared prompt have never looked at the workspace's alignment)
+    VH_REQUIRE(!pointers || (vh_aligned16(c.q) && vh_aligned16(c.k) && vh_aligned16(c.v) && vh_aligned16(c.kprefix) &&
+                             vh_aligned16(c.vprefix) && (vh_aligned16(c.ws) || !(prefix || c.kv16))), VH_EALIGN,
+               "%s: pointers must be 16-byte aligned", c.name);
+    const size_t need = attn_ws_bytes(c);
+    VH_REQUIRE(need == 0 || (c.ws && (c.ws_bytes == ATTN_WS_SIZE_NOT_GIVEN || c.ws_bytes >= need)), VH_EINVAL,
+               "%s: n_split=%d needs a workspace (%s) of %zu bytes (got %zu)", c.name, c.n_split, c.ws_name, need,
+               c.ws && c.ws_bytes != ATTN_WS_SIZE_NOT_GIVEN ? c.ws_bytes : (size_t)0);
+    return VH_OK;
+}
+
+// Which kernels a checked call launches: pure (no launch, no device memory), the shape part of the record and the knobs only.
+static int attn_plan(const DecodeAttnCall& c, const AttnKnobs& knobs, AttnForm& f) {
+    f = AttnForm{};
+    const unsigned bh = (unsigned)(c.B * c.n_heads);
+    f.records = attn_records(c);
+    f.record_floats = f.records ? attn_record_floats(c) : 0;
+    f.ws_bytes = attn_ws_bytes(c);
+    f.grid[0] = (unsigned)c.n_split, f.grid[1] = bh, f.grid[2] = 1;           // (split, (row, head)) unless said otherwise
+    // few workgroups -> many waves each (one (b, head) can own a whole CU); many -> 4 waves each, several per CU
+    const bool few = (int64_t)c.B * c.n_heads * c.n_split < 1024;
+    if (c.prefix_kind) {
+        VH_REQUIRE(!(c.kv16 && c.prefix_kind == ATTN_PREFIX_GROUPS) && !c.any_width, VH_EUNSUPPORTED,
+                   "%s: a shared prompt is served at width 64, groups over fp32 caches only", c.name);
+        // one launch whose workgroups take either four 32-key blocks of a prefix for all its beams or one (row, head, split) of the
+        // suffixes, and the merge of every (row, head)'s records
+        const unsigned n_groups = c.prefix_kind == ATTN_PREFIX_GROUPS ? c.B / c.beams : 1;
+        const unsigned prefix_wgs = ((unsigned)(c.prefix + 31) / 32 + 3) / 4 * c.n_heads * n_groups;
+        f.kernel = c.kv16 ? VH_ATTN_K_SHARED16 : c.prefix_kind == ATTN_PREFIX_GROUPS ? VH_ATTN_K_SHARED_GROUPS : VH_ATTN_K_SHARED;
+        f.grid[0] = prefix_wgs + c.n_split * bh, f.grid[1] = 1, f.block = 256;
+        f.second = c.prefix_kind == ATTN_PREFIX_GROUPS ? VH_ATTN_2ND_MERGE_GROUPS : VH_ATTN_2ND_MERGE;
+        f.second_grid = bh, f.second_block = 256;
+    } else if (c.any_width) {
+        // lane map: LK = min(16, next_pow2(hd / 4)) lanes per key, NV = ceil(hd / (4 LK)) 16-byte slots per lane
+        const int hd = c.head_dim;
+        f.kernel = VH_ATTN_K_HD, f.nw = 8, f.d = 2, f.block = 8 * 64;
+        f.lk = hd == 16 ? 4 : hd <= 32 ? 8 : 16;
+        f.nv = (hd + 4 * f.lk - 1) / (4 * f.lk);
+        if (c.n_split > 1) f.second = VH_ATTN_2ND_HD_COMBINE, f.second_grid = bh, f.second_block = VH_HEAD_DIM_MAX;
+    } else if (c.kv16 && c.n_split == 1) {
+        // ring shape (waves x register sets of 32 keys): 8 x 2 as the fp32 kernel; 16 x 1, 16 x 2, 8 x 3, 8 x 4 and 4 x 4
+        // measured within 3 % of it (461-477 us per decode step, profiles/r3_ab_decode_perf_mode.log)
+        f.kernel = VH_ATTN_K_RING16, f.nw = 8, f.d = 2, f.block = 8 * 64;
+    } else if (c.kv16) {
+        // few workgroups -> 8 waves each (the ring16 shape: a (row, head, split) may own a CU); many -> 4 waves, several per CU.
+        // The threshold is the fp32 launch's rule (`few`), taken over as it stands: NOT measured for the 16-bit stream.
+        f.kernel = VH_ATTN_K_RING16_SPLIT, f.nw = few ? 8 : 4, f.d = 2, f.block = f.nw * 64;
+        // records added in split order by the combine launch of the fp32 form: deterministic
+        f.second = VH_ATTN_2ND_COMBINE, f.second_grid = bh, f.second_block = 64;
+    } else if (knobs.variant != 1 && few && c.n_split == 1 && knobs.waves == 0) {
+        // default: one (b, head) per CU and no key split -> the ring kernel (8 waves x 2 register sets of 32 keys, speculative
+        // start: 605.9 vs 615.2 us per decode step, profiles/r2_ab_decode_ring.log); otherwise — key splits, more (b, head)
+        // pairs than CUs — the burst kernel.  VH_TUNE_DECODE_VARIANT = 1 forces the burst kernel (A/B); the other ring
+        // shapes round 2 measured (8x3, 16x1, 12x2, 16x2x16-key, 8x4x16-key; profiles/r2_attn_ab.log) were slower and are gone.
+        f.kernel = VH_ATTN_K_RING, f.nw = 8, f.d = 2, f.block = 8 * 64;
+    } else {
+        const int waves = knobs.waves ? knobs.waves : few ? 16 : 4;
+        f.kernel = VH_ATTN_K_BURST, f.nw = waves == 16 || waves == 8 ? waves : 4, f.block = f.nw * 64;
+        // key splits: combined by a second launch or by the last workgroup of a (row, head) to arrive (VH_TUNE_DECODE_COMBINE = 1).
+        // Measured on generate() at the reference defaults (4 beams, 8 splits, 12L/512d; profiles/r4_ab_default_generate_combine.log):
+        // second launch 364.6 us per step; in-launch with an agent-scope release + acquire 609.7 (the release writes back the
+        // L2); in-launch with write-through stores and agent-scope loads, no fences, 377.6 — the hand-off (drain, ticket,
+        // dependent loads from beyond the L2) still costs 1 us per layer more than the 1.75 us dependent-launch floor it saves.
+        // Knob 1: inside this launch; knob 2: the second launch; default: inside at TWO splits (configs[4], 8 rows x 16 heads:
+        // 1483.5 vs 1496.6 us per step at context 2.7 k, 1027.2 vs 1028.3 at 0.6 k, profiles/r6_ab_config5_combine.log), the
+        // second launch at more (4 beams x 8 heads, 8 splits: DESIGN 3.1)
+        f.fused_combine = c.n_split > 1 && (knobs.combine == 1 || (knobs.combine == 0 && c.n_split == 2));
+        if (f.fused_combine) f.ticket_offset = attn_records_bytes(c);
+        else if (c.n_split > 1) f.second = VH_ATTN_2ND_COMBINE, f.second_grid = bh, f.second_block = 64;
+    }
+    return VH_OK;
+}
+
+// the compiled first kernels: (kernel, NW, D, LK, NV) as attn_launch's switch (and attention_hd.hip's) instantiates them
+static const int ATTN_FORMS[][5] = {
+    {VH_ATTN_K_BURST, 4, 0, 0, 0},  {VH_ATTN_K_BURST, 8, 0, 0, 0},  {VH_ATTN_K_BURST, 16, 0, 0, 0}, {VH_ATTN_K_RING, 8, 2, 0, 0},
+    {VH_ATTN_K_RING16, 8, 2, 0, 0}, {VH_ATTN_K_RING16_SPLIT, 8, 2, 0, 0}, {VH_ATTN_K_RING16_SPLIT, 4, 2, 0, 0},
+    {VH_ATTN_K_HD, 8, 2, 4, 1},     {VH_ATTN_K_HD, 8, 2, 8, 1},     {VH_ATTN_K_HD, 8, 2, 16, 1},    {VH_ATTN_K_HD, 8, 2, 16, 2},
+    {VH_ATTN_K_HD, 8, 2, 16, 3},    {VH_ATTN_K_HD, 8, 2, 16, 4},    {VH_ATTN_K_SHARED, 0, 0, 0, 0}, {VH_ATTN_K_SHARED_GROUPS, 0, 0, 0, 0},
+    {VH_ATTN_K_SHARED16, 0, 0, 0, 0}};
+
+template <class T>
+static SharedArgs<T> shared_args(const AttnForm& f, const DecodeAttnCall& c) {
+    const bool groups = c.prefix_kind == ATTN_PREFIX_GROUPS;
+    const int n_pb = f.records - c.n_split;
+    return SharedArgs<T>{c.q, c.ldq, (const T*)c.kprefix, (const T*)c.vprefix, c.prefix, c.prefix_S, (const T*)c.k, (const T*)c.v,
+                         c.len, c.len_bias, c.S_max, c.n_split, (float*)c.ws, c.n_heads, c.B, n_pb, f.records,
+                         (int)f.grid[0] - c.n_split * c.B * c.n_heads, groups ? c.group_len : nullptr, groups ? c.B / c.beams : 1,
+                         groups ? c.beams : c.B};
+}
+
+// the first kernel with the profiling events on its dispatch packet, then the second launch: every template instantiation
+// of the decode attention is in this switch (the any-width kernels: in vh_internal_attn_decode_hd_launch's)
+static int attn_launch(const AttnForm& f, const DecodeAttnCall& c) {
+    hipStream_t s = (hipStream_t)c.stream;
+    const dim3 grid(f.grid[0], f.grid[1], f.grid[2]), block(f.block);
+    auto first = [&](auto kernel, auto... args) {
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, s, g_attn_ev[0], g_attn_ev[1], 0, args...);
+        return true;
+    };
+    auto burst = [&](auto kernel) {
+        return first(kernel, c.q, c.ldq, (const float*)c.k, (const float*)c.v, c.out, c.ldo, c.len, c.len_bias, c.n_heads, c.S_max,
+                     c.n_split, (float*)c.ws, f.fused_combine ? (unsigned*)((char*)c.ws + f.ticket_offset) : (unsigned*)nullptr);
+    };
+    auto ring16_split = [&](auto kernel) {
+        return first(kernel, c.q, c.ldq, (const uint16_t*)c.k, (const uint16_t*)c.v, c.len, c.len_bias, c.n_heads, c.S_max, c.n_split,
+                     (float*)c.ws);
+    };
+    bool compiled = false;
+    switch (f.kernel) {
+    case VH_ATTN_K_BURST:
+        compiled = f.nw == 16 ? burst(attn_decode_kernel<16>) : f.nw == 8 ? burst(attn_decode_kernel<8>)
+                   : f.nw == 4 ? burst(attn_decode_kernel<4>) : false;
+        break;
+    case VH_ATTN_K_RING:
+        compiled = f.nw == 8 && f.d == 2 && first(attn_decode_ring_kernel<8, 2>, c.q, c.ldq, (const float*)c.k, (const float*)c.v, c.out,
+                                                  c.ldo, c.len, c.len_bias, c.n_heads, c.S_max);
+        break;
+    case VH_ATTN_K_RING16:
+        compiled = f.nw == 8 && f.d == 2 && first(attn_decode_ring16_kernel<8, 2>, c.q, c.ldq, (const uint16_t*)c.k, (const uint16_t*)c.v,
+                                                  c.out, c.ldo, c.len, c.len_bias, c.n_heads, c.S_max);
+        break;
+    case VH_ATTN_K_RING16_SPLIT:
+        compiled = f.d != 2 ? false : f.nw == 8 ? ring16_split(attn_decode_ring16_split_kernel<8, 2>)
+                   : f.nw == 4 ? ring16_split(attn_decode_ring16_split_kernel<4, 2>) : false;
+        break;
+    case VH_ATTN_K_HD: compiled = vh_internal_attn_decode_hd_launch(f, c, g_attn_ev[0], g_attn_ev[1]); break;
+    case VH_ATTN_K_SHARED: compiled = first(attn_shared_kernel, shared_args<float>(f, c)); break;
+    case VH_ATTN_K_SHARED_GROUPS: compiled = first(attn_shared_groups_kernel, shared_args<float>(f, c)); break;
+    case VH_ATTN_K_SHARED16: compiled = first(attn_shared16_kernel, shared_args<uint16_t>(f, c)); break;
+    }
+    VH_REQUIRE(compiled, VH_EUNSUPPORTED, "%s: internal: no compiled kernel %d <NW %d, D %d, LK %d, NV %d>", c.name, f.kernel, f.nw, f.d,
+               f.lk, f.nv);
+    const dim3 grid2(f.second_grid), block2(f.second_block);
+    switch (f.second) {
+    case VH_ATTN_2ND_COMBINE:
+        hipLaunchKernelGGL(attn_decode_combine_kernel, grid2, block2, 0, s, (const float*)c.ws, c.out, c.ldo, c.n_heads, c.n_split);
+        break;
+    case VH_ATTN_2ND_MERGE:
+        hipLaunchKernelGGL(attn_records_merge_kernel, grid2, block2, 0, s, (const float*)c.ws, c.out, c.ldo, c.n_heads, f.records);
+        break;
+    case VH_ATTN_2ND_MERGE_GROUPS:
+        hipLaunchKernelGGL(attn_records_merge_groups_kernel, grid2, block2, 0, s, (const float*)c.ws, c.out, c.ldo, c.n_heads,
+                           f.records - c.n_split, c.n_split, c.group_len, c.beams);
+        break;
+    default: break;                                      // none, or the any-width combine (launched with its kernel)
+    }
+    VH_CHECK_LAUNCH(c.name);
+    return VH_OK;
+}
+
+// vh_attn_decode_form: the entry points run as they are, and the form is handed over instead of launched
+static thread_local AttnForm* t_attn_form_query = nullptr;
+
+int vh_internal_attn_decode(const DecodeAttnCall& c) {
+    const int rc = vh_internal_attn_decode_check(c, true);
+    if (rc != VH_OK) return rc;
+    AttnForm f;
+    const int prc = attn_plan(c, AttnKnobs{vh_tuning(VH_TUNE_DECODE_VARIANT), vh_tuning(VH_TUNE_DECODE_WAVES), vh_tuning(VH_TUNE_DECODE_COMBINE)}, f);
+    if (prc != VH_OK) return prc;
+    if (t_attn_form_query) {
+        *t_attn_form_query = f;
+        return VH_OK;
+    }
+    return attn_launch(f, c);
+}
+
+// the record of a width-64 call without a shared prompt; the entry points below fill in what they have beyond it
+static DecodeAttnCall attn_call(const char* name, const float* q, int ldq, const void* k, const void* v, float* out, int ldo,
+                                const int32_t* len, int len_bias, int B, int n_heads, int S_max, bool kv16, int n_split, void* ws,
+                                size_t ws_bytes, void* stream) {
+    return DecodeAttnCall{name, "partial", q, ldq, out, ldo, len, len_bias, B, n_heads, false, HD, 0.f, kv16, k, v, S_max,
+                          ATTN_PREFIX_NONE, nullptr, nullptr, 0, 0, nullptr, 1, n_split, ws, ws_bytes, stream};
+}
+static DecodeAttnCall attn_call_shared(DecodeAttnCall c, int kind, const void* kprefix, const void* vprefix, int prefix, int prefix_S,
+                                       const int32_t* group_len, int beams) {
+    c.prefix_kind = kind, c.kprefix = kprefix, c.vprefix = vprefix, c.prefix = prefix, c.prefix_S = prefix_S;
+    c.group_len = group_len, c.beams = beams;
+    return c;
+}
+
+extern "C" size_t vh_attn_decode_ws_bytes(int B, int n_heads, int n_split) {
+    return attn_ws_bytes(attn_call("", nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, B, n_heads, 0, false, n_split, nullptr, 0, nullptr));
+}
 extern "C" size_t vh_attn_decode_shared_ws_bytes(int B, int n_heads, int prefix_len, int n_split_suffix) {
     if (B <= 0 || n_heads <= 0 || prefix_len <= 0 || n_split_suffix < 1) return 0;
-    const int n_tot = (prefix_len + 31) / 32 + n_split_suffix;
-    return (size_t)B * n_heads * n_tot * PART_LD * sizeof(float);
+    DecodeAttnCall c = attn_call("", nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, B, n_heads, 0, false, n_split_suffix, nullptr, 0, nullptr);
+    return attn_ws_bytes(attn_call_shared(c, ATTN_PREFIX_ONE, nullptr, nullptr, prefix_len, prefix_len, nullptr, 1));
+}
+// several utterances at once: the records of the prefix CAPACITY
+extern "C" size_t vh_attn_decode_shared_groups_ws_bytes(int B, int n_heads, int prefix_cap, int n_split_suffix) {
+    return vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_cap, n_split_suffix);
+}
+static DecodeAttnCall attn_call_any_width(DecodeAttnCall c, int head_dim, float scale) {
+    c.any_width = true, c.head_dim = head_dim, c.scale = scale;
+    return c;
+}
+extern "C" size_t vh_attn_decode_hd_ws_bytes(int B, int n_heads, int head_dim, int n_split) {
+    if (n_split <= 1 || B <= 0 || n_heads <= 0 || head_dim <= 0) return 0;
+    DecodeAttnCall c = attn_call("", nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, B, n_heads, 0, false, n_split, nullptr, 0, nullptr);
+    return attn_ws_bytes(attn_call_any_width(c, head_dim, 0.f));
+}
+
+// a head width other than 64 (attention_hd.hip's kernels; 64 itself is served, for comparisons)
+extern "C" int vh_attn_decode_hd(const float* q, int ldq, const float* kcache, const float* vcache, float* out, int ldo,
+                                 const int32_t* cache_len, int len_bias, int B, int n_heads, int head_dim, int S_max, float scale,
+                                 int n_split, void* partial, size_t partial_bytes, void* stream) {
+    const DecodeAttnCall c = attn_call("vh_attn_decode_hd", q, ldq, kcache, vcache, out, ldo, cache_len, len_bias, B, n_heads, S_max, false,
+                                       n_split, partial, partial_bytes, stream);
+    return vh_internal_attn_decode(attn_call_any_width(c, head_dim, scale));
+}
+
+extern "C" int vh_attn_decode(const float* q, int ldq, const float* kcache, const float* vcache, float* out, int ldo,
+                              const int32_t* cache_len, int len_bias, int B, int n_heads, int S_max, int n_split, void* partial,
+                              void* stream) {
+    return vh_internal_attn_decode(attn_call("vh_attn_decode", q, ldq, kcache, vcache, out, ldo, cache_len, len_bias, B, n_heads, S_max,
+                                             false, n_split, partial, ATTN_WS_SIZE_NOT_GIVEN, stream));
+}
+
+extern "C" int vh_attn_decode_kv16(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, float* out, int ldo,
+                                   const int32_t* cache_len, int len_bias, int B, int n_heads, int S_max, void* stream) {
+    return vh_internal_attn_decode(attn_call("vh_attn_decode_kv16", q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, B, n_heads,
+                                             S_max, true, 1, nullptr, 0, stream));
+}
+
+// (n_split == 1 is the record of vh_attn_decode_kv16 but for the name: its launch, bit for bit)
+extern "C" int vh_attn_decode_kv16_split(const float* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, float* out,
+                                         int ldo, const int32_t* cache_len, int len_bias, int B, int n_heads, int S_max, int n_split,
+                                         void* partial, size_t partial_bytes, void* stream) {
+    return vh_internal_attn_decode(attn_call("vh_attn_decode_kv16_split", q, ldq, kcache16, vcache16, out, ldo, cache_len, len_bias, B,
+                                             n_heads, S_max, true, n_split, partial, partial_bytes, stream));
 }
 
 extern "C" int vh_attn_decode_shared(const float* q, int ldq, const float* kprefix, const float* vprefix, int prefix_len,
                                      int prefix_S, const float* ksuffix, const float* vsuffix, float* out, int ldo,
-                                     const int32_t* suffix_len, int len_bias, int B, int n_heads, int S_suf,
-                                     int n_split_suffix, void* partial, size_t partial_bytes, void* stream) {
-    VH_REQUIRE(q && kprefix && vprefix && ksuffix && vsuffix && out && suffix_len && partial, VH_EINVAL,
-               "vh_attn_decode_shared: null pointer");
-    VH_REQUIRE(B > 0 && B <= 64 && n_heads > 0 && prefix_len > 0 && prefix_len <= prefix_S && S_suf > 0 &&
-                   n_split_suffix >= 1 && n_split_suffix <= 64, VH_EINVAL,
-               "vh_attn_decode_shared: bad dims B=%d h=%d prefix=%d/%d S_suf=%d n_split=%d", B, n_heads, prefix_len, prefix_S,
-               S_suf, n_split_suffix);
-    const int n_pb = (prefix_len + 31) / 32, n_tot = n_pb + n_split_suffix;
-    VH_REQUIRE(n_tot <= 256, VH_EUNSUPPORTED, "vh_attn_decode_shared: %d prefix blocks + %d splits exceed the 256 records one merge serves",
-               n_pb, n_split_suffix);
-    VH_REQUIRE(len_bias == 0 || len_bias == 1, VH_EINVAL, "vh_attn_decode_shared: len_bias=%d", len_bias);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL, "vh_attn_decode_shared: ldq=%d ldo=%d", ldq, ldo);
-    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kprefix) && vh_aligned16(vprefix) && vh_aligned16(ksuffix) &&
-                   vh_aligned16(vsuffix) && vh_aligned16(partial), VH_EALIGN, "vh_attn_decode_shared: pointers must be 16-byte aligned");
-    VH_REQUIRE(partial_bytes >= vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split_suffix), VH_EINVAL,
-               "vh_attn_decode_shared: workspace of %zu bytes, need %zu", partial_bytes,
-               vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split_suffix));
-    hipStream_t s = (hipStream_t)stream;
-    const int prefix_wgs = (n_pb + 3) / 4 * n_heads;
-    SharedArgs<float> a{q, ldq, kprefix, vprefix, prefix_len, prefix_S, ksuffix, vsuffix, suffix_len, len_bias, S_suf, n_split_suffix,
-                 (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs, nullptr, 1, B};
-    // (the events of vh_ar_decoder_profile_attn bracket this launch: the step's attention kernel in this form)
-    hipExtLaunchKernelGGL(attn_shared_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s, g_attn_ev[0],
-                          g_attn_ev[1], 0, a);
-    hipLaunchKernelGGL(attn_records_merge_kernel, dim3(B * n_heads), dim3(256), 0, s, (const float*)partial, out, ldo, n_heads,
-                       n_tot);
-    VH_CHECK_LAUNCH("vh_attn_decode_shared");
-    return VH_OK;
+                                     const int32_t* suffix_len, int len_bias, int B, int n_heads, int S_suf, int n_split_suffix,
+                                     void* partial, size_t partial_bytes, void* stream) {
+    const DecodeAttnCall c = attn_call("vh_attn_decode_shared", q, ldq, ksuffix, vsuffix, out, ldo, suffix_len, len_bias, B, n_heads, S_suf,
+                                       false, n_split_suffix, partial, partial_bytes, stream);
+    return vh_internal_attn_decode(attn_call_shared(c, ATTN_PREFIX_ONE, kprefix, vprefix, prefix_len, prefix_S, nullptr, 1));
 }
 
-// ---- several utterances at once: B = n_groups * beams rows, rows g * beams .. g * beams + beams - 1 over group g's prompt ----
-extern "C" size_t vh_attn_decode_shared_groups_ws_bytes(int B, int n_heads, int prefix_cap, int n_split_suffix) {
-    return vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_cap, n_split_suffix);
-}
-
+// several utterances at once: B = n_groups * beams rows, rows g * beams .. g * beams + beams - 1 over group g's prompt
 extern "C" int vh_attn_decode_shared_groups(const float* q, int ldq, const float* kprefix, const float* vprefix,
                                             const int32_t* prefix_len, int prefix_cap, int prefix_S, const float* ksuffix,
                                             const float* vsuffix, float* out, int ldo, const int32_t* suffix_len, int len_bias,
                                             int B, int beams, int n_heads, int S_suf, int n_split_suffix, void* partial,
                                             size_t partial_bytes, void* stream) {
-    VH_REQUIRE(q && kprefix && vprefix && prefix_len && ksuffix && vsuffix && out && suffix_len && partial, VH_EINVAL,
-               "vh_attn_decode_shared_groups: null pointer");
-    VH_REQUIRE(B > 0 && B <= 64 && n_heads > 0 && prefix_cap > 0 && prefix_cap <= prefix_S && S_suf > 0 &&
-                   n_split_suffix >= 1 && n_split_suffix <= 64, VH_EINVAL,
-               "vh_attn_decode_shared_groups: bad dims B=%d h=%d prefix_cap=%d/%d S_suf=%d n_split=%d", B, n_heads, prefix_cap,
-               prefix_S, S_suf, n_split_suffix);
-    VH_REQUIRE(beams >= 1 && B % beams == 0, VH_EINVAL,
-               "vh_attn_decode_shared_groups: B=%d is not a multiple of beams=%d (the rows of a group)", B, beams);
-    const int n_pb = (prefix_cap + 31) / 32, n_tot = n_pb + n_split_suffix, n_groups = B / beams;
-    VH_REQUIRE(n_tot <= 256, VH_EUNSUPPORTED,
-               "vh_attn_decode_shared_groups: %d prefix blocks + %d splits exceed the 256 records one merge serves", n_pb,
-               n_split_suffix);
-    VH_REQUIRE(len_bias == 0 || len_bias == 1, VH_EINVAL, "vh_attn_decode_shared_groups: len_bias=%d", len_bias);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL,
-               "vh_attn_decode_shared_groups: ldq=%d ldo=%d", ldq, ldo);
-    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kprefix) && vh_aligned16(vprefix) && vh_aligned16(ksuffix) &&
-                   vh_aligned16(vsuffix) && vh_aligned16(partial), VH_EALIGN,
-               "vh_attn_decode_shared_groups: pointers must be 16-byte aligned");
-    VH_REQUIRE(partial_bytes >= vh_attn_decode_shared_groups_ws_bytes(B, n_heads, prefix_cap, n_split_suffix), VH_EINVAL,
-               "vh_attn_decode_shared_groups: workspace of %zu bytes, need %zu", partial_bytes,
-               vh_attn_decode_shared_groups_ws_bytes(B, n_heads, prefix_cap, n_split_suffix));
-    hipStream_t s = (hipStream_t)stream;
-    const int prefix_wgs = (n_pb + 3) / 4 * n_heads * n_groups;
-    SharedArgs<float> a{q, ldq, kprefix, vprefix, prefix_cap, prefix_S, ksuffix, vsuffix, suffix_len, len_bias, S_suf, n_split_suffix,
-                 (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs, prefix_len, n_groups, beams};
-    // (the events of vh_ar_decoder_profile_attn bracket this launch, as in the other forms)
-    hipExtLaunchKernelGGL(attn_shared_groups_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s,
-                          g_attn_ev[0], g_attn_ev[1], 0, a);
-    hipLaunchKernelGGL(attn_records_merge_groups_kernel, dim3(B * n_heads), dim3(256), 0, s, (const float*)partial, out, ldo,
-                       n_heads, n_pb, n_split_suffix, prefix_len, beams);
-    VH_CHECK_LAUNCH("vh_attn_decode_shared_groups");
-    return VH_OK;
+    const DecodeAttnCall c = attn_call("vh_attn_decode_shared_groups", q, ldq, ksuffix, vsuffix, out, ldo, suffix_len, len_bias, B, n_heads,
+                                       S_suf, false, n_split_suffix, partial, partial_bytes, stream);
+    return vh_internal_attn_decode(attn_call_shared(c, ATTN_PREFIX_GROUPS, kprefix, vprefix, prefix_cap, prefix_S, prefix_len, beams));
 }
 
 extern "C" int vh_attn_decode_shared_kv16(const float* q, int ldq, const uint16_t* kprefix16, const uint16_t* vprefix16,
                                           int prefix_len, int prefix_S, const uint16_t* ksuffix16, const uint16_t* vsuffix16,
                                           float* out, int ldo, const int32_t* suffix_len, int len_bias, int B, int n_heads,
                                           int S_suf, int n_split_suffix, void* partial, size_t partial_bytes, void* stream) {
-    VH_REQUIRE(q && kprefix16 && vprefix16 && ksuffix16 && vsuffix16 && out && suffix_len && partial, VH_EINVAL,
-               "vh_attn_decode_shared_kv16: null pointer");
-    VH_REQUIRE(n_split_suffix >= 1 && n_split_suffix <= 16, VH_EINVAL, "vh_attn_decode_shared_kv16: n_split=%d (1..16)",
-               n_split_suffix);
-    VH_REQUIRE(B > 0 && B <= 64 && n_heads > 0 && prefix_len > 0 && prefix_len <= prefix_S && S_suf > 0, VH_EINVAL,
-               "vh_attn_decode_shared_kv16: bad dims B=%d h=%d prefix=%d/%d S_suf=%d n_split=%d", B, n_heads, prefix_len,
-               prefix_S, S_suf, n_split_suffix);
-    const int n_pb = (prefix_len + 31) / 32, n_tot = n_pb + n_split_suffix;
-    VH_REQUIRE(n_tot <= 256, VH_EUNSUPPORTED,
-               "vh_attn_decode_shared_kv16: %d prefix blocks + %d splits exceed the 256 records one merge serves", n_pb,
-               n_split_suffix);
-    VH_REQUIRE(len_bias == 0 || len_bias == 1, VH_EINVAL, "vh_attn_decode_shared_kv16: len_bias=%d", len_bias);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD && ldo >= n_heads * HD, VH_EINVAL,
-               "vh_attn_decode_shared_kv16: ldq=%d ldo=%d", ldq, ldo);
-    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kprefix16) && vh_aligned16(vprefix16) && vh_aligned16(ksuffix16) &&
-                   vh_aligned16(vsuffix16) && vh_aligned16(partial), VH_EALIGN,
-               "vh_attn_decode_shared_kv16: pointers must be 16-byte aligned");
-    VH_REQUIRE(partial_bytes >= vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split_suffix), VH_EINVAL,
-               "vh_attn_decode_shared_kv16: workspace of %zu bytes, need %zu", partial_bytes,
-               vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split_suffix));
-    hipStream_t s = (hipStream_t)stream;
-    const int prefix_wgs = (n_pb + 3) / 4 * n_heads;
-    SharedArgs<uint16_t> a{q, ldq, kprefix16, vprefix16, prefix_len, prefix_S, ksuffix16, vsuffix16, suffix_len, len_bias, S_suf,
-                           n_split_suffix, (float*)partial, n_heads, B, n_pb, n_tot, prefix_wgs, nullptr, 1, B};
-    // (the events of vh_ar_decoder_profile_attn bracket this launch: the step's attention kernel in this form)
-    hipExtLaunchKernelGGL(attn_shared16_kernel, dim3(prefix_wgs + n_split_suffix * B * n_heads), dim3(256), 0, s, g_attn_ev[0],
-                          g_attn_ev[1], 0, a);
-    hipLaunchKernelGGL(attn_records_merge_kernel, dim3(B * n_heads), dim3(256), 0, s, (const float*)partial, out, ldo, n_heads,
-                       n_tot);
-    VH_CHECK_LAUNCH("vh_attn_decode_shared_kv16");
+    const DecodeAttnCall c = attn_call("vh_attn_decode_shared_kv16", q, ldq, ksuffix16, vsuffix16, out, ldo, suffix_len, len_bias, B,
+                                       n_heads, S_suf, true, n_split_suffix, partial, partial_bytes, stream);
+    return vh_internal_attn_decode(attn_call_shared(c, ATTN_PREFIX_ONE, kprefix16, vprefix16, prefix_len, prefix_S, nullptr, 1));
+}
+
+// ---- which kernels a call launches: the entry point itself runs, on operands that are never touched, up to its launch ----
+extern "C" int vh_attn_decode_form(int entry, int B, int n_heads, int head_dim, int S_max, int n_split, int prefix, int prefix_S,
+                                   int beams, size_t ws_bytes, vh_attn_decode_form_info* out) {
+    VH_REQUIRE(out, VH_EINVAL, "vh_attn_decode_form: null pointer");
+    *out = AttnForm{};
+    VH_REQUIRE(entry >= VH_ATTN_ENTRY_DECODE && entry <= VH_ATTN_ENTRY_HD, VH_EINVAL, "vh_attn_decode_form: entry=%d", entry);
+    alignas(16) static float operand[4];          // every pointer argument: non-null, 16-byte aligned, never dereferenced
+    float* const P = operand;
+    const uint16_t* const H = reinterpret_cast<const uint16_t*>(operand);
+    const int32_t* const I = reinterpret_cast<const int32_t*>(operand);
+    const int ld = n_heads * (entry == VH_ATTN_ENTRY_HD ? head_dim : HD);
+    AttnForm f{};
+    t_attn_form_query = &f;
+    int rc;
+    switch (entry) {
+    case VH_ATTN_ENTRY_DECODE: rc = vh_attn_decode(P, ld, P, P, P, ld, I, 1, B, n_heads, S_max, n_split, P, nullptr); break;
+    case VH_ATTN_ENTRY_KV16: rc = vh_attn_decode_kv16(P, ld, H, H, P, ld, I, 1, B, n_heads, S_max, nullptr); break;
+    case VH_ATTN_ENTRY_KV16_SPLIT:
+        rc = vh_attn_decode_kv16_split(P, ld, H, H, P, ld, I, 1, B, n_heads, S_max, n_split, P, ws_bytes, nullptr);
+        break;
+    case VH_ATTN_ENTRY_SHARED:
+        rc = vh_attn_decode_shared(P, ld, P, P, prefix, prefix_S, P, P, P, ld, I, 1, B, n_heads, S_max, n_split, P, ws_bytes, nullptr);
+        break;
+    case VH_ATTN_ENTRY_SHARED_GROUPS:
+        rc = vh_attn_decode_shared_groups(P, ld, P, P, I, prefix, prefix_S, P, P, P, ld, I, 1, B, beams, n_heads, S_max, n_split, P,
+                                          ws_bytes, nullptr);
+        break;
+    case VH_ATTN_ENTRY_SHARED_KV16:
+        rc = vh_attn_decode_shared_kv16(P, ld, H, H, prefix, prefix_S, H, H, P, ld, I, 1, B, n_heads, S_max, n_split, P, ws_bytes, nullptr);
+        break;
+    default:
+        rc = vh_attn_decode_hd(P, ld, P, P, P, ld, I, 1, B, n_heads, head_dim, S_max, 1.f, n_split, P, ws_bytes, nullptr);
+        break;
+    }
+    t_attn_form_query = nullptr;
+    if (rc == VH_OK) *out = f;
+    return rc;
+}
+
+// the compiled first kernels, i = 0, 1, ...: kernel and template arguments in *out; VH_EINVAL past the last row
+extern "C" int vh_attn_decode_form_row(int i, vh_attn_decode_form_info* out) {
+    const int rows = (int)(sizeof(ATTN_FORMS) / sizeof(ATTN_FORMS[0]));
+    VH_REQUIRE(out && i >= 0 && i < rows, VH_EINVAL, "vh_attn_decode_form_row: row %d of %d", i, rows);
+    *out = AttnForm{};
+    out->kernel = ATTN_FORMS[i][0], out->nw = ATTN_FORMS[i][1], out->d = ATTN_FORMS[i][2], out->lk = ATTN_FORMS[i][3], out->nv = ATTN_FORMS[i][4];
     return VH_OK;
 }
+

@@ -209,51 +209,31 @@ __global__ __launch_bounds__(HD_MAX) void attn_decode_hd_combine_kernel(
     out[(int64_t)b * ldo + head * hd + tid] = O / L;
 }
 
-// start / stop events attached to the kernel's own dispatch packet (set only by vh_ar_decoder_profile_attn, as
-// attention.hip's vh_internal_attn_decode_events does for the width-64 kernels)
-static thread_local hipEvent_t g_hd_ev[2] = {nullptr, nullptr};
-void vh_internal_attn_decode_hd_events(hipEvent_t start, hipEvent_t stop) { g_hd_ev[0] = start; g_hd_ev[1] = stop; }
+// ---- what attention.hip's check, plan and launcher (vh_attn_decode_hd is one of its entry points) need of this file ----
+static_assert(HD_MAX == VH_HEAD_DIM_MAX, "the plan sizes the combine launch by VH_HEAD_DIM_MAX");
+int vh_internal_attn_hd_record_floats(int hd) { return hd_record_floats(hd); }
 
-extern "C" size_t vh_attn_decode_hd_ws_bytes(int B, int n_heads, int head_dim, int n_split) {
-    if (n_split <= 1 || B <= 0 || n_heads <= 0 || head_dim <= 0) return 0;
-    return (size_t)B * n_heads * n_split * hd_record_floats(head_dim) * sizeof(float);
-}
-
-extern "C" int vh_attn_decode_hd(const float* q, int ldq, const float* kcache, const float* vcache, float* out, int ldo,
-                                 const int32_t* cache_len, int len_bias, int B, int n_heads, int head_dim, int S_max,
-                                 float scale, int n_split, void* partial, size_t partial_bytes, void* stream) {
-    const int hd = head_dim;
-    VH_REQUIRE(hd % 4 == 0 && hd >= 16 && hd <= HD_MAX, VH_EUNSUPPORTED,
-               "vh_attn_decode_hd: head_dim=%d (served: multiples of 4 from 16 to 256)", hd);
-    VH_REQUIRE(q && kcache && vcache && out && cache_len, VH_EINVAL, "vh_attn_decode_hd: null pointer");
-    VH_REQUIRE(B > 0 && n_heads > 0 && S_max > 0 && n_split >= 1 && n_split <= 64, VH_EINVAL,
-               "vh_attn_decode_hd: bad dims B=%d h=%d S_max=%d n_split=%d", B, n_heads, S_max, n_split);
-    VH_REQUIRE(len_bias == 0 || len_bias == 1, VH_EINVAL, "vh_attn_decode_hd: len_bias=%d", len_bias);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * hd && ldo >= n_heads * hd, VH_EINVAL, "vh_attn_decode_hd: ldq=%d ldo=%d",
-               ldq, ldo);
-    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kcache) && vh_aligned16(vcache), VH_EALIGN,
-               "vh_attn_decode_hd: pointers must be 16-byte aligned");
-    VH_REQUIRE(n_split == 1 || (partial && partial_bytes >= vh_attn_decode_hd_ws_bytes(B, n_heads, hd, n_split)), VH_EINVAL,
-               "vh_attn_decode_hd: n_split=%d needs a workspace of vh_attn_decode_hd_ws_bytes() = %zu bytes (got %zu)", n_split,
-               vh_attn_decode_hd_ws_bytes(B, n_heads, hd, n_split), partial ? partial_bytes : (size_t)0);
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(n_split, B * n_heads);
-#define ADH(LK, NV)                                                                                                      \
-    hipExtLaunchKernelGGL((attn_decode_hd_kernel<8, 2, LK, NV>), grid, dim3(8 * 64), 0, s, g_hd_ev[0], g_hd_ev[1], 0, q, ldq, kcache, \
-                          vcache, out, ldo, cache_len, len_bias, n_heads, hd, S_max, scale, n_split, (float*)partial)
-    // lane map: LK = min(16, next_pow2(hd / 4)) lanes per key, NV = ceil(hd / (4 LK)) 16-byte slots per lane
-    if (hd == 16) ADH(4, 1);
-    else if (hd <= 32) ADH(8, 1);
-    else if (hd <= 64) ADH(16, 1);
-    else if (hd <= 128) ADH(16, 2);
-    else if (hd <= 192) ADH(16, 3);
-    else ADH(16, 4);
-#undef ADH
-    if (n_split > 1)
-        hipLaunchKernelGGL(attn_decode_hd_combine_kernel, dim3(B * n_heads), dim3(HD_MAX), 0, s, (const float*)partial, out, ldo,
-                           n_heads, hd, n_split);
-    VH_CHECK_LAUNCH("vh_attn_decode_hd");
-    return VH_OK;
+// the planned kernel (events on its dispatch packet) and its combine launch; false: no such lane map is compiled
+bool vh_internal_attn_decode_hd_launch(const vh_attn_decode_form_info& f, const DecodeAttnCall& c, hipEvent_t start, hipEvent_t stop) {
+    hipStream_t s = (hipStream_t)c.stream;
+    auto launch = [&](auto kernel) {
+        hipExtLaunchKernelGGL(kernel, dim3(f.grid[0], f.grid[1], f.grid[2]), dim3(f.block), 0, s, start, stop, 0, c.q, c.ldq,
+                              (const float*)c.k, (const float*)c.v, c.out, c.ldo, c.len, c.len_bias, c.n_heads, c.head_dim, c.S_max,
+                              c.scale, c.n_split, (float*)c.ws);
+        return true;
+    };
+    const bool compiled = f.nw != 8 || f.d != 2 ? false
+                          : f.lk == 4 && f.nv == 1 ? launch(attn_decode_hd_kernel<8, 2, 4, 1>)
+                          : f.lk == 8 && f.nv == 1 ? launch(attn_decode_hd_kernel<8, 2, 8, 1>)
+                          : f.lk != 16 ? false
+                          : f.nv == 1 ? launch(attn_decode_hd_kernel<8, 2, 16, 1>)
+                          : f.nv == 2 ? launch(attn_decode_hd_kernel<8, 2, 16, 2>)
+                          : f.nv == 3 ? launch(attn_decode_hd_kernel<8, 2, 16, 3>)
+                          : f.nv == 4 ? launch(attn_decode_hd_kernel<8, 2, 16, 4>) : false;
+    if (compiled && f.second == VH_ATTN_2ND_HD_COMBINE)
+        hipLaunchKernelGGL(attn_decode_hd_combine_kernel, dim3(f.second_grid), dim3(f.second_block), 0, s, (const float*)c.ws, c.out,
+                           c.ldo, c.n_heads, c.head_dim, c.n_split);
+    return compiled;
 }
 
 // ---- prompt pass: K / V column blocks of the QKV projection into cache rows 0 .. T-1 ----

@@ -53,6 +53,25 @@ struct vh_ar_decoder {
     int ldl = 0;
 };
 
+// The decode attention of one layer as attention.hip's call record: any head width or 64, 16-bit or fp32 caches, one shared
+// prompt (the beams of one utterance: prompt K/V read once, each beam's own rows after it), one per group (the beams of
+// several utterances) or none.  The plain fp32 form at width 64 is vh_attn_decode's call, which takes no workspace size.
+static DecodeAttnCall decoder_attn_call(const vh_ar_decoder_desc& d, const vh_layer& L, void* stream) {
+    const int D = d.d_model, hd = D / d.n_heads;
+    const bool any_width = hd != VH_HEAD_DIM;
+    const int kind = any_width ? ATTN_PREFIX_NONE : d.n_groups > 0 ? ATTN_PREFIX_GROUPS : d.prefix_len > 0 ? ATTN_PREFIX_ONE : ATTN_PREFIX_NONE;
+    const bool sized = any_width || d.kv_bf16 || kind != ATTN_PREFIX_NONE;
+    void* const ws = d.n_split > 1 || kind != ATTN_PREFIX_NONE ? d.attn_partial : nullptr;   // an unsplit call leaves no records
+    const char* const ws_name = any_width                    ? "attn_partial, vh_attn_decode_hd_ws_bytes()"
+                                : kind == ATTN_PREFIX_GROUPS ? "attn_partial, vh_attn_decode_shared_groups_ws_bytes()"
+                                : kind == ATTN_PREFIX_ONE    ? "attn_partial, vh_attn_decode_shared_ws_bytes()"
+                                                             : "attn_partial, vh_attn_decode_ws_bytes()";
+    return DecodeAttnCall{"vh_ar_decoder", ws_name, d.q, D, d.attn, D, d.cache_len, 1, d.B, d.n_heads, any_width, hd,
+                          (float)(1.0 / sqrt((double)hd)), d.kv_bf16 != 0, L.kcache, L.vcache, d.S_max, kind, L.kprefix, L.vprefix,
+                          kind == ATTN_PREFIX_GROUPS ? d.prefix_cap : d.prefix_len, d.prefix_S, d.prefix_lens, d.beams_per_group,
+                          d.n_split, ws, sized ? d.attn_partial_bytes : ATTN_WS_SIZE_NOT_GIVEN, stream};
+}
+
 static int decoder_check(const vh_ar_decoder_desc* d) {
     VH_REQUIRE(d, VH_EINVAL, "vh_ar_decoder: null desc");
     VH_REQUIRE(d->B > 0 && d->B <= 64, VH_EUNSUPPORTED,
@@ -73,11 +92,6 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
                    "vh_ar_decoder: the shared prompt (prefix_len=%d) is width 64 only (head width %d)", d->prefix_len, hd);
         VH_REQUIRE(d->n_groups == 0, VH_EUNSUPPORTED,
                    "vh_ar_decoder: grouped shared prompts (n_groups=%d) are width 64 only (head width %d)", d->n_groups, hd);
-        VH_REQUIRE(d->n_split == 1 ||
-                       (d->attn_partial && d->attn_partial_bytes >= vh_attn_decode_hd_ws_bytes(d->B, d->n_heads, hd, d->n_split)),
-                   VH_EINVAL, "vh_ar_decoder: head width %d with n_split=%d needs attn_partial of vh_attn_decode_hd_ws_bytes() = %zu "
-                   "bytes (got %zu)", hd, d->n_split, vh_attn_decode_hd_ws_bytes(d->B, d->n_heads, hd, d->n_split),
-                   d->attn_partial_bytes);
     } else {
         // width 64: the prompt pass (vh_layernorm) and the folded decode GEMMs end at 4096
         VH_REQUIRE(d->d_model <= 4096, VH_EUNSUPPORTED, "vh_ar_decoder: d_model=%d: the cached decoder serves d_model <= 4096",
@@ -88,7 +102,6 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
     VH_REQUIRE(d->proj_w && d->audio_emb && d->audio_pe && d->x && d->q && d->attn && d->hidden &&
                    d->logits && d->cache_len && d->audio_pos && d->eos_count && d->codes,
                VH_EINVAL, "vh_ar_decoder: null buffer in desc");
-    VH_REQUIRE(d->n_split == 1 || d->attn_partial, VH_EINVAL, "vh_ar_decoder: n_split>1 needs attn_partial");
     VH_REQUIRE(d->prefix_len >= 0, VH_EINVAL, "vh_ar_decoder: prefix_len=%d", d->prefix_len);
     if (d->ffn_ws) {
         VH_REQUIRE(d->ffn_ws_bytes >= vh_ffn_decode_ws_bytes(d->B, d->d_model, d->dff) && d->ffn_ws_bytes > 0, VH_EINVAL,
@@ -102,22 +115,8 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
                    d->d_model);
         for (int i = 0; i < d->n_layers; ++i)
             VH_REQUIRE(d->layers[i].wqkv_f, VH_EINVAL, "vh_ar_decoder: the bf16 K/V cache needs folded weights (layer %d)", i);
-        VH_REQUIRE(d->n_split <= 16, VH_EUNSUPPORTED, "vh_ar_decoder: the bf16 K/V cache serves n_split 1..16 (got %d)", d->n_split);
-        // key splits over the 16-bit cache (vh_attn_decode_kv16_split); a shared prompt's workspace is checked below
-        VH_REQUIRE(d->n_split == 1 || d->prefix_len > 0 ||
-                       (d->attn_partial && d->attn_partial_bytes >= vh_attn_decode_ws_bytes(d->B, d->n_heads, d->n_split)),
-                   VH_EINVAL, "vh_ar_decoder: the bf16 K/V cache with n_split=%d needs attn_partial of vh_attn_decode_ws_bytes() = "
-                   "%zu bytes (got %zu)", d->n_split, vh_attn_decode_ws_bytes(d->B, d->n_heads, d->n_split), d->attn_partial_bytes);
     }
     if (d->prefix_len > 0) {
-        VH_REQUIRE((d->prefix_len + 31) / 32 + d->n_split <= 256, VH_EUNSUPPORTED,
-                   "vh_ar_decoder: a shared prompt of %d keys with %d suffix splits exceeds the 256 records vh_attn_decode_shared merges",
-                   d->prefix_len, d->n_split);
-        VH_REQUIRE(d->prefix_len <= d->prefix_S && d->attn_partial &&
-                       d->attn_partial_bytes >= vh_attn_decode_shared_ws_bytes(d->B, d->n_heads, d->prefix_len, d->n_split),
-                   VH_EINVAL, "vh_ar_decoder: shared prompt of %d / %d keys needs attn_partial of %zu bytes (got %zu)",
-                   d->prefix_len, d->prefix_S, vh_attn_decode_shared_ws_bytes(d->B, d->n_heads, d->prefix_len, d->n_split),
-                   d->attn_partial_bytes);
         for (int i = 0; i < d->n_layers; ++i)
             VH_REQUIRE(d->layers[i].kprefix && d->layers[i].vprefix, VH_EINVAL,
                        "vh_ar_decoder: shared prompt needs kprefix / vprefix in every layer (layer %d)", i);
@@ -134,18 +133,13 @@ static int decoder_check(const vh_ar_decoder_desc* d) {
         VH_REQUIRE(d->prefix_cap >= 1 && d->prefix_cap <= d->prefix_S && d->prefix_lens, VH_EINVAL,
                    "vh_ar_decoder: grouped shared prompts need prefix_lens and 1 <= prefix_cap=%d <= prefix_S=%d", d->prefix_cap,
                    d->prefix_S);
-        VH_REQUIRE((d->prefix_cap + 31) / 32 + d->n_split <= 256, VH_EUNSUPPORTED,
-                   "vh_ar_decoder: a prefix capacity of %d keys with %d suffix splits exceeds the 256 records "
-                   "vh_attn_decode_shared_groups merges", d->prefix_cap, d->n_split);
-        VH_REQUIRE(d->attn_partial &&
-                       d->attn_partial_bytes >= vh_attn_decode_shared_groups_ws_bytes(d->B, d->n_heads, d->prefix_cap, d->n_split),
-                   VH_EINVAL, "vh_ar_decoder: grouped shared prompts of capacity %d need attn_partial of "
-                   "vh_attn_decode_shared_groups_ws_bytes() = %zu bytes (got %zu)", d->prefix_cap,
-                   vh_attn_decode_shared_groups_ws_bytes(d->B, d->n_heads, d->prefix_cap, d->n_split), d->attn_partial_bytes);
         for (int i = 0; i < d->n_layers; ++i)
             VH_REQUIRE(d->layers[i].kprefix && d->layers[i].vprefix, VH_EINVAL,
                        "vh_ar_decoder: grouped shared prompts need kprefix / vprefix in every layer (layer %d)", i);
     }
+    // the attention's own rules (the n_split range of the cache type, the record bound of a shared prompt, attn_partial and its
+    // size): the check of the call every step will make.  Layer 0 stands for every layer: no pointer is looked at.
+    TRY(vh_internal_attn_decode_check(decoder_attn_call(*d, d->layers[0], nullptr), false));
     VH_REQUIRE(d->top_k == 1 || d->row_sampling || d->temperature > 0.f, VH_EINVAL,
                "vh_ar_decoder: sampling (top_k=%d) needs temperature > 0", d->top_k);
     VH_REQUIRE((d->top_k == 1 && !d->row_sampling) || d->V <= VH_SAMPLE_MAX_V, VH_EUNSUPPORTED,
@@ -192,7 +186,6 @@ extern "C" void vh_ar_decoder_destroy(vh_ar_decoder* dec) {
 // One decode step for every row: x (B,d) holds the new token's embedding on entry and the NEXT
 // token's embedding on exit.  `ev` (optional) brackets each decode-attention launch.
 void vh_internal_attn_decode_events(hipEvent_t start, hipEvent_t stop);   // attention.hip
-void vh_internal_attn_decode_hd_events(hipEvent_t start, hipEvent_t stop);   // attention_hd.hip
 int vh_internal_linear_w16(const float* A, int lda, const uint16_t* W16, const float* bias, const float* residual, int ldr,
                            float* out, int ldo, int M, int N, int K, void* stream);                                   // gemm.hip
 int vh_internal_linear_qkv_folded_kv16_w16(const float* A, int lda, const uint16_t* Wf16, const float* c1, const float* c2,
@@ -230,31 +223,7 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
     const bool ln_apart = D > 1024;
     // decode attention of one layer, optionally bracketed by events (vh_ar_decoder_profile_attn)
     auto attention = [&](const vh_layer& L) -> int {
-        if (hd != VH_HEAD_DIM)
-            return vh_attn_decode_hd(d.q, D, L.kcache, L.vcache, d.attn, D, d.cache_len, 1, B, d.n_heads, hd, d.S_max,
-                                     (float)(1.0 / sqrt((double)hd)), d.n_split, d.attn_partial, d.attn_partial_bytes, s);
-        if (d.kv_bf16 && d.prefix_len > 0)   // perf mode over a shared prompt: 16-bit prefix and suffix caches
-            return vh_attn_decode_shared_kv16(d.q, D, (const uint16_t*)L.kprefix, (const uint16_t*)L.vprefix, d.prefix_len,
-                                              d.prefix_S, (const uint16_t*)L.kcache, (const uint16_t*)L.vcache, d.attn, D,
-                                              d.cache_len, 1, B, d.n_heads, d.S_max, d.n_split, d.attn_partial,
-                                              d.attn_partial_bytes, s);
-        if (d.kv_bf16 && d.n_split > 1)
-            return vh_attn_decode_kv16_split(d.q, D, (const uint16_t*)L.kcache, (const uint16_t*)L.vcache, d.attn, D,
-                                             d.cache_len, 1, B, d.n_heads, d.S_max, d.n_split, d.attn_partial,
-                                             d.attn_partial_bytes, s);
-        if (d.kv_bf16)
-            return vh_attn_decode_kv16(d.q, D, (const uint16_t*)L.kcache, (const uint16_t*)L.vcache, d.attn, D, d.cache_len,
-                                       1, B, d.n_heads, d.S_max, s);
-        if (d.n_groups > 0)          // the beams of several utterances: each group's prompt K/V read once for its beams
-            return vh_attn_decode_shared_groups(d.q, D, L.kprefix, L.vprefix, d.prefix_lens, d.prefix_cap, d.prefix_S, L.kcache,
-                                                L.vcache, d.attn, D, d.cache_len, 1, B, d.beams_per_group, d.n_heads, d.S_max,
-                                                d.n_split, d.attn_partial, d.attn_partial_bytes, s);
-        if (d.prefix_len > 0)        // the beams of one utterance: prompt K/V read once, each beam's own rows after it
-            return vh_attn_decode_shared(d.q, D, L.kprefix, L.vprefix, d.prefix_len, d.prefix_S, L.kcache, L.vcache, d.attn, D,
-                                         d.cache_len, 1, B, d.n_heads, d.S_max, d.n_split, d.attn_partial,
-                                         d.attn_partial_bytes, s);
-        return vh_attn_decode(d.q, D, L.kcache, L.vcache, d.attn, D, d.cache_len, 1, B, d.n_heads, d.S_max, d.n_split,
-                              d.attn_partial, s);
+        return vh_internal_attn_decode(decoder_attn_call(d, L, s));
     };
     auto run_attention = [&](const vh_layer& L) -> int {
         if (!ev) return attention(L);
@@ -266,7 +235,6 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         hipEvent_t k0 = nullptr, k1 = nullptr;
         if (kev && hipEventCreate(&k0) == hipSuccess && hipEventCreate(&k1) == hipSuccess) {
             vh_internal_attn_decode_events(k0, k1);
-            vh_internal_attn_decode_hd_events(k0, k1);
             kev->push_back(k0);
             kev->push_back(k1);
         }
@@ -274,7 +242,6 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
         const int arc = attention(L);
         (void)hipEventRecord(e1, s);
         vh_internal_attn_decode_events(nullptr, nullptr);
-        vh_internal_attn_decode_hd_events(nullptr, nullptr);
         ev->push_back(e0);
         ev->push_back(e1);
         return arc;

@@ -98,6 +98,35 @@ static inline bool vh_aligned16(const void* p) { return (reinterpret_cast<uintpt
 // tuning knobs (vh_set_tuning); 0 = built-in default
 int vh_tuning(int knob);
 
+// ---- decode attention: one call record behind the seven vh_attn_decode* entry points and the decoder (attention.hip) ----
+#define VH_HEAD_DIM_MAX 256                      // widest head of the any-width decode attention (attention_hd.hip)
+enum { ATTN_PREFIX_NONE = 0, ATTN_PREFIX_ONE = 1, ATTN_PREFIX_GROUPS = 2 };
+#define ATTN_WS_SIZE_NOT_GIVEN SIZE_MAX          // vh_attn_decode takes a workspace without its size
+struct DecodeAttnCall {
+    const char* name;                            // the entry point, for messages
+    const char* ws_name;                         // what the caller calls the workspace ("partial", "attn_partial")
+    const float* q; int ldq;
+    float* out; int ldo;
+    const int32_t* len; int len_bias;            // keys of row b in its own cache: len[b] + len_bias
+    int B, n_heads;
+    bool any_width;                              // the kernels of attention_hd.hip (head_dim, scale); otherwise width 64
+    int head_dim; float scale;
+    bool kv16;                                   // 16-bit caches (fp32 otherwise)
+    const void* k; const void* v; int S_max;     // the rows' own cache (B, h, S_max, head_dim)
+    int prefix_kind;                             // ATTN_PREFIX_*: no shared prompt, one for all rows, one per group of `beams` rows
+    const void* kprefix; const void* vprefix;
+    int prefix, prefix_S;                        // ONE: the prompt's keys; GROUPS: the capacity; of prefix_S cache rows
+    const int32_t* group_len; int beams;         // GROUPS only
+    int n_split;
+    void* ws; size_t ws_bytes;                   // ATTN_WS_SIZE_NOT_GIVEN: only the pointer is checked
+    void* stream;
+};
+// every rule of the seven entry points, each once; pointers = false skips the null and alignment rules (the decoder's
+// descriptor check: nothing is dereferenced either way)
+int vh_internal_attn_decode_check(const DecodeAttnCall& c, bool pointers);
+// check -> plan -> launch
+int vh_internal_attn_decode(const DecodeAttnCall& c);
+
 // ---- device side -----------------------------------------------------------------------------
 // Cross-lane reductions on DPP (data-parallel primitives): one VALU instruction per step and no
 // LDS crossbar traffic (ds_bpermute), which matters twice here: the decode kernels are latency

@@ -523,9 +523,6 @@ def _transformer_forward_generic(transformer, x, *, mode, x_len, x_len_dev, kv_l
     return x
 
 
-SHARED_MAX_RECORDS = 256          # vh_attn_decode_shared: prefix blocks of 32 keys + suffix splits one merge launch serves
-
-
 def shared_n_split(batch: int, n_heads: int) -> int:
     """Key splits of the beams' own rows under a shared prompt (two workgroups per CU keep twice the loads in flight:
     profiles/r5_ab_shared_prompt.log).  VALLE2_SHARED_SPLIT: the A/B knob."""
@@ -535,7 +532,7 @@ def shared_n_split(batch: int, n_heads: int) -> int:
 def shared_prompt_fits(batch: int, n_heads: int, prefix_len: int) -> bool:
     """Whether vh_attn_decode_shared takes a prompt of prefix_len keys for `batch` beams (its merge serves at most 256
     records per (row, head): ceil(prefix_len / 32) prefix blocks + the suffix splits) — 4 beams x 8 heads: up to 7680 keys."""
-    return (prefix_len + 31) // 32 + shared_n_split(batch, n_heads) <= SHARED_MAX_RECORDS
+    return _lib.attn_decode_form(_lib.ATTN_ENTRY_SHARED, batch, n_heads, shared_n_split(batch, n_heads), prefix=prefix_len) is not None
 
 
 GROUP_PREFIX_STEP = 128           # grouped shared prompts: the prefix capacity is the longest prompt rounded up to this many keys
@@ -550,7 +547,7 @@ def group_prefix_cap(longest: int) -> int:
 
 def grouped_prompts_fit(batch: int, n_heads: int, prefix_cap: int) -> bool:
     """`shared_prompt_fits` for vh_attn_decode_shared_groups: the record slots of the prefix CAPACITY + the suffix splits."""
-    return (prefix_cap + 31) // 32 + shared_n_split(batch, n_heads) <= SHARED_MAX_RECORDS
+    return _lib.attn_decode_form(_lib.ATTN_ENTRY_SHARED_GROUPS, batch, n_heads, shared_n_split(batch, n_heads), prefix=prefix_cap) is not None
 
 
 # ---- queued decoding (ValleAR.generate_queued): which utterance holds which slot between which polls -------------------------
