@@ -16,8 +16,10 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+import typing
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib, kernels
@@ -207,7 +209,6 @@ def adaln_table(transformer, embedding):
     tensor's entry dies with it, and a recycled address can never alias a live entry) and reused while neither that
     tensor's version, nor any projection parameter's, nor the weights epoch (flat optimizer steps) has moved — the 7
     stages of ValleNAR.generate_batch build 7 tables once, not 7 per call."""
-    import numpy as np
     layers = list(transformer.layers)
     d = embedding.shape[-1]
     projs = [(n.project_layer.weight, n.project_layer.bias) for l in layers for n in (l.norm1, l.norm2)]
@@ -318,6 +319,48 @@ def perf_forward_supported(cfg):
     return cfg.d_model == cfg.n_heads * HEAD_DIM and cfg.d_model % 128 == 0 and cfg.dim_feedforward % 128 == 0
 
 
+def _adaln(transformer, embedding):
+    """The stack's `adaln_table` for `embedding`; None for a stack of plain LayerNorms."""
+    if transformer.hparams.norm == 'LayerNorm':
+        return None
+    if embedding is None:
+        raise TypeError('AdaptiveLayerNorm needs `embedding` (reference: Linear(None) TypeError)')
+    return adaln_table(transformer, embedding)
+
+
+def _check_x(x):
+    if not x.is_contiguous() or x.dtype != torch.float32:
+        raise _lib.VhError('x must be contiguous fp32')
+
+
+def _check_cache(cache, cfg, batch, rows, *, bf16=None, head=None, text=None):
+    """A forward over `batch` x `rows` writes its K/V to `cache`: refuse one it does not fit.  bf16: the storage the forward
+    writes (None: not looked at); head: the (n_heads, head_dim) it writes (None: not looked at)."""
+    if cache is None or cache.batch != batch or cache.s_max < rows or cache.n_layers != cfg.num_layers or \
+            (bf16 is not None and cache.bf16 != bf16) or (head is not None and (cache.n_heads, cache.head_dim) != head):
+        raise _lib.VhError(text or 'KV cache does not fit this forward')
+
+
+def _forward_front(transformer, x, batch, rows, cache, embedding, scratch, bf16=None):
+    """What the native front-ends do alike once their own refusals have passed: x and the cache checked, the default scratch,
+    and the fields the fp32 and the 16-bit descriptor share.  bf16=True: the perf-mode forward (16-bit cache and scratch, the
+    layer table not bound to the cache).  Returns (scratch, fields)."""
+    cfg = transformer.hparams
+    _check_x(x)
+    _check_cache(cache, cfg, batch, rows, bf16=bf16,
+                 text='perf mode needs a bf16 KV cache that fits this forward' if bf16 else None)
+    d = x.shape[-1]
+    scratch = scratch or (ForwardScratch16 if bf16 else ForwardScratch)(batch * rows, d, cfg.dim_feedforward, x.device)
+    return scratch, dict(B=batch, T=rows, d_model=d, n_heads=cfg.n_heads, dff=cfg.dim_feedforward, n_layers=cfg.num_layers,
+                         S_max=cache.s_max, ln_eps=1e-5, layers=layer_table(transformer, None if bf16 else cache),
+                         ada=ptr(_adaln(transformer, embedding)), x=ptr(x))
+
+
+def _fp32_scratch_fields(scratch):
+    return dict(xn=ptr(scratch.xn), q=ptr(scratch.q), attn=ptr(scratch.attn), hidden=ptr(scratch.hidden),
+                gemm_ws=ptr(scratch.ws), gemm_ws_bytes=scratch.ws_bytes)
+
+
 def transformer_forward_bf16(transformer, x, cache: 'KVCache', *, mode, x_len=0, x_len_dev=None, kv_len=None, embedding=None,
                              scratch=None, x_in=None):
     """`transformer_forward` in PERF MODE (SECONDARY): every product of the stack on the bf16 matrix
@@ -325,30 +368,18 @@ def transformer_forward_bf16(transformer, x, cache: 'KVCache', *, mode, x_len=0,
     masks only.  Teacher-forced logits agree with the reference to 5e-2, not to the parity path's 2e-4."""
     cfg = transformer.hparams
     B, T, d = x.shape
-    if not x.is_contiguous() or x.dtype != torch.float32:
-        raise _lib.VhError('x must be contiguous fp32')
     if not perf_forward_supported(cfg):
         raise _lib.VhError(f'perf mode needs d_model = n_heads x 64 and d_model, dim_feedforward multiples of 128 '
                            f'(got {cfg.d_model}, {cfg.n_heads}, {cfg.dim_feedforward})')
-    if cache is None or not cache.bf16 or cache.batch != B or cache.s_max < T or cache.n_layers != cfg.num_layers:
-        raise _lib.VhError('perf mode needs a bf16 KV cache that fits this forward')
-    scratch = scratch or ForwardScratch16(B * T, d, cfg.dim_feedforward, x.device)
-    w16 = bf16_weights(transformer)
-    table = layer_table(transformer, None)
+    scratch, common = _forward_front(transformer, x, B, T, cache, embedding, scratch, bf16=True)
     t16 = (_lib.VhLayer16 * cfg.num_layers)()
-    for i, (wq, wo, w1, w2) in enumerate(w16):
+    for i, (wq, wo, w1, w2) in enumerate(bf16_weights(transformer)):
         t16[i].wqkv, t16[i].wo, t16[i].w1, t16[i].w2 = wq.data_ptr(), wo.data_ptr(), w1.data_ptr(), w2.data_ptr()
         t16[i].kcache16, t16[i].vcache16 = cache.k(i).data_ptr(), cache.v(i).data_ptr()
-    ada = None
-    if cfg.norm != 'LayerNorm':
-        if embedding is None:
-            raise TypeError('AdaptiveLayerNorm needs `embedding` (reference: Linear(None) TypeError)')
-        ada = adaln_table(transformer, embedding)
     desc = _lib.VhForward16Desc(
-        B=B, T=T, d_model=d, n_heads=cfg.n_heads, dff=cfg.dim_feedforward, n_layers=cfg.num_layers, S_max=cache.s_max,
-        mode=mode, x_len=int(x_len), ln_eps=1e-5, layers=table, layers16=t16, ada=ptr(ada), x_len_dev=ptr(x_len_dev),
-        kv_len=ptr(kv_len), x=ptr(x), x_in=ptr(x_in), xn16=scratch.xn.data_ptr(), q16=scratch.q.data_ptr(),
-        attn16=scratch.attn.data_ptr(), hidden16=scratch.hidden.data_ptr())
+        mode=mode, x_len=int(x_len), layers16=t16, x_len_dev=ptr(x_len_dev), kv_len=ptr(kv_len), x_in=ptr(x_in),
+        xn16=scratch.xn.data_ptr(), q16=scratch.q.data_ptr(), attn16=scratch.attn.data_ptr(),
+        hidden16=scratch.hidden.data_ptr(), **common)
     check(_lib.lib().vh_transformer_forward_bf16(C.byref(desc), stream()), 'vh_transformer_forward_bf16')
     return x
 
@@ -384,8 +415,6 @@ def transformer_forward(transformer, x, cache: KVCache, *, mode, x_len=0, x_len_
     read from there and left untouched, x is output only."""
     cfg = transformer.hparams
     B, T, d = x.shape
-    if not x.is_contiguous():
-        raise _lib.VhError('x must be contiguous')
     if x_in is not None and (tuple(x_in.shape) != tuple(x.shape) or x_in.dtype != torch.float32):
         raise _lib.VhError('x_in must match x')
     if d != cfg.n_heads * HEAD_DIM:                          # a head width the native composite is not built for
@@ -393,21 +422,9 @@ def transformer_forward(transformer, x, cache: KVCache, *, mode, x_len=0, x_len_
         kv = cache if cache is not None and getattr(cache, 'head_dim', HEAD_DIM) == d // cfg.n_heads else None
         return _transformer_forward_generic(transformer, x, mode=mode, x_len=x_len, x_len_dev=x_len_dev, kv_len=kv_len,
                                             mask=mask, pad=pad, embedding=embedding, x_in=x_in, cache=kv)
-    if cache is None or cache.batch != B or cache.s_max < T or cache.n_layers != cfg.num_layers:
-        raise _lib.VhError('KV cache does not fit this forward')
-    scratch = scratch or ForwardScratch(B * T, d, cfg.dim_feedforward, x.device)
-    table = layer_table(transformer, cache)
-    ada = None
-    if cfg.norm != 'LayerNorm':
-        if embedding is None:
-            raise TypeError('AdaptiveLayerNorm needs `embedding` (reference: Linear(None) TypeError)')
-        ada = adaln_table(transformer, embedding)
-    desc = VhForwardDesc(
-        B=B, T=T, d_model=d, n_heads=cfg.n_heads, dff=cfg.dim_feedforward, n_layers=cfg.num_layers,
-        S_max=cache.s_max, mode=mode, x_len=int(x_len), ln_eps=1e-5, layers=table, ada=ptr(ada),
-        x_len_dev=ptr(x_len_dev), kv_len=ptr(kv_len), mask=ptr(mask), pad=ptr(pad),
-        x=ptr(x), xn=ptr(scratch.xn), q=ptr(scratch.q), attn=ptr(scratch.attn),
-        hidden=ptr(scratch.hidden), gemm_ws=ptr(scratch.ws), gemm_ws_bytes=scratch.ws_bytes, x_in=ptr(x_in))
+    scratch, common = _forward_front(transformer, x, B, T, cache, embedding, scratch)
+    desc = VhForwardDesc(mode=mode, x_len=int(x_len), x_len_dev=ptr(x_len_dev), kv_len=ptr(kv_len), mask=ptr(mask), pad=ptr(pad),
+                         x_in=ptr(x_in), **_fp32_scratch_fields(scratch), **common)
     check(_lib.lib().vh_transformer_forward(C.byref(desc), stream()), 'vh_transformer_forward')
     return x
 
@@ -446,6 +463,71 @@ class PackedRows:
         self.seg_start, self.seg_len, self.blocks = i32(self.starts), i32(self.lengths), i32(blocks)
 
 
+class NarRows(typing.NamedTuple):
+    """`nar_rows`: where the rows of a NAR batch lie in its one (rows, d) buffer.  Python ints and lists only."""
+    packed: bool
+    lengths: list             # len_b = tx_b + tc_b + ty_b (the packed kind: what `PackedRows` takes)
+    starts: list              # first row of utterance b
+    rows: int
+    t0_prompt: list           # first row of utterance b's acoustic prompt
+    t0_target: list           # ... of its target frames
+    target_rows: list         # the row of every target frame, utterance by utterance and frame by frame
+    logit_starts: list        # where utterance b's run starts in the gathered target rows (B + 1 entries)
+    kv_len: list | None       # the padded kind: every utterance's keys, None where all lengths are equal
+
+
+def nar_rows(txs, tcs, tys, packed: bool) -> NarRows:
+    """The row layout of ValleNAR's stage loop for B utterances [text_b | prompt_b | target_b] of txs[b] + tcs[b] + tys[b]
+    rows (pure Python, no device).  Padded: utterance b at row b * max(len), the rows after its own are padding, each
+    utterance attends its kv_len keys.  Packed: back to back as `pack_plan` lays them out, no padding row.  The padded
+    layout is the packed one with other starts; everything that places a row reads `starts`."""
+    lengths = [int(a) + int(b) + int(c) for a, b, c in zip(txs, tcs, tys)]
+    if packed:
+        starts, rows, _ = pack_plan(lengths)
+    else:
+        starts, rows = [b * max(lengths) for b in range(len(lengths))], len(lengths) * max(lengths)
+    t0_prompt = [s + a for s, a in zip(starts, txs)]
+    t0_target = [s + c for s, c in zip(t0_prompt, tcs)]
+    target_rows, logit_starts = [], [0]
+    for t0, ty in zip(t0_target, tys):
+        target_rows.extend(range(t0, t0 + ty))
+        logit_starts.append(logit_starts[-1] + ty)
+    return NarRows(packed, lengths, starts, rows, t0_prompt, t0_target, target_rows, logit_starts,
+                   lengths if not packed and len(set(lengths)) > 1 else None)
+
+
+class NarLayout:
+    """`nar_rows` on the device, its int32 tensors uploaded once per call, and what depends on the kind of layout: the K/V
+    cache and scratch a stack forward over the buffer needs, whether the buffer's rows must start as zeros (the padded
+    kind's padding rows are read by the row-wise kernels; the packed kind writes every row) and the forward itself."""
+
+    def __init__(self, txs, tcs, tys, packed, device):
+        p = self.plan = nar_rows(txs, tcs, tys, packed)
+        i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), device)   # noqa: E731
+        self.device, self.rows, self.zeroed = device, p.rows, not packed
+        self.segments = PackedRows(p.lengths, device) if packed else None
+        self.t0_text = self.segments.seg_start if packed else i32(p.starts)
+        self.t0_prompt, self.t0_target = i32(p.t0_prompt), i32(p.t0_target)
+        # (through numpy: torch.tensor() of a 40 k-entry list costs twice as long on the host)
+        self.target_rows = _lib.to_device_async(torch.from_numpy(np.array(p.target_rows, dtype=np.int64)), device)
+        self.kv_len = None if p.kv_len is None else i32(p.kv_len)
+
+    def cache_and_scratch(self, cfg, perf_mode=False):
+        """(KVCache, scratch) of one stack forward over the buffer: (1, rows) fp32 packed, (B, max(len)) padded — 16-bit in
+        perf mode, which the packed kind does not have."""
+        B = 1 if self.segments else len(self.plan.lengths)
+        cache = KVCache(cfg.num_layers, B, cfg.n_heads, self.rows // B, self.device, dtype=kernels.H16 if perf_mode else torch.float32)
+        return cache, (ForwardScratch16 if perf_mode else ForwardScratch)(self.rows, cfg.d_model, cfg.dim_feedforward, self.device)
+
+    def forward(self, transformer, x, cache, scratch, embedding):
+        """The stack under the full mask over x (rows, d) in place, every utterance attending its own rows."""
+        if self.segments:
+            return transformer_forward_packed(transformer, x, cache, self.segments, embedding=embedding, scratch=scratch)
+        forward = transformer_forward_bf16 if cache.bf16 else transformer_forward
+        return forward(transformer, x.view(cache.batch, -1, x.shape[-1]), cache, mode=kernels.MASK_FULL, kv_len=self.kv_len,
+                       embedding=embedding, scratch=scratch)
+
+
 def transformer_forward_packed(transformer, x, cache: KVCache, rows: PackedRows, embedding=None, scratch=None):
     """`transformer_forward(mode=MASK_FULL)` of a ragged batch over PACKED rows: x (M, d) holds utterance b at rows
     rows.starts[b] .. + rows.lengths[b] - 1 and is updated in place; each utterance attends its own rows only
@@ -455,26 +537,12 @@ def transformer_forward_packed(transformer, x, cache: KVCache, rows: PackedRows,
     if x.dim() != 2:
         raise _lib.VhError(f'transformer_forward_packed: x must be (M, d), got {tuple(x.shape)}')
     M, d = x.shape
-    if not x.is_contiguous():
-        raise _lib.VhError('x must be contiguous')
     if d != cfg.n_heads * HEAD_DIM:
         raise _lib.VhError(f'transformer_forward_packed: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
     if M != rows.rows:
         raise _lib.VhError(f'transformer_forward_packed: x has {M} rows, the packed rows {rows.rows}')
-    if cache is None or cache.batch != 1 or cache.s_max < M or cache.n_layers != cfg.num_layers or cache.bf16:
-        raise _lib.VhError('KV cache does not fit this forward')
-    scratch = scratch or ForwardScratch(M, d, cfg.dim_feedforward, x.device)
-    table = layer_table(transformer, cache)
-    ada = None
-    if cfg.norm != 'LayerNorm':
-        if embedding is None:
-            raise TypeError('AdaptiveLayerNorm needs `embedding` (reference: Linear(None) TypeError)')
-        ada = adaln_table(transformer, embedding)
-    desc = VhForwardDesc(
-        B=1, T=M, d_model=d, n_heads=cfg.n_heads, dff=cfg.dim_feedforward, n_layers=cfg.num_layers,
-        S_max=cache.s_max, mode=kernels.MASK_FULL, x_len=0, ln_eps=1e-5, layers=table, ada=ptr(ada),
-        x=ptr(x), xn=ptr(scratch.xn), q=ptr(scratch.q), attn=ptr(scratch.attn),
-        hidden=ptr(scratch.hidden), gemm_ws=ptr(scratch.ws), gemm_ws_bytes=scratch.ws_bytes)
+    scratch, common = _forward_front(transformer, x, 1, M, cache, embedding, scratch, bf16=False)
+    desc = VhForwardDesc(mode=kernels.MASK_FULL, x_len=0, **_fp32_scratch_fields(scratch), **common)
     check(_lib.lib().vh_transformer_forward_packed(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg,
                                                    ptr(rows.blocks), rows.n_blocks, stream()),
           'vh_transformer_forward_packed')
@@ -494,14 +562,10 @@ def _transformer_forward_generic(transformer, x, *, mode, x_len, x_len_dev, kv_l
     hd = d // h
     if hd % 4:
         raise _lib.VhError(f'head_dim {hd}: the general attention path needs a multiple of 4')
-    if cache is not None and (cache.bf16 or cache.head_dim != hd or cache.batch != B or cache.s_max < T
-                              or cache.n_layers != cfg.num_layers or cache.n_heads != h):
-        raise _lib.VhError('KV cache does not fit this forward')
-    ada = None
-    if cfg.norm != 'LayerNorm':
-        if embedding is None:
-            raise TypeError('AdaptiveLayerNorm needs `embedding` (reference: Linear(None) TypeError)')
-        ada = adaln_table(transformer, embedding)
+    _check_x(x)
+    if cache is not None:
+        _check_cache(cache, cfg, B, T, bf16=False, head=(h, hd))
+    ada = _adaln(transformer, embedding)
     cur = (x_in if x_in is not None else x).reshape(B * T, d)
     spec = dict(mode=mode, x_len=int(x_len), x_len_dev=x_len_dev, kv_len=kv_len, mask=mask, pad=pad)
     f32 = dict(device=x.device, dtype=torch.float32)

@@ -17,8 +17,7 @@ import torch.nn as nn
 
 from . import _lib, dropout, kernels
 from . import sampling as _sampling
-from .engine import (ForwardScratch, ForwardScratch16, KVCache, PackedRows, head16, transformer_forward, transformer_forward_bf16,
-                     transformer_forward_packed)
+from .engine import KVCache, NarLayout, head16, transformer_forward, transformer_forward_bf16
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device
 from .valle_ar import _Base
 
@@ -228,7 +227,8 @@ class ValleNAR(_Base):
                                    sampling=None if sampling is None else [sampling])[0]
 
     def _ragged_inputs(self, name, dev, texts, prompt_codes, first_layers):
-        """The input checks of `generate_batch` / `generate_packed`: the three id lists on the device and their lengths."""
+        """The input checks of `generate_batch` / `generate_packed`: the three id lists on the device, and their lengths
+        (txs, tcs, tys)."""
         cfg = self.config
         B = len(texts)
         if B == 0 or len(prompt_codes) != B or len(first_layers) != B:
@@ -243,7 +243,7 @@ class ValleNAR(_Base):
         if max(tc + ty for tc, ty in zip(tcs, tys)) > self.audio_position_emb.pe.shape[0] or \
                 max(txs) > self.tokens_position_emb.pe.shape[0]:
             raise _lib.VhError('sequence exceeds the positional table (max_len 5000)')
-        return texts, pcs, firsts, txs, tcs, tys
+        return (texts, pcs, firsts), (txs, tcs, tys)
 
     @_sampling_refused_early
     @_on_device
@@ -255,12 +255,12 @@ class ValleNAR(_Base):
         prompt; first_layers[b]: (Ty_b,) int64 first-codebook codes of the target (the AR model's
         output).  Rows may differ in every length.  Returns a list of (Ty_b, Q) int64 device tensors.
 
-        Row b is laid out [text_b | prompt_b | target_b | padding]; attention is full over the row's
-        own length (per-row key length in the kernel, nothing materialised).  Per stage n = 1..Q-1
-        (valle_nar.py:142-160): the target frames carry sum_{j<n} codes_embs[j](out[j]) + PE, one stack
-        forward with AdaLN on stage_embs[n-1], head proj_layers[n-1] on the target frames of all rows at
-        once, and codebook n is drawn on the device by `vh_categorical_rows` (Categorical(logits /
-        temperature), or the arg-max when greedy).
+        Utterance b's rows [text_b | prompt_b | target_b] lie in one (rows, d) buffer, here PADDED to the longest
+        (`engine.nar_rows`); attention is full over the utterance's own length (per-row key length in the kernel, nothing
+        materialised).  Per stage n = 1..Q-1 (valle_nar.py:142-160): the target frames carry sum_{j<n} codes_embs[j](out[j]) +
+        PE, one stack forward with AdaLN on stage_embs[n-1], head proj_layers[n-1] on the target frames of all utterances at
+        once, and codebook n is drawn on the device by `vh_categorical_rows` (Categorical(logits / temperature), or the
+        arg-max when greedy).
         perf_mode=True: the seven stack forwards on the bf16 matrix cores (see `stage_logits`); the drawn codes are then not
         guaranteed to be the parity path's.
         sampling (keyword-only): a list with one valle2_amd.Sampling per utterance (every entry or None).  Frame t of codebook
@@ -271,68 +271,8 @@ class ValleNAR(_Base):
         between two calls only where the utterance's own logits do.  greedy=True makes every request greedy; refused with
         seed= (ValueError)."""
         dev = self._dev()
-        cfg = self.config
-        q, d = cfg.num_quantizers, cfg.d_model
-        B = len(texts)
-        texts, pcs, firsts, txs, tcs, tys = self._ragged_inputs('generate_batch', dev, texts, prompt_codes, first_layers)
-        lens = [a + b + c for a, b, c in zip(txs, tcs, tys)]
-        total = max(lens)
-        pe_a, pe_t = self.audio_position_emb.pe, self.tokens_position_emb.pe
-        ty_max = max(tys)
-        pad = torch.nn.utils.rnn.pad_sequence                      # index plumbing: ragged id lists -> padded id tensors
-        i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), dev)   # noqa: E731
-        out = torch.zeros(B, ty_max, q, device=dev, dtype=torch.int64)
-        out[:, :, 0] = pad(firsts, batch_first=True)
-        tx_d, tc_d, ty_d = i32(txs), i32(tcs), i32(tys)
-        t0_target = i32([a + c for a, c in zip(txs, tcs)])
-        valid = torch.arange(ty_max, device=dev)[None, :] < ty_d[:, None]          # (B, ty_max) target frames that exist
-        # text and acoustic-prompt embeddings do not change from stage to stage: build them once, ONE launch each for
-        # the whole ragged batch (per-row lengths and offsets travel to the kernel)
-        base = torch.zeros(B, total, d, device=dev, dtype=torch.float32)
-        kernels.embed_sum_pe(pad(texts, batch_first=True), [self.tokens_emb.weight.detach()], pe_t, 0, base, lens=tx_d,
-                             row_t0=torch.zeros_like(tx_d), max_pos=max(txs))
-        if max(tcs):
-            kernels.embed_sum_pe(pad(pcs, batch_first=True), self._tables(q), pe_a, 0, base, lens=tc_d, row_t0=tx_d,
-                                 max_pos=max(tcs))
-        kv_len = i32(lens) if len(set(lens)) > 1 else None
-        # flat row indices of every target frame, and where each row's run starts in the packed logits
-        idx = torch.cat([torch.arange(tys[b], device=dev) + (b * total + txs[b] + tcs[b]) for b in range(B)])
-        starts = [0]
-        for ty in tys:
-            starts.append(starts[-1] + ty)
-        cache = KVCache(cfg.num_layers, B, cfg.n_heads, total, dev, dtype=kernels.H16 if perf_mode else torch.float32)
-        scratch = (ForwardScratch16 if perf_mode else ForwardScratch)(B * total, d, cfg.dim_feedforward, dev)
-        forward = transformer_forward_bf16 if perf_mode else transformer_forward
-        x = torch.empty_like(base)
-        sampling = _sampling.check_list('generate_batch', sampling, B)
-        if sampling is not None:
-            # one record per utterance and the (utterance, frame) of every packed row, once per call
-            records = [s.nar_record(cfg) for s in sampling]
-            if greedy:
-                records = [(sd, key, 1, top_p, temperature) for sd, key, _, top_p, temperature in records]
-            requests = _lib.to_device_async(kernels.pack_row_sampling(records), dev)
-            row_request = i32([b for b in range(B) for _ in range(tys[b])])
-            row_key = i32([t for b in range(B) for t in range(tys[b])])
-        else:
-            if seed is None:       # drawn from torch's generator, so torch.manual_seed() makes a run repeatable
-                seed = 0 if greedy else int(torch.randint(0, 2 ** 62, (1,)).item())
-            toks = torch.empty(starts[-1], device=dev, dtype=torch.int64)
-        for n in range(1, q):
-            x.copy_(base)
-            kernels.embed_sum_pe(out, self._tables(n), pe_a, 0, x, lens=ty_d, row_pos0=tc_d, row_t0=t0_target,
-                                 max_pos=max(tc + ty for tc, ty in zip(tcs, tys)))
-            forward(self.transformer, x, cache, mode=kernels.MASK_FULL, kv_len=kv_len,
-                    embedding=self.stage_embs[n - 1].weight, scratch=scratch)                # (cached AdaLN table per stage)
-            z = x.view(B * total, d).index_select(0, idx)                      # target frames of every row
-            logits = self._head(z, n, perf_mode)
-            if sampling is not None:
-                kernels.categorical_rows_keyed(logits, out[:, :, n], requests, row_request, row_key, _sampling.NAR_STREAM | n)
-                continue
-            kernels.categorical_rows(logits, toks, temperature=cfg.temperature, greedy=greedy, seed=seed,
-                                     stream_id=n)
-            out[:, :, n][valid] = toks                                          # packed row-major -> (B, ty_max)
-        _lib.raise_device_errors(dev)
-        return [out[b, :tys[b]].clone() for b in range(B)]
+        ids, lens = self._ragged_inputs('generate_batch', dev, texts, prompt_codes, first_layers)
+        return self._generate_stages('generate_batch', NarLayout(*lens, False, dev), ids, lens, greedy, seed, sampling, perf_mode)
 
     @_packed_width_refused_early
     @_sampling_refused_early
@@ -342,21 +282,25 @@ class ValleNAR(_Base):
         """`generate_batch` computed over PACKED rows: same inputs, checks, return value and sampling semantics (see there),
         fp32 only (no perf_mode), head width 64 only (ValueError otherwise, before any device work).
 
-        The B utterances lie back to back in ONE (M, d) buffer, M = sum of the row lengths, utterance b —
-        [text_b | prompt_b | target_b] — at rows start_b .. start_b + len_b - 1 (`engine.pack_plan`); there is no padding
-        row.  LayerNorm, the GEMMs and the K/V append run over the M rows as one sequence; the attention runs each
-        utterance over its own rows (`vh_attn_rows_packed`), so a ragged batch computes sum(len_b) rows and
-        sum(len_b^2) scores where generate_batch computes B max(len) and max(len) sum(len_b).  The packed logits rows keep
-        generate_batch's order, utterance by utterance and frame by frame: the draws are keyed as there.  The GEMMs see
-        another row count than the padded form's, so logits agree with it to summation order, not to the bit; a greedy
-        token can differ where the two leading logits are closer than that."""
+        The utterances lie back to back, no padding row (`engine.nar_rows`, packed).  LayerNorm, the GEMMs and the K/V append
+        run over the M = sum(len_b) rows as one sequence; the attention runs each utterance over its own rows
+        (`vh_attn_rows_packed`), so a ragged batch computes sum(len_b) rows and sum(len_b^2) scores where generate_batch
+        computes B max(len) and max(len) sum(len_b).  The GEMMs see another row count than the padded form's, so logits agree
+        with it to summation order, not to the bit; a greedy token can differ where the two leading logits are closer than
+        that."""
         dev = self._dev()
+        ids, lens = self._ragged_inputs('generate_packed', dev, texts, prompt_codes, first_layers)
+        return self._generate_stages('generate_packed', NarLayout(*lens, True, dev), ids, lens, greedy, seed, sampling)
+
+    def _generate_stages(self, name, layout, ids, lens, greedy, seed, sampling, perf_mode=False):
+        """The stage loop of `generate_batch` / `generate_packed` over `layout` (an engine.NarLayout of `lens`): the only
+        difference between the two is where a row lies and which forward runs over the buffer, and the layout knows both.
+        The gathered target rows, hence the logits rows and the draws' keys, are utterance by utterance and frame by frame
+        under either layout."""
         cfg = self.config
         q, d = cfg.num_quantizers, cfg.d_model
-        B = len(texts)
-        texts, pcs, firsts, txs, tcs, tys = self._ragged_inputs('generate_packed', dev, texts, prompt_codes, first_layers)
-        rows = PackedRows([a + b + c for a, b, c in zip(txs, tcs, tys)], dev)
-        M = rows.rows
+        (texts, pcs, firsts), (txs, tcs, tys) = ids, lens
+        B, dev = len(texts), layout.device
         pe_a, pe_t = self.audio_position_emb.pe, self.tokens_position_emb.pe
         ty_max = max(tys)
         pad = torch.nn.utils.rnn.pad_sequence                      # index plumbing: ragged id lists -> padded id tensors
@@ -364,27 +308,20 @@ class ValleNAR(_Base):
         out = torch.zeros(B, ty_max, q, device=dev, dtype=torch.int64)
         out[:, :, 0] = pad(firsts, batch_first=True)
         tx_d, tc_d, ty_d = i32(txs), i32(tcs), i32(tys)
-        t0_prompt = i32([s + a for s, a in zip(rows.starts, txs)])
-        t0_target = i32([s + a + c for s, a, c in zip(rows.starts, txs, tcs)])
         valid = torch.arange(ty_max, device=dev)[None, :] < ty_d[:, None]          # (B, ty_max) target frames that exist
-        # text and acoustic-prompt embeddings, once per call and ONE launch each for the whole batch: row_t0 places
-        # utterance b's rows at its packed start (every row of `base` but the target frames' is written here)
-        base = torch.empty(M, d, device=dev, dtype=torch.float32)
+        # text and acoustic-prompt embeddings do not change from stage to stage: build them once, ONE launch each for
+        # the whole ragged batch (per-utterance lengths and first rows travel to the kernel)
+        base = (torch.zeros if layout.zeroed else torch.empty)(layout.rows, d, device=dev, dtype=torch.float32)
         kernels.embed_sum_pe(pad(texts, batch_first=True), [self.tokens_emb.weight.detach()], pe_t, 0, base, lens=tx_d,
-                             row_t0=rows.seg_start, max_pos=max(txs))
+                             row_t0=layout.t0_text, max_pos=max(txs))
         if max(tcs):
-            kernels.embed_sum_pe(pad(pcs, batch_first=True), self._tables(q), pe_a, 0, base, lens=tc_d, row_t0=t0_prompt,
+            kernels.embed_sum_pe(pad(pcs, batch_first=True), self._tables(q), pe_a, 0, base, lens=tc_d, row_t0=layout.t0_prompt,
                                  max_pos=max(tcs))
-        # packed row of every target frame, and where each utterance's run starts in the packed logits
-        idx = torch.cat([torch.arange(tys[b], device=dev) + (rows.starts[b] + txs[b] + tcs[b]) for b in range(B)])
-        starts = [0]
-        for ty in tys:
-            starts.append(starts[-1] + ty)
-        cache = KVCache(cfg.num_layers, 1, cfg.n_heads, M, dev)
-        scratch = ForwardScratch(M, d, cfg.dim_feedforward, dev)
+        cache, scratch = layout.cache_and_scratch(cfg, perf_mode)
         x = torch.empty_like(base)
-        sampling = _sampling.check_list('generate_packed', sampling, B)
+        sampling = _sampling.check_list(name, sampling, B)
         if sampling is not None:
+            # one record per utterance and the (utterance, frame) of every logits row, once per call
             records = [s.nar_record(cfg) for s in sampling]
             if greedy:
                 records = [(sd, key, 1, top_p, temperature) for sd, key, _, top_p, temperature in records]
@@ -394,20 +331,19 @@ class ValleNAR(_Base):
         else:
             if seed is None:       # drawn from torch's generator, so torch.manual_seed() makes a run repeatable
                 seed = 0 if greedy else int(torch.randint(0, 2 ** 62, (1,)).item())
-            toks = torch.empty(starts[-1], device=dev, dtype=torch.int64)
+            toks = torch.empty(layout.plan.logit_starts[-1], device=dev, dtype=torch.int64)
         for n in range(1, q):
             x.copy_(base)
-            kernels.embed_sum_pe(out, self._tables(n), pe_a, 0, x, lens=ty_d, row_pos0=tc_d, row_t0=t0_target,
+            kernels.embed_sum_pe(out, self._tables(n), pe_a, 0, x, lens=ty_d, row_pos0=tc_d, row_t0=layout.t0_target,
                                  max_pos=max(tc + ty for tc, ty in zip(tcs, tys)))
-            transformer_forward_packed(self.transformer, x, cache, rows, embedding=self.stage_embs[n - 1].weight,
-                                       scratch=scratch)
-            z = x.index_select(0, idx)                                          # target frames of every utterance
-            logits = self._head(z, n, False)
+            layout.forward(self.transformer, x, cache, scratch, self.stage_embs[n - 1].weight)   # (cached AdaLN table per stage)
+            z = x.index_select(0, layout.target_rows)                           # target frames of every utterance
+            logits = self._head(z, n, perf_mode)
             if sampling is not None:
                 kernels.categorical_rows_keyed(logits, out[:, :, n], requests, row_request, row_key, _sampling.NAR_STREAM | n)
                 continue
             kernels.categorical_rows(logits, toks, temperature=cfg.temperature, greedy=greedy, seed=seed,
                                      stream_id=n)
-            out[:, :, n][valid] = toks                                          # packed row-major -> (B, ty_max)
+            out[:, :, n][valid] = toks                                          # logits rows -> (B, ty_max)
         _lib.raise_device_errors(dev)
         return [out[b, :tys[b]].clone() for b in range(B)]
