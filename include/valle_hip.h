@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 139            /* 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 140            /* 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -994,6 +994,35 @@ typedef struct {
     uint16_t *xn16, *q16, *attn16, *hidden16;
 } vh_forward16_desc;
 int vh_transformer_forward_bf16(const vh_forward16_desc* desc, void* stream);
+
+/* vh_attn_rows_bf16 over the SEGMENTS of one packed row stream, VH_MASK_FULL only: vh_attn_rows_packed in the 16-bit format.
+ * Utterance s owns rows seg_start[s] .. seg_start[s] + seg_len[s] - 1 of q' (M, ldq; PRE-SCALED as for vh_attn_rows_bf16), of
+ * out (M, ldo) and of ONE 16-bit K/V stream per head, kcache16 / vcache16 (1, h, S_max >= M, 64), M = the sum of the lengths:
+ * query row seg_start[s] + i attends keys seg_start[s] + j, j < seg_len[s], of the same cache and nothing else.  One
+ * workgroup = the 128 queries from blocks[2 i + 1] on of segment blocks[2 i] x one head, over that segment's keys in 64-key
+ * tiles counted from the segment's key 0 — vh_attn_rows_bf16's tile order, and its arithmetic, for that utterance alone
+ * (B = 1, Tq = Tk = seg_len[s], full mask): the same bits.  K/V rows past a segment's end are clamped to its last row and
+ * masked (a tail tile re-reads the segment's own last row, never a row of the next segment or one at or beyond M); query
+ * rows past it are not stored.  Workgroups run in table order, workgroup id = block * n_heads + head: list the blocks of the
+ * longest segment first.  ldq, ldo: multiples of 8, >= n_heads * 64; q, out and the caches 16-byte aligned.
+ * seg_start, seg_len (n_seg) and blocks (n_blocks pairs) are DEVICE int32 arrays the host cannot check: the caller vouches
+ * that the segments are disjoint and inside [0, M), that every block names a segment < n_seg and a first query
+ * 0 <= q0 < seg_len, and that the blocks cover every query once (a query no block covers keeps its old `out` row).  Inside
+ * such segments no row of another segment is read as a visible key and no row at or beyond M is touched.  (A block naming
+ * no segment is skipped and a segment reaching past S_max is cut there, so the caches are never overrun; q and out have
+ * no such guard.) */
+int vh_attn_rows_packed_bf16(const uint16_t* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, uint16_t* out,
+                             int ldo, int n_heads, int S_max, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
+                             const int32_t* blocks, int n_blocks, void* stream);
+/* vh_transformer_forward_bf16 over packed rows (the perf-mode NAR stage of a ragged batch): desc->B = 1, desc->T = the sum of
+ * the segment lengths, desc->mode = VH_MASK_FULL, kv_len / x_len_dev NULL (anything else is refused: VH_EINVAL for B,
+ * VH_EUNSUPPORTED for the mask fields and for a d_model / dff vh_transformer_forward_bf16 does not take); x (T, d) holds
+ * utterance s at rows seg_start[s] .. + seg_len[s] - 1 and every layer's K/V lands at the same rows of its 16-bit
+ * (1, h, S_max, 64) cache.  The launches of vh_transformer_forward_bf16 with vh_attn_rows_packed_bf16 for vh_attn_rows_bf16;
+ * the segment and block arrays are its arguments, under its contract.  A null or misaligned pointer in the descriptor or in
+ * either layer table is refused here, before any launch, not by the launch that would meet it. */
+int vh_transformer_forward_packed_bf16(const vh_forward16_desc* desc, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
+                                       const int32_t* blocks, int n_blocks, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,9 @@ over --reps repetitions of the wall time between two device synchronisations wit
 of greedy tokens on which the two forms agree is printed too: they run other GEMM row counts, so they agree to summation order
 and a token may flip where the two leading logits are closer than that.
 
-    python tools/ab_nar_packed.py [--utterances 64] [--reps 7] [--max-len 1024]   (one JSON line per set)
+--perf-mode: the same comparison between the two 16-bit forms, generate_batch(perf_mode=True) and generate_packed_perf.
+
+    python tools/ab_nar_packed.py [--utterances 64] [--reps 7] [--max-len 1024] [--perf-mode]   (one JSON line per set)
 """
 from __future__ import annotations
 
@@ -39,6 +41,7 @@ def main():
     ap.add_argument('--utterances', type=int, default=64)
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--max-len', type=int, default=1024)
+    ap.add_argument('--perf-mode', action='store_true', help='compare generate_batch(perf_mode=True) with generate_packed_perf')
     args = ap.parse_args()
     os.chdir(tempfile.mkdtemp(prefix='ab_nar_packed_'))      # ConfigValle() mkdirs under the CWD
     import torch
@@ -66,8 +69,9 @@ def main():
             texts.append(torch.randint(0, cfg.vocab_size, (tx,), generator=g).to(dev))
             pcs.append(torch.randint(0, cfg.num_audio_tokens, (tc, cfg.num_quantizers), generator=g).to(dev))
             firsts.append(torch.randint(0, cfg.num_audio_tokens, (n - tx - tc,), generator=g).to(dev))
-        forms = {'padded': lambda: m.generate_batch(texts, pcs, firsts, greedy=True),
-                 'packed': lambda: m.generate_packed(texts, pcs, firsts, greedy=True)}
+        packed = m.generate_packed_perf if args.perf_mode else m.generate_packed
+        forms = {'padded': lambda: m.generate_batch(texts, pcs, firsts, greedy=True, perf_mode=args.perf_mode),
+                 'packed': lambda: packed(texts, pcs, firsts, greedy=True)}
         outs = {k: timed(fn)[1] for k, fn in forms.items()}                      # warm-up of every shape the timed calls use
         ms = {k: [] for k in forms}
         for _ in range(args.reps):
@@ -76,7 +80,7 @@ def main():
         tokens = sum(o.numel() for o in outs['padded'])
         same = sum(int((a == b).sum()) for a, b in zip(outs['padded'], outs['packed']))
         lmax, total = max(lengths), sum(lengths)
-        report = dict(set=name, utterances=len(lengths), reps=args.reps, rows_padded=lmax * len(lengths), rows_packed=total,
+        report = dict(set=name, perf_mode=args.perf_mode, utterances=len(lengths), reps=args.reps, rows_padded=lmax * len(lengths), rows_packed=total,
                       row_share=round(total / (lmax * len(lengths)), 3),
                       key_tile_share=round(sum(n * n for n in lengths) / (lmax * total), 3),
                       tokens=tokens, tokens_equal_share=round(same / tokens, 6))

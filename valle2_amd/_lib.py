@@ -281,6 +281,11 @@ SIGNATURES = {
     'vh_attn_rows_bf16': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, C.c_void_p]),
     'vh_transformer_forward_bf16': (C.c_int, [C.POINTER(VhForward16Desc), C.c_void_p]),
+    # packed NAR decoding in perf mode (ABI 140)
+    'vh_attn_rows_packed_bf16': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_void_p]),
+    'vh_transformer_forward_packed_bf16': (C.c_int, [C.POINTER(VhForward16Desc), c_i32p, c_i32p, C.c_int, c_i32p, C.c_int,
+                                                     C.c_void_p]),
 }
 
 _lib = None

@@ -10,6 +10,8 @@
 //   attn16_kernel        flash attention over bf16 q / K / V: S^T = K Q^T (a query is a lane), online softmax in fp32 on
 //                        the accumulator registers, P^T narrowed in registers into the B operand of O^T = V^T P^T (keys of
 //                        a k-step in accumulator order), V^T fragments by ds_read_b64_tr_b16 from the row-major V tile.
+//   attn16_packed_kernel the same body (attn16_body.inc) over the SEGMENTS of one packed row stream under the full mask:
+//                        the NAR stage of a ragged batch with no padding rows (vh_attn_rows_packed_bf16).
 //   layernorm16_kernel   LayerNorm / AdaptiveLayerNorm of the fp32 residual stream written as bf16.
 //
 // MFMA operand maps (cdna_hip_programming.md section 3), lane l: r = l & 31, h = l >> 5:
@@ -610,232 +612,20 @@ struct Attn16Args {
     int n_qb;
 };
 
-__global__ __launch_bounds__(256, 2) void attn16_kernel(Attn16Args a) {
-    __shared__ __attribute__((aligned(16))) char lds[A16_RING * 2 * A16_KT * 128];   // ring of [K | V][64 keys][128 B] = 48 KB
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    // Workgroup ids go round-robin over the 8 XCDs, each with its own L2; the grid is padded to 8 x ceil(n_bh / 8) (batch row,
-    // head) pairs x n_qb query blocks.  FULL mask (every block of a pair costs the same): XCD x takes the pairs x, x + 8, ... and
-    // runs the query blocks of ONE pair back to back, so the pair's K / V (2 x Tk x 128 B) is fetched once into that L2 and
-    // re-read from there by the other blocks (NAR-stage shape: 0.93x the time of the order below).  PREFIX mask: the last
-    // query block of a pair sees up to 4x the keys of the first, and the launch wants the heaviest blocks of ALL pairs
-    // first (grouped by pair it took 1.4x the time at the prompt-pass shape); a pair's blocks still share an XCD.
-    const int n_bh8 = (a.B * a.n_heads + 7) & ~7;
-    int bh, qb;
-    // (grouped only when the pairs deal evenly over the 8 XCDs, or are many: 4 pairs would leave half the chip without work)
-    if (a.mode == VH_MASK_FULL && (a.B * a.n_heads == n_bh8 || a.B * a.n_heads >= 64)) {
-        bh = (int)(blockIdx.x & 7) + 8 * (int)((blockIdx.x >> 3) / a.n_qb);
-        qb = (int)((blockIdx.x >> 3) % a.n_qb);
-    } else {
-        bh = (int)(blockIdx.x % n_bh8);
-        qb = a.n_qb - 1 - (int)(blockIdx.x / n_bh8);
-    }
-    if (bh >= a.B * a.n_heads) return;                       // (the whole workgroup)
-    const int b = bh / a.n_heads, head = bh - b * a.n_heads;
-    const int q_off = a.Tk - a.Tq;
-    const int kvl = a.kv_len ? min(a.kv_len[b], a.Tk) : a.Tk;
-    const int xl = a.mode == VH_MASK_PREFIX ? (a.x_len_dev ? a.x_len_dev[b] : a.x_len) : 0;
-    const bool prefix = a.mode == VH_MASK_PREFIX;
+// The segments of vh_attn_rows_packed_bf16 (attention.hip's PackedSegs for the 16-bit stream): utterance s owns rows
+// seg_start[s] .. seg_start[s] + seg_len[s] - 1 of ONE (M, ·) q / out and of one (1, h, S_max, 64) K/V stream;
+// blocks[2 i], blocks[2 i + 1] = (segment, first query inside it) of workgroup row i.  The bound on rows is Attn16Args::S_max.
+struct Packed16Segs {
+    const int32_t* seg_start; const int32_t* seg_len; const int32_t* blocks;
+    int n_seg;
+};
 
-    const int q0 = qb * A16_QB + 32 * w;                     // this wave's first query
-    const int qi = min(q0 + r, a.Tq - 1);                    // this lane's query (clamped: rows beyond Tq are never stored)
-    const int qpos = q_off + qi;
-    // this lane's query sees exactly the keys [0, klim): key < kv_len and (key < x_len or (qpos >= x_len and key <= qpos))
-    const int klim = prefix ? min(kvl, qpos >= xl ? qpos + 1 : xl) : kvl;
-    // keys any query of the WORKGROUP can see: [0, kend)
-    const int wg_qlast = q_off + min(qb * A16_QB + A16_QB, a.Tq) - 1;
-    int kend = kvl;
-    if (prefix) kend = min(kvl, wg_qlast >= xl ? max(xl, wg_qlast + 1) : xl);
-    const int n_tiles = (kend + A16_KT - 1) / A16_KT;
-    // ... and of this WAVE (wave-uniform): tiles from wave_kend on are skipped by the wave (it still stages and syncs)
-    const int wv_qfirst = q_off + min(q0, a.Tq - 1), wv_qlast = q_off + min(q0 + 31, a.Tq - 1);
-    int wave_kend = kvl;
-    if (prefix) wave_kend = min(kvl, wv_qlast >= xl ? max(xl, wv_qlast + 1) : xl);
-
-    // staging by LDS-DMA (global_load_lds_dwordx4: one 1-KiB piece = 8 key rows x 128 B per wave-instruction, no staging
-    // registers, no ds_write): a tile is 8 pieces of K + 8 of V; waves 0 / 1 bring the K rows 0..31 / 32..63, waves 2 / 3
-    // the V rows.  Lane L fills slot (row L >> 3 of the piece, 16-byte chunk L & 7) of the lane-linear image, so it FETCHES
-    // chunk (L & 7) ^ swz(row): the swizzle lives in the source address.  Keys beyond Tk re-read the last written row
-    // (a masked weight is 0, but 0 x the NaN an unwritten cache row may hold is NaN).  Three images in a ring: tile t + 2 is
-    // requested at the top of tile t (two tiles of flight time); the barrier at the end of tile t orders tile t + 1.
-    const bool stage_v = w >= 2;
-    const char* sbase = (const char*)((stage_v ? a.vc : a.kc) + ((int64_t)b * a.n_heads + head) * a.S_max * VH_HEAD_DIM);
-    const uint32_t lds0 = (uint32_t)(uintptr_t)lds + (stage_v ? A16_KT * 128 : 0) + (w & 1) * 4096;
-    int srow[4];
-    uint32_t schunk[4], soff[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        srow[i] = 32 * (w & 1) + 8 * i + (lane >> 3);
-        const int swz = stage_v ? ((srow[i] >> 1) & 1) << 2 : (srow[i] >> 1) & 7;
-        schunk[i] = (uint32_t)(((lane & 7) ^ swz) << 4);
-        soff[i] = (uint32_t)srow[i] * 128u + schunk[i];      // byte offset inside a tile that lies wholly below Tk
-    }
-    auto dma_tile = [&](int k0, int buf) {
-        const bool whole = k0 + A16_KT <= a.Tk;               // (wave-uniform) no row of the tile needs the clamp
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t voff = whole ? soff[i] + (uint32_t)k0 * 128u : (uint32_t)min(k0 + srow[i], a.Tk - 1) * 128u + schunk[i];
-            const uint32_t dst = lds0 + buf * (2 * A16_KT * 128) + i * 1024;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(voff), "s"(sbase) : "memory");
-        }
-    };
-    if (n_tiles > 0) dma_tile(0, 0);
-    if (n_tiles > 1) dma_tile(A16_KT, 1);
-
-    // Q^T fragments (B operand of S^T = K Q^T): lane (r, h) holds Q'[query r][d = 16 s + 8 h + j].  Q' = c Q with
-    // c = 1 / sqrt(64) * log2(e) comes PRE-SCALED from the producer (vh_linear_qkv_bf16 scales in fp32 before the one
-    // narrowing: no second rounding), so the score accumulators are base-2 exponents.
-    bf16x8 qf[4];
-    {
-        const uint16_t* qr = a.q + ((int64_t)b * a.Tq + qi) * a.ldq + head * VH_HEAD_DIM + 8 * h;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = __builtin_bit_cast(bf16x8, ldq(qr + 16 * s));
-    }
-    // Softmax without a per-element subtraction or sum (the kernel is bound by vector ISSUE slots, ~200 per 32 x 64 scores
-    // before this; profiles/r6_pmc_attn16.md): the reference point m_ref of a row moves only when a tile's maximum exceeds it
-    // by more than A16_LAZY (weights then reach at most 2^A16_LAZY: exact in the 16-bit formats, fp32 sums), and -m_ref sits
-    // in sixteen registers that are the INITIAL ACCUMULATOR of the score MFMAs — the chain delivers c S - m_ref, the weight
-    // is one v_exp_f32 of that.  The row sum comes out of the matrix pipe as well: a third accumulator block whose A operand
-    // is 1 on rows 0 and 4 (lacc[0] of every lane = its query's sum over both key halves, taken from the ROUNDED weights
-    // the products see).  Moving m_ref rescales O, the sums and the pending scores by 2^-delta, all of them (tile 0 always moves).
-    f32x16 oacc[2], lacc, minit;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { oacc[0][e] = 0.f; oacc[1][e] = 0.f; lacc[e] = 0.f; minit[e] = 0.f; }
-    float m_ref = 0.f;
-    bf16x8 ones;
-    {
-        const uint32_t one2 = vh_pack_h16(1.f, 1.f), w1 = (r == 0 || r == 4) ? one2 : 0u;
-        ones = __builtin_bit_cast(bf16x8, u32x4{w1, w1, w1, w1});
-    }
-
-    // K fragment addresses (A operand of S^T): key row 32 u + r, chunk (2 s + h) ^ ((r >> 1) & 7)
-    const int kswz = (r >> 1) & 7;
-    // V^T fragment addresses: group g = lane >> 4 (h = g >> 1), lane 4 q4 + p of the group supplies key row kb + q4,
-    // columns d = 32 db + 16 (g & 1) + 4 p .. + 3 -> chunk 4 db + 2 (g & 1) + (p >> 1), byte 8 (p & 1) in it
-    const int g = lane >> 4, q4 = (lane >> 2) & 3, p = lane & 3;
-
-    // vmcnt(0), unconditionally and BEFORE the loop: the first two tiles and the Q fragments have landed.  (The Q fragments
-    // are first used inside the loop; left to the compiler's wait insertion, vmcnt(3..0) lands in front of the first four
-    // score MFMAs of EVERY tile — a wait for the tile's own prefetches.  Seen in the ISA in round 6.)
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __syncthreads();
-    int buf = 0;
-    for (int it = 0; it < n_tiles; ++it) {
-        const int k0 = it * A16_KT;
-        const bool ahead = it + 2 < n_tiles;                 // (wave-uniform)
-        if (ahead) dma_tile(k0 + 2 * A16_KT, buf >= 1 ? buf - 1 : 2);      // into image (it + 2) % 3, free since the last barrier
-        if (k0 < wave_kend) {
-            const char* kl = lds + buf * 2 * A16_KT * 128;
-            const char* vl = kl + A16_KT * 128;
-            // ---- c S^T - m_ref = K (c Q)^T + (-m_ref) for the two 32-key sub-tiles
-            f32x16 sacc[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const bf16x8 kf = __builtin_bit_cast(bf16x8, ldq(kl + (32 * u + r) * 128 + (((2 * s + h) ^ kswz) << 4)));
-                    sacc[u] = VH_MFMA16(kf, qf[s], s ? sacc[u] : minit);
-                }
-            // ---- mask (only on tiles that need it: wave-uniform test): register x of sub-tile u holds key
-            // k0 + 32 u + (x & 3) + 8 (x >> 2) + 4 h, visible iff it is below the lane's bound — one compare + select each
-            const bool need_mask = k0 + A16_KT > kvl || (prefix && k0 + A16_KT > xl && (wv_qfirst < xl || k0 + A16_KT - 1 > wv_qfirst));
-            if (need_mask) {
-                const int t = klim - k0 - 4 * h;
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int x = 0; x < 16; ++x) sacc[u][x] = 32 * u + (x & 3) + 8 * (x >> 2) < t ? sacc[u][x] : A16_NEG;
-            }
-            // ---- the tile's row maximum relative to m_ref (the query's other key half sits in lane ^ 32)
-            float mx = A16_NEG;
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int x = 0; x < 16; ++x) mx = fmaxf(mx, sacc[u][x]);
-            {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, mx), __builtin_bit_cast(uint32_t, mx), false, false);
-                mx = fmaxf(__builtin_bit_cast(float, sw[0]), __builtin_bit_cast(float, sw[1]));
-            }
-            if (it == 0 || __builtin_amdgcn_readfirstlane(__builtin_amdgcn_ballot_w64(mx > A16_LAZY) != 0)) {
-                // move the reference point: to the row's maximum on the first tile, up to it (never down) later
-                // (a row without any visible key in tile 0 — none under the analytic masks while kv_len >= 1 — stays at 0)
-                const float delta = it == 0 ? (mx > 0.5f * A16_NEG ? mx : 0.f) : fmaxf(mx, 0.f);
-                m_ref += delta;
-                const float alpha = vh_exp2(-delta);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { minit[e] = -m_ref; sacc[0][e] -= delta; sacc[1][e] -= delta; }
-                if (it) {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) { oacc[0][e] *= alpha; oacc[1][e] *= alpha; }
-                    lacc[0] *= alpha;
-                }
-            }
-            // ---- P^T = 2^(c S - m_ref) narrowed into the B operands (keys of a k-step in accumulator order)
-            bf16x8 pf[2][2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    u32x4 pk;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pk[j] = vh_pack_h16_unit(vh_exp2(sacc[u][8 * s + 2 * j]), vh_exp2(sacc[u][8 * s + 2 * j + 1]));
-                    pf[u][s] = __builtin_bit_cast(bf16x8, pk);
-                }
-            // ---- O^T += V^T P^T: A operand element j of lane half h = V[key 32 u + 16 s + 8 (j >> 2) + 4 h + (j & 3)][d = 32 db + r];
-            // and the row sums, l += 1^T P^T
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-#pragma unroll
-                    for (int db = 0; db < 2; ++db) {
-                        u32x2 lo, hi;
-                        {
-                            const int key = 32 * u + 16 * s + 4 * (g >> 1) + q4;
-                            const int c = 4 * db + 2 * (g & 1) + (p >> 1);
-                            const char* ad = vl + key * 128 + ((c ^ (((key >> 1) & 1) << 2)) << 4) + 8 * (p & 1);
-                            lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                                               (s16x4 __attribute__((address_space(3)))*)ad));
-                            const int key2 = key + 8;
-                            const char* ad2 = vl + key2 * 128 + ((c ^ (((key2 >> 1) & 1) << 2)) << 4) + 8 * (p & 1);
-                            hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                                               (s16x4 __attribute__((address_space(3)))*)ad2));
-                        }
-                        const bf16x8 vf = __builtin_bit_cast(bf16x8, u32x4{lo.x, lo.y, hi.x, hi.y});
-                        oacc[db] = VH_MFMA16(vf, pf[u][s], oacc[db]);
-                    }
-                    lacc = VH_MFMA16(ones, pf[u][s], lacc);
-                }
-        }
-        // tile it + 1 (this wave's pieces of it: the four requests BEFORE the ones issued above) has landed; after the barrier
-        // every wave's pieces have, and nobody reads image `buf` any more
-        if (ahead) __builtin_amdgcn_s_waitcnt(0x0F74);       // vmcnt(4)
-        else __builtin_amdgcn_s_waitcnt(0x0F70);             // vmcnt(0)
-        __syncthreads();
-        buf = buf == 2 ? 0 : buf + 1;
-    }
-    // ---- epilogue: O / l, narrowed, transposed through LDS (per wave: 32 queries x 64 d) and stored as whole 128-B rows
-    const float l_tot = lacc[0];
-    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
-    char* ow = lds + w * 32 * 144;                           // 144-B rows (128 + 16 of padding)
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const u32x2 pk = {pack_bf16(oacc[db][4 * g4] * inv, oacc[db][4 * g4 + 1] * inv),
-                              pack_bf16(oacc[db][4 * g4 + 2] * inv, oacc[db][4 * g4 + 3] * inv)};
-            *reinterpret_cast<u32x2*>(ow + r * 144 + (32 * db + 8 * g4 + 4 * h) * 2) = pk;
-        }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                       // lgkmcnt(0): the wave's own writes are in LDS (wave-private region)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int id = lane + 64 * i, row = id >> 3, c = id & 7;
-        const int qrow = q0 + row;
-        if (qrow < a.Tq && qrow < qb * A16_QB + A16_QB)
-            stq(a.out + ((int64_t)b * a.Tq + qrow) * a.ldo + head * VH_HEAD_DIM + 8 * c, ldq(ow + row * 144 + 16 * c));
-    }
-}
+#define ATTN16_PACKED 0
+#include "attn16_body.inc"          // attn16_kernel(Attn16Args)
+#undef ATTN16_PACKED
+#define ATTN16_PACKED 1
+#include "attn16_body.inc"          // attn16_packed_kernel(Attn16Args, Packed16Segs)
+#undef ATTN16_PACKED
 
 extern "C" int vh_attn_rows_bf16(const uint16_t* q, int ldq_, const uint16_t* kcache16, const uint16_t* vcache16, uint16_t* out,
                                  int ldo, int B, int n_heads, int Tq, int Tk, int S_max, int mode, int x_len,
@@ -858,10 +648,78 @@ extern "C" int vh_attn_rows_bf16(const uint16_t* q, int ldq_, const uint16_t* kc
     return VH_OK;
 }
 
+extern "C" int vh_attn_rows_packed_bf16(const uint16_t* q, int ldq_, const uint16_t* kcache16, const uint16_t* vcache16, uint16_t* out,
+                                        int ldo, int n_heads, int S_max, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
+                                        const int32_t* blocks, int n_blocks, void* stream) {
+    VH_REQUIRE(q && kcache16 && vcache16 && out, VH_EINVAL, "vh_attn_rows_packed_bf16: null pointer (q, kcache16, vcache16 or out)");
+    VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL, "vh_attn_rows_packed_bf16: null pointer (seg_start, seg_len or blocks)");
+    VH_REQUIRE(n_heads > 0 && S_max >= 1, VH_EINVAL, "vh_attn_rows_packed_bf16: bad dims n_heads=%d S_max=%d", n_heads, S_max);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_packed_bf16: n_seg=%d", n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_attn_rows_packed_bf16: n_blocks=%d", n_blocks);
+    VH_REQUIRE(ldq_ % 8 == 0 && ldq_ >= n_heads * VH_HEAD_DIM, VH_EINVAL, "vh_attn_rows_packed_bf16: ldq=%d", ldq_);
+    VH_REQUIRE(ldo % 8 == 0 && ldo >= n_heads * VH_HEAD_DIM, VH_EINVAL, "vh_attn_rows_packed_bf16: ldo=%d", ldo);
+    VH_REQUIRE(vh_aligned16(q), VH_EALIGN, "vh_attn_rows_packed_bf16: q must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(out), VH_EALIGN, "vh_attn_rows_packed_bf16: out must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(kcache16) && vh_aligned16(vcache16), VH_EALIGN,
+               "vh_attn_rows_packed_bf16: kcache16 and vcache16 must be 16-byte aligned");
+    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
+               "vh_attn_rows_packed_bf16: n_blocks=%d x n_heads=%d workgroups", n_blocks, n_heads);
+    // (B, Tq, Tk, the mask fields and n_qb are the padded kernel's: the packed one reads them from the segment table)
+    Attn16Args a{q, ldq_, kcache16, vcache16, out, ldo, 1, n_heads, 0, 0, S_max, VH_MASK_FULL, 0, nullptr, nullptr, 0};
+    Packed16Segs ps{seg_start, seg_len, blocks, n_seg};
+    hipLaunchKernelGGL(attn16_packed_kernel, dim3((unsigned)(n_blocks * n_heads)), dim3(256), 0, (hipStream_t)stream, a, ps);
+    VH_CHECK_LAUNCH("vh_attn_rows_packed_bf16");
+    return VH_OK;
+}
+
 // =============================================================================================
 // composite: the full-sequence forward of vh_transformer_forward with bf16 operands
 // =============================================================================================
 #define TRY16(call) do { int rc_ = (call); if (rc_ != VH_OK) return rc_; } while (0)
+
+// the segments of a packed forward (vh_transformer_forward_packed_bf16); null: the padded (B, T) layout
+struct packed_rows16 {
+    const int32_t *seg_start, *seg_len, *blocks;
+    int n_seg, n_blocks;
+};
+
+// every layer's 16-bit matrices and caches are there, said before the first layer is launched (`name`: the entry point
+// the refusal is reported under)
+static int layers16_complete(const vh_forward16_desc* f, const char* name) {
+    for (int i = 0; i < f->n_layers; ++i) {
+        const vh_layer16& H = f->layers16[i];
+        VH_REQUIRE(H.wqkv && H.wo && H.w1 && H.w2 && H.kcache16 && H.vcache16, VH_EINVAL,
+                   "%s: layer %d has a null bf16 pointer", name, i);
+    }
+    return VH_OK;
+}
+
+// the layers of both forwards: the same launches in the same order, the packed one with vh_attn_rows_packed_bf16 for
+// vh_attn_rows_bf16
+static int forward16_layers(const vh_forward16_desc* f, const packed_rows16* pk, void* stream) {
+    const int B = f->B, T = f->T, D = f->d_model, M = B * T;
+    for (int i = 0; i < f->n_layers; ++i) {
+        const vh_layer& L = f->layers[i];
+        const vh_layer16& H = f->layers16[i];
+        const float* ada = f->ada ? f->ada + (int64_t)i * 4 * D : nullptr;
+        const float* src = (i == 0 && f->x_in) ? f->x_in : f->x;
+        TRY16(vh_layernorm_bf16(src, L.ln1_g, L.ln1_b, ada, ada ? ada + D : nullptr, f->xn16, M, D, f->ln_eps, stream));
+        TRY16(vh_linear_qkv_bf16(f->xn16, D, H.wqkv, f->q16, D, H.kcache16, H.vcache16, nullptr, B, T, D, f->n_heads,
+                                 f->S_max, stream));
+        if (pk)
+            TRY16(vh_attn_rows_packed_bf16(f->q16, D, H.kcache16, H.vcache16, f->attn16, D, f->n_heads, f->S_max, pk->seg_start,
+                                           pk->seg_len, pk->n_seg, pk->blocks, pk->n_blocks, stream));
+        else
+            TRY16(vh_attn_rows_bf16(f->q16, D, H.kcache16, H.vcache16, f->attn16, D, B, f->n_heads, T, T, f->S_max, f->mode,
+                                    f->x_len, f->x_len_dev, f->kv_len, stream));
+        TRY16(vh_linear_bf16(f->attn16, D, H.wo, L.bo, src, D, f->x, D, 0, M, D, D, VH_ACT_NONE, stream));
+        TRY16(vh_layernorm_bf16(f->x, L.ln2_g, L.ln2_b, ada ? ada + 2 * D : nullptr, ada ? ada + 3 * D : nullptr, f->xn16, M, D,
+                                f->ln_eps, stream));
+        TRY16(vh_linear_bf16(f->xn16, D, H.w1, L.b1, nullptr, 0, f->hidden16, f->dff, 1, M, f->dff, D, VH_ACT_GELU_ERF, stream));
+        TRY16(vh_linear_bf16(f->hidden16, f->dff, H.w2, L.b2, f->x, D, f->x, D, 0, M, D, f->dff, VH_ACT_NONE, stream));
+    }
+    return VH_OK;
+}
 
 extern "C" int vh_transformer_forward_bf16(const vh_forward16_desc* f, void* stream) {
     VH_REQUIRE(f && f->layers && f->layers16 && f->x && f->xn16 && f->q16 && f->attn16 && f->hidden16, VH_EINVAL,
@@ -872,24 +730,52 @@ extern "C" int vh_transformer_forward_bf16(const vh_forward16_desc* f, void* str
                "vh_transformer_forward_bf16: d_model=%d dff=%d (n_heads x 64, multiples of 128)", f->d_model, f->dff);
     VH_REQUIRE(f->mode == VH_MASK_FULL || f->mode == VH_MASK_PREFIX, VH_EUNSUPPORTED,
                "vh_transformer_forward_bf16: analytic masks only (mode=%d)", f->mode);
-    const int B = f->B, T = f->T, D = f->d_model, M = B * T;
+    TRY16(layers16_complete(f, "vh_transformer_forward_bf16"));
+    return forward16_layers(f, nullptr, stream);
+}
+
+extern "C" int vh_transformer_forward_packed_bf16(const vh_forward16_desc* f, const int32_t* seg_start, const int32_t* seg_len,
+                                                  int n_seg, const int32_t* blocks, int n_blocks, void* stream) {
+    VH_REQUIRE(f && f->layers && f->layers16 && f->x && f->xn16 && f->q16 && f->attn16 && f->hidden16, VH_EINVAL,
+               "vh_transformer_forward_packed_bf16: null pointer in desc");
+    VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL,
+               "vh_transformer_forward_packed_bf16: null pointer (seg_start, seg_len or blocks)");
+    VH_REQUIRE(f->B == 1, VH_EINVAL, "vh_transformer_forward_packed_bf16: B=%d (the packed rows are ONE row stream: B = 1, T = the "
+               "sum of the segment lengths)", f->B);
+    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "vh_transformer_forward_packed_bf16: bad dims T=%d L=%d", f->T, f->n_layers);
+    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "vh_transformer_forward_packed_bf16: S_max=%d < T=%d", f->S_max, f->T);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_transformer_forward_packed_bf16: n_seg=%d", n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_transformer_forward_packed_bf16: n_blocks=%d", n_blocks);
+    VH_REQUIRE(f->mode == VH_MASK_FULL, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed_bf16: mode=%d (segments attend under the full mask only)", f->mode);
+    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: kv_len is set (a segment's length is its key length)");
+    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: x_len_dev is set (no prefix mask over segments)");
+    VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM && f->d_model % 128 == 0 && f->dff % 128 == 0, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed_bf16: d_model=%d dff=%d (n_heads x 64, multiples of 128)", f->d_model, f->dff);
+    VH_REQUIRE(f->d_model <= 4096, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: d_model=%d (vh_layernorm_bf16 serves <= 4096)",
+               f->d_model);
+    VH_REQUIRE((int64_t)n_blocks * f->n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed_bf16: n_blocks=%d x n_heads=%d workgroups", n_blocks, f->n_heads);
+    // what the launches of any layer would refuse for a pointer — null or not 16-byte aligned — said here, under this entry
+    // point's name, before anything is launched
+    VH_REQUIRE(vh_aligned16(f->x) && vh_aligned16(f->x_in) && vh_aligned16(f->ada), VH_EALIGN,
+               "vh_transformer_forward_packed_bf16: x, x_in and ada must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(f->xn16) && vh_aligned16(f->q16) && vh_aligned16(f->attn16) && vh_aligned16(f->hidden16), VH_EALIGN,
+               "vh_transformer_forward_packed_bf16: xn16, q16, attn16 and hidden16 must be 16-byte aligned");
+    TRY16(layers16_complete(f, "vh_transformer_forward_packed_bf16"));
     for (int i = 0; i < f->n_layers; ++i) {
         const vh_layer& L = f->layers[i];
         const vh_layer16& H = f->layers16[i];
-        VH_REQUIRE(H.wqkv && H.wo && H.w1 && H.w2 && H.kcache16 && H.vcache16, VH_EINVAL,
-                   "vh_transformer_forward_bf16: layer %d has a null bf16 pointer", i);
-        const float* ada = f->ada ? f->ada + (int64_t)i * 4 * D : nullptr;
-        const float* src = (i == 0 && f->x_in) ? f->x_in : f->x;
-        TRY16(vh_layernorm_bf16(src, L.ln1_g, L.ln1_b, ada, ada ? ada + D : nullptr, f->xn16, M, D, f->ln_eps, stream));
-        TRY16(vh_linear_qkv_bf16(f->xn16, D, H.wqkv, f->q16, D, H.kcache16, H.vcache16, nullptr, B, T, D, f->n_heads,
-                                 f->S_max, stream));
-        TRY16(vh_attn_rows_bf16(f->q16, D, H.kcache16, H.vcache16, f->attn16, D, B, f->n_heads, T, T, f->S_max, f->mode,
-                                f->x_len, f->x_len_dev, f->kv_len, stream));
-        TRY16(vh_linear_bf16(f->attn16, D, H.wo, L.bo, src, D, f->x, D, 0, M, D, D, VH_ACT_NONE, stream));
-        TRY16(vh_layernorm_bf16(f->x, L.ln2_g, L.ln2_b, ada ? ada + 2 * D : nullptr, ada ? ada + 3 * D : nullptr, f->xn16, M, D,
-                                f->ln_eps, stream));
-        TRY16(vh_linear_bf16(f->xn16, D, H.w1, L.b1, nullptr, 0, f->hidden16, f->dff, 1, M, f->dff, D, VH_ACT_GELU_ERF, stream));
-        TRY16(vh_linear_bf16(f->hidden16, f->dff, H.w2, L.b2, f->x, D, f->x, D, 0, M, D, f->dff, VH_ACT_NONE, stream));
+        VH_REQUIRE(vh_aligned16(H.kcache16) && vh_aligned16(H.vcache16), VH_EALIGN,
+                   "vh_transformer_forward_packed_bf16: kcache16 and vcache16 must be 16-byte aligned (layer %d)", i);
+        VH_REQUIRE(vh_aligned16(H.wqkv) && vh_aligned16(H.wo) && vh_aligned16(H.w1) && vh_aligned16(H.w2), VH_EALIGN,
+                   "vh_transformer_forward_packed_bf16: wqkv, wo, w1 and w2 must be 16-byte aligned (layer %d)", i);
+        VH_REQUIRE(L.ln1_g && L.ln1_b && L.ln2_g && L.ln2_b, VH_EINVAL,
+                   "vh_transformer_forward_packed_bf16: layer %d has a null LayerNorm parameter", i);
+        VH_REQUIRE(vh_aligned16(L.ln1_g) && vh_aligned16(L.ln1_b) && vh_aligned16(L.ln2_g) && vh_aligned16(L.ln2_b) &&
+                       vh_aligned16(L.bo) && vh_aligned16(L.b1) && vh_aligned16(L.b2), VH_EALIGN,
+                   "vh_transformer_forward_packed_bf16: LayerNorm parameters and biases must be 16-byte aligned (layer %d)", i);
     }
-    return VH_OK;
+    const packed_rows16 pk{seg_start, seg_len, blocks, n_seg, n_blocks};
+    return forward16_layers(f, &pk, stream);
 }

@@ -361,6 +361,24 @@ def _fp32_scratch_fields(scratch):
                 gemm_ws=ptr(scratch.ws), gemm_ws_bytes=scratch.ws_bytes)
 
 
+def _refuse_unless_perf_forward(cfg):
+    if not perf_forward_supported(cfg):
+        raise _lib.VhError(f'perf mode needs d_model = n_heads x 64 and d_model, dim_feedforward multiples of 128 '
+                           f'(got {cfg.d_model}, {cfg.n_heads}, {cfg.dim_feedforward})')
+
+
+def _forward16_desc(transformer, cache, scratch, common, **fields):
+    """The 16-bit descriptor of both perf-mode forwards: the narrowed weights and the cache of every layer, the 16-bit scratch
+    and `common` (`_forward_front`)."""
+    t16 = (_lib.VhLayer16 * transformer.hparams.num_layers)()
+    for i, (wq, wo, w1, w2) in enumerate(bf16_weights(transformer)):
+        t16[i].wqkv, t16[i].wo, t16[i].w1, t16[i].w2 = wq.data_ptr(), wo.data_ptr(), w1.data_ptr(), w2.data_ptr()
+        t16[i].kcache16, t16[i].vcache16 = cache.k(i).data_ptr(), cache.v(i).data_ptr()
+    return _lib.VhForward16Desc(
+        layers16=t16, xn16=scratch.xn.data_ptr(), q16=scratch.q.data_ptr(), attn16=scratch.attn.data_ptr(),
+        hidden16=scratch.hidden.data_ptr(), **fields, **common)
+
+
 def transformer_forward_bf16(transformer, x, cache: 'KVCache', *, mode, x_len=0, x_len_dev=None, kv_len=None, embedding=None,
                              scratch=None, x_in=None):
     """`transformer_forward` in PERF MODE (SECONDARY): every product of the stack on the bf16 matrix
@@ -368,18 +386,10 @@ def transformer_forward_bf16(transformer, x, cache: 'KVCache', *, mode, x_len=0,
     masks only.  Teacher-forced logits agree with the reference to 5e-2, not to the parity path's 2e-4."""
     cfg = transformer.hparams
     B, T, d = x.shape
-    if not perf_forward_supported(cfg):
-        raise _lib.VhError(f'perf mode needs d_model = n_heads x 64 and d_model, dim_feedforward multiples of 128 '
-                           f'(got {cfg.d_model}, {cfg.n_heads}, {cfg.dim_feedforward})')
+    _refuse_unless_perf_forward(cfg)
     scratch, common = _forward_front(transformer, x, B, T, cache, embedding, scratch, bf16=True)
-    t16 = (_lib.VhLayer16 * cfg.num_layers)()
-    for i, (wq, wo, w1, w2) in enumerate(bf16_weights(transformer)):
-        t16[i].wqkv, t16[i].wo, t16[i].w1, t16[i].w2 = wq.data_ptr(), wo.data_ptr(), w1.data_ptr(), w2.data_ptr()
-        t16[i].kcache16, t16[i].vcache16 = cache.k(i).data_ptr(), cache.v(i).data_ptr()
-    desc = _lib.VhForward16Desc(
-        mode=mode, x_len=int(x_len), layers16=t16, x_len_dev=ptr(x_len_dev), kv_len=ptr(kv_len), x_in=ptr(x_in),
-        xn16=scratch.xn.data_ptr(), q16=scratch.q.data_ptr(), attn16=scratch.attn.data_ptr(),
-        hidden16=scratch.hidden.data_ptr(), **common)
+    desc = _forward16_desc(transformer, cache, scratch, common, mode=mode, x_len=int(x_len), x_len_dev=ptr(x_len_dev),
+                           kv_len=ptr(kv_len), x_in=ptr(x_in))
     check(_lib.lib().vh_transformer_forward_bf16(C.byref(desc), stream()), 'vh_transformer_forward_bf16')
     return x
 
@@ -513,8 +523,8 @@ class NarLayout:
         self.kv_len = None if p.kv_len is None else i32(p.kv_len)
 
     def cache_and_scratch(self, cfg, perf_mode=False):
-        """(KVCache, scratch) of one stack forward over the buffer: (1, rows) fp32 packed, (B, max(len)) padded — 16-bit in
-        perf mode, which the packed kind does not have."""
+        """(KVCache, scratch) of one stack forward over the buffer: (1, rows) packed, (B, max(len)) padded — fp32, or 16-bit in
+        perf mode (either kind)."""
         B = 1 if self.segments else len(self.plan.lengths)
         cache = KVCache(cfg.num_layers, B, cfg.n_heads, self.rows // B, self.device, dtype=kernels.H16 if perf_mode else torch.float32)
         return cache, (ForwardScratch16 if perf_mode else ForwardScratch)(self.rows, cfg.d_model, cfg.dim_feedforward, self.device)
@@ -522,7 +532,8 @@ class NarLayout:
     def forward(self, transformer, x, cache, scratch, embedding):
         """The stack under the full mask over x (rows, d) in place, every utterance attending its own rows."""
         if self.segments:
-            return transformer_forward_packed(transformer, x, cache, self.segments, embedding=embedding, scratch=scratch)
+            forward = transformer_forward_packed_bf16 if cache.bf16 else transformer_forward_packed
+            return forward(transformer, x, cache, self.segments, embedding=embedding, scratch=scratch)
         forward = transformer_forward_bf16 if cache.bf16 else transformer_forward
         return forward(transformer, x.view(cache.batch, -1, x.shape[-1]), cache, mode=kernels.MASK_FULL, kv_len=self.kv_len,
                        embedding=embedding, scratch=scratch)
@@ -546,6 +557,28 @@ def transformer_forward_packed(transformer, x, cache: KVCache, rows: PackedRows,
     check(_lib.lib().vh_transformer_forward_packed(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg,
                                                    ptr(rows.blocks), rows.n_blocks, stream()),
           'vh_transformer_forward_packed')
+    return x
+
+
+def transformer_forward_packed_bf16(transformer, x, cache: KVCache, rows: PackedRows, embedding=None, scratch=None):
+    """`transformer_forward_packed` in PERF MODE: `transformer_forward_bf16(mode=MASK_FULL)` of a ragged batch over packed rows.
+    x (M, d) fp32 holds utterance b at rows rows.starts[b] .. + rows.lengths[b] - 1 and is updated in place; each utterance
+    attends its own rows only (`vh_attn_rows_packed_bf16`), every other launch is the row-wise 16-bit one over M rows.
+    `cache`: a one-row 16-bit KVCache of s_max >= M; `scratch`: a ForwardScratch16.  Returns x."""
+    cfg = transformer.hparams
+    if x.dim() != 2:
+        raise _lib.VhError(f'transformer_forward_packed_bf16: x must be (M, d), got {tuple(x.shape)}')
+    M, d = x.shape
+    if d != cfg.n_heads * HEAD_DIM:
+        raise _lib.VhError(f'transformer_forward_packed_bf16: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
+    if M != rows.rows:
+        raise _lib.VhError(f'transformer_forward_packed_bf16: x has {M} rows, the packed rows {rows.rows}')
+    _refuse_unless_perf_forward(cfg)
+    scratch, common = _forward_front(transformer, x, 1, M, cache, embedding, scratch, bf16=True)
+    desc = _forward16_desc(transformer, cache, scratch, common, mode=kernels.MASK_FULL, x_len=0)
+    check(_lib.lib().vh_transformer_forward_packed_bf16(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg,
+                                                        ptr(rows.blocks), rows.n_blocks, stream()),
+          'vh_transformer_forward_packed_bf16')
     return x
 
 

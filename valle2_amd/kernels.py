@@ -680,6 +680,24 @@ def attn_rows_bf16(q, kcache16, vcache16, out, B, n_heads, Tq, Tk, mode, x_len=0
     return out
 
 
+def attn_rows_packed_bf16(q, kcache, vcache, out, n_heads, rows):
+    """`attn_rows_packed` in the 16-bit format of perf mode: full-mask attention of every segment of `rows` (an
+    engine.PackedRows) over its own rows of ONE 16-bit K/V stream.  q (pre-scaled by Q16_PRESCALE, as `linear_qkv_bf16` leaves
+    it) / out (M, ·) H16 with heads at columns head*64, kcache / vcache (1, n_heads, S_max >= M, 64) H16 — `attn_rows_bf16` of
+    each utterance alone, in one launch and with no padding rows (vh_attn_rows_packed_bf16)."""
+    S_max = kcache.shape[2]
+    M = rows.rows
+    if tuple(kcache.shape) != (1, n_heads, S_max, HEAD_DIM) or kcache.shape != vcache.shape or M > S_max:
+        raise _lib.VhError(f'attn_rows_packed_bf16: cache {tuple(kcache.shape)} M={M}')
+    if q.shape[0] != M or out.shape[0] != M:
+        raise _lib.VhError('attn_rows_packed_bf16: q/out rows')
+    check(_lib.lib().vh_attn_rows_packed_bf16(
+        _bf16(q, 'q'), q.stride(0), _bf16(kcache, 'kcache'), _bf16(vcache, 'vcache'), _bf16(out, 'out'), out.stride(0), n_heads,
+        S_max, ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()),
+        'vh_attn_rows_packed_bf16')
+    return out
+
+
 def greedy_step(logits, V, eos, codes, eos_count, audio_emb, pe, audio_pos, cache_len, x_next,
                 pos_base=None):
     B = logits.shape[0]

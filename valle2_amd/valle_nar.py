@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from . import _lib, dropout, kernels
 from . import sampling as _sampling
-from .engine import KVCache, NarLayout, head16, transformer_forward, transformer_forward_bf16
+from .engine import KVCache, NarLayout, head16, perf_forward_supported, transformer_forward, transformer_forward_bf16
 from .modules import PositionalEncoding, TokenEmbedding, Transformer, _on_device
 from .valle_ar import _Base
 
@@ -57,6 +57,18 @@ def _packed_width_refused_early(fn):
         if cfg.d_model != cfg.n_heads * kernels.HEAD_DIM:
             raise ValueError(f'{fn.__name__}: head width {cfg.d_model // cfg.n_heads} (d_model={cfg.d_model} / n_heads={cfg.n_heads}): '
                              'the packed attention serves width 64 only — generate_batch serves the others')
+        return fn(self, *args, **kwargs)
+    return wrapper
+
+
+def _packed_perf_shape_refused_early(fn):
+    """generate_packed_perf: a shape the 16-bit tile kernels are not built for is said before anything touches a device."""
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        cfg = self.config
+        if not perf_forward_supported(cfg):
+            raise ValueError(f'{fn.__name__}: d_model={cfg.d_model}, dim_feedforward={cfg.dim_feedforward}: perf mode serves '
+                             'multiples of 128 only — generate_packed serves the others in fp32')
         return fn(self, *args, **kwargs)
     return wrapper
 
@@ -292,10 +304,27 @@ class ValleNAR(_Base):
         ids, lens = self._ragged_inputs('generate_packed', dev, texts, prompt_codes, first_layers)
         return self._generate_stages('generate_packed', NarLayout(*lens, True, dev), ids, lens, greedy, seed, sampling)
 
+    @_packed_width_refused_early
+    @_packed_perf_shape_refused_early
+    @_sampling_refused_early
+    @_on_device
+    @torch.inference_mode()
+    def generate_packed_perf(self, texts, prompt_codes, first_layers, greedy: bool = False, seed=None, *, sampling=None):
+        """`generate_packed` in PERF MODE: the same inputs, checks, return value and sampling keys, the packed rows of
+        `generate_packed` and the arithmetic of `generate_batch(perf_mode=True)` — the stack forwards on the 16-bit matrix
+        cores over the M = sum(len_b) rows, each utterance attending its own rows of a one-row 16-bit K/V cache
+        (`vh_attn_rows_packed_bf16`), and the stage heads on 16-bit weights.  Head width 64 only, and d_model and
+        dim_feedforward multiples of 128 (ValueError otherwise, before any device work).  As with perf_mode=True the drawn
+        codes are not guaranteed to be the parity path's; against the padded perf-mode form the attention of an utterance is
+        the same bits and the GEMMs see another row count, so logits agree with it to 16-bit rounding, not to the bit."""
+        dev = self._dev()
+        ids, lens = self._ragged_inputs('generate_packed_perf', dev, texts, prompt_codes, first_layers)
+        return self._generate_stages('generate_packed_perf', NarLayout(*lens, True, dev), ids, lens, greedy, seed, sampling, True)
+
     def _generate_stages(self, name, layout, ids, lens, greedy, seed, sampling, perf_mode=False):
-        """The stage loop of `generate_batch` / `generate_packed` over `layout` (an engine.NarLayout of `lens`): the only
-        difference between the two is where a row lies and which forward runs over the buffer, and the layout knows both.
-        The gathered target rows, hence the logits rows and the draws' keys, are utterance by utterance and frame by frame
+        """The stage loop of `generate_batch`, `generate_packed` and `generate_packed_perf` over `layout` (an engine.NarLayout of
+        `lens`): they differ only in where a row lies and which forward runs over the buffer (padded or packed, fp32 or
+        `perf_mode`), and the layout knows both.  The gathered target rows, hence the logits rows and the draws' keys, are utterance by utterance and frame by frame
         under either layout."""
         cfg = self.config
         q, d = cfg.num_quantizers, cfg.d_model
