@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 140            /* 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 141            /* 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -598,7 +598,7 @@ int vh_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k,
 
 /* ---- K12 (stochastic) with PER-ROW sampling: every row's seed, draw key and filter from device memory ----------
  * One record per row, indexed as logits / codes / audio_pos are.  32 bytes, 16-byte aligned (two 16-byte loads per
- * workgroup): seed at byte 0, key at 8, top_k at 12, top_p at 16, temperature at 20, 8 reserved bytes (write zeros).
+ * workgroup): seed at byte 0, key at 8, top_k at 12, top_p at 16, temperature at 20, reserved[0] at 24, reserved[1] at 28.
  *   seed         the row's own seed: the draw at audio position p is uniform01(seed, key, p) — nothing of the launch (its
  *                scalar seed, the decoder's seed_dev, the row's index in the launch) enters it;
  *   key          the `row` of the counter-based generator: the beam index WITHIN the request, so the beams of one request
@@ -608,6 +608,20 @@ int vh_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k,
  *   top_p        as vh_sample_step's;
  *   temperature  > 0 (NOT checked: the records live on the device); the kernel divides 1.0f by it in fp32, as the host does
  *                for vh_sample_step, so a record that holds a call's values filters exactly as that call.
+ *   reserved[0]  window K of REPETITION-AWARE sampling (VALL-E 2); 0: off — the row samples exactly as above, bit for bit;
+ *   reserved[1]  max_repeats R (read only when window != 0).  With window = K >= 1, at audio position p (BOS at 0):
+ *                  1. the first draw is exactly the draw above: same filter, u1 = uniform01(seed, key, p), same token c;
+ *                  2. n_c = how many of the row's own codes[max(1, p - K) .. p - 1] equal c (prompt codes count, BOS never
+ *                     does, fewer than K entries early on);
+ *                  3. n_c > R: the token is drawn again from softmax(logits / temperature) over all V entries — no top-k, no
+ *                     top-p, walked in index order — with u2 = uniform01(seed, key, p | 0x40000000) (bit 30: apart from
+ *                     every first draw and from the NAR stage's streams, bit 31).  It may be c again and may be EOS;
+ *                     sum_logprobs takes ITS log-probability under the unfiltered distribution in place of the filtered one;
+ *                  4. a finished row (codes[p - 1] == eos) skips 2 and 3 and writes EOS as ever;
+ *                  5. top_k == 1 stays greedy whatever else the record says: the two words are ignored.
+ *                The ratio threshold t_r of the paper over its window K is max_repeats = floor(t_r * K) (K = 10, t_r = 0.1:
+ *                window 10, max_repeats 1).  The scalar entries (one filter for every row) and vh_categorical_rows_keyed (the
+ *                NAR stage) do not read the two words.
  * The caller may rewrite records between launches (stream-ordered); a captured graph holds the pointer, not the values. */
 typedef struct {
     uint64_t seed;

@@ -385,7 +385,9 @@ extern "C" int vh_greedy_step(const float* logits, int ldl, int V, int eos, int6
 //   4. draw from the renormalised kept set with a counter-based RNG keyed on (seed, row, position)
 //      — a captured graph replays with fresh randomness because the position advances;
 //   5. logprob = log p(token) under the filtered distribution; sum_logprobs[b] += logprob while the
-//      row has not finished (valle_ar.py:167).
+//      row has not finished (valle_ar.py:167);
+//   6. per-row records only (rs != NULL) and only where the record asks for it: the repetition-aware redraw of a token
+//      that fills too much of the row's last tokens (ROW_SAMPLING_LOAD below).
 // The RNG stream differs from torch.multinomial's (CPU mt19937 / Philox): parity with the reference
 // is distributional, not sample-exact (SURVEY.md §8c "parity unpinned" for top_k > 1).
 // ---------------------------------------------------------------------------------------------
@@ -411,6 +413,14 @@ __device__ __forceinline__ uint32_t okey(float x) {
 // index on ties and a log-probability of exactly 0 (greedy_step_kernel's token): the scores stay unscaled (a scale could
 // merge neighbouring logits into a tie), zeros of either sign become +0.0 (greedy_step_kernel compares values, for which
 // -0.0 == +0.0; the radix keys would order them), top_p is off and only the first survivor in index order is kept.
+//
+// Repetition-aware sampling (reserved[0] = window K, reserved[1] = max_repeats R; K == 0: off, nothing below runs).  Once the
+// filtered draw c is known, a row that has not finished counts c among its own codes[max(1, pos - K) .. pos - 1] (the prompt
+// counts, BOS at 0 never does); more than R of them and the token is drawn again from softmax(logits / temperature) over all
+// V entries in index order, with u2 = uniform01(seed, key, pos | RAS_STREAM), and the row's score takes the log-probability
+// under that unfiltered distribution.  Everything the branch tests is block-uniform (one block, one row); top_k == 1 never
+// takes it.
+#define RAS_STREAM 0x40000000u    // bit 30: apart from every first draw (pos < 2^30) and from the NAR stage's streams (bit 31)
 #define ROW_SAMPLING_LOAD(rec)                                            \
     do {                                                                  \
         const vh_row_sampling r_ = (rec);                                 \
@@ -419,9 +429,86 @@ __device__ __forceinline__ uint32_t okey(float x) {
         top_k = r_.top_k;                                                 \
         top_p = r_.top_p;                                                 \
         inv_temp = 1.0f / r_.temperature;                                 \
+        ras_window = r_.reserved[0];                                      \
+        ras_max = r_.reserved[1];                                         \
         greedy = top_k == 1;                                              \
         if (greedy) { top_p = 1.0f; inv_temp = 1.0f; }                    \
     } while (0)
+
+// scan over a block of NW waves in thread order (the wide kernel's 16, the narrow kernel's 4 for its redraw): *excl / return
+// value = the exclusive / inclusive prefix of v, *total = the sum over the block.  The values are consistent: a thread's
+// excl is bit-equal to the previous thread's incl, the last thread's incl to *total.  s_w holds NW entries and may be
+// reused once this returns.
+template <int NW, typename T>
+__device__ __forceinline__ T wide_block_scan(T v, T* s_w, T* excl, T* total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    T prev = __shfl_up(incl, 1, 64);
+    if (lane == 0) prev = 0;
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        if (w == wv) before = all;
+        all += s_w[w];
+    }
+    __syncthreads();
+    *excl = before + prev;
+    *total = all;
+    return before + incl;
+}
+
+// inverse CDF over the weights exp(s_val[j] - m), j < n, in array order, by a block of NW waves: s_out[0] = the first j
+// whose inclusive sum exceeds u01 * total (the last entry when rounding leaves none), s_tot[0] = total.  Ends with a barrier.
+template <int NW>
+__device__ __forceinline__ void wide_draw(const float* s_val, int n, float m, float u01, float* s_w, int* s_out,
+                                          float* s_tot) {
+    const int tid = threadIdx.x;
+    const int per = (n + NW * 64 - 1) / (NW * 64);
+    const int j0 = min(n, tid * per), j1 = min(n, j0 + per);
+    float s = 0.f;
+    for (int j = j0; j < j1; ++j) s += expf(s_val[j] - m);
+    if (tid == 0) s_out[0] = n - 1;
+    float excl, total;
+    const float incl = wide_block_scan<NW>(s, s_w, &excl, &total);
+    const float u = u01 * total;
+    if (j1 > j0 && excl <= u && incl > u) {     // the intervals [excl, incl) tile [0, total): one owner at most
+        float acc = excl;
+        int pick = j1 - 1;
+        for (int j = j0; j < j1; ++j) {
+            acc += expf(s_val[j] - m);
+            if (acc > u) { pick = j; break; }
+        }
+        s_out[0] = pick;
+    }
+    if (tid == 0) s_tot[0] = total;
+    __syncthreads();
+}
+
+// how many of row[lo .. hi) equal tok, known to every thread of the NW-wave block; s_w holds NW entries and may be reused
+// once this returns.  It holds two barriers: what any thread read from shared memory before the call has been read by the
+// time another thread returns, so the caller may overwrite it.
+template <int NW>
+__device__ __forceinline__ int block_count_eq(const int64_t* row, int lo, int hi, int tok, int* s_w) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int c = 0;
+    for (int i = lo + (int)threadIdx.x; i < hi; i += NW * 64) c += row[i] == (int64_t)tok;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) s_w[wv] = c;
+    __syncthreads();
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) n += s_w[w];
+    __syncthreads();
+    return n;
+}
 
 __global__ __launch_bounds__(256) void sample_step_kernel(
     const float* __restrict__ logits, int ldl, int V, int eos, int top_k, float top_p, float inv_temp,
@@ -431,6 +518,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, int npow2, const uint64_t* __restrict__ seed_dev,
     const vh_row_sampling* __restrict__ rs) {
     uint32_t draw_key = blockIdx.x;   // the `row` of uniform01: the launch's row index, or the request's own key
+    uint32_t ras_window = 0, ras_max = 0;
     bool greedy = false;
     if (rs) {
         ROW_SAMPLING_LOAD(rs[blockIdx.x]);
@@ -617,6 +705,26 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
         pick_logprob = s_red[4];
     }
     if (greedy) pick_logprob = 0.f;
+    const int64_t* hist = codes + (int64_t)b * codes_stride;
+    if (ras_window != 0 && !greedy && hist[pos - 1] != (int64_t)eos) {
+        const int lo = (int)max((int64_t)1, (int64_t)pos - (int64_t)ras_window);
+        if ((uint32_t)block_count_eq<4>(hist, lo, pos, pick_tok, s_hist) > ras_max) {
+            // the redraw: every scaled logit back into s_val in index order, their maximum, the block-parallel draw
+            float vmax = -INFINITY;
+            for (int i = tid; i < V; i += 256) {
+                const float x = lr[i] * inv_temp;
+                s_val[i] = x;
+                vmax = fmaxf(vmax, x);
+            }
+            vmax = wave_max(vmax);
+            if (lane == 0) s_red[4 + wv] = vmax;
+            __syncthreads();
+            const float m = fmaxf(fmaxf(s_red[4], s_red[5]), fmaxf(s_red[6], s_red[7]));
+            wide_draw<4>(s_val, V, m, uniform01(seed, draw_key, (uint32_t)pos | RAS_STREAM), s_red, &s_sel[2], &s_red[4]);
+            pick_tok = s_sel[2];
+            pick_logprob = (s_val[pick_tok] - m) - logf(s_red[4]);
+        }
+    }
     if (tid == 0) {
         int64_t* row = codes + (int64_t)b * codes_stride;
         int tok = pick_tok;
@@ -704,60 +812,6 @@ extern "C" int vh_sample_step_rows(const float* logits, int ldl, int V, int eos,
 #define WIDE_WAVES (WIDE_THREADS / 64)
 #define WIDE_PER (VH_SAMPLE_MAX_V / WIDE_THREADS)   // indices per lane and 64-wide round of the compaction, at most
 
-// block-wide scan in thread order: *excl / return value = the exclusive / inclusive prefix of v, *total = the sum over
-// the block.  The values are consistent: a thread's excl is bit-equal to the previous thread's incl, the last thread's
-// incl to *total.  s_w holds WIDE_WAVES entries and may be reused once this returns.
-template <typename T>
-__device__ __forceinline__ T wide_block_scan(T v, T* s_w, T* excl, T* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-    }
-    T prev = __shfl_up(incl, 1, 64);
-    if (lane == 0) prev = 0;
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < WIDE_WAVES; ++w) {
-        if (w == wv) before = all;
-        all += s_w[w];
-    }
-    __syncthreads();
-    *excl = before + prev;
-    *total = all;
-    return before + incl;
-}
-
-// inverse CDF over the weights exp(s_val[j] - m), j < n, in array order: s_out[0] = the first j whose inclusive sum
-// exceeds u01 * total (the last entry when rounding leaves none), s_tot[0] = total.  Ends with a barrier.
-__device__ __forceinline__ void wide_draw(const float* s_val, int n, float m, float u01, float* s_w, int* s_out,
-                                          float* s_tot) {
-    const int tid = threadIdx.x;
-    const int per = (n + WIDE_THREADS - 1) / WIDE_THREADS;
-    const int j0 = min(n, tid * per), j1 = min(n, j0 + per);
-    float s = 0.f;
-    for (int j = j0; j < j1; ++j) s += expf(s_val[j] - m);
-    if (tid == 0) s_out[0] = n - 1;
-    float excl, total;
-    const float incl = wide_block_scan(s, s_w, &excl, &total);
-    const float u = u01 * total;
-    if (j1 > j0 && excl <= u && incl > u) {     // the intervals [excl, incl) tile [0, total): one owner at most
-        float acc = excl;
-        int pick = j1 - 1;
-        for (int j = j0; j < j1; ++j) {
-            acc += expf(s_val[j] - m);
-            if (acc > u) { pick = j; break; }
-        }
-        s_out[0] = pick;
-    }
-    if (tid == 0) s_tot[0] = total;
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
     const float* __restrict__ logits, int ldl, int V, int eos, int top_k, float top_p, float inv_temp,
     uint64_t seed, int64_t* __restrict__ codes, int64_t codes_stride, int32_t* __restrict__ eos_count,
@@ -766,6 +820,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
     int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, const uint64_t* __restrict__ seed_dev,
     const vh_row_sampling* __restrict__ rs) {
     uint32_t draw_key = blockIdx.x;
+    uint32_t ras_window = 0, ras_max = 0;
     bool greedy = false;
     if (rs) {
         ROW_SAMPLING_LOAD(rs[blockIdx.x]);
@@ -881,7 +936,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
 
     if (top_k > 0 && top_k < V && top_p == 1.0f) {
         // fast path: the draw over the survivors in index order
-        wide_draw(s_val, n, m, u01, s_wf, &s_sel[2], &s_tot);
+        wide_draw<WIDE_WAVES>(s_val, n, m, u01, s_wf, &s_sel[2], &s_tot);
     } else {
         // general path: sort the survivors descending (ties: lower index first) over the next power of two
         int np2 = 1;
@@ -912,7 +967,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
             float s = 0.f;
             for (int j = j1 - 1; j >= j0; --j) s += expf(s_val[j] - m);
             float after, total;
-            wide_block_scan(s, s_wf, &after, &total);
+            wide_block_scan<WIDE_WAVES>(s, s_wf, &after, &total);
             const float limit = (1.0f - top_p) * total;
             float tail = after;
             int over = 0;
@@ -921,14 +976,26 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
                 over += j >= 1 && tail > limit;
             }
             int ex, n_over;
-            wide_block_scan(over, s_wi, &ex, &n_over);
+            wide_block_scan<WIDE_WAVES>(over, s_wi, &ex, &n_over);
             n_keep = 1 + n_over;
         }
-        wide_draw(s_val, n_keep, m, u01, s_wf, &s_sel[2], &s_tot);
+        wide_draw<WIDE_WAVES>(s_val, n_keep, m, u01, s_wf, &s_sel[2], &s_tot);
     }
     const int slot = s_sel[2];
-    const int pick_tok = s_idx[slot];
-    const float pick_logprob = greedy ? 0.f : (s_val[slot] - m) - logf(s_tot);
+    int pick_tok = s_idx[slot];
+    float pick_logprob = greedy ? 0.f : (s_val[slot] - m) - logf(s_tot);
+    const int64_t* hist = codes + (int64_t)b * codes_stride;
+    if (ras_window != 0 && !greedy && hist[pos - 1] != (int64_t)eos) {
+        const int lo = (int)max((int64_t)1, (int64_t)pos - (int64_t)ras_window);
+        if ((uint32_t)block_count_eq<WIDE_WAVES>(hist, lo, pos, pick_tok, s_wi) > ras_max) {
+            // the redraw: every scaled logit back into s_val in index order (m is their maximum already), then the draw
+            for (int i = tid; i < V; i += WIDE_THREADS) s_val[i] = lr[i] * inv_temp;
+            __syncthreads();
+            wide_draw<WIDE_WAVES>(s_val, V, m, uniform01(seed, draw_key, (uint32_t)pos | RAS_STREAM), s_wf, &s_sel[2], &s_tot);
+            pick_tok = s_sel[2];
+            pick_logprob = (s_val[pick_tok] - m) - logf(s_tot);
+        }
+    }
 
     if (tid == 0) {
         int64_t* row = codes + (int64_t)b * codes_stride;

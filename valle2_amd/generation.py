@@ -53,10 +53,10 @@ def _check_grouped_decoder(entry, cfg, beams, needs):
                          f'{kernels.HEAD_DIM} (d_model <= {MAX_DECODE_D_MODEL})')
 
 
-def check_sampling(sampling, n, forced=None):
-    """The refusals of generate_batch(sampling=...): one Sampling per utterance or none at all, and no teacher forcing.
-    Returns the list, or None for a call without row sampling."""
-    sampling = _sampling.check_list('generate_batch', sampling, n)
+def check_sampling(sampling, n, forced=None, cfg=None):
+    """The refusals of generate_batch(sampling=...): one Sampling per utterance or none at all, each one the config can
+    resolve (cfg), and no teacher forcing.  Returns the list, or None for a call without row sampling."""
+    sampling = _sampling.check_list('generate_batch', sampling, n, cfg=cfg)
     if sampling is not None and forced is not None:
         raise ValueError('generate_batch: sampling with forced: teacher forcing appends the given tokens, nothing is drawn')
     return sampling
@@ -506,6 +506,7 @@ def _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode
     merged['sum_logprobs'] = torch.cat([st['sum_logprobs'] for st in stats])
     merged['tokens_appended'] = max(st['tokens_appended'] for st in stats)
     merged['groups'] = sum(st['groups'] for st in stats)
+    merged['repetition_aware'] = any(st['repetition_aware'] for st in stats)
     model.last_generate_stats = merged
     return out
 
@@ -519,7 +520,7 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
     if G == 0 or len(first_codes) != G:
         raise ValueError('generate_batch: texts and first_codes must be non-empty lists of equal length')
     check_beams(cfg, beams, shared_prompt, perf_mode, forced)
-    sampling = check_sampling(sampling, G, forced)
+    sampling = check_sampling(sampling, G, forced, cfg)
     by_hand = forced is not None or bool(profile_attn)
     check_forms(cfg, perf_mode, by_hand, shared_prompt)
     max_new = cfg.max_audio_len if max_new is None else max_new
@@ -594,6 +595,7 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
             'attn_mean_ms': attn_ms, 'attn_floor_ms': attn_floor_ms, 'attn_kernel_ms': attn_kernel_ms, 's0': plan.s0,
             'prompt_lens': plan.row_pls, 'groups': G, 'beams': beams, 'grouped_shared': plan.kind == GROUPED,
             'sum_logprobs': dec.sum_logprobs.clone(), 'sampling': 'rows' if plan.row_sampling else 'call',
+            'repetition_aware': _sampling.repetition_aware(sampling),
             # host time this call spent OUTSIDE enqueueing the prompt pass and the replays and waiting for them: set-up of
             # the call's state + building / capturing the decoder (nothing on a reused slot) + the tail after the last step
             # has finished
@@ -615,7 +617,7 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
     check_queued(model.config, beams, slots)
     cfg, dev, d = model.config, model.device, model.config.d_model
     texts, firsts = unpack_utterances(utterances)
-    sampling = _sampling.of_utterances('generate_queued', utterances)
+    sampling = _sampling.of_utterances('generate_queued', utterances, cfg)
     n = len(texts)
     if n == 0:
         raise ValueError('generate_queued: utterances must be a non-empty list')
@@ -742,7 +744,7 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
             'decoder_reused': state.reused, 'slot_uses': state.uses if state.busy else 0,
             'n_split': dec.n_split, 'prefill_ms': marks[0].elapsed_time(marks[1]),
             'decode_ms': marks[1].elapsed_time(done_mark), 'poll_gap_ms': gap_s * 1e3, 'kv_cache': True,
-            'sampling': 'rows' if plan.row_sampling else 'call'}
+            'sampling': 'rows' if plan.row_sampling else 'call', 'repetition_aware': _sampling.repetition_aware(sampling)}
         ok = True
         return [best_beam_tokens(model, *saved[u], pls[u]) for u in range(n)]
     finally:

@@ -755,13 +755,16 @@ _ROW_SAMPLING_DTYPE = [('seed', '<u8'), ('key', '<u4'), ('top_k', '<i4'), ('top_
 
 
 def pack_row_sampling(records):
-    """[(seed, key, top_k, top_p, temperature), ...] -> a HOST uint8 tensor (n, ROW_SAMPLING_BYTES) in the layout of
-    vh_row_sampling (include/valle_hip.h), one record per decode row."""
+    """[(seed, key, top_k, top_p, temperature[, window, max_repeats]), ...] -> a HOST uint8 tensor (n, ROW_SAMPLING_BYTES)
+    in the layout of vh_row_sampling (include/valle_hip.h), one record per decode row.  The two reserved words are the
+    repetition-aware rule's (sampling.RepetitionAware.records); a 5-tuple leaves them (0, 0): the rule off."""
     import numpy as np
     arr = np.zeros(len(records), dtype=np.dtype(_ROW_SAMPLING_DTYPE))
     assert arr.dtype.itemsize == ROW_SAMPLING_BYTES
-    for i, (seed, key, top_k, top_p, temperature) in enumerate(records):
-        arr[i] = (int(seed), int(key), int(top_k), float(top_p), float(temperature), (0, 0))
+    for i, (seed, key, top_k, top_p, temperature, *ras) in enumerate(records):
+        if len(ras) not in (0, 2):
+            raise ValueError(f'pack_row_sampling: record {i} holds {5 + len(ras)} values (5, or 7 with window and max_repeats)')
+        arr[i] = (int(seed), int(key), int(top_k), float(top_p), float(temperature), tuple(int(v) for v in ras) or (0, 0))
     return torch.from_numpy(arr.view(np.uint8).reshape(len(records), ROW_SAMPLING_BYTES).copy())
 
 

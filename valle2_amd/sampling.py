@@ -1,5 +1,6 @@
-"""Per-request sampling: what one utterance of a generate call asks of the sampler (seed, top-k, top-p, temperature), and
-the records the sample kernels read it from (include/valle_hip.h, vh_row_sampling).  Pure Python, no device."""
+"""Per-request sampling: what one utterance of a generate call asks of the sampler (seed, top-k, top-p, temperature, and with
+RepetitionAware the redraw of a token that repeats), and the records the sample kernels read it from (include/valle_hip.h,
+vh_row_sampling).  Pure Python, no device."""
 from __future__ import annotations
 
 import math
@@ -73,6 +74,62 @@ class Sampling:
         return (self.seed, 0, 1 if self.top_k == 1 else 0, 1.0, temperature)
 
 
+# A redraw at audio position p takes its uniform from position p | RAS_STREAM: bit 30 keeps it apart from every first draw
+# (positions < 5000) and from the NAR stage's streams (bit 31).
+RAS_STREAM = 0x40000000
+
+
+@dataclass(frozen=True)
+class RepetitionAware(Sampling):
+    """Sampling with VALL-E 2's repetition-aware rule for the AR stage: RepetitionAware(seed, top_k=None, tok_p=None,
+    temperature=None, window=10, max_repeats=1).
+
+    The token c of audio position p is drawn as Sampling draws it.  If c stands MORE than `max_repeats` times among the row's
+    own last `window` tokens (codes[max(1, p - window) .. p - 1]: the prompt counts, BOS does not, fewer than `window` early
+    on), the token is drawn again from softmax(logits / temperature) over the whole vocabulary — no top-k, no top-p, index
+    order, uniform01(seed, beam, p | RAS_STREAM) — and the beam's score takes that draw's unfiltered log-probability.  The
+    redrawn token may be c again, or EOS.  A finished row keeps writing EOS.  The paper's ratio threshold t_r over a window K
+    is max_repeats = floor(t_r * K): its K = 10, t_r = 0.1 are the defaults.  The draws stay a function of the request alone.
+
+    An extension (the reference has no such rule) of the AR stage only: the NAR stage reads nar_record(), which is
+    Sampling's, and ignores window and max_repeats.  Greedy decoding has nothing to redraw: an explicit top_k == 1 is a
+    ValueError here, and so is top_k=None under a config whose top_k is 1 (raised where the request meets the config, before
+    any device work).  Ranges (ValueError): window an int in [1, 2**31), max_repeats an int in [0, window) — a count of
+    `window` tokens never exceeds `window`."""
+    window: int = 10
+    max_repeats: int = 1
+
+    def __post_init__(self):
+        super().__post_init__()
+        if not _is_int(self.window) or not 1 <= self.window < 2 ** 31:
+            raise ValueError(f'RepetitionAware: window={self.window!r} (an int in [1, 2**31))')
+        if not _is_int(self.max_repeats) or not 0 <= self.max_repeats < self.window:
+            raise ValueError(f'RepetitionAware: max_repeats={self.max_repeats!r} (an int in [0, window={self.window}): more '
+                             'repeats than the window holds could never be counted)')
+        if self.top_k == 1:
+            raise ValueError('RepetitionAware: top_k=1 is greedy decoding, which draws nothing again (use Sampling)')
+
+    def resolved(self, cfg):
+        top_k, tok_p, temperature = super().resolved(cfg)
+        if top_k == 1:
+            raise ValueError(f'RepetitionAware: top_k={self.top_k!r} takes the config\'s top_k={cfg.top_k!r}, which is greedy '
+                             'decoding and draws nothing again (give the request a top_k of its own, or use Sampling)')
+        return top_k, tok_p, temperature
+
+    def records(self, cfg, beams, first_key=0):
+        """Sampling.records with the rule's two words: (seed, key, top_k, top_p, temperature, window, max_repeats)."""
+        return [r + (self.window, self.max_repeats) for r in super().records(cfg, beams, first_key)]
+
+
+def _request(s):
+    return s.request if isinstance(s, KeyedRows) else s
+
+
+def repetition_aware(sampling):
+    """Whether any request of a call's sampling list (or None) carries the repetition-aware rule."""
+    return any(isinstance(_request(s), RepetitionAware) for s in sampling or ())
+
+
 class KeyedRows(NamedTuple):
     """Internal: rows of a request handed over as utterances of their own, keyed from `first_key` on (generate() and the
     independent-rows fallback pass one utterance's beams as single rows: row j carries beam j).  Not part of the public
@@ -91,9 +148,10 @@ def beam_rows(request, beams, first_key=0):
     return [KeyedRows(request, first_key + j) for j in range(beams)]
 
 
-def check_list(entry, sampling, n, what='utterance'):
+def check_list(entry, sampling, n, what='utterance', cfg=None):
     """None when no entry of `sampling` (None, or a list of n) is a Sampling, the list when every one is; a mix is a
-    ValueError naming the first without one."""
+    ValueError naming the first without one.  With cfg every request is also resolved against the config, so what the two
+    cannot do together (Sampling.resolved, RepetitionAware.resolved) is said here."""
     if sampling is None:
         return None
     sampling = list(sampling)
@@ -108,14 +166,17 @@ def check_list(entry, sampling, n, what='utterance'):
         if s is None:
             raise ValueError(f'{entry}: {what} {i} carries no Sampling and others do: either every {what} of a call '
                              'carries one or none does')
+    if cfg is not None:
+        for s in sampling:
+            _request(s).resolved(cfg)
     return sampling
 
 
-def of_utterances(entry, utterances):
+def of_utterances(entry, utterances, cfg=None):
     """check_list over the optional fourth element of [(prompt_tokens, prompt_codes, target_tokens[, sampling]), ...]."""
     utterances = list(utterances)
     for i, u in enumerate(utterances):
         if len(u) not in (3, 4):
             raise ValueError(f'{entry}: utterance {i} has {len(u)} elements: (prompt_tokens, prompt_codes, target_tokens) '
                              'with an optional Sampling as the fourth')
-    return check_list(entry, [u[3] if len(u) == 4 else None for u in utterances], len(utterances))
+    return check_list(entry, [u[3] if len(u) == 4 else None for u in utterances], len(utterances), cfg=cfg)

@@ -43,7 +43,7 @@ def _beams_refused_early(fn):
         if kwargs.get('beams', 1) != 1 or kwargs.get('sampling') is not None:
             a = sig.bind(self, *args, **kwargs).arguments
             generation.check_beams(self.config, a.get('beams', 1), a.get('shared_prompt', False), a.get('perf_mode', False), a.get('forced'))
-            generation.check_sampling(a.get('sampling'), len(a['texts']), a.get('forced'))
+            generation.check_sampling(a.get('sampling'), len(a['texts']), a.get('forced'), self.config)
         return fn(self, *args, **kwargs)
     return wrapper
 
@@ -57,9 +57,11 @@ def _sampling_refused_early(fn):
     def wrapper(self, *args, **kwargs):
         a = sig.bind(self, *args, **kwargs).arguments
         if 'utterances' in a:
-            _sampling.of_utterances(fn.__name__, a['utterances'])
-        elif a.get('sampling') is not None and not isinstance(a['sampling'], _sampling.Sampling):
-            raise ValueError(f'{fn.__name__}: sampling is {type(a["sampling"]).__name__}, not a valle2_amd.Sampling')
+            _sampling.of_utterances(fn.__name__, a['utterances'], self.config)
+        elif a.get('sampling') is not None:
+            if not isinstance(a['sampling'], _sampling.Sampling):
+                raise ValueError(f'{fn.__name__}: sampling is {type(a["sampling"]).__name__}, not a valle2_amd.Sampling')
+            a['sampling'].resolved(self.config)
         return fn(self, *args, **kwargs)
     return wrapper
 
@@ -257,7 +259,7 @@ class ValleAR(_Base):
         generated, cut at max_audio_len; a call that fell back to generate_many records none)."""
         beams = self.config.num_beams if beams is None else beams
         generation.check_queued(self.config, beams, slots)
-        _sampling.of_utterances('generate_queued', utterances)
+        _sampling.of_utterances('generate_queued', utterances, self.config)
         return self._generate_queued(utterances, beams, slots)
 
     @_on_device
