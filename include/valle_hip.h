@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 141            /* 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 142            /* 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -643,6 +643,37 @@ int vh_sample_step_wide_rows(const float* logits, int ldl, int V, int eos, const
                              const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
                              float* x_next, int B, int d, void* stream);
 
+/* ---- K12 (stochastic) with PER-ROW LENGTH BOUNDS: at least min_new, at most max_new audio tokens per row ----------
+ * One record per decode row, a device array indexed like rs.  8 bytes, 8-byte aligned (one load per workgroup).  A bound
+ * of 0 is off; an all-zero record changes nothing.  For row b let p = audio_pos[b] (the position of the token being drawn)
+ * and n = p - pos_base[b] (the audio tokens the row has produced before this step):
+ *   1. a finished row (codes[p - 1] == eos) writes EOS as ever and reads neither word;
+ *   2. max_new > 0 and n >= max_new: the token is EOS, FORCED.  No draw, no repetition-aware count, no redraw;
+ *      sum_logprobs[b] is unchanged (a forced token is not the model's choice); eos_count, the token write, x_next,
+ *      audio_pos and cache_len behave as for any EOS.  The row produces at most max_new non-EOS tokens.  This test comes
+ *      before 3: a record with min_new > max_new behaves as its max_new;
+ *   3. n < min_new: EOS is OUTSIDE THE SUPPORT.  Its scaled score is -inf before top-k (ties included), top-p, the
+ *      top_k == 1 arg-max and the draw, and in the repetition-aware redraw over all V entries; the row's log-probability is
+ *      the one under the distribution without EOS.  The row produces at least min_new non-EOS tokens before EOS can
+ *      appear; no path returns a suppressed EOS (not the walk's last entry when rounding leaves none, not the sorted path
+ *      with top_k <= 0 or top_k >= V, where the -inf entry stays in the array);
+ *   4. the draws stay uniform01(seed, key, p) and uniform01(seed, key, p | 0x40000000): a request's rows remain a function
+ *      of the request alone. */
+typedef struct {
+    int32_t min_new, max_new;
+} vh_row_limits;
+
+/* vh_sample_step_rows / vh_sample_step_wide_rows with limits[b] beside rs[b].  limits == NULL: the _rows launch, bit for
+ * bit.  With limits, pos_base must not be NULL and V >= 2 (VH_EINVAL), limits 8-byte aligned (VH_EALIGN). */
+int vh_sample_step_rows_bounded(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs,
+                                const vh_row_limits* limits, int64_t* codes, int64_t codes_stride, int32_t* eos_count,
+                                const int32_t* pos_base, float* sum_logprobs, const float* audio_emb, const float* pe,
+                                int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d, void* stream);
+int vh_sample_step_wide_rows_bounded(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs,
+                                     const vh_row_limits* limits, int64_t* codes, int64_t codes_stride, int32_t* eos_count,
+                                     const int32_t* pos_base, float* sum_logprobs, const float* audio_emb, const float* pe,
+                                     int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d, void* stream);
+
 /* ---- composite: one AR decode step / hipGraph replay ----------------------------------------
  * The 5 launches per layer of one decode step (LN1+QKV+append, decode attention, out-proj+
  * residual, FeedForward slices, slab reduce + residual) plus head GEMM and vh_greedy_step, enqueued natively
@@ -738,6 +769,13 @@ typedef struct {
 typedef struct vh_ar_decoder vh_ar_decoder;
 vh_ar_decoder* vh_ar_decoder_create(const vh_ar_decoder_desc* desc);   /* NULL on bad desc */
 void vh_ar_decoder_destroy(vh_ar_decoder* dec);
+/* attach (or, with NULL, clear) the per-row length bounds the decoder's sample steps read: a device array of B
+ * vh_row_limits records, 8-byte aligned (VH_EALIGN).  Needs a decoder with row_sampling and pos_base (VH_EINVAL) and
+ * V >= 2.  Such a decoder always samples through vh_sample_step_rows / vh_sample_step_wide_rows: vh_ar_decoder_create
+ * refuses row_sampling together with head_ws, so the fused greedy head (which reads no limits) is never its step.  The captured graphs hold the pointer, so it is set BEFORE vh_ar_decoder_capture (after it: VH_ESTATE); the
+ * caller may rewrite the records between steps and replays (stream-ordered).  The descriptor keeps row_sampling as its
+ * trailing field. */
+int vh_ar_decoder_set_row_limits(vh_ar_decoder* dec, const vh_row_limits* limits);
 /* enqueue one step eagerly (no graph) */
 int vh_ar_decoder_step(vh_ar_decoder* dec, void* stream);
 /* capture one step into a hipGraph on `stream` (which must be a non-null, idle stream) */

@@ -138,24 +138,26 @@ def compile_elementwise_asm():
 
 
 # kernels that index per-table / per-entry data with runtime indices and must keep them out of scratch: the 9..32-table
-# embedding sum (no per-table array) and the wide sampler (16 registers per lane in its compaction, fully unrolled)
-NO_SCRATCH_KERNELS = ['embed_sum_pe_many_kernel', 'sample_step_wide_kernel']
+# embedding sum (no per-table array), the wide sampler (16 registers per lane in its compaction, fully unrolled) and the
+# narrow one (8 survivors per lane in its compaction); both samplers in both instantiations (with and without length bounds)
+NO_SCRATCH_KERNELS = ['embed_sum_pe_many_kernel', 'sample_step_wide_kernel', 'sample_step_kernel']
 
 
 def check_no_scratch(asm, names=NO_SCRATCH_KERNELS):
-    """No scratch access and a zero private segment in the named kernels (matched by their unmangled name)."""
+    """No scratch access and a zero private segment in the named kernels (matched by their unmangled name; every
+    instantiation of a templated one, e.g. the samplers with and without length bounds)."""
     problems = []
     for name in names:
-        m = re.search(r'^(_Z\d+%s\w*):[^\n]*\n(.*?)^\.Lfunc_end' % re.escape(name), asm, re.S | re.M)
-        if not m:
+        found = list(re.finditer(r'^(_Z\d+%s\w*):[^\n]*\n(.*?)^\.Lfunc_end' % re.escape(name), asm, re.S | re.M))
+        if not found:
             problems.append(f'{name} not found')
-            continue
-        if any(l.strip().startswith(('scratch_', 'buffer_store', 'buffer_load')) for l in m.group(2).splitlines()):
-            problems.append(f'{name}: scratch access')
-        seg = re.search(r'\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel' % re.escape(m.group(1)), asm, re.S)
-        size = re.search(r'\.amdhsa_private_segment_fixed_size (\d+)', seg.group(1)) if seg else None
-        if size is None or int(size.group(1)) != 0:
-            problems.append(f'{name}: private segment {size.group(1) if size else "unknown"} bytes')
+        for m in found:
+            if any(l.strip().startswith(('scratch_', 'buffer_store', 'buffer_load')) for l in m.group(2).splitlines()):
+                problems.append(f'{m.group(1)}: scratch access')
+            seg = re.search(r'\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel' % re.escape(m.group(1)), asm, re.S)
+            size = re.search(r'\.amdhsa_private_segment_fixed_size (\d+)', seg.group(1)) if seg else None
+            if size is None or int(size.group(1)) != 0:
+                problems.append(f'{m.group(1)}: private segment {size.group(1) if size else "unknown"} bytes')
     return problems
 
 

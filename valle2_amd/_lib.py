@@ -38,6 +38,11 @@ class VhRowSampling(C.Structure):
                 ('temperature', C.c_float), ('reserved', C.c_uint32 * 2)]
 
 
+class VhRowLimits(C.Structure):
+    """include/valle_hip.h vh_row_limits: one row's length bounds (8 bytes; 0 switches a bound off)."""
+    _fields_ = [('min_new', C.c_int32), ('max_new', C.c_int32)]
+
+
 class VhLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         'ln1_g', 'ln1_b', 'wqkv', 'wo', 'bo', 'ln2_g', 'ln2_b', 'w1', 'b1', 'w2', 'b2',
@@ -219,6 +224,11 @@ SIGNATURES = {
                                       c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
     'vh_sample_step_wide_rows': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64p, C.c_int64, c_i32p, c_i32p,
                                            c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    'vh_sample_step_rows_bounded': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_i64p, C.c_int64, c_i32p,
+                                              c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    'vh_sample_step_wide_rows_bounded': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_i64p, C.c_int64,
+                                                   c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int,
+                                                   C.c_void_p]),
     'vh_categorical_rows': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint32,
                                       c_i64p, C.c_int64, c_f32p, C.c_void_p]),
     # the NAR stage sampler keyed on (request, frame) (ABI 136)
@@ -230,6 +240,7 @@ SIGNATURES = {
                                 c_f32p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
     'vh_ar_decoder_create': (C.c_void_p, [C.POINTER(VhArDecoderDesc)]),
     'vh_ar_decoder_destroy': (None, [C.c_void_p]),
+    'vh_ar_decoder_set_row_limits': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vh_ar_decoder_step': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vh_ar_decoder_capture': (C.c_int, [C.c_void_p, C.c_void_p]),
     'vh_ar_decoder_replay': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

@@ -190,10 +190,10 @@ def synthesize_requests(ar, nar, items, codec=None, *, queued=False, slots=None)
     changes, but it is taken against the request's own fp32 logits, and those can differ in their last bits with the GEMM
     kernel the batch size selects (M <= 64 rows take the skinny kernels, more rows the tiles, with split-K at K >= 1024);
     a token changes only where such a difference moves a cumulative boundary across the draw."""
-    from .sampling import Sampling
+    from .sampling import Bounded, Sampling
     items = list(items)
     for i, item in enumerate(items):
-        if len(item) != 4 or not isinstance(item[3], Sampling):
+        if len(item) != 4 or not isinstance(item[3], (Sampling, Bounded)):     # (a Bounded's bounds hold in the AR stage only)
             raise ValueError(f'synthesize_requests: item {i} carries no valle2_amd.Sampling: every item is (prompt_tokens, '
                              'prompt, target_tokens, Sampling)')
     ar_generate = (lambda utts: ar.generate_queued(utts, slots=slots)) if queued else (lambda utts: ar.generate_many(utts))

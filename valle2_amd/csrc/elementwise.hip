@@ -435,6 +435,32 @@ __device__ __forceinline__ uint32_t okey(float x) {
         if (greedy) { top_p = 1.0f; inv_temp = 1.0f; }                    \
     } while (0)
 
+// Per-row length bounds (limits != NULL, which the entry points allow only with rs and pos_base): the block of row b loads
+// limits[b] once (block-uniform, 8 bytes) and, only where a word is set and the row has not finished, the two values that
+// place the row: n = pos - pos_base[b] tokens produced so far.  force_eos (max_new > 0 and n >= max_new): the token is EOS
+// with no draw, no repetition-aware count and no redraw, and the score does not move.  suppress_eos (otherwise, n <
+// min_new): the EOS score is -inf wherever scores enter LDS, so top-k, top-p, the arg-max, the draw and the redraw run over
+// the distribution without it.  An all-zero record sets neither.
+#define ROW_LIMITS_LOAD(lim, hist_last)                                   \
+    do {                                                                  \
+        const vh_row_limits l_ = (lim);                                   \
+        if ((l_.min_new | l_.max_new) != 0 && (hist_last) != (int64_t)eos) { \
+            const int n_ = pos - pos_base[blockIdx.x];                    \
+            force_eos = l_.max_new > 0 && n_ >= l_.max_new;               \
+            suppress_eos = !force_eos && n_ < l_.min_new;                 \
+        }                                                                 \
+    } while (0)
+// what a launch with limits needs (host side, before the launch): the records they sit beside, the base n is counted
+// from, a vocabulary that holds a token besides EOS, and the alignment of the one 8-byte load
+#define CHECK_ROW_LIMITS(name)                                                                                              \
+    do {                                                                                                                    \
+        VH_REQUIRE(!limits || rs, VH_EINVAL, name ": limits without rs (the length bounds sit beside per-row sampling records)"); \
+        VH_REQUIRE(!limits || pos_base, VH_EINVAL, name ": limits need pos_base (a row's tokens are counted from it)");      \
+        VH_REQUIRE(!limits || (V >= 2 && eos >= 0 && eos < V), VH_EINVAL,                                                   \
+                   name ": limits need V >= 2 and 0 <= eos < V (a token besides EOS to draw below min_new), got V=%d eos=%d", V, eos); \
+        VH_REQUIRE(((uintptr_t)limits & 7u) == 0, VH_EALIGN, name ": limits (vh_row_limits records) must be 8-byte aligned"); \
+    } while (0)
+
 // scan over a block of NW waves in thread order (the wide kernel's 16, the narrow kernel's 4 for its redraw): *excl / return
 // value = the exclusive / inclusive prefix of v, *total = the sum over the block.  The values are consistent: a thread's
 // excl is bit-equal to the previous thread's incl, the last thread's incl to *total.  s_w holds NW entries and may be
@@ -510,16 +536,21 @@ __device__ __forceinline__ int block_count_eq(const int64_t* row, int lo, int hi
     return n;
 }
 
+// BOUNDED: the instantiation that reads `limits` (launched only with limits != NULL).  Without it suppress_eos and force_eos
+// are constants and the kernel is the one it was: a launch without limits pays nothing for them (one kernel with a run-time
+// test of the pointer was measured once and not kept: its NULL launch cost 0.23 us more than the parent's at V = 1025,
+// profiles/ab_length_bounds_untemplated.log).
+template <bool BOUNDED>
 __global__ __launch_bounds__(256) void sample_step_kernel(
     const float* __restrict__ logits, int ldl, int V, int eos, int top_k, float top_p, float inv_temp,
     uint64_t seed, int64_t* __restrict__ codes, int64_t codes_stride, int32_t* __restrict__ eos_count,
     const int32_t* __restrict__ pos_base, float* __restrict__ sum_logprobs,
     const float* __restrict__ audio_emb, const float* __restrict__ pe, int32_t* __restrict__ audio_pos,
     int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, int npow2, const uint64_t* __restrict__ seed_dev,
-    const vh_row_sampling* __restrict__ rs) {
+    const vh_row_sampling* __restrict__ rs, const vh_row_limits* __restrict__ limits) {
     uint32_t draw_key = blockIdx.x;   // the `row` of uniform01: the launch's row index, or the request's own key
     uint32_t ras_window = 0, ras_max = 0;
-    bool greedy = false;
+    bool greedy = false, suppress_eos = false, force_eos = false;
     if (rs) {
         ROW_SAMPLING_LOAD(rs[blockIdx.x]);
     } else if (seed_dev) {
@@ -535,20 +566,25 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* lr = logits + (int64_t)b * ldl;
     const int pos = audio_pos[b];
-    int pick_tok = 0;
+    int pick_tok = eos;               // (what a forced row writes)
     float pick_logprob = 0.f;
+    if (BOUNDED) ROW_LIMITS_LOAD(limits[b], codes[(int64_t)b * codes_stride + pos - 1]);
 
     // ---- fast path: top-k only (top_p == 1, the reference's default top_k = 50, tok_p = 1.0) ---------------
     // No sort: the k-th largest score is found by a 4 x 8-bit radix select on order-preserving keys,
     // the survivors (>= k-th, ties kept) are compacted in index order and the draw walks their
     // cumulative probabilities.  (The sorted path below costs 66 barrier-separated bitonic stages and
     // serial exp loops on one thread: 89 us per launch against the 5 us of a greedy step.)
+    // (a suppressed EOS is -inf and top_k < V, so it never survives the select: the walk's fallback cannot return it)
     const bool fast = top_k > 0 && top_k < V && top_p == 1.0f;
-    if (fast) {
+    if (force_eos) {
+        // nothing is drawn
+    } else if (fast) {
         float vmax = -INFINITY;
         for (int i = tid; i < V; i += 256) {
             float x = lr[i] * inv_temp;
             if (greedy) x += 0.0f;                      // -0.0 -> +0.0: the keys then order the scores as a float compare does
+            if (suppress_eos && i == eos) x = -INFINITY;
             s_val[i] = x;
             vmax = fmaxf(vmax, x);
         }
@@ -646,7 +682,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     } else {
         // ---- general path: full descending sort, then top-k / top-p on the sorted scores -------------------
         for (int i = tid; i < npow2; i += 256) {
-            s_val[i] = i < V ? lr[i] * inv_temp : -INFINITY;
+            s_val[i] = i < V && !(suppress_eos && i == eos) ? lr[i] * inv_temp : -INFINITY;
             s_idx[i] = i;
         }
         __syncthreads();
@@ -674,6 +710,9 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
                 while (n_keep < V && s_val[n_keep] >= kth) ++n_keep;         // ties kept
                 if (greedy) n_keep = 1;                                      // (V == 1: the only row top_k == 1 brings here)
             }
+            // a suppressed EOS sorts to the tail as -inf (top_k <= 0 or >= V keeps it in the array): out of the kept set,
+            // so that neither the top-p walk nor the draw's last-entry fallback can return it
+            while (suppress_eos && n_keep > 1 && s_val[n_keep - 1] == -INFINITY) --n_keep;
             const float m = s_val[0];
             float total = 0.f;
             for (int i = 0; i < n_keep; ++i) total += expf(s_val[i] - m);
@@ -706,13 +745,14 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     }
     if (greedy) pick_logprob = 0.f;
     const int64_t* hist = codes + (int64_t)b * codes_stride;
-    if (ras_window != 0 && !greedy && hist[pos - 1] != (int64_t)eos) {
+    if (ras_window != 0 && !greedy && !force_eos && hist[pos - 1] != (int64_t)eos) {
         const int lo = (int)max((int64_t)1, (int64_t)pos - (int64_t)ras_window);
         if ((uint32_t)block_count_eq<4>(hist, lo, pos, pick_tok, s_hist) > ras_max) {
             // the redraw: every scaled logit back into s_val in index order, their maximum, the block-parallel draw
             float vmax = -INFINITY;
             for (int i = tid; i < V; i += 256) {
-                const float x = lr[i] * inv_temp;
+                float x = lr[i] * inv_temp;
+                if (suppress_eos && i == eos) x = -INFINITY;
                 s_val[i] = x;
                 vmax = fmaxf(vmax, x);
             }
@@ -722,6 +762,9 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
             const float m = fmaxf(fmaxf(s_red[4], s_red[5]), fmaxf(s_red[6], s_red[7]));
             wide_draw<4>(s_val, V, m, uniform01(seed, draw_key, (uint32_t)pos | RAS_STREAM), s_red, &s_sel[2], &s_red[4]);
             pick_tok = s_sel[2];
+            // (the walk's last entry when rounding leaves none may be the suppressed EOS: its neighbour then; V >= 2.  Only a
+            // row whose neighbour's logit is -inf as well could take a log-probability of -inf here: pathological logits)
+            if (suppress_eos && pick_tok == eos) pick_tok = eos > 0 ? eos - 1 : 1;
             pick_logprob = (s_val[pick_tok] - m) - logf(s_red[4]);
         }
     }
@@ -729,7 +772,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
         int64_t* row = codes + (int64_t)b * codes_stride;
         int tok = pick_tok;
         const bool finished = row[pos - 1] == (int64_t)eos;
-        if (sum_logprobs && !finished) sum_logprobs[b] += pick_logprob;      // valle_ar.py:167
+        if (sum_logprobs && !finished && !force_eos) sum_logprobs[b] += pick_logprob;   // valle_ar.py:167 (a forced EOS is not the model's choice)
         if (finished) tok = eos;                                             // valle_ar.py:168
         row[pos] = tok;
         if (tok == eos) atomicAdd(&eos_count[pos - (pos_base ? pos_base[b] : 0)], 1);
@@ -750,9 +793,11 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
 }
 
 // vh_sample_step with the seed = seed + *seed_dev (seed_dev may be NULL), or with per-row records (rs != NULL: top_k, top_p,
-// temperature, seed and seed_dev are not read): the decoder plan's form (plan.hip)
+// temperature, seed and seed_dev are not read; limits: the rows' length bounds beside them, or NULL): the decoder plan's form
+// (plan.hip)
 int vh_internal_sample_step(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
-                            float temperature, uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs, int64_t* codes, int64_t codes_stride,
+                            float temperature, uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs,
+                            const vh_row_limits* limits, int64_t* codes, int64_t codes_stride,
                             int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                             const float* audio_emb, const float* pe, int32_t* audio_pos,
                             int32_t* cache_len, float* x_next, int B, int d, void* stream) {
@@ -762,13 +807,15 @@ int vh_internal_sample_step(const float* logits, int ldl, int V, int eos, int to
                "vh_sample_step: bad dims B=%d V=%d (<= %d) ldl=%d d=%d", B, V, SAMPLE_MAXV, ldl, d);
     VH_REQUIRE(rs || temperature > 0.f, VH_EINVAL, "vh_sample_step: temperature must be positive");
     VH_REQUIRE(vh_aligned16(rs), VH_EALIGN, "vh_sample_step: the per-row sampling records must be 16-byte aligned");
+    CHECK_ROW_LIMITS("vh_sample_step");
     VH_REQUIRE(vh_aligned16(audio_emb) && vh_aligned16(pe) && vh_aligned16(x_next), VH_EALIGN,
                "vh_sample_step: audio_emb/pe/x_next must be 16-byte aligned");
     int npow2 = 2;
     while (npow2 < V) npow2 <<= 1;
-    hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
+    const auto kernel = limits ? sample_step_kernel<true> : sample_step_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
                        eos, top_k, top_p, rs ? 1.0f : 1.0f / temperature, seed, codes, codes_stride, eos_count,
-                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, npow2, seed_dev, rs);
+                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, npow2, seed_dev, rs, limits);
     VH_CHECK_LAUNCH("vh_sample_step");
     return VH_OK;
 }
@@ -778,8 +825,8 @@ extern "C" int vh_sample_step(const float* logits, int ldl, int V, int eos, int 
                               int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                               const float* audio_emb, const float* pe, int32_t* audio_pos,
                               int32_t* cache_len, float* x_next, int B, int d, void* stream) {
-    return vh_internal_sample_step(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, nullptr, codes, codes_stride, eos_count,
-                                   pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
+    return vh_internal_sample_step(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, nullptr, nullptr, codes, codes_stride,
+                                   eos_count, pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
 }
 
 extern "C" int vh_sample_step_rows(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs, int64_t* codes,
@@ -787,8 +834,17 @@ extern "C" int vh_sample_step_rows(const float* logits, int ldl, int V, int eos,
                                   const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
                                   float* x_next, int B, int d, void* stream) {
     VH_REQUIRE(rs, VH_EINVAL, "vh_sample_step_rows: null sampling records (vh_sample_step takes one filter for every row)");
-    return vh_internal_sample_step(logits, ldl, V, eos, 0, 1.f, 1.f, 0, nullptr, rs, codes, codes_stride, eos_count, pos_base, sum_logprobs,
-                                  audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
+    return vh_internal_sample_step(logits, ldl, V, eos, 0, 1.f, 1.f, 0, nullptr, rs, nullptr, codes, codes_stride, eos_count, pos_base,
+                                  sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
+}
+
+extern "C" int vh_sample_step_rows_bounded(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs,
+                                          const vh_row_limits* limits, int64_t* codes, int64_t codes_stride, int32_t* eos_count,
+                                          const int32_t* pos_base, float* sum_logprobs, const float* audio_emb, const float* pe,
+                                          int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d, void* stream) {
+    VH_REQUIRE(rs, VH_EINVAL, "vh_sample_step_rows_bounded: null sampling records (vh_sample_step takes one filter for every row)");
+    return vh_internal_sample_step(logits, ldl, V, eos, 0, 1.f, 1.f, 0, nullptr, rs, limits, codes, codes_stride, eos_count, pos_base,
+                                  sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -812,16 +868,17 @@ extern "C" int vh_sample_step_rows(const float* logits, int ldl, int V, int eos,
 #define WIDE_WAVES (WIDE_THREADS / 64)
 #define WIDE_PER (VH_SAMPLE_MAX_V / WIDE_THREADS)   // indices per lane and 64-wide round of the compaction, at most
 
+template <bool BOUNDED>     // as sample_step_kernel's
 __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
     const float* __restrict__ logits, int ldl, int V, int eos, int top_k, float top_p, float inv_temp,
     uint64_t seed, int64_t* __restrict__ codes, int64_t codes_stride, int32_t* __restrict__ eos_count,
     const int32_t* __restrict__ pos_base, float* __restrict__ sum_logprobs,
     const float* __restrict__ audio_emb, const float* __restrict__ pe, int32_t* __restrict__ audio_pos,
     int32_t* __restrict__ cache_len, float* __restrict__ x_next, int d, const uint64_t* __restrict__ seed_dev,
-    const vh_row_sampling* __restrict__ rs) {
+    const vh_row_sampling* __restrict__ rs, const vh_row_limits* __restrict__ limits) {
     uint32_t draw_key = blockIdx.x;
     uint32_t ras_window = 0, ras_max = 0;
-    bool greedy = false;
+    bool greedy = false, suppress_eos = false, force_eos = false;
     if (rs) {
         ROW_SAMPLING_LOAD(rs[blockIdx.x]);
     } else if (seed_dev) {
@@ -839,160 +896,171 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* lr = logits + (int64_t)b * ldl;
     const int pos = audio_pos[b];
+    if (BOUNDED) ROW_LIMITS_LOAD(limits[b], codes[(int64_t)b * codes_stride + pos - 1]);
+    float m = 0.f;
+    int pick_tok = eos;               // (what a forced row writes: nothing below runs for it)
+    float pick_logprob = 0.f;
 
-    // 1. scores and their maximum
-    float vmax = -INFINITY;
-    for (int i = tid; i < V; i += WIDE_THREADS) {
-        float x = lr[i] * inv_temp;
-        if (greedy) x += 0.0f;                          // -0.0 -> +0.0, as in the narrow kernel
-        s_val[i] = x;
-        vmax = fmaxf(vmax, x);
-    }
-    vmax = wave_max(vmax);
-    if (lane == 0) s_max[wv] = vmax;
-    __syncthreads();
-    float m = s_max[0];
-#pragma unroll
-    for (int w = 1; w < WIDE_WAVES; ++w) m = fmaxf(m, s_max[w]);
-
-    // 2. key of the k-th largest score (survivors: key >= prefix; prefix 0 keeps every score)
-    uint32_t prefix = 0;
-    if (top_k > 0 && top_k < V) {
-        uint32_t mask = 0;
-        int want = top_k;                               // rank (from the top) of the k-th value among candidates
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            if (tid < 256) s_hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < V; i += WIDE_THREADS) {
-                const uint32_t key = okey(s_val[i]);
-                if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            if (wv == 0) {                              // lane l owns bins 255-4l .. 252-4l (descending)
-                int c[4], tot = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { c[j] = s_hist[255 - 4 * lane - j]; tot += c[j]; }
-                int incl = tot;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int up = __shfl_up(incl, o, 64);
-                    if (lane >= o) incl += up;
-                }
-                const int before = incl - tot;
-                if (before < want && incl >= want) {     // exactly one lane
-                    int acc = before;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (acc < want && acc + c[j] >= want) { s_sel[0] = 255 - 4 * lane - j; s_sel[1] = want - acc; }
-                        acc += c[j];
-                    }
-                }
-            }
-            __syncthreads();
-            prefix |= (uint32_t)s_sel[0] << shift;
-            mask |= 255u << shift;
-            want = s_sel[1];
+    if (!force_eos) {
+        // 1. scores and their maximum (a suppressed EOS enters as -inf: outside the maximum, the select and the survivors)
+        float vmax = -INFINITY;
+        for (int i = tid; i < V; i += WIDE_THREADS) {
+            float x = lr[i] * inv_temp;
+            if (greedy) x += 0.0f;                          // -0.0 -> +0.0, as in the narrow kernel
+            if (suppress_eos && i == eos) x = -INFINITY;
+            s_val[i] = x;
+            vmax = fmaxf(vmax, x);
         }
-    }
-
-    // 3. compact the survivors in index order: (score, index) pairs into s_val[0..n) / s_idx[0..n)
-    const int per = (V + WIDE_THREADS - 1) / WIDE_THREADS;       // 64-wide rounds per wave
-    const int w0 = wv * 64 * per;
-    float v[WIDE_PER];
-    uint32_t keep = 0;
-    int cnt = 0;
-#pragma unroll
-    for (int r = 0; r < WIDE_PER; ++r) {
-        const int i = w0 + r * 64 + lane;
-        const bool in = r < per && i < V;
-        v[r] = in ? s_val[i] : 0.f;
-        const bool k = in && okey(v[r]) >= prefix;
-        keep |= (uint32_t)k << r;
-        cnt += __popcll(__ballot(k));
-    }
-    if (lane == 0) s_wi[wv] = cnt;
-    __syncthreads();                                   // every read of s_val above precedes the writes below
-    int at = 0, n = 0;
-#pragma unroll
-    for (int w = 0; w < WIDE_WAVES; ++w) {
-        if (w == wv) at = n;
-        n += s_wi[w];
-    }
-    const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int r = 0; r < WIDE_PER; ++r) {
-        const bool k = (keep >> r) & 1u;
-        const uint64_t bal = __ballot(k);
-        if (k) {
-            const int slot = at + __popcll(bal & below);
-            s_val[slot] = v[r];
-            s_idx[slot] = w0 + r * 64 + lane;
-        }
-        at += __popcll(bal);
-    }
-    __syncthreads();
-    if (greedy) n = 1;                                 // slot 0: the lowest index of the ties for the maximum
-    const float u01 = uniform01(seed, draw_key, (uint32_t)pos);
-
-    if (top_k > 0 && top_k < V && top_p == 1.0f) {
-        // fast path: the draw over the survivors in index order
-        wide_draw<WIDE_WAVES>(s_val, n, m, u01, s_wf, &s_sel[2], &s_tot);
-    } else {
-        // general path: sort the survivors descending (ties: lower index first) over the next power of two
-        int np2 = 1;
-        while (np2 < n) np2 <<= 1;
-        for (int i = n + tid; i < np2; i += WIDE_THREADS) { s_val[i] = -INFINITY; s_idx[i] = 0x7fffffff; }
+        vmax = wave_max(vmax);
+        if (lane == 0) s_max[wv] = vmax;
         __syncthreads();
-        for (int k = 2; k <= np2; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int q = tid; q < (np2 >> 1); q += WIDE_THREADS) {
-                    const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), p = i | j;   // the pair (i, i ^ j), i < p
-                    const bool desc = (i & k) == 0;
-                    const float a = s_val[i], c = s_val[p];
-                    const int ia = s_idx[i], ic = s_idx[p];
-                    const bool a_first = a > c || (a == c && ia < ic);   // a belongs before c
-                    if (desc ? !a_first : a_first) {
-                        s_val[i] = c; s_val[p] = a; s_idx[i] = ic; s_idx[p] = ia;
+        m = s_max[0];
+#pragma unroll
+        for (int w = 1; w < WIDE_WAVES; ++w) m = fmaxf(m, s_max[w]);
+
+        // 2. key of the k-th largest score (survivors: key >= prefix; prefix 0 keeps every score)
+        uint32_t prefix = 0;
+        if (top_k > 0 && top_k < V) {
+            uint32_t mask = 0;
+            int want = top_k;                               // rank (from the top) of the k-th value among candidates
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                if (tid < 256) s_hist[tid] = 0;
+                __syncthreads();
+                for (int i = tid; i < V; i += WIDE_THREADS) {
+                    const uint32_t key = okey(s_val[i]);
+                    if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
+                }
+                __syncthreads();
+                if (wv == 0) {                              // lane l owns bins 255-4l .. 252-4l (descending)
+                    int c[4], tot = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { c[j] = s_hist[255 - 4 * lane - j]; tot += c[j]; }
+                    int incl = tot;
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const int up = __shfl_up(incl, o, 64);
+                        if (lane >= o) incl += up;
+                    }
+                    const int before = incl - tot;
+                    if (before < want && incl >= want) {     // exactly one lane
+                        int acc = before;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            if (acc < want && acc + c[j] >= want) { s_sel[0] = 255 - 4 * lane - j; s_sel[1] = want - acc; }
+                            acc += c[j];
+                        }
                     }
                 }
                 __syncthreads();
+                prefix |= (uint32_t)s_sel[0] << shift;
+                mask |= 255u << shift;
+                want = s_sel[1];
             }
-        int n_keep = n;
-        if (top_p >= 0.f && top_p <= 1.f) {
-            // drop entries from the smallest up while the cumulative probability of the dropped ones is <= 1 - top_p,
-            // always keeping the largest: n_keep = 1 + #{j >= 1 : sum_{i >= j} e_i > (1 - top_p) * total}.  Thread t
-            // owns the run that ends at n - t * run, so its exclusive prefix is the suffix sum after its run.
-            const int run = (n + WIDE_THREADS - 1) / WIDE_THREADS;
-            const int j1 = max(0, n - tid * run), j0 = max(0, j1 - run);
-            float s = 0.f;
-            for (int j = j1 - 1; j >= j0; --j) s += expf(s_val[j] - m);
-            float after, total;
-            wide_block_scan<WIDE_WAVES>(s, s_wf, &after, &total);
-            const float limit = (1.0f - top_p) * total;
-            float tail = after;
-            int over = 0;
-            for (int j = j1 - 1; j >= j0; --j) {
-                tail += expf(s_val[j] - m);
-                over += j >= 1 && tail > limit;
-            }
-            int ex, n_over;
-            wide_block_scan<WIDE_WAVES>(over, s_wi, &ex, &n_over);
-            n_keep = 1 + n_over;
         }
-        wide_draw<WIDE_WAVES>(s_val, n_keep, m, u01, s_wf, &s_sel[2], &s_tot);
+
+        // 3. compact the survivors in index order: (score, index) pairs into s_val[0..n) / s_idx[0..n).  A suppressed EOS is
+        // never one of them (prefix 0 would keep its -inf): no sort, top-p walk or last-entry fallback below can return it
+        const int per = (V + WIDE_THREADS - 1) / WIDE_THREADS;       // 64-wide rounds per wave
+        const int w0 = wv * 64 * per;
+        float v[WIDE_PER];
+        uint32_t keep = 0;
+        int cnt = 0;
+#pragma unroll
+        for (int r = 0; r < WIDE_PER; ++r) {
+            const int i = w0 + r * 64 + lane;
+            const bool in = r < per && i < V && !(suppress_eos && i == eos);
+            v[r] = in ? s_val[i] : 0.f;
+            const bool k = in && okey(v[r]) >= prefix;
+            keep |= (uint32_t)k << r;
+            cnt += __popcll(__ballot(k));
+        }
+        if (lane == 0) s_wi[wv] = cnt;
+        __syncthreads();                                   // every read of s_val above precedes the writes below
+        int at = 0, n = 0;
+#pragma unroll
+        for (int w = 0; w < WIDE_WAVES; ++w) {
+            if (w == wv) at = n;
+            n += s_wi[w];
+        }
+        const uint64_t below = (1ull << lane) - 1ull;
+#pragma unroll
+        for (int r = 0; r < WIDE_PER; ++r) {
+            const bool k = (keep >> r) & 1u;
+            const uint64_t bal = __ballot(k);
+            if (k) {
+                const int slot = at + __popcll(bal & below);
+                s_val[slot] = v[r];
+                s_idx[slot] = w0 + r * 64 + lane;
+            }
+            at += __popcll(bal);
+        }
+        __syncthreads();
+        if (greedy) n = 1;                                 // slot 0: the lowest index of the ties for the maximum
+        const float u01 = uniform01(seed, draw_key, (uint32_t)pos);
+
+        if (top_k > 0 && top_k < V && top_p == 1.0f) {
+            // fast path: the draw over the survivors in index order
+            wide_draw<WIDE_WAVES>(s_val, n, m, u01, s_wf, &s_sel[2], &s_tot);
+        } else {
+            // general path: sort the survivors descending (ties: lower index first) over the next power of two
+            int np2 = 1;
+            while (np2 < n) np2 <<= 1;
+            for (int i = n + tid; i < np2; i += WIDE_THREADS) { s_val[i] = -INFINITY; s_idx[i] = 0x7fffffff; }
+            __syncthreads();
+            for (int k = 2; k <= np2; k <<= 1)
+                for (int j = k >> 1; j > 0; j >>= 1) {
+                    for (int q = tid; q < (np2 >> 1); q += WIDE_THREADS) {
+                        const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), p = i | j;   // the pair (i, i ^ j), i < p
+                        const bool desc = (i & k) == 0;
+                        const float a = s_val[i], c = s_val[p];
+                        const int ia = s_idx[i], ic = s_idx[p];
+                        const bool a_first = a > c || (a == c && ia < ic);   // a belongs before c
+                        if (desc ? !a_first : a_first) {
+                            s_val[i] = c; s_val[p] = a; s_idx[i] = ic; s_idx[p] = ia;
+                        }
+                    }
+                    __syncthreads();
+                }
+            int n_keep = n;
+            if (top_p >= 0.f && top_p <= 1.f) {
+                // drop entries from the smallest up while the cumulative probability of the dropped ones is <= 1 - top_p,
+                // always keeping the largest: n_keep = 1 + #{j >= 1 : sum_{i >= j} e_i > (1 - top_p) * total}.  Thread t
+                // owns the run that ends at n - t * run, so its exclusive prefix is the suffix sum after its run.
+                const int run = (n + WIDE_THREADS - 1) / WIDE_THREADS;
+                const int j1 = max(0, n - tid * run), j0 = max(0, j1 - run);
+                float s = 0.f;
+                for (int j = j1 - 1; j >= j0; --j) s += expf(s_val[j] - m);
+                float after, total;
+                wide_block_scan<WIDE_WAVES>(s, s_wf, &after, &total);
+                const float limit = (1.0f - top_p) * total;
+                float tail = after;
+                int over = 0;
+                for (int j = j1 - 1; j >= j0; --j) {
+                    tail += expf(s_val[j] - m);
+                    over += j >= 1 && tail > limit;
+                }
+                int ex, n_over;
+                wide_block_scan<WIDE_WAVES>(over, s_wi, &ex, &n_over);
+                n_keep = 1 + n_over;
+            }
+            wide_draw<WIDE_WAVES>(s_val, n_keep, m, u01, s_wf, &s_sel[2], &s_tot);
+        }
+        const int slot = s_sel[2];
+        pick_tok = s_idx[slot];
+        pick_logprob = greedy ? 0.f : (s_val[slot] - m) - logf(s_tot);
     }
-    const int slot = s_sel[2];
-    int pick_tok = s_idx[slot];
-    float pick_logprob = greedy ? 0.f : (s_val[slot] - m) - logf(s_tot);
     const int64_t* hist = codes + (int64_t)b * codes_stride;
-    if (ras_window != 0 && !greedy && hist[pos - 1] != (int64_t)eos) {
+    if (ras_window != 0 && !greedy && !force_eos && hist[pos - 1] != (int64_t)eos) {
         const int lo = (int)max((int64_t)1, (int64_t)pos - (int64_t)ras_window);
         if ((uint32_t)block_count_eq<WIDE_WAVES>(hist, lo, pos, pick_tok, s_wi) > ras_max) {
             // the redraw: every scaled logit back into s_val in index order (m is their maximum already), then the draw
-            for (int i = tid; i < V; i += WIDE_THREADS) s_val[i] = lr[i] * inv_temp;
+            for (int i = tid; i < V; i += WIDE_THREADS) s_val[i] = suppress_eos && i == eos ? -INFINITY : lr[i] * inv_temp;
             __syncthreads();
             wide_draw<WIDE_WAVES>(s_val, V, m, uniform01(seed, draw_key, (uint32_t)pos | RAS_STREAM), s_wf, &s_sel[2], &s_tot);
             pick_tok = s_sel[2];
+            // (the walk's last entry when rounding leaves none may be the suppressed EOS: its neighbour then; V >= 2.  Only a
+            // row whose neighbour's logit is -inf as well could take a log-probability of -inf here: pathological logits)
+            if (suppress_eos && pick_tok == eos) pick_tok = eos > 0 ? eos - 1 : 1;
             pick_logprob = (s_val[pick_tok] - m) - logf(s_tot);
         }
     }
@@ -1001,7 +1069,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
         int64_t* row = codes + (int64_t)b * codes_stride;
         int tok = pick_tok;
         const bool finished = row[pos - 1] == (int64_t)eos;
-        if (sum_logprobs && !finished) sum_logprobs[b] += pick_logprob;      // valle_ar.py:167
+        if (sum_logprobs && !finished && !force_eos) sum_logprobs[b] += pick_logprob;   // valle_ar.py:167 (a forced EOS is not the model's choice)
         if (finished) tok = eos;                                             // valle_ar.py:168
         row[pos] = tok;
         if (tok == eos) atomicAdd(&eos_count[pos - (pos_base ? pos_base[b] : 0)], 1);
@@ -1022,10 +1090,11 @@ __global__ __launch_bounds__(WIDE_THREADS) void sample_step_wide_kernel(
 }
 
 // vh_sample_step_wide with the seed = seed + *seed_dev (seed_dev may be NULL), or with per-row records (rs != NULL: top_k, top_p,
-// temperature, seed and seed_dev are not read): the decoder plan's form (plan.hip)
+// temperature, seed and seed_dev are not read; limits: the rows' length bounds beside them, or NULL): the decoder plan's form
+// (plan.hip)
 int vh_internal_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k, float top_p,
-                                 float temperature, uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs, int64_t* codes,
-                                 int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                                 float temperature, uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs,
+                                 const vh_row_limits* limits, int64_t* codes, int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                                  const float* audio_emb, const float* pe, int32_t* audio_pos,
                                  int32_t* cache_len, float* x_next, int B, int d, void* stream) {
     VH_REQUIRE(logits && codes && eos_count && audio_emb && pe && audio_pos && cache_len && x_next,
@@ -1034,11 +1103,13 @@ int vh_internal_sample_step_wide(const float* logits, int ldl, int V, int eos, i
                "vh_sample_step_wide: bad dims B=%d V=%d (<= %d) ldl=%d d=%d", B, V, VH_SAMPLE_MAX_V, ldl, d);
     VH_REQUIRE(rs || temperature > 0.f, VH_EINVAL, "vh_sample_step_wide: temperature must be positive");
     VH_REQUIRE(vh_aligned16(rs), VH_EALIGN, "vh_sample_step_wide: the per-row sampling records must be 16-byte aligned");
+    CHECK_ROW_LIMITS("vh_sample_step_wide");
     VH_REQUIRE(vh_aligned16(audio_emb) && vh_aligned16(pe) && vh_aligned16(x_next), VH_EALIGN,
                "vh_sample_step_wide: audio_emb/pe/x_next must be 16-byte aligned");
-    hipLaunchKernelGGL(sample_step_wide_kernel, dim3(B), dim3(WIDE_THREADS), 0, (hipStream_t)stream, logits, ldl, V,
+    const auto kernel = limits ? sample_step_wide_kernel<true> : sample_step_wide_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(WIDE_THREADS), 0, (hipStream_t)stream, logits, ldl, V,
                        eos, top_k, top_p, rs ? 1.0f : 1.0f / temperature, seed, codes, codes_stride, eos_count,
-                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, seed_dev, rs);
+                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, d, seed_dev, rs, limits);
     VH_CHECK_LAUNCH("vh_sample_step_wide");
     return VH_OK;
 }
@@ -1048,9 +1119,9 @@ extern "C" int vh_sample_step_wide(const float* logits, int ldl, int V, int eos,
                                    int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
                                    const float* audio_emb, const float* pe, int32_t* audio_pos,
                                    int32_t* cache_len, float* x_next, int B, int d, void* stream) {
-    return vh_internal_sample_step_wide(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, nullptr, codes, codes_stride,
-                                        eos_count, pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d,
-                                        stream);
+    return vh_internal_sample_step_wide(logits, ldl, V, eos, top_k, top_p, temperature, seed, nullptr, nullptr, nullptr, codes,
+                                        codes_stride, eos_count, pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next,
+                                        B, d, stream);
 }
 
 extern "C" int vh_sample_step_wide_rows(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs, int64_t* codes,
@@ -1058,8 +1129,19 @@ extern "C" int vh_sample_step_wide_rows(const float* logits, int ldl, int V, int
                                        const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
                                        float* x_next, int B, int d, void* stream) {
     VH_REQUIRE(rs, VH_EINVAL, "vh_sample_step_wide_rows: null sampling records (vh_sample_step_wide takes one filter for every row)");
-    return vh_internal_sample_step_wide(logits, ldl, V, eos, 0, 1.f, 1.f, 0, nullptr, rs, codes, codes_stride, eos_count, pos_base, sum_logprobs,
-                                       audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
+    return vh_internal_sample_step_wide(logits, ldl, V, eos, 0, 1.f, 1.f, 0, nullptr, rs, nullptr, codes, codes_stride, eos_count, pos_base,
+                                       sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
+}
+
+extern "C" int vh_sample_step_wide_rows_bounded(const float* logits, int ldl, int V, int eos, const vh_row_sampling* rs,
+                                               const vh_row_limits* limits, int64_t* codes, int64_t codes_stride,
+                                               int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                                               const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len,
+                                               float* x_next, int B, int d, void* stream) {
+    VH_REQUIRE(rs, VH_EINVAL,
+               "vh_sample_step_wide_rows_bounded: null sampling records (vh_sample_step_wide takes one filter for every row)");
+    return vh_internal_sample_step_wide(logits, ldl, V, eos, 0, 1.f, 1.f, 0, nullptr, rs, limits, codes, codes_stride, eos_count,
+                                       pos_base, sum_logprobs, audio_emb, pe, audio_pos, cache_len, x_next, B, d, stream);
 }
 
 

@@ -51,6 +51,7 @@ struct vh_ar_decoder {
     hipGraph_t graph_n = nullptr;        // VH_GRAPH_STEPS consecutive steps in one graph (fewer graph launches per generate)
     hipGraphExec_t exec_n = nullptr;
     int ldl = 0;
+    const vh_row_limits* row_limits = nullptr;   // vh_ar_decoder_set_row_limits: the rows' length bounds, beside d.row_sampling
 };
 
 // The decode attention of one layer as attention.hip's call record: any head width or 64, 16-bit or fp32 caches, one shared
@@ -195,14 +196,15 @@ int vh_internal_ffn_decode_w16(const float* x, int ldx, const uint16_t* w1f16, c
                                const uint16_t* w2_16, const float* b2, float* out, int ldo, int M, int d_model, int dff,
                                float ln_eps, void* workspace, size_t workspace_bytes, void* stream);                  // ffn.hip
 int vh_internal_sample_step(const float* logits, int ldl, int V, int eos, int top_k, float top_p, float temperature, uint64_t seed,
-                            const uint64_t* seed_dev, const vh_row_sampling* rs, int64_t* codes, int64_t codes_stride, int32_t* eos_count,
-                            const int32_t* pos_base, float* sum_logprobs, const float* audio_emb, const float* pe,
-                            int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d, void* stream);   // elementwise.hip
+                            const uint64_t* seed_dev, const vh_row_sampling* rs, const vh_row_limits* limits, int64_t* codes,
+                            int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs,
+                            const float* audio_emb, const float* pe, int32_t* audio_pos, int32_t* cache_len, float* x_next, int B,
+                            int d, void* stream);   // elementwise.hip
 int vh_internal_sample_step_wide(const float* logits, int ldl, int V, int eos, int top_k, float top_p, float temperature,
-                                 uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs, int64_t* codes,
-                                 int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base, float* sum_logprobs, const float* audio_emb,
-                                 const float* pe, int32_t* audio_pos, int32_t* cache_len, float* x_next, int B, int d,
-                                 void* stream);   // elementwise.hip
+                                 uint64_t seed, const uint64_t* seed_dev, const vh_row_sampling* rs, const vh_row_limits* limits,
+                                 int64_t* codes, int64_t codes_stride, int32_t* eos_count, const int32_t* pos_base,
+                                 float* sum_logprobs, const float* audio_emb, const float* pe, int32_t* audio_pos,
+                                 int32_t* cache_len, float* x_next, int B, int d, void* stream);   // elementwise.hip
 
 static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEvent_t>* ev,
                            std::vector<hipEvent_t>* kev = nullptr) {
@@ -320,12 +322,31 @@ static int decoder_enqueue(vh_ar_decoder* dec, hipStream_t s, std::vector<hipEve
                            d.pos_base, d.audio_emb, d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
     else if (d.V > 2048)              // wider than vh_sample_step's LDS row (decoder_check bounds V by VH_SAMPLE_MAX_V)
         TRY(vh_internal_sample_step_wide(d.logits, dec->ldl, d.V, d.eos, d.top_k, d.top_p, d.temperature, d.seed, d.seed_dev,
-                                         d.row_sampling, d.codes, d.codes_stride, d.eos_count, d.pos_base, d.sum_logprobs, d.audio_emb,
-                                         d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
+                                         d.row_sampling, dec->row_limits, d.codes, d.codes_stride, d.eos_count, d.pos_base,
+                                         d.sum_logprobs, d.audio_emb, d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
     else
         TRY(vh_internal_sample_step(d.logits, dec->ldl, d.V, d.eos, d.top_k, d.top_p, d.temperature, d.seed, d.seed_dev,
-                                    d.row_sampling, d.codes, d.codes_stride, d.eos_count, d.pos_base, d.sum_logprobs, d.audio_emb,
-                                    d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
+                                    d.row_sampling, dec->row_limits, d.codes, d.codes_stride, d.eos_count, d.pos_base,
+                                    d.sum_logprobs, d.audio_emb, d.audio_pe, d.audio_pos, d.cache_len, d.x, B, D, s));
+    return VH_OK;
+}
+
+// The per-row length bounds of the decoder's sample steps (elementwise.hip, ROW_LIMITS_LOAD).  Not a descriptor field: the
+// descriptor keeps row_sampling as its trailing field.  The captured graphs hold the pointer, so it cannot change under them.
+extern "C" int vh_ar_decoder_set_row_limits(vh_ar_decoder* dec, const vh_row_limits* limits) {
+    VH_REQUIRE(dec, VH_EINVAL, "vh_ar_decoder_set_row_limits: null decoder");
+    VH_REQUIRE(!dec->exec && !dec->exec_n, VH_ESTATE,
+               "vh_ar_decoder_set_row_limits: called after vh_ar_decoder_capture (the graphs hold the pointer: set it before capture)");
+    // (with row_sampling the step is the sampler on every row: decoder_check refuses row_sampling with head_ws, so no decoder
+    // that passes here enqueues vh_head_greedy or vh_greedy_step, which read no limits)
+    VH_REQUIRE(dec->d.row_sampling, VH_EINVAL,
+               "vh_ar_decoder_set_row_limits: a decoder without row_sampling (the length bounds sit beside per-row sampling records)");
+    VH_REQUIRE(dec->d.pos_base, VH_EINVAL,
+               "vh_ar_decoder_set_row_limits: a decoder without pos_base (a row's tokens are counted from it)");
+    VH_REQUIRE(dec->d.V >= 2, VH_EINVAL, "vh_ar_decoder_set_row_limits: V=%d (a token besides EOS to draw below min_new: V >= 2)",
+               dec->d.V);
+    VH_REQUIRE(((uintptr_t)limits & 7u) == 0, VH_EALIGN, "vh_ar_decoder_set_row_limits: limits must be 8-byte aligned");
+    dec->row_limits = limits;
     return VH_OK;
 }
 

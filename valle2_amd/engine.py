@@ -770,16 +770,26 @@ def _check_row_sampling(rs, batch):
     return rs
 
 
+def _check_row_limits(limits, batch, rs):
+    if limits is not None and (rs is None or limits.dtype != torch.uint8 or tuple(limits.shape) != (batch, kernels.ROW_LIMITS_BYTES)
+                               or not limits.is_cuda or not limits.is_contiguous()):
+        raise _lib.VhError(f'row_limits must be a contiguous uint8 device tensor ({batch}, {kernels.ROW_LIMITS_BYTES}) beside '
+                           'row_sampling (kernels.pack_row_limits)')
+    return limits
+
+
 class StepSampler:
     """Head + sampling step on the last hidden row of a full forward (valle_ar.py:158-171: logits, top-k / top-p / greedy
     draw, EOS bookkeeping, token append) with the decode state on the device — what ArDecoder.sample_from does, without
     the native decoder behind it: the recompute path of ValleAR.generate_batch (use_kv_cache=False, or a head width the
     decoder is not built for) samples through this."""
 
-    def __init__(self, model, batch, codes, cache_len, audio_pos, pos_base, seed=0, row_sampling=None):
+    def __init__(self, model, batch, codes, cache_len, audio_pos, pos_base, seed=0, row_sampling=None, row_limits=None):
         """row_sampling: a uint8 device tensor (batch, kernels.ROW_SAMPLING_BYTES) of vh_row_sampling records, or None.  With
         it every row samples from its own record (seed, draw key, filter) and the config's top_k, tok_p, temperature and
-        `seed` are not read; the caller owns the tensor and may rewrite it between steps."""
+        `seed` are not read; the caller owns the tensor and may rewrite it between steps.  row_limits: beside it, a uint8
+        device tensor (batch, kernels.ROW_LIMITS_BYTES) of vh_row_limits records (min_new, max_new per row; zeros: no
+        bound), read by every sample — the first after a prompt pass included — and rewritten the same way."""
         cfg = model.config
         dev = codes.device
         self.B, self.V, self.d = batch, cfg.num_audio_tokens + 1, cfg.d_model
@@ -790,6 +800,7 @@ class StepSampler:
         self.sum_logprobs = torch.zeros(batch, device=dev, dtype=torch.float32)
         self.sampling = (int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature), int(seed))
         self.row_sampling = _check_row_sampling(row_sampling, batch)
+        self.row_limits = _check_row_limits(row_limits, batch, self.row_sampling)
         self.codes, self.cache_len, self.audio_pos, self.pos_base = codes, cache_len, audio_pos, pos_base
         self._keep = (model.proj.weight.detach(), model.audio_emb.weight.detach(), model.audio_position_emb.pe)
         self.n_split, self.ffn_ws, self.kv_bf16, self.head_ws = 0, None, False, None
@@ -806,7 +817,8 @@ class StepSampler:
         if self.row_sampling is not None:
             kernels.sample_step(self.logits[rows], self.V, self.eos, 0, 1.0, 1.0, 0, self.codes[rows], self.eos_count,
                                 self.sum_logprobs[rows], m[1], m[2], self.audio_pos[rows], cache_len, self.x[rows],
-                                pos_base=self.pos_base[rows], rs=self.row_sampling[rows])
+                                pos_base=self.pos_base[rows], rs=self.row_sampling[rows],
+                                limits=None if self.row_limits is None else self.row_limits[rows])
         elif self.sampling[0] == 1:
             kernels.greedy_step(self.logits[rows], self.V, self.eos, self.codes[rows], self.eos_count, m[1], m[2],
                                 self.audio_pos[rows], cache_len, self.x[rows], pos_base=self.pos_base[rows])
@@ -830,7 +842,7 @@ class ArDecoder(StepSampler):
 
     def __init__(self, model, batch, s_max, codes, cache: KVCache, cache_len, audio_pos, pos_base,
                  n_split=None, use_graph=True, seed=0, prefix: KVCache | None = None, prefix_len=0,
-                 prefix_lens=None, prefix_cap=0, beams=1, row_sampling=None):
+                 prefix_lens=None, prefix_cap=0, beams=1, row_sampling=None, row_limits=None):
         """prefix / prefix_len: SHARED-PROMPT decoding (the beams of ONE utterance, valle_ar.py:135-138): `prefix` is a
         one-row cache holding the prompt's K/V (its first prefix_len rows), `cache` then holds only the generated rows of
         every beam (s_max = its capacity) and cache_len counts those.  A 16-bit `cache` is perf mode; it takes key splits
@@ -842,7 +854,8 @@ class ArDecoder(StepSampler):
         caches only; prefix_len is not used.
 
         row_sampling: as StepSampler's; the captured steps read the records through the pointer, so rewriting the tensor
-        between replays re-keys the rows."""
+        between replays re-keys the rows.  row_limits: as StepSampler's, attached to the native decoder before any capture
+        (vh_ar_decoder_set_row_limits) and read through the pointer the same way."""
         cfg = model.config
         dev = cache.buf.device
         d, dff, V = cfg.d_model, cfg.dim_feedforward, cfg.num_audio_tokens + 1
@@ -899,6 +912,7 @@ class ArDecoder(StepSampler):
         # the sampling seed lives in device memory (desc.seed = 0 + *seed_dev): a captured graph would freeze a by-value
         # seed, and this decoder may serve many generate() calls (`reset`)
         self.row_sampling = _check_row_sampling(row_sampling, batch)
+        self.row_limits = _check_row_limits(row_limits, batch, self.row_sampling)
         self.seed_dev = torch.tensor([int(seed)], dtype=torch.int64).to(dev) if self.sampling[0] != 1 and row_sampling is None else None
         self.codes, self.cache, self.cache_len, self.audio_pos = codes, cache, cache_len, audio_pos
         self.pos_base = pos_base
@@ -963,6 +977,8 @@ class ArDecoder(StepSampler):
         if not self._h:
             msg = _lib.lib().vh_last_error()
             raise _lib.VhError(f'vh_ar_decoder_create: {msg.decode() if msg else "failed"}')
+        if self.row_limits is not None:
+            check(_lib.lib().vh_ar_decoder_set_row_limits(self._h, ptr(self.row_limits)), 'vh_ar_decoder_set_row_limits')
         self._captured = False
         self.use_graph = use_graph
 

@@ -53,10 +53,11 @@ def _check_grouped_decoder(entry, cfg, beams, needs):
                          f'{kernels.HEAD_DIM} (d_model <= {MAX_DECODE_D_MODEL})')
 
 
-def check_sampling(sampling, n, forced=None, cfg=None):
+def check_sampling(sampling, n, forced=None, cfg=None, max_new=None):
     """The refusals of generate_batch(sampling=...): one Sampling per utterance or none at all, each one the config can
-    resolve (cfg), and no teacher forcing.  Returns the list, or None for a call without row sampling."""
-    sampling = _sampling.check_list('generate_batch', sampling, n, cfg=cfg)
+    resolve (cfg), a Bounded's min_new within the call's cap (max_new, else the config's max_audio_len), and no teacher
+    forcing.  Returns the list, or None for a call without row sampling."""
+    sampling = _sampling.check_list('generate_batch', sampling, n, cfg=cfg, cap=max_new)
     if sampling is not None and forced is not None:
         raise ValueError('generate_batch: sampling with forced: teacher forcing appends the given tokens, nothing is drawn')
     return sampling
@@ -147,6 +148,7 @@ class DecodePlan:
     queued: bool          # the plan of generate_queued
     slot_eligible: bool   # the decoder may survive the call in a slot of the model
     row_sampling: bool = False   # every utterance carries its own Sampling: the sampler reads per-row records, not the config
+    row_limits: bool = False     # a request of the call carries a length bound (sampling.Bounded): vh_row_limits beside the records
 
 
 def _caches(kind, cfg, G, B, s0, s_max, cap, max_new, perf_mode):
@@ -172,7 +174,7 @@ def _caches(kind, cfg, G, B, s0, s_max, cap, max_new, perf_mode):
 
 
 def plan_decode(cfg, txs, pls, *, max_new, beams=1, shared_prompt=False, perf_mode=False, use_graph=True, by_hand=False,
-                queued=False, cap=None, pos_limits=None, row_sampling=False):
+                queued=False, cap=None, pos_limits=None, row_sampling=False, row_limits=False):
     """The DecodePlan of a call over utterances of text lengths `txs` and prompt lengths `pls` (BOS included).  by_hand:
     profile_attn or forced, the forms that drive the decoder themselves.  queued: generate_queued's rows (GROUPED whatever
     `beams`, `cap` given: of the longest prompt of the whole list, max_new: its steps cap).  pos_limits: (audio, text) rows
@@ -209,7 +211,7 @@ def plan_decode(cfg, txs, pls, *, max_new, beams=1, shared_prompt=False, perf_mo
         # (perf_mode='kv' with rows of their own narrows into a fresh cache per call: no slot; over a shared prompt it narrows
         # into the slot's 16-bit prefix)
         slot_eligible=not (no_cache or by_hand or (bool(perf_mode) and not prefill_bf16 and kind != SHARED)),
-        row_sampling=bool(row_sampling))
+        row_sampling=bool(row_sampling), row_limits=bool(row_sampling and row_limits))
 
 
 def slot_key(plan, cfg, device, weights):
@@ -223,7 +225,8 @@ def slot_key(plan, cfg, device, weights):
             plan.codes_width, plan.max_new, (plan.G, plan.beams, plan.cap) if grouped else None,
             int(cfg.max_audio_len) if plan.queued else None, plan.prefill_bf16, bool(plan.perf_mode), plan.use_graph,
             int(cfg.top_k), float(cfg.tok_p), float(cfg.temperature), str(device), _lib.TUNING_EPOCH,
-            tuple(os.environ.get(k) for k in _DECODER_ENV), weights) + (('row_sampling',) if plan.row_sampling else ())
+            tuple(os.environ.get(k) for k in _DECODER_ENV), weights) + (('row_sampling',) if plan.row_sampling else ()) + \
+        (('row_limits',) if plan.row_limits else ())    # (a decoder with the limits array attached: measured dearer per launch)
 
 
 def weights_key(model):
@@ -244,6 +247,7 @@ class DecodeState:
         self.codes = self.cache_len = self.audio_pos = self.pos_base = self.group_len = None
         self.poll_dev = self.poll_host = self.first_len = None            # generate_queued only
         self.row_sampling = None                                          # (B, 32) uint8: vh_row_sampling records of a call with Sampling
+        self.row_limits = None                                            # (B, 8) uint8 beside them when a request carries a bound: vh_row_limits (zeros: none)
         self.cache = self.prefix = self.dec = None
         self.reused = self.busy = False
         self.uses = 0
@@ -263,6 +267,10 @@ class DecodeState:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if cfg.top_k != 1 and not plan.row_sampling else 0
         if plan.row_sampling:
             host['row_sampling'] = kernels.pack_row_sampling([r for s in sampling for r in s.records(cfg, plan.beams)])
+        if plan.row_limits:
+            # beside the records whenever ANY request of the call carries a bound (zeros for those without): the decoder of
+            # such a call has the array attached before capture and serves every mix of bounds
+            host['row_limits'] = kernels.pack_row_limits(_sampling.row_limits(sampling, plan.beams))
         self.reused = self.dec is not None
         if self.reused:
             self.codes.fill_(model.eos_token)
@@ -289,11 +297,11 @@ class DecodeState:
         """The call's decoder, built over the armed buffers AFTER the prompt pass is enqueued (host work the pass hides)."""
         if self.dec is None and plan.kind == RECOMPUTE_GENERAL:
             self.dec = StepSampler(model, plan.B, self.codes, self.cache_len, self.audio_pos, self.pos_base, seed=seed,
-                                   row_sampling=self.row_sampling)
+                                   row_sampling=self.row_sampling, row_limits=self.row_limits)
         elif self.dec is None:
             self.dec = ArDecoder(model, plan.B, self.cache.s_max, self.codes, self.cache, self.cache_len, self.audio_pos,
                                  self.pos_base, use_graph=plan.use_graph and not plan.no_cache, seed=seed, prefix=self.prefix,
-                                 prefix_len=plan.s0, row_sampling=self.row_sampling,
+                                 prefix_len=plan.s0, row_sampling=self.row_sampling, row_limits=self.row_limits,
                                  **(dict(prefix_lens=self.group_len, prefix_cap=plan.cap, beams=plan.beams) if plan.kind == GROUPED else {}))
         return self.dec
 
@@ -507,6 +515,7 @@ def _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode
     merged['tokens_appended'] = max(st['tokens_appended'] for st in stats)
     merged['groups'] = sum(st['groups'] for st in stats)
     merged['repetition_aware'] = any(st['repetition_aware'] for st in stats)
+    merged['bounded'] = any(st['bounded'] for st in stats)
     model.last_generate_stats = merged
     return out
 
@@ -520,7 +529,7 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
     if G == 0 or len(first_codes) != G:
         raise ValueError('generate_batch: texts and first_codes must be non-empty lists of equal length')
     check_beams(cfg, beams, shared_prompt, perf_mode, forced)
-    sampling = check_sampling(sampling, G, forced, cfg)
+    sampling = check_sampling(sampling, G, forced, cfg, max_new)
     by_hand = forced is not None or bool(profile_attn)
     check_forms(cfg, perf_mode, by_hand, shared_prompt)
     max_new = cfg.max_audio_len if max_new is None else max_new
@@ -533,7 +542,7 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
     plan = plan_decode(cfg, [int(t.shape[0]) for t in texts], [int(c.shape[0]) + 1 for c in first_codes],   # BOS + prompt
                        max_new=max_new, beams=beams, shared_prompt=bool(shared_prompt), perf_mode=perf_mode, use_graph=use_graph,
                        by_hand=by_hand, pos_limits=(model.audio_position_emb.pe.shape[0], model.tokens_position_emb.pe.shape[0]),
-                       row_sampling=sampling is not None)
+                       row_sampling=sampling is not None, row_limits=_sampling.bounded(sampling))
     if not plan.fits:
         # beyond the 256 records one merge serves: the same rows, each with its own prompt pass and K/V
         out = model.generate_batch([t for t in texts for _ in range(beams)], [c for c in first_codes for _ in range(beams)],
@@ -595,7 +604,7 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
             'attn_mean_ms': attn_ms, 'attn_floor_ms': attn_floor_ms, 'attn_kernel_ms': attn_kernel_ms, 's0': plan.s0,
             'prompt_lens': plan.row_pls, 'groups': G, 'beams': beams, 'grouped_shared': plan.kind == GROUPED,
             'sum_logprobs': dec.sum_logprobs.clone(), 'sampling': 'rows' if plan.row_sampling else 'call',
-            'repetition_aware': _sampling.repetition_aware(sampling),
+            'repetition_aware': _sampling.repetition_aware(sampling), 'bounded': _sampling.bounded(sampling),
             # host time this call spent OUTSIDE enqueueing the prompt pass and the replays and waiting for them: set-up of
             # the call's state + building / capturing the decoder (nothing on a reused slot) + the tail after the last step
             # has finished
@@ -629,7 +638,8 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
     # the rows the call starts with; the capacity of the longest prompt of the CALL: any refill fits.  Every row may run
     # whole polls up to the one that covers max_new before the host rewinds or re-arms it
     plan = plan_decode(cfg, txs[:slots], pls[:slots], max_new=queue_steps_cap(max_new, poll), beams=beams, use_graph=use_graph,
-                       queued=True, cap=group_prefix_cap(max(ctx)), row_sampling=sampling is not None)
+                       queued=True, cap=group_prefix_cap(max(ctx)), row_sampling=sampling is not None,
+                       row_limits=_sampling.bounded(sampling))     # (of the whole list: a refill may bring the first bound)
     if not plan.fits:
         out = model.generate_many(utterances, beams=beams)
         model.last_generate_stats.update(queued=False)
@@ -647,9 +657,11 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
         firsts = [kernels.ids_to_device(c, dev, cfg.num_audio_tokens, 'prompt codes').contiguous() for c in firsts]
         seed = state.arm(model, plan, sampling and sampling[:slots])
         # the records of the utterances that wait: a refill copies its own over the group's, device to device
-        waiting = None
+        waiting = waiting_limits = None
         if sampling is not None and n > slots:
             waiting = _lib.to_device_async(kernels.pack_row_sampling([r for s in sampling[slots:] for r in s.records(cfg, beams)]), dev)
+            if plan.row_limits:
+                waiting_limits = _lib.to_device_async(kernels.pack_row_limits(_sampling.row_limits(sampling[slots:], beams)), dev)
         last, _, _ = prompt_pass(model, plan, state, texts[:slots], firsts[:slots])
         dec = state.decoder(model, plan, seed)
         codes, cache_len, audio_pos, pos_base, group_len = state.codes, state.cache_len, state.audio_pos, state.pos_base, state.group_len
@@ -725,8 +737,11 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
                                     scratch=scratch.fit(ctx[nxt]), x_len=txs[nxt])
                 if waiting is not None:
                     # the group's rows take the new utterance's seed, keys 0 .. beams - 1 and filter: a stream-ordered write
-                    # between replays (the captured steps hold the pointer), before the first sample reads them
+                    # between replays (the captured steps hold the pointer), before the first sample reads them; its length
+                    # bounds travel with them
                     state.row_sampling[rows].copy_(waiting[(nxt - slots) * beams:(nxt - slots + 1) * beams])
+                    if waiting_limits is not None:
+                        state.row_limits[rows].copy_(waiting_limits[(nxt - slots) * beams:(nxt - slots + 1) * beams])
                 # (first_len stands in for cache_len: the first sample appends no K/V row, and vh_decode_group_reset left
                 # cache_len where the first step appends)
                 dec.sample_from(x[:, -1].expand(beams, d).contiguous(), rows, state.first_len)
@@ -744,7 +759,8 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
             'decoder_reused': state.reused, 'slot_uses': state.uses if state.busy else 0,
             'n_split': dec.n_split, 'prefill_ms': marks[0].elapsed_time(marks[1]),
             'decode_ms': marks[1].elapsed_time(done_mark), 'poll_gap_ms': gap_s * 1e3, 'kv_cache': True,
-            'sampling': 'rows' if plan.row_sampling else 'call', 'repetition_aware': _sampling.repetition_aware(sampling)}
+            'sampling': 'rows' if plan.row_sampling else 'call', 'repetition_aware': _sampling.repetition_aware(sampling),
+            'bounded': _sampling.bounded(sampling)}
         ok = True
         return [best_beam_tokens(model, *saved[u], pls[u]) for u in range(n)]
     finally:

@@ -723,20 +723,35 @@ def head_greedy(x, proj_w, logits, V, eos, codes, eos_count, audio_emb, pe, audi
 
 
 def sample_step(logits, V, eos, top_k, top_p, temperature, seed, codes, eos_count, sum_logprobs, audio_emb,
-                pe, audio_pos, cache_len, x_next, pos_base=None, wide=None, rs=None):
+                pe, audio_pos, cache_len, x_next, pos_base=None, wide=None, rs=None, limits=None):
     """The stochastic decode step: `vh_sample_step` up to V = SAMPLE_NARROW_V, `vh_sample_step_wide` above it (up to
     SAMPLE_MAX_V).  wide=True / False forces one kernel (tests compare the two at V <= 2048).  rs: a uint8 device tensor
     (B, ROW_SAMPLING_BYTES) of vh_row_sampling records (`pack_row_sampling`) — every row's seed, draw key and filter come
-    from its record (`vh_sample_step_rows` / `vh_sample_step_wide_rows`) and top_k, top_p, temperature and seed are not read."""
+    from its record (`vh_sample_step_rows` / `vh_sample_step_wide_rows`) and top_k, top_p, temperature and seed are not read.
+    limits (with rs and pos_base): a uint8 device tensor (B, ROW_LIMITS_BYTES) of vh_row_limits records (`pack_row_limits`)
+    — every row's (min_new, max_new), through `vh_sample_step_rows_bounded` / `vh_sample_step_wide_rows_bounded`."""
     B = logits.shape[0]
     d = x_next.shape[1]
     if wide is None:
         wide = V > SAMPLE_NARROW_V
     name = 'vh_sample_step_wide' if wide else 'vh_sample_step'
+    if limits is not None:
+        if rs is None:
+            raise _lib.VhError('sample_step: limits without rs (the length bounds sit beside per-row sampling records)')
+        if limits.dtype != torch.uint8 or tuple(limits.shape) != (B, ROW_LIMITS_BYTES) or not limits.is_cuda or not limits.is_contiguous():
+            raise _lib.VhError(f'sample_step: limits must be a contiguous uint8 device tensor ({B}, {ROW_LIMITS_BYTES}), got '
+                               f'{tuple(limits.shape)} {limits.dtype}')
     if rs is not None:
         if rs.dtype != torch.uint8 or tuple(rs.shape) != (B, ROW_SAMPLING_BYTES) or not rs.is_cuda:
             raise _lib.VhError(f'sample_step: rs must be a uint8 device tensor ({B}, {ROW_SAMPLING_BYTES}), got {tuple(rs.shape)} {rs.dtype}')
         name += '_rows'
+        if limits is not None:
+            name += '_bounded'
+            check(getattr(_lib.lib(), name)(
+                logits.data_ptr(), logits.stride(0), V, eos, ptr(rs), ptr(limits), ptr(codes), codes.stride(0), ptr(eos_count),
+                ptr(pos_base), ptr(sum_logprobs), ptr(audio_emb), ptr(pe), ptr(audio_pos), ptr(cache_len),
+                ptr(_f32(x_next, 'x_next')), B, d, stream()), name)
+            return
         check(getattr(_lib.lib(), name)(
             logits.data_ptr(), logits.stride(0), V, eos, ptr(rs), ptr(codes), codes.stride(0), ptr(eos_count), ptr(pos_base),
             ptr(sum_logprobs), ptr(audio_emb), ptr(pe), ptr(audio_pos), ptr(cache_len), ptr(_f32(x_next, 'x_next')),
@@ -768,7 +783,22 @@ def pack_row_sampling(records):
     return torch.from_numpy(arr.view(np.uint8).reshape(len(records), ROW_SAMPLING_BYTES).copy())
 
 
-POLL_NONE = -(1 << 30)            # vh_decode_groups_poll: a maximum over no rows
+ROW_LIMITS_BYTES = 8      # sizeof(vh_row_limits)
+
+
+def pack_row_limits(pairs):
+    """[(min_new, max_new), ...] -> a HOST uint8 tensor (n, ROW_LIMITS_BYTES) in the layout of vh_row_limits
+    (include/valle_hip.h): two little-endian int32 per decode row, min_new at byte 0, max_new at 4; 0 switches a bound off."""
+    import numpy as np
+    arr = np.zeros((len(pairs), 2), dtype='<i4')
+    for i, pair in enumerate(pairs):
+        if len(pair) != 2 or not all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v < 2 ** 31 for v in pair):
+            raise ValueError(f'pack_row_limits: record {i} is {pair!r} ((min_new, max_new), ints in [0, 2**31))')
+        arr[i] = pair
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(pairs), ROW_LIMITS_BYTES).copy())
+
+
+POLL_NONE = -(1 << 30)           # vh_decode_groups_poll: a maximum over no rows
 
 
 def _i32_dev(t, n, what):

@@ -121,13 +121,88 @@ class RepetitionAware(Sampling):
         return [r + (self.window, self.max_repeats) for r in super().records(cfg, beams, first_key)]
 
 
+@dataclass(frozen=True)
+class Bounded:
+    """Length bounds of ONE utterance in the AR stage, around its Sampling or RepetitionAware: Bounded(request, min_new=None,
+    max_new=None).  It goes wherever a Sampling goes and mixes with plain requests in one call.
+
+    With n the audio tokens a row has produced so far: while n < min_new EOS is outside the support — its score is -inf
+    before top-k (ties included), top-p, the top_k == 1 arg-max, the draw and the repetition-aware redraw, and the beam's
+    score takes the log-probability under the distribution without EOS — so every beam produces at least min_new tokens;
+    once n >= max_new the token is EOS, forced: nothing is drawn or redrawn and the beam's score does not move (a forced
+    token is not the model's choice), so every beam produces at most max_new tokens.  None (or 0 for min_new) switches a
+    bound off.  The draws stay uniform01(seed, beam, position): the rows remain a function of the request alone, from
+    every entry point, in any slot.  The NAR stage ignores the bounds: its length is the first layer's.
+
+    Ranges (ValueError, before any device work): each bound an int in [0, 2**31) or None, max_new >= 1 when set, min_new <=
+    max_new when both are set, and min_new within the call's own cap (generate_batch's max_new, else config.max_audio_len);
+    a max_new above that cap is allowed and has no effect."""
+    request: Sampling
+    min_new: int | None = None
+    max_new: int | None = None
+
+    def __post_init__(self):
+        if not isinstance(self.request, Sampling):
+            raise ValueError(f'Bounded: request is {type(self.request).__name__}, not a valle2_amd.Sampling or RepetitionAware')
+        for name in ('min_new', 'max_new'):
+            v = getattr(self, name)
+            if v is not None and (not _is_int(v) or not 0 <= v < 2 ** 31):
+                raise ValueError(f'Bounded: {name}={v!r} (an int in [0, 2**31), or None)')
+        if self.max_new is not None and self.max_new < 1:
+            raise ValueError(f'Bounded: max_new={self.max_new!r} (at least 1 when set: a row always writes one token; None '
+                             'switches the bound off)')
+        if self.min_new is not None and self.max_new is not None and self.min_new > self.max_new:
+            raise ValueError(f'Bounded: min_new={self.min_new} exceeds max_new={self.max_new}')
+
+    # what a Sampling answers, from the request it wraps
+    seed = property(lambda self: self.request.seed)
+    top_k = property(lambda self: self.request.top_k)
+    tok_p = property(lambda self: self.request.tok_p)
+    temperature = property(lambda self: self.request.temperature)
+
+    def resolved(self, cfg):
+        return self.request.resolved(cfg)
+
+    def records(self, cfg, beams, first_key=0):
+        return self.request.records(cfg, beams, first_key)
+
+    def nar_record(self, cfg):
+        return self.request.nar_record(cfg)
+
+    def limits(self, beams):
+        """The (min_new, max_new) of this utterance's `beams` rows (kernels.pack_row_limits); 0 is a bound switched off."""
+        return [(self.min_new or 0, self.max_new or 0)] * beams
+
+    def check_cap(self, entry, cap):
+        """min_new against the steps the call itself allows (ValueError)."""
+        if (self.min_new or 0) > cap:
+            raise ValueError(f'{entry}: Bounded min_new={self.min_new} exceeds the call\'s cap of {cap} new tokens (max_new of '
+                             'generate_batch, else config.max_audio_len): no row could reach it')
+
+
 def _request(s):
     return s.request if isinstance(s, KeyedRows) else s
 
 
+def _unbounded(s):
+    s = _request(s)
+    return s.request if isinstance(s, Bounded) else s
+
+
 def repetition_aware(sampling):
     """Whether any request of a call's sampling list (or None) carries the repetition-aware rule."""
-    return any(isinstance(_request(s), RepetitionAware) for s in sampling or ())
+    return any(isinstance(_unbounded(s), RepetitionAware) for s in sampling or ())
+
+
+def bounded(sampling):
+    """Whether any request of a call's sampling list (or None) carries a length bound that is switched on."""
+    return any(isinstance(_request(s), Bounded) and any(v for v in _request(s).limits(1)[0]) for s in sampling or ())
+
+
+def row_limits(sampling, beams):
+    """[(min_new, max_new)] per decode row of a call's sampling list: a request's bounds for each of its beams, (0, 0) for a
+    request without any (kernels.pack_row_limits)."""
+    return [lim for s in sampling for lim in (s.limits(beams) if isinstance(s, (Bounded, KeyedRows)) else [(0, 0)] * beams)]
 
 
 class KeyedRows(NamedTuple):
@@ -140,25 +215,29 @@ class KeyedRows(NamedTuple):
     def records(self, cfg, beams):
         return self.request.records(cfg, beams, self.first_key)
 
+    def limits(self, beams):
+        return self.request.limits(beams) if isinstance(self.request, Bounded) else [(0, 0)] * beams
+
 
 def beam_rows(request, beams, first_key=0):
-    """[KeyedRows] for the `beams` rows of `request` (a Sampling or a KeyedRows), one entry per row."""
+    """[KeyedRows] for the `beams` rows of `request` (a Sampling, a Bounded or a KeyedRows), one entry per row."""
     if isinstance(request, KeyedRows):
         request, first_key = request.request, request.first_key + first_key
     return [KeyedRows(request, first_key + j) for j in range(beams)]
 
 
-def check_list(entry, sampling, n, what='utterance', cfg=None):
-    """None when no entry of `sampling` (None, or a list of n) is a Sampling, the list when every one is; a mix is a
-    ValueError naming the first without one.  With cfg every request is also resolved against the config, so what the two
-    cannot do together (Sampling.resolved, RepetitionAware.resolved) is said here."""
+def check_list(entry, sampling, n, what='utterance', cfg=None, cap=None):
+    """None when no entry of `sampling` (None, or a list of n) is a Sampling (or a Bounded around one), the list when every
+    one is; a mix is a ValueError naming the first without one.  With cfg every request is also resolved against the config,
+    so what the two cannot do together (Sampling.resolved, RepetitionAware.resolved) is said here, and a Bounded's min_new is
+    held against the call's cap (`cap`, else cfg.max_audio_len)."""
     if sampling is None:
         return None
     sampling = list(sampling)
     if len(sampling) != n:
         raise ValueError(f'{entry}: sampling holds {len(sampling)} entries for {n} {what}s (one Sampling each)')
     for i, s in enumerate(sampling):
-        if s is not None and not isinstance(s, (Sampling, KeyedRows)):
+        if s is not None and not isinstance(s, (Sampling, Bounded, KeyedRows)):
             raise ValueError(f'{entry}: sampling of {what} {i} is {type(s).__name__}, not a valle2_amd.Sampling')
     if all(s is None for s in sampling):
         return None
@@ -169,6 +248,8 @@ def check_list(entry, sampling, n, what='utterance', cfg=None):
     if cfg is not None:
         for s in sampling:
             _request(s).resolved(cfg)
+            if isinstance(_request(s), Bounded):
+                _request(s).check_cap(entry, int(cfg.max_audio_len) if cap is None else int(cap))
     return sampling
 
 

@@ -43,7 +43,7 @@ def _beams_refused_early(fn):
         if kwargs.get('beams', 1) != 1 or kwargs.get('sampling') is not None:
             a = sig.bind(self, *args, **kwargs).arguments
             generation.check_beams(self.config, a.get('beams', 1), a.get('shared_prompt', False), a.get('perf_mode', False), a.get('forced'))
-            generation.check_sampling(a.get('sampling'), len(a['texts']), a.get('forced'), self.config)
+            generation.check_sampling(a.get('sampling'), len(a['texts']), a.get('forced'), self.config, a.get('max_new'))
         return fn(self, *args, **kwargs)
     return wrapper
 
@@ -59,9 +59,11 @@ def _sampling_refused_early(fn):
         if 'utterances' in a:
             _sampling.of_utterances(fn.__name__, a['utterances'], self.config)
         elif a.get('sampling') is not None:
-            if not isinstance(a['sampling'], _sampling.Sampling):
+            if not isinstance(a['sampling'], (_sampling.Sampling, _sampling.Bounded)):
                 raise ValueError(f'{fn.__name__}: sampling is {type(a["sampling"]).__name__}, not a valle2_amd.Sampling')
             a['sampling'].resolved(self.config)
+            if isinstance(a['sampling'], _sampling.Bounded):
+                a['sampling'].check_cap(fn.__name__, int(self.config.max_audio_len))
         return fn(self, *args, **kwargs)
     return wrapper
 

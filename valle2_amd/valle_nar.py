@@ -38,7 +38,7 @@ def _sampling_refused_early(fn):
             elif not isinstance(given, (list, tuple)):
                 raise ValueError(f'{name}: sampling is {type(given).__name__}, not a list with one valle2_amd.Sampling per utterance')
             for i, s in enumerate(given):
-                if s is not None and not isinstance(s, _sampling.Sampling):
+                if s is not None and not isinstance(s, (_sampling.Sampling, _sampling.Bounded)):   # (a Bounded's bounds are the AR stage's)
                     raise ValueError(f'{name}: sampling{f" of utterance {i}" if "texts" in a else ""} is {type(s).__name__}, '
                                      'not a valle2_amd.Sampling')
             if a.get('seed') is not None:
