@@ -1106,7 +1106,7 @@ def attn_visible(name, spec, fault=None):
     return vis
 
 
-def attn_geometry_reference(name, dtype=torch.float64, fault=None, h16=None):
+def attn_geometry_reference(name, dtype=torch.float64, fault=None, h16=None, operands=None):
     """out, lse2 (B, h, Tq) and — where Tq == Tk — dq, dk, dv of the case, written out from the definition in `dtype`
     (float64: what the GPU tests compare against; float32: the emulation of a kernel):
       P = softmax(q k^T / 8 + mask), lse2 = logsumexp / ln 2, out = P v, dV = P^T dO, dS = P o (dP - rowsum(dO o out)),
@@ -1116,8 +1116,11 @@ def attn_geometry_reference(name, dtype=torch.float64, fault=None, h16=None):
     fault: one of attn_visible's, or in the chunk bookkeeping of the fused backward at the fewest chunks —
       'dq_chunk_lost'   dQ leaves out every key chunk that starts at or after x_len, whatever the query
       'dq_chunk_extra'  dQ adds a slab of ones for every chunk the fused kernel never wrote for the query (a chunk of
-                        padding; under the prefix mask a chunk starting at or after x_len and after the query)."""
+                        padding; under the prefix mask a chunk starting at or after x_len and after the query).
+    operands: (q, k, v, dout) to take in place of the case's own, its masks kept (tests/attn_scores.py moves the scores)."""
     q, k, v, dout, mode, spec = attn_geometry_inputs(name)
+    if operands is not None:
+        q, k, v, dout = operands
     B, h, Tq, Tk, _ = ATTN_GEOMETRY_CASES[name]
     if h16 is not None:
         q = (q * ATTN_Q16_PRESCALE).to(h16).double() / ATTN_Q16_PRESCALE

@@ -85,11 +85,13 @@ class Forward:
     NaN; out goes into the first d columns of a NaN-filled (B * Tq, d + 8) buffer; the caches hold S_max = Tk + 9 rows, NaN (K)
     and Inf (V) from Tk on, finite randn in [kv_len, Tk) (the kernel multiplies those by p = 0)."""
 
-    def __init__(self, name):
+    def __init__(self, name, operands=None):
         from valle2_amd import kernels as K
         self.K, self.name = K, name
         self.B, self.h, self.Tq, self.Tk, mode = R.ATTN_GEOMETRY_CASES[name]
         q, k, v, dout, _, spec = R.attn_geometry_inputs(name)
+        if operands is not None:                       # (q, k, v, dout) in place of the case's own (tests/attn_scores.py)
+            q, k, v, dout = operands
         self.d = d = 64 * self.h
         qkv = torch.full((self.B * self.Tq, 3 * d), float('nan'))
         qkv[:, :d] = rows(q)

@@ -773,7 +773,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(BwdArgs a) {
         const float* vp = a.vc + ((int64_t)bh * a.S_max + min(kj, a.T - 1)) * HD + 4 * h;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
-            kf[t] = ld4(kp + 8 * t) * qscale;
+            kf[t] = ld4(kp + 8 * t);
             vf[t] = ld4(vp + 8 * t);
         }
     }
@@ -799,7 +799,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(BwdArgs a) {
         float* dd = qd + KT * KLD;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            st4(qd + (sq + 16 * i) * KLD + squad, rq[i]);
+            // Q is staged PRE-SCALED, as the forward holds it: S = (c Q) K^T then has the forward's bits (same products, same
+            // order), so P = exp2(S - lse2) is the forward's own P.  With c folded into K instead S differs from the forward's
+            // by an ulp — 3e-5 at |S| = 290 —, independently per key, and the row sum of dS no longer cancels.
+            st4(qd + (sq + 16 * i) * KLD + squad, rq[i] * qscale);
             st4(dd + (sq + 16 * i) * KLD + squad, rd[i]);
         }
         if (tid < 2 * KT) stat[buf][tid >> 5][tid & 31] = rstat;
@@ -886,7 +889,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(BwdArgs a) {
     for (int which = 0; which < 2; ++which) {
         const f32x16& A0 = which ? GV0 : GK0;
         const f32x16& A1 = which ? GV1 : GK1;
-        const float sc = which ? 1.0f : 0.125f;
+        const float sc = which ? 1.0f : 0.125f / qscale;       // dK was added up over the pre-scaled Q rows
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             f32x4 v0 = {A0[4 * g4], A0[4 * g4 + 1], A0[4 * g4 + 2], A0[4 * g4 + 3]};
@@ -984,7 +987,6 @@ __global__ __launch_bounds__(FW * 64, FW == 8 ? 1 : 2) void attn_bwd_fused_kerne
                 const int d = 8 * t + 4 * h + j;
                 kt[d * KEYS + ((((kl >> 2) ^ (d & 15)) << 2) | (kl & 3))] = kf[t][j];
             }
-            kf[t] = kf[t] * qscale;
         }
     }
     f32x4 rq[RPT], rd[RPT], ro[RPT];
@@ -1017,7 +1019,7 @@ __global__ __launch_bounds__(FW * 64, FW == 8 ? 1 : 2) void attn_bwd_fused_kerne
     auto lstore = [&]() {
 #pragma unroll
         for (int i = 0; i < RPT; ++i) {
-            st4(lds + (sq + 16 * i) * KLD + squad, rq[i]);
+            st4(lds + (sq + 16 * i) * KLD + squad, rq[i] * qscale);     // pre-scaled, as the forward holds Q (attn_bwd_dkv_kernel)
             st4(lds + KT * KLD + (sq + 16 * i) * KLD + squad, rd[i]);
             const float dsum = row16_sum((rd[i].x * ro[i].x + rd[i].y * ro[i].y) + (rd[i].z * ro[i].z + rd[i].w * ro[i].w));
             if ((tid & 15) == 0) stat[KT + sq + 16 * i] = dsum;                  // D of the staged row
@@ -1173,7 +1175,7 @@ __global__ __launch_bounds__(FW * 64, FW == 8 ? 1 : 2) void attn_bwd_fused_kerne
     for (int which = 0; which < 2; ++which) {
         const f32x16& A0 = which ? GV0 : GK0;
         const f32x16& A1 = which ? GV1 : GK1;
-        const float sc = which ? 1.0f : 0.125f;
+        const float sc = which ? 1.0f : 0.125f / qscale;       // dK was added up over the pre-scaled Q rows
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             f32x4 v0 = {A0[4 * g4], A0[4 * g4 + 1], A0[4 * g4 + 2], A0[4 * g4 + 3]};
