@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 142            /* 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 143            /* 0.2.19: packed AR training — vh_attn_rows_packed_lse (vh_attn_rows_packed with a mask mode, per-segment text lengths and lse2), vh_attn_rows_bwd_packed + vh_attn_rows_bwd_packed_ws_bytes (the five-product backward over segments); nothing earlier changes; 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -368,6 +368,37 @@ int vh_attn_rows_bwd_ws(const float* q, int ldq, const float* kcache, const floa
                         int ldg, int B, int n_heads, int T, int S_max, int mode, int x_len,
                         const int32_t* x_len_dev, const int32_t* kv_len, const uint8_t* mask,
                         const uint8_t* pad, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- packed AR training (ABI 143): the training forms of the attention over the SEGMENTS of one packed row stream -----
+ * vh_attn_rows_packed plus a mask mode (VH_MASK_FULL or VH_MASK_PREFIX; anything else is VH_EINVAL), seg_x_len (device
+ * int32 (n_seg), read only under the prefix mask: the text length inside segment s, clamped to 0 .. seg_len[s]) and lse2
+ * (n_heads, M): the log2-sum-exp of the scaled scores of every packed row, as vh_attn_rows_lse writes it.  Segment s is a
+ * sequence of its own: key j of it is visible to its query i when j < x_len || (i >= x_len && j <= i); no key is padding.
+ * out and lse2 of a segment are bit for bit those of vh_attn_rows_lse on it alone (B = 1, Tq = Tk = seg_len[s], the same mode
+ * and x_len).  M: rows of q / out / lse2 (S_max >= M); the tables are under vh_attn_rows_packed's contract, and a segment
+ * reaching past M is cut there. */
+int vh_attn_rows_packed_lse(const float* q, int ldq, const float* kcache, const float* vcache, float* out, int ldo,
+                            int n_heads, int M, int S_max, int mode, const int32_t* seg_start, const int32_t* seg_len,
+                            const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks, float* lse2,
+                            void* stream);
+/* Its backward: vh_attn_rows_bwd_ws' five-product kernel (eight waves) with the sequence taken from the segment table.
+ * q / out / dout (M, ld·), kcache / vcache (1, h, S_max >= M, 64), lse2 (n_heads, M) from vh_attn_rows_packed_lse; dq, dk,
+ * dv (M, ldg) views.  Work items are (segment, key chunk) pairs x head: items[2 i], items[2 i + 1] (device int32, n_items
+ * pairs), chunk c of a segment = its keys [c chunk_keys, (c + 1) chunk_keys); chunk_keys a multiple of 32, at most 256, one
+ * per launch; workgroups run in table order (list the heaviest first).  max_chunks = the largest chunk count of a segment:
+ * above 1 the dQ partials go to slabs (max_chunks, n_heads, M, 64) inside ws (vh_attn_rows_bwd_packed_ws_bytes, 16-byte
+ * aligned) and a second launch adds them in chunk order over `blocks` (the forward's table: every query once); at 1 the
+ * kernel writes dq itself and ws may be NULL.  No atomics: two runs give the same bits.  With tables that list every
+ * (segment, chunk) and every query block once, every row of dq, dk and dv in [0, M) is written exactly once.  The tables are
+ * DEVICE arrays the host cannot check: an entry out of range (segment >= n_seg, a segment outside [0, M), chunk >=
+ * max_chunks or beyond the segment) makes its workgroup return without touching memory. */
+size_t vh_attn_rows_bwd_packed_ws_bytes(int n_heads, int M, int max_chunks);
+int vh_attn_rows_bwd_packed(const float* q, int ldq, const float* kcache, const float* vcache, const float* out,
+                            int ldo, const float* dout, int lddo, const float* lse2, float* dq, float* dk, float* dv,
+                            int ldg, int n_heads, int M, int S_max, int mode, const int32_t* seg_start,
+                            const int32_t* seg_len, const int32_t* seg_x_len, int n_seg, const int32_t* items,
+                            int n_items, int chunk_keys, int max_chunks, const int32_t* blocks, int n_blocks,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* ---- K8b: single-row decode attention over the KV cache (HBM-bound) -------------------------
  * replaces SDPA with q-len 1 (valle/models/modules.py:167 reached via :336-338).

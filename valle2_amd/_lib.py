@@ -297,6 +297,14 @@ SIGNATURES = {
                                            c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_void_p]),
     'vh_transformer_forward_packed_bf16': (C.c_int, [C.POINTER(VhForward16Desc), c_i32p, c_i32p, C.c_int, c_i32p, C.c_int,
                                                      C.c_void_p]),
+    # packed AR training: the attention's training forms over segments (ABI 143)
+    'vh_attn_rows_packed_lse': (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, c_f32p, C.c_void_p]),
+    'vh_attn_rows_bwd_packed_ws_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'vh_attn_rows_bwd_packed': (C.c_int, [C.c_void_p, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_f32p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -187,6 +187,24 @@ class LayerNormFn(torch.autograd.Function):
         return dx, dg, db, ds, dt, None
 
 
+def _attn_rows(q, k, v, out, B, n_heads, T, lse2, spec):
+    """The training forward of the attention core.  A spec that carries `rows` (an engine.PackedRows; B = 1, T = its row
+    count) sends the call to the packed kernel: every segment attends its own rows under spec['mode']."""
+    rows = spec.get('rows')
+    if rows is None:
+        return kernels.attn_rows(q, k, v, out, B, n_heads, T, T, lse2=lse2, **spec)
+    if B != 1 or T != rows.rows:
+        raise _lib.VhError(f'packed attention: B={B} T={T} for {rows.rows} packed rows')
+    return kernels.attn_rows_packed_lse(q, k, v, out, lse2.view(n_heads, T), n_heads, rows, spec['mode'])
+
+
+def _attn_rows_bwd(q, k, v, out, dout, lse2, dq, dk, dv, B, n_heads, T, spec):
+    rows = spec.get('rows')
+    if rows is None:
+        return kernels.attn_rows_bwd(q, k, v, out, dout, lse2, dq, dk, dv, B, n_heads, T, **spec)
+    return kernels.attn_rows_bwd_packed(q, k, v, out, dout, lse2.view(n_heads, T), dq, dk, dv, n_heads, rows, spec['mode'])
+
+
 class QkvAttentionFn(torch.autograd.Function):
     """out (B*T, d) = SDPA(split_heads(x @ Wqkv.T)) with the analytic / explicit masks of
     vh_attn_rows (modules.py:146-170).  Backward recomputes P from the saved q, k, v."""
@@ -202,7 +220,7 @@ class QkvAttentionFn(torch.autograd.Function):
         kernels.linear_qkv(x, wqkv.detach(), q, k, v, B, T, n_heads)
         out = torch.empty(B * T, d, device=dev, dtype=torch.float32)
         lse2 = torch.empty(B, n_heads, T, device=dev, dtype=torch.float32)
-        kernels.attn_rows(q, k, v, out, B, n_heads, T, T, lse2=lse2, **spec)
+        _attn_rows(q, k, v, out, B, n_heads, T, lse2, spec)
         ctx.save_for_backward(x, wqkv, q, k, v, out, lse2)
         ctx.dims, ctx.spec = (B, T, n_heads), spec
         return out
@@ -215,8 +233,7 @@ class QkvAttentionFn(torch.autograd.Function):
         spec = ctx.spec
         if ATTENTION_BACKWARD == 'flash':
             dqkv = torch.empty(B * T, 3 * d, device=x.device, dtype=torch.float32)
-            kernels.attn_rows_bwd(q, k, v, out, dout.contiguous(), lse2, dqkv[:, :d], dqkv[:, d:2 * d],
-                                  dqkv[:, 2 * d:], B, h, T, **spec)
+            _attn_rows_bwd(q, k, v, out, dout.contiguous(), lse2, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], B, h, T, spec)
             dx = dw = None
             if ctx.needs_input_grad[0]:
                 dx = _dx(dqkv, wqkv, 3 * d)
@@ -224,6 +241,8 @@ class QkvAttentionFn(torch.autograd.Function):
                 dw = optim.grad_out(wqkv)
                 kernels.gemm_tn(dqkv, x, out=dw)
             return dx, dw, None, None, None, None
+        if spec.get('rows') is not None:
+            raise _lib.VhError("packed rows train on the 'flash' attention backward only")
         scale = HEAD_DIM ** -0.5
         L = _lib.lib()
         tp = (T + 3) // 4 * 4                                              # row stride of the (T,T) maps
@@ -376,6 +395,42 @@ class EmbedConcatFn(torch.autograd.Function):
         return (None, *grads)
 
 
+class EmbedPackedFn(torch.autograd.Function):
+    """The model input x (M, d) of a PACKED training step: utterance b's rows lie back to back from row starts[b] on, part i
+    of it = sum_j tables[idx][ids_i[b, t]] + pe_i[t] for t < lens_i[b] at rows row_t0_i[b] + t (positions restart at 0 for
+    every part of every utterance).  parts: [(ids (B, T_i), pe, lens_i, row_t0_i (device int32 (B) each), max(lens_i),
+    index into `tables`, drop, dest, src)] — drop: the part's PositionalEncoding dropout spec or None, its field keyed on the
+    PACKED row; dest / src (device int64, sum(lens_i)): the packed row and b * T_i + t of every valid (b, t).  Backward: the field is
+    applied to the packed gradient, whose rows travel to a zeroed padded (B, T_i, d) buffer (torch index ops: plumbing),
+    and the tables receive vh_embed_bwd's scatter from there."""
+
+    @staticmethod
+    def forward(ctx, parts, M, *tables):
+        d = tables[0].shape[1]
+        out = torch.empty(M, d, device=tables[0].device, dtype=torch.float32)
+        for ids, pe, lens, row_t0, max_len, j, drop, _, _ in parts:
+            kernels.embed_sum_pe(ids, [tables[j].detach()], pe, 0, out, lens=lens, row_t0=row_t0, max_pos=max_len, drop=drop)
+        ctx.parts, ctx.tables = parts, tables
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = dout.contiguous()
+        d = dout.shape[1]
+        grads = [optim.grad_out(t, zero=True) if ctx.needs_input_grad[2 + j] else None for j, t in enumerate(ctx.tables)]
+        for ids, pe, lens, row_t0, max_len, j, drop, dest, src in ctx.parts:
+            if grads[j] is None:
+                continue
+            B, T = ids.shape
+            dd = dout if drop is None else dropout.apply_raw(dout, drop)
+            padded = torch.zeros(B, T, d, device=dout.device, dtype=torch.float32)
+            padded.view(B * T, d).index_copy_(0, src, dd.index_select(0, dest))
+            check(_lib.lib().vh_embed_bwd(ids.data_ptr(), ids.stride(0), ids.stride(1), ptr(padded), padded.stride(0), 0,
+                                          ptr(grads[j]), int(ctx.tables[j].shape[0]), B, T, d,
+                                          ptr(_lib.err_flag(dout.device)), None, stream()), 'vh_embed_bwd')
+        return (None, None, *grads)
+
+
 class CrossEntropyFn(torch.autograd.Function):
     """Mean cross entropy over every row of (R, V) logits against (R,) int64 targets."""
 
@@ -502,7 +557,7 @@ class EncoderLayerFn(torch.autograd.Function):
         kernels.linear_qkv(xn1, wqkv.detach(), q, k, v, B, T, n_heads)
         a = torch.empty(B * T, d, device=dev, dtype=torch.float32)
         lse2 = torch.empty(B, n_heads, T, device=dev, dtype=torch.float32)
-        kernels.attn_rows(q, k, v, a, B, n_heads, T, T, lse2=lse2, **spec)
+        _attn_rows(q, k, v, a, B, n_heads, T, lse2, spec)
         xm = torch.empty_like(x)
         kernels.linear_ex(a, wo.detach(), bias=bo.detach(), residual=x, out=xm, drop=dr1)    # (tile kernel with the tail split)
         xn2 = kernels.layernorm(xm, g2.detach(), be2.detach(), ada_scale=det(s2), ada_shift=det(t2), eps=eps)
@@ -576,7 +631,7 @@ class EncoderLayerFn(torch.autograd.Function):
         kernels.linear_ex(dbr, wo_t, out=da, K=wo_t.shape[1])
         # ---- attention core + QKV projection
         dqkv = torch.empty(B * T, 3 * d, device=x.device, dtype=torch.float32)
-        kernels.attn_rows_bwd(q, k, v, a, da, lse2, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], B, h, T, **spec)
+        _attn_rows_bwd(q, k, v, a, da, lse2, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], B, h, T, spec)
         dwqkv = optim.grad_out(wqkv)
         kernels.gemm_tn(dqkv, xn1, out=dwqkv)
         dxn1 = torch.empty_like(x)

@@ -9,6 +9,7 @@
 //                       (prefix-LM / full / key length), never materialised.   MFMA-bound.
 //  attn_rows_packed_kernel : the same body (attn_rows_body.inc) over the SEGMENTS of one packed row
 //                       stream under the full mask: a ragged NAR batch with no padding rows.
+//  attn_rows_packed_lse_kernel, attn_bwd_packed_kernel : its training forms (packed AR training), at the end of the file.
 //  attn_decode_kernel : one query row per (batch, head) against the whole cache — the dominant
 //                       kernel of AR decoding.  Pure HBM streaming: every K/V byte is read once
 //                       with 16-B loads, 1 KiB per wave-instruction, 16 KiB in flight per wave;
@@ -929,271 +930,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(BwdArgs a) {
 // CU (65 KB each) — the same eight waves per CU in half-size work items.  The Q / dO tile is single-buffered: every read
 // of tile i happens before the tile's first barrier and the staged rows of tile i + 1 are stored after it, so the two
 // barriers the dS hand-over needs anyway also order the tile buffer.
-template <int FW>
-__global__ __launch_bounds__(FW * 64, FW == 8 ? 1 : 2) void attn_bwd_fused_kernel(BwdArgs a) {
-    constexpr int KEYS = FW * 32;                    // row length of Kt and dS
-    constexpr int RPT = 8 / FW;                      // staged tile rows per thread (32 rows x 16 threads over FW x 64 threads)
-    constexpr int QB_W = 8 / FW;                     // 16-query blocks of the dQ tile per wave (FW = 4: both, one d-block per wave)
-    // [Q|dO][query][KLD] | [lse|D][32] | Kt [64 d][KEYS] | dS [32 q][KEYS]
-    __shared__ __attribute__((aligned(16))) float lds[2 * KT * KLD + 2 * KT + HD * KEYS + KT * KEYS];
-    float* const stat = lds + 2 * KT * KLD;
-    float* const kt = stat + 2 * KT;
-    float* const dsb = kt + HD * KEYS;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int n_bh = gridDim.x / a.n_blocks;
-    const int bh = blockIdx.x % n_bh, b = bh / a.n_heads, head = bh - b * a.n_heads;
-    const int chunk = (int)(blockIdx.x / n_bh);                 // chunk 0 first: under the prefix mask it sees every query
-    const int kb0 = chunk * a.chunk_keys;
-    const int kend = min(kb0 + a.chunk_keys, a.T);              // keys [kb0, kend) belong to this workgroup
-    const int kvl = a.kv_len ? min(a.kv_len[b], a.T) : a.T;
-    const int xl = a.x_len_dev ? a.x_len_dev[b] : a.x_len;
-    const int sq = tid >> 4, squad = (tid & 15) * 4;            // staging: row sq (+ 16 with four waves), one 16-byte chunk
-
-    if (a.mode != VH_MASK_EXPLICIT && kb0 >= kvl) {
-        // every key of the chunk is padding: dK = dV = 0, no dQ contribution (the reduce kernel skips this chunk too)
-        for (int row = kb0 + sq; row < kend; row += FW * 4) {
-            const int64_t o = ((int64_t)b * a.T + row) * a.ldg + head * HD + squad;
-            st4(a.dk + o, f32x4{0.f, 0.f, 0.f, 0.f});
-            st4(a.dv + o, f32x4{0.f, 0.f, 0.f, 0.f});
-        }
-        // a single chunk writes dQ itself (no slab, no reduce launch): a row without any valid key (kv_len = 0, T <= 256)
-        // must leave zeros there, not the caller's uninitialised buffer (round-4 advisor finding)
-        if (a.slab == nullptr)
-            for (int row = sq; row < a.T; row += FW * 4)
-                st4(a.dq + ((int64_t)b * a.T + row) * a.ldg + head * HD + squad, f32x4{0.f, 0.f, 0.f, 0.f});
-        return;
-    }
-    int qmin = 0;
-    if (a.mode == VH_MASK_PREFIX && kb0 >= xl) qmin = kb0;
-    const int t_first = qmin / KT, n_tiles = (a.T + KT - 1) / KT;
-
-    const int wk_min = kb0 + w * 32, wk_max = wk_min + 31;
-    const int kj = wk_min + r;                   // this lane's key
-    const bool kin = kj < kend;
-    const float qscale = 0.125f * LOG2E;
-    f32x4 kf[8], vf[8];
-    {
-        const int64_t krow = (int64_t)bh * a.S_max + min(kj, a.T - 1);
-        const float* kp = a.kc + krow * HD + 4 * h;
-        const float* vp = a.vc + krow * HD + 4 * h;
-        const int kl = w * 32 + r;               // key inside the chunk
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            kf[t] = ld4(kp + 8 * t);
-            vf[t] = ld4(vp + 8 * t);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {        // Kt[d][key], 16-byte slot (key >> 2) XOR-swizzled by d & 15
-                const int d = 8 * t + 4 * h + j;
-                kt[d * KEYS + ((((kl >> 2) ^ (d & 15)) << 2) | (kl & 3))] = kf[t][j];
-            }
-        }
-    }
-    f32x4 rq[RPT], rd[RPT], ro[RPT];
-    float rlse = 0.f;
-    const float* qbase = a.q + (int64_t)b * a.T * a.ldq + head * HD;
-    const float* dbase = a.dout + (int64_t)b * a.T * a.lddo + head * HD;
-    const float* obase = a.o + (int64_t)b * a.T * a.ldo + head * HD;
-    // loads only: nothing here may wait for them.  Q and dO rows are requested at the top of a tile and land under its
-    // MFMAs; the O row (needed only for D) and lse are requested after the tile's first barrier, when the S / dP
-    // registers are dead (the kernel sits at the register limit), and land under the dQ product.
-    // (four waves stage two rows per thread: the second row's Q / dO are requested late as well — eight registers less
-    // across the S / dP / dV / dK phase, where the count peaks)
-    auto gload = [&](int q0t) {
-        const int qrow = min(q0t + sq, a.T - 1);
-        rq[0] = ld4((const float*)((const char*)qbase + (uint32_t)(qrow * a.ldq + squad) * 4u));
-        rd[0] = ld4((const float*)((const char*)dbase + (uint32_t)(qrow * a.lddo + squad) * 4u));
-    };
-    auto gload_late = [&](int q0t) {
-#pragma unroll
-        for (int i = 0; i < RPT; ++i) {
-            const int qrow = min(q0t + sq + 16 * i, a.T - 1);
-            if (i > 0) {
-                rq[i] = ld4((const float*)((const char*)qbase + (uint32_t)(qrow * a.ldq + squad) * 4u));
-                rd[i] = ld4((const float*)((const char*)dbase + (uint32_t)(qrow * a.lddo + squad) * 4u));
-            }
-            ro[i] = ld4((const float*)((const char*)obase + (uint32_t)(qrow * a.ldo + squad) * 4u));
-        }
-        if (tid < KT) rlse = a.lse2[(int64_t)bh * a.T + min(q0t + tid, a.T - 1)];
-    };
-    auto lstore = [&]() {
-#pragma unroll
-        for (int i = 0; i < RPT; ++i) {
-            st4(lds + (sq + 16 * i) * KLD + squad, rq[i] * qscale);     // pre-scaled, as the forward holds Q (attn_bwd_dkv_kernel)
-            st4(lds + KT * KLD + (sq + 16 * i) * KLD + squad, rd[i]);
-            const float dsum = row16_sum((rd[i].x * ro[i].x + rd[i].y * ro[i].y) + (rd[i].z * ro[i].z + rd[i].w * ro[i].w));
-            if ((tid & 15) == 0) stat[KT + sq + 16 * i] = dsum;                  // D of the staged row
-        }
-        if (tid < KT) stat[tid] = rlse;
-    };
-    f32x16 GK0, GK1, GV0, GV1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { GK0[e] = 0.f; GK1[e] = 0.f; GV0[e] = 0.f; GV1[e] = 0.f; }
-    // the dQ block(s) of this wave: d0 = 16 (w & 3); q0 = 16 (w >> 2) with eight waves, both q-blocks with four;
-    // lane (i, g) reads row i of both operands
-    const int mi = lane & 15, mg = lane >> 4;
-    const float* ap = kt + (16 * (w & 3) + mi) * KEYS;
-    const float* bp = dsb + (FW == 8 ? 16 * (w >> 2) + mi : mi) * KEYS;
-    const int n_waves_keys = (kend - kb0 + 31) >> 5;            // waves that own at least one key of the chunk
-    if (t_first < n_tiles) {
-        gload(t_first * KT);
-        gload_late(t_first * KT);
-        lstore();
-    }
-    // vmcnt(0), unconditionally: the K / V fragments are first USED inside the loop and are still outstanding on the path
-    // around the conditional above — without this the wait insertion puts vmcnt(3..0) in front of the first score MFMAs
-    // of EVERY tile, which makes the tile wait for its own prefetch of the next Q / dO rows (seen in the ISA, round 6)
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __syncthreads();
-    for (int qt = t_first; qt < n_tiles; ++qt) {
-        const int q0t = qt * KT;
-        if (qt + 1 < n_tiles) gload(q0t + KT);
-        // waves of this workgroup that see a query of the tile: a prefix of the waves (every term falls with the key index)
-        int n_act = n_waves_keys;
-        if (a.mode != VH_MASK_EXPLICIT) {
-            n_act = min(n_act, (kvl - kb0 + 31) >> 5);
-            if (a.mode == VH_MASK_PREFIX) {
-                // wave v is active iff kb0 + 32 v < xl  or  kb0 + 32 v <= q0t + 31
-                const int lim = max(xl - 1, q0t + KT - 1) - kb0;   // largest admissible 32 v
-                n_act = min(n_act, lim < 0 ? 0 : (lim >> 5) + 1);
-            }
-        }
-        const bool any = w < n_act;
-        const float* qs = lds;
-        const float* ds = qs + KT * KLD;
-        const float* st = stat;
-        if (any) {
-            f32x16 S, P;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const f32x4 qv = ld4(qs + r * KLD + 8 * t + 4 * h);
-                const f32x4 dv = ld4(ds + r * KLD + 8 * t + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    S = __builtin_amdgcn_mfma_f32_32x32x2f32(qv[j], kf[t][j], (t | j) ? S : f32x16{}, 0, 0, 0);   // S[q][key]
-                    P = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[j], vf[t][j], (t | j) ? P : f32x16{}, 0, 0, 0);   // dP[q][key]
-                }
-            }
-            bool all = wk_max < min(kvl, kend) && q0t + KT <= a.T;
-            if (a.mode == VH_MASK_PREFIX) all = all && (wk_max < xl || (q0t >= xl && wk_max <= q0t));
-            else if (a.mode == VH_MASK_EXPLICIT) all = false;
-            if (all) {
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const f32x4 lse4 = ld4(st + 8 * g4 + 4 * h);
-                    const f32x4 d4 = ld4(st + KT + 8 * g4 + 4 * h);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int e = 4 * g4 + j;
-                        const float p = vh_exp2(S[e] - lse4[j]);
-                        S[e] = p;                                   // P[q][key]
-                        P[e] = p * (P[e] - d4[j]);                  // dS[q][key]
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const f32x4 lse4 = ld4(st + 8 * g4 + 4 * h);
-                    const f32x4 d4 = ld4(st + KT + 8 * g4 + 4 * h);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int e = 4 * g4 + j;
-                        const int qi = q0t + 8 * g4 + 4 * h + j;
-                        const bool vis = kin && qi < a.T && bwd_visible(a, b, qi, kj, kvl, xl);
-                        const float p = vis ? vh_exp2(S[e] - lse4[j]) : 0.f;
-                        S[e] = p;
-                        P[e] = p * (P[e] - d4[j]);
-                    }
-                }
-            }
-            // dS → the shared tile, [q][key] with the slot swizzle: one ds_write_b32 per register, 32 consecutive keys per half-wave
-            {
-                const int kl = w * 32 + r;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int qrow = (e & 3) + 8 * (e >> 2) + 4 * h;
-                    dsb[qrow * KEYS + ((((kl >> 2) ^ (qrow & 15)) << 2) | (kl & 3))] = P[e];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int qrow = (e & 3) + 8 * (e >> 2) + 4 * h;
-                const float* dorow = ds + qrow * KLD + r;
-                const float* qrowp = qs + qrow * KLD + r;
-                GV0 = __builtin_amdgcn_mfma_f32_32x32x2f32(dorow[0], S[e], GV0, 0, 0, 0);    // dVᵀ[d][key]
-                GV1 = __builtin_amdgcn_mfma_f32_32x32x2f32(dorow[32], S[e], GV1, 0, 0, 0);
-                GK0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qrowp[0], P[e], GK0, 0, 0, 0);    // dKᵀ[d][key]
-                GK1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qrowp[32], P[e], GK1, 0, 0, 0);
-            }
-        }
-        __syncthreads();                     // the dS blocks of the n_act active waves are in LDS; the Q / dO tile is free
-        if (qt + 1 < n_tiles) gload_late(q0t + KT);
-        {
-            // dQ[q][d] block = Σ_key dS[q][key]·K[key][d] over the active waves' keys: A = Kᵀ rows (d), B = dS rows (q)
-            f32x4 c[QB_W][4];
-#pragma unroll
-            for (int qb = 0; qb < QB_W; ++qb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) c[qb][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const int nu = 2 * n_act;                    // 16-key groups of the active waves (n_act >= 1 on every visited tile)
-            f32x4 a4 = ld4(ap + ((mg ^ mi) << 2)), b4[QB_W];
-#pragma unroll
-            for (int qb = 0; qb < QB_W; ++qb) b4[qb] = ld4(bp + qb * 16 * KEYS + ((mg ^ mi) << 2));
-            for (int u = 0; u < nu; ++u) {               // operands of group u + 1 requested BEFORE group u's MFMAs
-                const int slot = ((4 * min(u + 1, nu - 1) + mg) ^ mi) << 2;
-                const f32x4 an = ld4(ap + slot);
-                f32x4 bn[QB_W];
-#pragma unroll
-                for (int qb = 0; qb < QB_W; ++qb) bn[qb] = ld4(bp + qb * 16 * KEYS + slot);
-                __builtin_amdgcn_sched_barrier(0);       // (left alone the compiler sinks the reads below the MFMAs)
-#pragma unroll
-                for (int qb = 0; qb < QB_W; ++qb)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        c[qb][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], b4[qb][j], c[qb][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                a4 = an;
-#pragma unroll
-                for (int qb = 0; qb < QB_W; ++qb) b4[qb] = bn[qb];
-            }
-            const uint32_t dcol = 16 * (w & 3) + 4 * mg;
-#pragma unroll
-            for (int qb = 0; qb < QB_W; ++qb) {
-                const f32x4 cc = (c[qb][0] + c[qb][1]) + (c[qb][2] + c[qb][3]);   // lane (q = mi, d = 4 mg + e)
-                const int qi = q0t + (FW == 8 ? 16 * (w >> 2) : 16 * qb) + mi;
-                if (qi < a.T) {                          // wave-uniform 64-bit base + one 32-bit lane offset
-                    if (a.slab) st4((float*)((char*)(a.slab + ((int64_t)chunk * n_bh + bh) * a.T * HD) + (uint32_t)(qi * HD + dcol) * 4u), cc);
-                    else st4((float*)((char*)(a.dq + (int64_t)b * a.T * a.ldg + head * HD) + (uint32_t)(qi * a.ldg + dcol) * 4u), cc * 0.125f);
-                }
-            }
-        }
-        if (qt + 1 < n_tiles) lstore();
-        __syncthreads();                     // next tile staged; every wave is done with this tile's dS
-    }
-    // ---- dK, dV: transposed through LDS (everything above is dead), whole rows out
-    float* ob = lds;                         // [KEYS][KLD]
-    for (int which = 0; which < 2; ++which) {
-        const f32x16& A0 = which ? GV0 : GK0;
-        const f32x16& A1 = which ? GV1 : GK1;
-        const float sc = which ? 1.0f : 0.125f / qscale;       // dK was added up over the pre-scaled Q rows
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            f32x4 v0 = {A0[4 * g4], A0[4 * g4 + 1], A0[4 * g4 + 2], A0[4 * g4 + 3]};
-            f32x4 v1 = {A1[4 * g4], A1[4 * g4 + 1], A1[4 * g4 + 2], A1[4 * g4 + 3]};
-            st4(ob + (w * 32 + r) * KLD + 8 * g4 + 4 * h, v0 * sc);
-            st4(ob + (w * 32 + r) * KLD + 32 + 8 * g4 + 4 * h, v1 * sc);
-        }
-        __syncthreads();
-        float* dst = which ? a.dv : a.dk;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int row = sq + FW * 4 * i;
-            if (kb0 + row < kend)
-                st4(dst + ((int64_t)b * a.T + kb0 + row) * a.ldg + head * HD + squad, ld4(ob + row * KLD + squad));
-        }
-        __syncthreads();
-    }
-}
+#define ATTN_BWD_PACKED 0
+#include "attn_bwd_fused_body.inc"   // attn_bwd_fused_kernel<FW>(BwdArgs)
+#undef ATTN_BWD_PACKED
 
 // dq[row][head*64 + d] = 1/8 · Σ_chunks slab[chunk][b,head][q][d], chunks in index order; a chunk contributes to a query
 // exactly when the fused kernel visited the pair (same rule, so no slab element is read that was not written).
@@ -1984,3 +1723,127 @@ extern "C" int vh_attn_decode_form_row(int i, vh_attn_decode_form_info* out) {
     return VH_OK;
 }
 
+
+// =============================================================================================
+// many-row attention over packed rows, TRAINING forms (packed AR training: a ragged batch without padding rows).  The
+// kernels are stamped out here, behind everything else, so every earlier kernel lies in the code object where it did.
+//   attn_rows_packed_lse_kernel  attn_rows_packed_kernel with the launch's mask mode (full / prefix per segment) and lse2
+//   attn_bwd_packed_kernel<8>    attn_bwd_fused_kernel<8> with the sequence taken from the segment table; work items
+//                                (segment, key chunk) x head from a host-built table, heaviest first
+//   attn_dq_reduce_packed_kernel the dQ slabs (max_chunks, n_heads, M, 64) added in chunk order, per 128-query block of the
+//                                forward's block table: every row of dq once, no atomics
+// =============================================================================================
+#define ATTN_ROWS_PACKED 2
+#include "attn_rows_body.inc"       // attn_rows_packed_lse_kernel(RowsArgs, PackedSegs, seg_x_len)
+#undef ATTN_ROWS_PACKED
+
+// The segments of vh_attn_rows_bwd_packed: PackedSegs' arrays plus the text lengths, and items[2 i], items[2 i + 1] =
+// (segment, key chunk) of work item i.  n_rows = M: lse2 and the slabs are (·, M) and no row at or beyond M is touched.
+struct PackedBwdSegs {
+    const int32_t* seg_start; const int32_t* seg_len; const int32_t* seg_x_len; const int32_t* items; const int32_t* blocks;
+    int n_seg, n_rows;
+};
+
+#define ATTN_BWD_PACKED 1
+#include "attn_bwd_fused_body.inc"   // attn_bwd_packed_kernel<FW>(BwdArgs, PackedBwdSegs)
+#undef ATTN_BWD_PACKED
+
+// dq[seg_start + q][head*64 + d] = 1/8 · Σ_chunks slab[chunk][head][seg_start + q][d] for the 128 queries of one block of
+// the forward's table, chunks in index order under attn_dq_reduce_kernel's rule (a chunk contributes to a query exactly
+// when the packed kernel visited the pair).  A segment of one chunk goes through here as well: one slab read.
+__global__ __launch_bounds__(256) void attn_dq_reduce_packed_kernel(BwdArgs a, PackedBwdSegs ps) {
+    const int blk = blockIdx.x / a.n_heads;
+    const int head = blockIdx.x - blk * a.n_heads;
+    const int seg = ps.blocks[2 * blk], q0 = ps.blocks[2 * blk + 1];
+    if ((unsigned)seg >= (unsigned)ps.n_seg) return;
+    const int s0 = ps.seg_start[seg], len = ps.seg_len[seg];
+    if (s0 < 0 || len < 1 || (int64_t)s0 + len > ps.n_rows || q0 < 0 || q0 >= len) return;
+    const int xl = a.mode == VH_MASK_PREFIX ? min(max(ps.seg_x_len[seg], 0), len) : len;   // full mask: every chunk sees every query
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        const int q = q0 + (idx >> 4), d4 = idx & 15;
+        if (q >= len) break;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < a.n_blocks; ++c) {
+            const int kb0 = c * a.chunk_keys;
+            if (kb0 >= len) break;
+            if (kb0 >= xl && q < kb0) break;
+            acc = acc + ld4(a.slab + ((((int64_t)c * a.n_heads + head) * ps.n_rows + s0 + q) * HD + 4 * d4));
+        }
+        st4(a.dq + ((int64_t)s0 + q) * a.ldg + head * HD + 4 * d4, acc * 0.125f);
+    }
+}
+
+extern "C" int vh_attn_rows_packed_lse(const float* q, int ldq, const float* kcache, const float* vcache, float* out, int ldo,
+                                       int n_heads, int M, int S_max, int mode, const int32_t* seg_start, const int32_t* seg_len,
+                                       const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks, float* lse2,
+                                       void* stream) {
+    VH_REQUIRE(q && kcache && vcache && out && lse2, VH_EINVAL, "vh_attn_rows_packed_lse: null pointer (q, kcache, vcache, out or lse2)");
+    VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL, "vh_attn_rows_packed_lse: null pointer (seg_start, seg_len or blocks)");
+    VH_REQUIRE(mode == VH_MASK_FULL || mode == VH_MASK_PREFIX, VH_EINVAL, "vh_attn_rows_packed_lse: mode=%d (full or prefix)", mode);
+    VH_REQUIRE(mode != VH_MASK_PREFIX || seg_x_len, VH_EINVAL, "vh_attn_rows_packed_lse: the prefix mask needs seg_x_len");
+    VH_REQUIRE(n_heads > 0 && M >= 1 && S_max >= M, VH_EINVAL, "vh_attn_rows_packed_lse: bad dims n_heads=%d M=%d S_max=%d", n_heads, M, S_max);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_packed_lse: n_seg=%d", n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_attn_rows_packed_lse: n_blocks=%d", n_blocks);
+    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD, VH_EINVAL, "vh_attn_rows_packed_lse: ldq=%d", ldq);
+    VH_REQUIRE(ldo % 4 == 0 && ldo >= n_heads * HD, VH_EINVAL, "vh_attn_rows_packed_lse: ldo=%d", ldo);
+    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(out), VH_EALIGN, "vh_attn_rows_packed_lse: q and out must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(kcache) && vh_aligned16(vcache), VH_EALIGN,
+               "vh_attn_rows_packed_lse: kcache and vcache must be 16-byte aligned");
+    VH_REQUIRE(((uintptr_t)lse2 & 3) == 0, VH_EALIGN, "vh_attn_rows_packed_lse: lse2 must be 4-byte aligned");
+    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED, "vh_attn_rows_packed_lse: n_blocks=%d x n_heads=%d workgroups",
+               n_blocks, n_heads);
+    RowsArgs a{q, ldq, kcache, vcache, out, ldo, n_heads, M, 0, S_max, mode, 0,
+               nullptr, nullptr, nullptr, nullptr, 0, lse2, 0};
+    PackedSegs ps{seg_start, seg_len, blocks, n_seg, M};        // n_rows = M: a segment reaching past it is cut (lse2 has M rows)
+    hipLaunchKernelGGL(attn_rows_packed_lse_kernel, dim3(n_blocks * n_heads), dim3(256), 0, (hipStream_t)stream, a, ps, seg_x_len);
+    VH_CHECK_LAUNCH("vh_attn_rows_packed_lse");
+    return VH_OK;
+}
+
+extern "C" size_t vh_attn_rows_bwd_packed_ws_bytes(int n_heads, int M, int max_chunks) {
+    if (n_heads <= 0 || M <= 0 || max_chunks <= 1) return 0;
+    return (size_t)max_chunks * n_heads * M * HD * sizeof(float);
+}
+
+extern "C" int vh_attn_rows_bwd_packed(const float* q, int ldq, const float* kcache, const float* vcache, const float* out,
+                                       int ldo, const float* dout, int lddo, const float* lse2, float* dq, float* dk, float* dv,
+                                       int ldg, int n_heads, int M, int S_max, int mode, const int32_t* seg_start,
+                                       const int32_t* seg_len, const int32_t* seg_x_len, int n_seg, const int32_t* items,
+                                       int n_items, int chunk_keys, int max_chunks, const int32_t* blocks, int n_blocks,
+                                       void* ws, size_t ws_bytes, void* stream) {
+    VH_REQUIRE(q && kcache && vcache && out && dout && lse2 && dq && dk && dv, VH_EINVAL, "vh_attn_rows_bwd_packed: null pointer");
+    VH_REQUIRE(seg_start && seg_len && items && blocks, VH_EINVAL,
+               "vh_attn_rows_bwd_packed: null pointer (seg_start, seg_len, items or blocks)");
+    VH_REQUIRE(mode == VH_MASK_FULL || mode == VH_MASK_PREFIX, VH_EINVAL, "vh_attn_rows_bwd_packed: mode=%d (full or prefix)", mode);
+    VH_REQUIRE(mode != VH_MASK_PREFIX || seg_x_len, VH_EINVAL, "vh_attn_rows_bwd_packed: the prefix mask needs seg_x_len");
+    VH_REQUIRE(n_heads > 0 && M >= 1 && S_max >= M, VH_EINVAL, "vh_attn_rows_bwd_packed: bad dims n_heads=%d M=%d S_max=%d", n_heads, M, S_max);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_bwd_packed: n_seg=%d", n_seg);
+    VH_REQUIRE(n_items >= 1 && n_blocks >= 1, VH_EINVAL, "vh_attn_rows_bwd_packed: n_items=%d n_blocks=%d", n_items, n_blocks);
+    VH_REQUIRE(chunk_keys >= 32 && chunk_keys <= FKMAX && chunk_keys % 32 == 0, VH_EINVAL,
+               "vh_attn_rows_bwd_packed: chunk_keys=%d (a multiple of 32, at most %d)", chunk_keys, FKMAX);
+    VH_REQUIRE(max_chunks >= 1 && (int64_t)max_chunks * chunk_keys <= 0x7fffffffLL, VH_EINVAL,
+               "vh_attn_rows_bwd_packed: max_chunks=%d", max_chunks);
+    const int wd = n_heads * HD;
+    VH_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && lddo % 4 == 0 && ldg % 4 == 0 && ldq >= wd && ldo >= wd && lddo >= wd && ldg >= wd,
+               VH_EINVAL, "vh_attn_rows_bwd_packed: leading dimensions");
+    VH_REQUIRE(vh_aligned16(q) && vh_aligned16(kcache) && vh_aligned16(vcache) && vh_aligned16(out) && vh_aligned16(dout) &&
+                   vh_aligned16(dq) && vh_aligned16(dk) && vh_aligned16(dv),
+               VH_EALIGN, "vh_attn_rows_bwd_packed: pointers must be 16-byte aligned");
+    const size_t need = vh_attn_rows_bwd_packed_ws_bytes(n_heads, M, max_chunks);
+    VH_REQUIRE(ws_bytes >= need, VH_EINVAL, "vh_attn_rows_bwd_packed: workspace of %zu bytes, need %zu", ws_bytes, need);
+    VH_REQUIRE(need == 0 || (ws && vh_aligned16(ws)), VH_EALIGN,
+               "vh_attn_rows_bwd_packed: workspace must be a 16-byte aligned device pointer");
+    VH_REQUIRE((int64_t)n_items * n_heads <= 0x7fffffffLL && (int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
+               "vh_attn_rows_bwd_packed: n_items=%d, n_blocks=%d x n_heads=%d workgroups", n_items, n_blocks, n_heads);
+    // max_chunks == 1: every segment fits one chunk and the kernel writes dq itself (no slab, no reduce launch)
+    BwdArgs a{q, ldq, kcache, vcache, out, ldo, dout, lddo, lse2, nullptr, dq, dk, dv, ldg,
+              n_heads, 0, S_max, mode, 0, nullptr, nullptr, nullptr, nullptr, max_chunks, need ? (float*)ws : nullptr, chunk_keys};
+    PackedBwdSegs ps{seg_start, seg_len, seg_x_len, items, blocks, n_seg, M};
+    hipLaunchKernelGGL(attn_bwd_packed_kernel<8>, dim3(n_items * n_heads), dim3(512), 0, (hipStream_t)stream, a, ps);
+    if (need)
+        hipLaunchKernelGGL(attn_dq_reduce_packed_kernel, dim3(n_blocks * n_heads), dim3(256), 0, (hipStream_t)stream, a, ps);
+    VH_CHECK_LAUNCH("vh_attn_rows_bwd_packed");
+    return VH_OK;
+}

@@ -10,7 +10,13 @@
 // b of a padded (B, Tq, ·) layout (attn_rows_kernel, every mask mode) or one segment of a packed row stream
 // (attn_rows_packed_kernel, full mask): there Tq = Tk = kvl = the segment's length, row 0 of the sequence is row seg_start
 // of q / out / the cache, and everything below — tile order, clamps, arithmetic — is the same code.
-#if ATTN_ROWS_PACKED
+//
+// ATTN_ROWS_PACKED 2: attn_rows_packed_lse_kernel, the packed kernel as the TRAINING forward — the mask mode (full or prefix)
+// is the launch's, a prefix segment's text length comes from seg_x_len, and the log2-sum-exp of every row goes to
+// lse2 (n_heads, M), M = a.Tq.  The first two kernels compile to what they were before it existed.
+#if ATTN_ROWS_PACKED == 2
+__global__ __launch_bounds__(256, 2) void attn_rows_packed_lse_kernel(RowsArgs a, PackedSegs ps, const int32_t* seg_x_len) {
+#elif ATTN_ROWS_PACKED
 __global__ __launch_bounds__(256, 2) void attn_rows_packed_kernel(RowsArgs a, PackedSegs ps) {
 #else
 __global__ __launch_bounds__(256, 2) void attn_rows_kernel(RowsArgs a) {
@@ -29,10 +35,16 @@ __global__ __launch_bounds__(256, 2) void attn_rows_kernel(RowsArgs a) {
     if (s0 < 0 || s0 >= ps.n_rows) return;
     const int len = min(ps.seg_len[seg], ps.n_rows - s0);      // never a cache row at or beyond S_max, whatever the table says
     if (q0 < 0 || q0 >= len) return;
+#if ATTN_ROWS_PACKED == 2
+    const int pmode = a.mode == VH_MASK_PREFIX ? VH_MASK_PREFIX : VH_MASK_FULL;
+    const int kvl = len, xl = pmode == VH_MASK_PREFIX ? min(max(seg_x_len[seg], 0), len) : 0, q_off = 0;
+#define AR_MODE pmode
+#else
     const int kvl = len, xl = 0, q_off = 0;
+#define AR_MODE VH_MASK_FULL
+#endif
 #define AR_TQ len                                              /* queries = keys = the segment's rows */
 #define AR_TK len
-#define AR_MODE VH_MASK_FULL
 #define AR_ROW0 (int64_t)s0                                    /* row of q / out that holds the sequence's query 0 */
 #define AR_KV(p) ((p) + ((int64_t)bh * a.S_max + s0) * HD)     /* the sequence's key 0 in the head's K / V stream */
 #else
@@ -192,7 +204,11 @@ __global__ __launch_bounds__(256, 2) void attn_rows_kernel(RowsArgs a) {
     // ---- normalise, transpose through LDS, store coalesced rows
     const float ltot = l + __shfl_xor(l, 32, 64);
     const float inv = 1.0f / ltot;  // fully masked row → 0/0 = NaN, as SDPA gives
+#if ATTN_ROWS_PACKED == 2
+    if (h == 0 && qi < AR_TQ) a.lse2[(int64_t)head * a.Tq + s0 + qi] = m + log2f(ltot);
+#else
     if (!ATTN_ROWS_PACKED && a.lse2 && h == 0 && qi < AR_TQ) a.lse2[(int64_t)bh * AR_TQ + qi] = m + log2f(ltot);
+#endif
     float* ob = lds;                // [128][KLD]; all K/V reads finished at the last barrier
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {

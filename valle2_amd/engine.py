@@ -461,16 +461,63 @@ def pack_plan(lengths):
     return starts, m, blocks
 
 
+PACK_BWD_CHUNK_KEYS = 256         # keys one workgroup of vh_attn_rows_bwd_packed takes (attention.hip FKMAX: the eight-wave kernel)
+
+
+def pack_bwd_plan(lengths, chunk_keys=PACK_BWD_CHUNK_KEYS, x_lens=None):
+    """The work items of the packed attention backward (pure Python, no device): every segment's keys in chunks of
+    `chunk_keys` (a multiple of 32, at most 256; the last chunk of a segment may be short).  Returns (items, max_chunks):
+    items the (segment, chunk) pairs, each once, HEAVIEST first — weight = the chunk's keys x the 32-query tiles it visits:
+    all of the segment's, or under the prefix mask (x_lens given: the text length inside each segment) only those from the
+    chunk's first key on when that key lies past the text; ties keep (segment, chunk) order — and max_chunks the largest
+    chunk count of a segment (the dQ slabs the launch needs; 1: none)."""
+    lengths = [int(n) for n in lengths]
+    chunk_keys = int(chunk_keys)
+    if not lengths:
+        raise ValueError('pack_bwd_plan: no lengths')
+    if min(lengths) < 1:
+        raise ValueError(f'pack_bwd_plan: every length must be >= 1, got {min(lengths)}')
+    if chunk_keys < 32 or chunk_keys > 256 or chunk_keys % 32:
+        raise ValueError(f'pack_bwd_plan: chunk_keys={chunk_keys} must be a multiple of 32 in 32..256')
+    if x_lens is not None:
+        x_lens = [int(x) for x in x_lens]
+        if len(x_lens) != len(lengths) or any(not 0 <= x <= n for x, n in zip(x_lens, lengths)):
+            raise ValueError('pack_bwd_plan: one text length per segment, 0 <= x_len <= length')
+    weighted = []
+    for s, n in enumerate(lengths):
+        tiles = (n + 31) // 32
+        for c in range((n + chunk_keys - 1) // chunk_keys):
+            k0 = c * chunk_keys
+            first = k0 // 32 if x_lens is not None and k0 >= x_lens[s] else 0
+            weighted.append((-(min(chunk_keys, n - k0) * (tiles - first)), s, c))
+    weighted.sort()
+    return [(s, c) for _, s, c in weighted], (max(lengths) + chunk_keys - 1) // chunk_keys
+
+
 class PackedRows:
     """`pack_plan(lengths)` as device int32 tensors, built once per call: what `kernels.attn_rows_packed` and
-    `transformer_forward_packed` take."""
+    `transformer_forward_packed` take.  x_lens (packed training under the prefix mask): the text length inside each segment;
+    `bwd_table` is the backward's work table (`pack_bwd_plan`), built on first use."""
 
-    def __init__(self, lengths, device):
+    def __init__(self, lengths, device, x_lens=None):
         self.lengths = [int(n) for n in lengths]
         self.starts, self.rows, blocks = pack_plan(self.lengths)
         self.n_seg, self.n_blocks = len(self.lengths), len(blocks)
-        i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), device)   # noqa: E731
+        i32 = self._i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), device)   # noqa: E731
         self.seg_start, self.seg_len, self.blocks = i32(self.starts), i32(self.lengths), i32(blocks)
+        self.x_lens = None if x_lens is None else [int(x) for x in x_lens]
+        if self.x_lens is not None and (len(self.x_lens) != self.n_seg or any(not 0 <= x <= n for x, n in zip(self.x_lens, self.lengths))):
+            raise ValueError('PackedRows: one text length per segment, 0 <= x_len <= length')
+        self.seg_x_len = None if x_lens is None else i32(self.x_lens)
+        self._bwd = {}
+
+    def bwd_table(self, chunk_keys=None):
+        """(chunk_keys, max_chunks, items as a device int32 tensor, n_items) of `pack_bwd_plan`, cached per chunk_keys."""
+        chunk_keys = PACK_BWD_CHUNK_KEYS if chunk_keys is None else int(chunk_keys)
+        if chunk_keys not in self._bwd:
+            items, max_chunks = pack_bwd_plan(self.lengths, chunk_keys, self.x_lens)
+            self._bwd[chunk_keys] = (chunk_keys, max_chunks, self._i32(items), len(items))
+        return self._bwd[chunk_keys]
 
 
 class NarRows(typing.NamedTuple):

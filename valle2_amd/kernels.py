@@ -328,6 +328,53 @@ def attn_rows_packed(q, kcache, vcache, out, n_heads, rows):
     return out
 
 
+def _packed_train_args(what, q, kcache, vcache, out, lse2, n_heads, rows, mode):
+    S_max = kcache.shape[2]
+    M = rows.rows
+    if tuple(kcache.shape) != (1, n_heads, S_max, HEAD_DIM) or kcache.shape != vcache.shape or M > S_max:
+        raise _lib.VhError(f'{what}: cache {tuple(kcache.shape)} M={M}')
+    if q.shape[0] != M or out.shape[0] != M:
+        raise _lib.VhError(f'{what}: q/out rows')
+    if tuple(lse2.shape) != (n_heads, M) or lse2.dtype != torch.float32 or not lse2.is_contiguous():
+        raise _lib.VhError(f'{what}: lse2 must be contiguous float32 (n_heads, M)')
+    if mode == MASK_PREFIX and rows.seg_x_len is None:
+        raise _lib.VhError(f'{what}: the prefix mask needs PackedRows(lengths, device, x_lens)')
+    return M, S_max
+
+
+def attn_rows_packed_lse(q, kcache, vcache, out, lse2, n_heads, rows, mode):
+    """The training forward over packed rows: `attn_rows(..., lse2=)` of every segment of `rows` (an engine.PackedRows) alone —
+    B = 1, Tq = Tk = its length, mask `mode` (MASK_FULL, or MASK_PREFIX with the segment's text length rows.x_lens[s]) — in
+    one launch, the same bits.  q / out (M, ·), kcache / vcache (1, n_heads, S_max >= M, 64), lse2 (n_heads, M)
+    (vh_attn_rows_packed_lse)."""
+    M, S_max = _packed_train_args('attn_rows_packed_lse', q, kcache, vcache, out, lse2, n_heads, rows, mode)
+    check(_lib.lib().vh_attn_rows_packed_lse(
+        _dev_f32(q, 'q'), q.stride(0), ptr(kcache), ptr(vcache), _dev_f32(out, 'out'), out.stride(0), n_heads, M, S_max, mode,
+        ptr(rows.seg_start), ptr(rows.seg_len), ptr(rows.seg_x_len), rows.n_seg, ptr(rows.blocks), rows.n_blocks, ptr(lse2),
+        stream()), 'vh_attn_rows_packed_lse')
+    return out
+
+
+def attn_rows_bwd_packed(q, kcache, vcache, out, dout, lse2, dq, dk, dv, n_heads, rows, mode, chunk_keys=None):
+    """dq, dk, dv ((M, d) views with a common row stride) of `attn_rows_packed_lse` given dout: the five-product kernel over
+    the (segment, key chunk) items of `rows.bwd_table(chunk_keys)` and, when a segment has more than one chunk, the reduce
+    over the dQ slabs in chunk order (vh_attn_rows_bwd_packed).  No atomics: two runs give the same bits."""
+    M, S_max = _packed_train_args('attn_rows_bwd_packed', q, kcache, vcache, out, lse2, n_heads, rows, mode)
+    if not (dq.stride(0) == dk.stride(0) == dv.stride(0)) or dq.stride(1) != 1:
+        raise _lib.VhError('attn_rows_bwd_packed: dq/dk/dv must share one row stride')
+    if dq.shape[0] != M or dout.shape[0] != M:
+        raise _lib.VhError('attn_rows_bwd_packed: dq/dout rows')
+    chunk_keys, max_chunks, items, n_items = rows.bwd_table(chunk_keys)
+    need = _lib.lib().vh_attn_rows_bwd_packed_ws_bytes(n_heads, M, max_chunks)
+    ws = _stream_ws(_BWD_WS, q.device, need)
+    check(_lib.lib().vh_attn_rows_bwd_packed(
+        q.data_ptr(), q.stride(0), ptr(kcache), ptr(vcache), out.data_ptr(), out.stride(0), dout.data_ptr(), dout.stride(0),
+        ptr(lse2), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dq.stride(0), n_heads, M, S_max, mode, ptr(rows.seg_start),
+        ptr(rows.seg_len), ptr(rows.seg_x_len), rows.n_seg, ptr(items), n_items, chunk_keys, max_chunks, ptr(rows.blocks),
+        rows.n_blocks, ptr(ws), ws.numel() * 4, stream()), 'vh_attn_rows_bwd_packed')
+    return dq, dk, dv
+
+
 def attn_rows_bwd(q, kcache, vcache, out, dout, lse2, dq, dk, dv, B, n_heads, T, mode, x_len=0,
                   x_len_dev=None, kv_len=None, mask=None, pad=None):
     """dq, dk, dv (each (B*T, d) views with a common row stride, heads at columns h*64) of

@@ -54,6 +54,9 @@ def train(hparams_fp: Path, model_name: str, batches=None, device=None, log=prin
     accum = max(1, config.grad_accum)
     if batches is None:
         batches = synthetic_batches(model_name, config, rank, world, config.max_steps * accum)
+    # VALLE2_TRAIN_PACKED=1 (opt-in): the AR model's steps run over packed rows, no padding (ValleAR.training_step_packed);
+    # read here, per call, like the project's other environment opt-ins
+    packed = os.environ.get('VALLE2_TRAIN_PACKED') == '1' and model_name == 'ValleAR'
     step, t0, losses = 0, time.perf_counter(), []
     optimizer.zero_grad()
     one_shot = iter(batches) is batches                  # a generator: a single epoch, then stop
@@ -77,7 +80,7 @@ def train(hparams_fp: Path, model_name: str, batches=None, device=None, log=prin
             pending += 1
             last = pending == accum                      # counted within the epoch: Lightning's accumulation window
             reducer.enabled = last                       # accumulate locally, exchange once per step
-            loss = model.training_step(batch)
+            loss = model.training_step_packed(batch) if packed else model.training_step(batch)
             (loss / accum).backward()                    # buckets are all-reduced as they complete
             losses.append(loss.detach())                 # stays on the device: no host synchronisation per step
             if last:

@@ -186,6 +186,88 @@ class ValleAR(_Base):
         self.log('train/loss', loss)
         return loss
 
+    def training_step_packed(self, batch, **kwargs):
+        """`training_step` of a ragged batch WITHOUT its padding (extension, opt-in; `training_step` is untouched).  The same
+        collated batch; utterance b contributes the rows [tokens[b, :tokens_lens[b]] | codes[b, :codes_lens[b]]], the
+        utterances lie back to back in one (M, d) buffer, positions restart at 0 for each stream of each utterance, and every
+        utterance attends its own rows only under its own prefix-LM mask (`vh_attn_rows_packed_lse` /
+        `vh_attn_rows_bwd_packed`; every other kernel is the row-wise one over M rows).  The loss is the mean cross entropy
+        over the sum(codes_lens) REAL target positions: the reference's training_step on each utterance alone (B = 1, nothing
+        padded), the per-utterance losses combined token-weighted.  It differs from `training_step` on a ragged batch —
+        that one averages over padded positions and lets every row see text padding (valle_ar.py:69-73,86) — and equals it
+        when all lengths are equal.  Dropout as in training_step, the fields keyed on the packed row.  Head width 64,
+        LayerNorm; under no_grad the same value without a graph."""
+        self._require_layernorm()
+        cfg = self.config
+        if cfg.d_model != kernels.HEAD_DIM * cfg.n_heads:
+            raise ValueError(f'training_step_packed: head width {cfg.d_model // cfg.n_heads} (d_model={cfg.d_model}, '
+                             f'n_heads={cfg.n_heads}): the packed attention serves width {kernels.HEAD_DIM} only — '
+                             'training_step serves the others')
+        txs, tys = [int(n) for n in batch['tokens_lens']], [int(n) for n in batch['codes_lens']]
+        n = batch['tokens'].shape[0]
+        if len(txs) != n or len(tys) != n or batch['codes'].shape[0] != n or batch['target'].shape[0] != n:
+            raise ValueError(f'training_step_packed: {n} rows of tokens, {len(txs)} tokens_lens, {len(tys)} codes_lens')
+        for what, lens, width in (('tokens_lens', txs, batch['tokens'].shape[1]),
+                                  ('codes_lens', tys, min(batch['codes'].shape[1], batch['target'].shape[1]))):
+            bad = [v for v in lens if not 1 <= v <= width]
+            if bad:
+                raise ValueError(f'training_step_packed: {what} entry {bad[0]} is outside 1 .. {width} (the batch\'s padded width)')
+        if not torch.is_grad_enabled():
+            with torch.no_grad():
+                loss = self._packed_loss_on_device(batch)
+        elif self.device.type != 'cuda':
+            raise _lib.VhError('ValleAR.training_step_packed with gradients needs the model on its HIP device '
+                               '(model.to("cuda")): gradients cannot flow into a CPU copy of the parameters')
+        else:
+            loss = self._packed_loss(batch)
+        self.log('train/loss', loss)
+        return loss
+
+    @_on_device
+    def _packed_loss_on_device(self, batch):
+        return self._packed_loss(batch)
+
+    def _packed_loss(self, batch):
+        from . import autograd as A
+        from .engine import PackedRows
+        dev, cfg = self.device, self.config
+        d = cfg.d_model
+        tokens = kernels.ids_to_device(batch['tokens'], dev, cfg.vocab_size, 'tokens')
+        codes = kernels.ids_to_device(batch['codes'], dev, cfg.num_audio_tokens + 2, 'codes')
+        target = kernels.ids_to_device(batch['target'], dev, cfg.num_audio_tokens + 1, 'target')
+        txs, tys = torch.as_tensor(batch['tokens_lens']).cpu().long(), torch.as_tensor(batch['codes_lens']).cpu().long()
+        tx, ty = int(txs.max()), int(tys.max())
+        rows = PackedRows((txs + tys).tolist(), dev, x_lens=txs.tolist())
+        M = rows.rows
+        starts = torch.tensor(rows.starts, dtype=torch.int64)
+        put = lambda t, dt=None: _lib.to_device_async(t, dev, dt)   # noqa: E731
+
+        def ragged(lens, base, width):
+            """(packed row, b * width + t) of every (b, t < lens[b]), row-major."""
+            b = torch.repeat_interleave(torch.arange(len(lens)), lens)
+            t = torch.arange(int(lens.sum())) - torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens)
+            return base[b] + t, b * width + t
+
+        dest_t, src_t = ragged(txs, starts, tx)
+        dest_a, src_a = ragged(tys, starts + txs, ty)
+        _, src_target = ragged(tys, starts, target.shape[1])
+        dest_a_dev = put(dest_a)
+        # PE dropout as in training_step (live in train mode whatever config.dropout says, D9): the fields of both streams
+        # are keyed on the row of the packed buffer
+        seed = dropout.seed_if(dropout.live(self.tokens_position_emb.dropout), dropout.live(self.audio_position_emb.dropout))
+        dr_t = dropout.spec(seed, dropout.site(dropout.PE_TEXT), dropout.live(self.tokens_position_emb.dropout))
+        dr_a = dropout.spec(seed, dropout.site(dropout.PE_AUDIO), dropout.live(self.audio_position_emb.dropout))
+        dropout.record('tokens_position_emb.dropout', dr_t, M, d)
+        dropout.record('audio_position_emb.dropout', dr_a, M, d)
+        x = A.EmbedPackedFn.apply(
+            [(tokens[:, :tx], self.tokens_position_emb.pe, put(txs, torch.int32), rows.seg_start, tx, 0, dr_t, put(dest_t), put(src_t)),
+             (codes[:, :ty], self.audio_position_emb.pe, put(tys, torch.int32), put(starts + txs, torch.int32), ty, 1, dr_a,
+              dest_a_dev, put(src_a))],
+            M, self.tokens_emb.weight, self.audio_emb.weight)
+        x = A.transformer_train(self.transformer, x, 1, M, dict(mode=kernels.MASK_PREFIX, rows=rows))
+        logits = A.linear(x.index_select(0, dest_a_dev), self.proj.weight)
+        return A.CrossEntropyFn.apply(logits, target.reshape(-1).index_select(0, put(src_target)))
+
     # ------------------------------------------------------------------------------------
     @_sampling_refused_early
     @_on_device
