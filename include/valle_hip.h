@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 143            /* 0.2.19: packed AR training — vh_attn_rows_packed_lse (vh_attn_rows_packed with a mask mode, per-segment text lengths and lse2), vh_attn_rows_bwd_packed + vh_attn_rows_bwd_packed_ws_bytes (the five-product backward over segments); nothing earlier changes; 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 144            /* 0.2.20: packed NAR training — vh_embed_nar_packed and vh_embed_nar_packed_bwd (the NAR model input over packed rows: text rows and audio rows of every segment in one launch, the codebook count changing at each segment's own prefix boundary; the backward reads every gradient row once for all its tables); nothing earlier changes; 0.2.19: packed AR training — vh_attn_rows_packed_lse (vh_attn_rows_packed with a mask mode, per-segment text lengths and lse2), vh_attn_rows_bwd_packed + vh_attn_rows_bwd_packed_ws_bytes (the five-product backward over segments); nothing earlier changes; 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -860,6 +860,43 @@ int vh_cross_entropy(const float* logits, int ld, int V, const int64_t* target, 
 int vh_embed_bwd(const int64_t* ids, int64_t ids_bstride, int64_t ids_tstride, const float* dout,
                  int64_t dout_bstride, int out_t0, float* dtable, int vocab, int B, int T, int d,
                  int32_t* err_flag, const vh_dropout_spec* drop, void* stream);
+/* ---- packed NAR training (ABI 144): the model input over the SEGMENTS of one packed row stream ----------------------
+ * n_seg segments lie back to back in out (M, d): segment s starts at row seg_start[s] (ASCENDING in s: the kernels find a
+ * row's segment by a binary search over seg_start) and holds x_len[s] text rows, then a_len[s] audio rows:
+ *   text row i   = text_table[tokens[s, i]] + pe_text[i]
+ *   audio row t  = sum_{j < n(t)} code_tables[j][codes[s, t, j]] + pe_audio[t],  n(t) = n_full for t < prefix[s], else n_rest
+ * (the NAR training input: all codebooks for the acoustic prefix, the codebooks below the stage after it; positions restart
+ * at 0 for each stream of each segment).  seg_start, x_len, a_len, prefix: device int32 (n_seg); tokens (n_seg, >= max_x_len)
+ * int64 with a batch stride; codes (n_seg, >= max_a_len, >= n_full) int64 with batch, frame and codebook strides; code_tables
+ * / code_vocab: HOST arrays of n_full device tables and their row counts, 1 <= n_rest <= n_full <= VH_MAX_TABLES.  The
+ * additions are vh_embed_sum_pe's in its order — tables in ascending j, the position, then the dropout field of the row's
+ * own stream (drop_text / drop_audio, NULL: none) whose row is the PACKED row — so every row of a segment is bit for bit
+ * what vh_embed_sum_pe writes for that utterance alone at the same rows of out.  An id outside its table reads row 0 and
+ * ORs VH_DEVERR_EMBED_ID into *err_flag.  max_x_len / max_a_len: the longest text / audio stream, which the host holds
+ * against pe_text_rows / pe_audio_rows before any launch; a device length beyond them is cut there.  A row in [0, M) that
+ * lies in no segment is left alone; no row at or beyond M is written.  VH_EINVAL names the argument for: a null pointer,
+ * d not a positive multiple of 4, n_rest / n_full out of range, M <= 0, n_seg <= 0, a PE row count below the longest
+ * stream. */
+int vh_embed_nar_packed(const int64_t* tokens, int64_t tokens_bstride, const int64_t* codes, int64_t codes_bstride,
+                        int64_t codes_tstride, int64_t codes_jstride, const float* text_table, int text_vocab,
+                        const float* const* code_tables, const int32_t* code_vocab, int n_full, int n_rest,
+                        const float* pe_text, int pe_text_rows, const float* pe_audio, int pe_audio_rows,
+                        const int32_t* seg_start, const int32_t* x_len, const int32_t* a_len, const int32_t* prefix,
+                        int n_seg, int max_x_len, int max_a_len, float* out, int M, int d, int32_t* err_flag,
+                        const vh_dropout_spec* drop_text, const vh_dropout_spec* drop_audio, void* stream);
+/* Its backward: dout (M, d) is multiplied by the regenerated field of each row's stream on the way in and every packed row is
+ * ADDED (fp32 atomics, no promise of order, as vh_embed_bwd) into the table row its id names: dtext_table for a text row,
+ * dcode_tables[j] for j < n(t) for an audio row, so tables j >= n_rest receive prefix frames only.  The gradient row is read
+ * once for all its tables; consecutive packed rows that name the same row of a table are added up before the atomic is
+ * issued.  dtext_table and any entry of dcode_tables (a HOST array of n_full device pointers) may be NULL: skipped.  Ids out
+ * of range are skipped and flagged; nothing is scattered outside a table.  The same refusals as the forward. */
+int vh_embed_nar_packed_bwd(const int64_t* tokens, int64_t tokens_bstride, const int64_t* codes, int64_t codes_bstride,
+                            int64_t codes_tstride, int64_t codes_jstride, const float* dout, float* dtext_table,
+                            int text_vocab, float* const* dcode_tables, const int32_t* code_vocab, int n_full, int n_rest,
+                            int pe_text_rows, int pe_audio_rows, const int32_t* seg_start, const int32_t* x_len,
+                            const int32_t* a_len, const int32_t* prefix, int n_seg, int max_x_len, int max_a_len, int M,
+                            int d, int32_t* err_flag, const vh_dropout_spec* drop_text, const vh_dropout_spec* drop_audio,
+                            void* stream);
 /* bias gradient: out[c] += sum_r x[r, c] */
 int vh_colsum(const float* x, int ld, float* out, int rows, int cols, void* stream);
 

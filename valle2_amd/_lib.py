@@ -305,6 +305,15 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int,
                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    # packed NAR training: the model input over segments, forward and backward (ABI 144)
+    'vh_embed_nar_packed': (C.c_int, [c_i64p, C.c_int64, c_i64p, C.c_int64, C.c_int64, C.c_int64, c_f32p, C.c_int,
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, c_f32p, C.c_int, c_f32p,
+                                      C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
+                                      C.c_int, c_i32p, c_dropp, c_dropp, C.c_void_p]),
+    'vh_embed_nar_packed_bwd': (C.c_int, [c_i64p, C.c_int64, c_i64p, C.c_int64, C.c_int64, C.c_int64, c_f32p, c_f32p, C.c_int,
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                          c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p,
+                                          c_dropp, c_dropp, C.c_void_p]),
 }
 
 _lib = None

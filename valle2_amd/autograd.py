@@ -431,6 +431,33 @@ class EmbedPackedFn(torch.autograd.Function):
         return (None, None, *grads)
 
 
+class EmbedNarPackedFn(torch.autograd.Function):
+    """The model input x (M, d) of a PACKED NAR training step, one launch forward and one backward over the packed rows
+    themselves (vh_embed_nar_packed / vh_embed_nar_packed_bwd): utterance b's text rows, then its frames — all of
+    `code_tables` for its own acoustic prefix, the first n_rest after — at the rows `layout` (an engine.NarTrainLayout) names.
+    drop_text / drop_audio: the two PositionalEncoding dropout specs or None, fields keyed on the packed row.  Every table
+    receives ONE gradient; the backward reads each gradient row once for all the tables the row summed."""
+
+    @staticmethod
+    def forward(ctx, tokens, codes, layout, n_rest, pe_text, pe_audio, drop_text, drop_audio, text_table, *code_tables):
+        out = torch.empty(layout.rows, text_table.shape[1], device=text_table.device, dtype=torch.float32)
+        kernels.embed_nar_packed(tokens, codes, text_table.detach(), [t.detach() for t in code_tables], n_rest, pe_text, pe_audio,
+                                 layout, out, drop_text, drop_audio)
+        ctx.args = (tokens, codes, layout, n_rest, pe_text.shape[0], pe_audio.shape[0], drop_text, drop_audio)
+        ctx.tables = (text_table, *code_tables)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        tokens, codes, layout, n_rest, pe_text_rows, pe_audio_rows, drop_text, drop_audio = ctx.args
+        grads = [optim.grad_out(t, zero=True) if ctx.needs_input_grad[8 + j] else None for j, t in enumerate(ctx.tables)]
+        if any(g is not None for g in grads):
+            kernels.embed_nar_packed_bwd(tokens, codes, dout.contiguous(), grads[0], grads[1:], ctx.tables[0].shape[0],
+                                         [t.shape[0] for t in ctx.tables[1:]], n_rest, pe_text_rows, pe_audio_rows, layout,
+                                         drop_text, drop_audio)
+        return (None,) * 8 + tuple(grads)
+
+
 class CrossEntropyFn(torch.autograd.Function):
     """Mean cross entropy over every row of (R, V) logits against (R,) int64 targets."""
 

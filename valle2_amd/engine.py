@@ -520,6 +520,54 @@ class PackedRows:
         return self._bwd[chunk_keys]
 
 
+def nar_train_plan(x_lens, a_lens, prefixes):
+    """The packed layout of a NAR training batch (pure Python, no device): utterance b's rows [x_lens[b] text | a_lens[b]
+    frames] lie back to back, its first prefixes[b] frames are the acoustic prefix (all codebooks, no target) and the rest
+    are targets.  Returns (starts, M, target_rows, target_frames, weights): starts the first row of every utterance, M the
+    row count, target_rows the packed row of every target frame and target_frames its (b, t), both utterance by utterance
+    and frame by frame, weights the share (a_len_b - prefix_b) / sum of each utterance in the mean over target frames."""
+    x_lens, a_lens, prefixes = ([int(v) for v in seq] for seq in (x_lens, a_lens, prefixes))
+    if not x_lens or len(a_lens) != len(x_lens) or len(prefixes) != len(x_lens):
+        raise ValueError('nar_train_plan: one text length, frame count and prefix per utterance')
+    if min(x_lens) < 1 or min(a_lens) < 1:
+        raise ValueError('nar_train_plan: every length must be >= 1')
+    if any(not 0 <= p < a for p, a in zip(prefixes, a_lens)):
+        raise ValueError('nar_train_plan: 0 <= prefix < frames for every utterance (at least one target frame)')
+    starts, _, _ = pack_plan([x + a for x, a in zip(x_lens, a_lens)])
+    m = starts[-1] + x_lens[-1] + a_lens[-1]
+    target_rows = [starts[b] + x_lens[b] + t for b in range(len(x_lens)) for t in range(prefixes[b], a_lens[b])]
+    target_frames = [(b, t) for b in range(len(x_lens)) for t in range(prefixes[b], a_lens[b])]
+    total = len(target_rows)
+    return starts, m, target_rows, target_frames, [(a - p) / total for a, p in zip(a_lens, prefixes)]
+
+
+class NarTrainLayout:
+    """`nar_train_plan` as device tensors, built once per step: what `kernels.embed_nar_packed` and its backward take
+    (seg_start, x_len, a_len, prefix: int32 (B); max_x_len, max_a_len, n_seg, rows) and the step's gathers (target_rows:
+    int64 packed rows of the target frames; target_index: int64 b * width + t of each, into a (B, width) view of the
+    codes).  `packed` is the `PackedRows` of the same segments for the attention."""
+
+    def __init__(self, x_lens, a_lens, prefixes, width, device):
+        self.x_lens, self.a_lens, self.prefixes = ([int(v) for v in seq] for seq in (x_lens, a_lens, prefixes))
+        self.packed = PackedRows([x + a for x, a in zip(self.x_lens, self.a_lens)], device)
+        self.starts, self.rows, self.n_seg = self.packed.starts, self.packed.rows, self.packed.n_seg
+        if any(not 0 <= p < a for p, a in zip(self.prefixes, self.a_lens)) or min(self.x_lens) < 1:
+            raise ValueError('NarTrainLayout: every text length >= 1 and 0 <= prefix < frames for every utterance')
+        i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), device)   # noqa: E731
+        self.seg_start, self.x_len, self.a_len, self.prefix = self.packed.seg_start, i32(self.x_lens), i32(self.a_lens), i32(self.prefixes)
+        self.max_x_len, self.max_a_len = max(self.x_lens), max(self.a_lens)
+        # nar_train_plan's target lists as tensor arithmetic (the plan itself is the readable form, and what the tests hold
+        # this against): a step of 16 k rows should not walk them in Python
+        x, a, p, s0 = (torch.tensor(v, dtype=torch.int64) for v in (self.x_lens, self.a_lens, self.prefixes, self.starts))
+        n = a - p
+        b = torch.repeat_interleave(torch.arange(self.n_seg), n)
+        t = torch.arange(int(n.sum())) - torch.repeat_interleave(torch.cumsum(n, 0) - n, n) + p[b]
+        self.n_targets = int(n.sum())
+        self.weights = (n.double() / self.n_targets).tolist()
+        self.target_rows = _lib.to_device_async(s0[b] + x[b] + t, device)
+        self.target_index = _lib.to_device_async(b * int(width) + t, device)
+
+
 class NarRows(typing.NamedTuple):
     """`nar_rows`: where the rows of a NAR batch lie in its one (rows, d) buffer.  Python ints and lists only."""
     packed: bool

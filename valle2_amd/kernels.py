@@ -82,6 +82,73 @@ def embed_sum_pe(ids, tables, pe, pos0, out, out_t0=0, lens=None, row_pos0=None,
     return out
 
 
+def _nar_packed_args(what, tokens, codes, text_table, code_tables, n_rest, layout, rows):
+    """The host checks the two packed NAR input launches share; returns the argument run both entry points start with up to
+    the segment tables (the tables / gradient tables go in between)."""
+    n_full = len(code_tables)
+    if not 1 <= n_rest <= n_full <= MAX_TABLES:
+        raise _lib.VhError(f'{what}: n_rest={n_rest}, n_full={n_full}: need 1 <= n_rest <= n_full <= {MAX_TABLES} (VH_MAX_TABLES)')
+    if tokens.dtype != torch.int64 or codes.dtype != torch.int64 or not tokens.is_cuda or not codes.is_cuda:
+        raise _lib.VhError(f'{what}: tokens / codes must be int64 tensors on the HIP device')
+    B = layout.n_seg
+    if tokens.dim() != 2 or codes.dim() != 3 or tokens.shape[0] != B or codes.shape[0] != B or tokens.stride(1) != 1:
+        raise _lib.VhError(f'{what}: tokens {tuple(tokens.shape)} / codes {tuple(codes.shape)} for {B} segments')
+    if layout.max_x_len > tokens.shape[1] or layout.max_a_len > codes.shape[1] or n_full > codes.shape[2]:
+        raise _lib.VhError(f'{what}: streams of up to {layout.max_x_len} text ids and {layout.max_a_len} frames of {n_full} '
+                           f'codebooks do not fit tokens {tuple(tokens.shape)} / codes {tuple(codes.shape)}')
+    d = text_table.shape[1]
+    if tuple(rows.shape) != (layout.rows, d) or not rows.is_contiguous():
+        raise _lib.VhError(f'{what}: packed rows {tuple(rows.shape)} must be contiguous ({layout.rows}, {d})')
+    if any(t is not None and (t.dim() != 2 or t.shape[1] != d) for t in code_tables):
+        raise _lib.VhError(f'{what}: every table must be (vocab, {d})')
+    for t_ in (layout.seg_start, layout.x_len, layout.a_len, layout.prefix):
+        if t_.dtype != torch.int32 or t_.numel() != B or not t_.is_cuda:
+            raise _lib.VhError(f'{what}: seg_start / x_len / a_len / prefix must be device int32 tensors of {B} entries')
+    return d, (tokens.data_ptr(), tokens.stride(0), codes.data_ptr(), codes.stride(0), codes.stride(1), codes.stride(2))
+
+
+def embed_nar_packed(tokens, codes, text_table, code_tables, n_rest, pe_text, pe_audio, layout, out, drop_text=None,
+                     drop_audio=None):
+    """The model input of packed NAR training in ONE launch (vh_embed_nar_packed).  `layout` (an engine.NarTrainLayout):
+    segment s of out (M, d) starts at layout.seg_start[s] and holds x_len[s] text rows — text_table[tokens[s, i]] +
+    pe_text[i] — then a_len[s] audio rows — sum_{j < n(t)} code_tables[j][codes[s, t, j]] + pe_audio[t] with n(t) =
+    len(code_tables) for t < prefix[s] and n_rest after.  Every row is bit for bit `embed_sum_pe`'s for that utterance alone
+    at the same rows of out; drop_text / drop_audio: the two PositionalEncoding dropout specs, fields keyed on the packed row."""
+    d, ids = _nar_packed_args('embed_nar_packed', tokens, codes, text_table, code_tables, n_rest, layout, out)
+    n = len(code_tables)
+    arr = (C.c_void_p * n)(*[ptr(_f32(t, 'table')) for t in code_tables])
+    vocab = (C.c_int32 * n)(*[int(t.shape[0]) for t in code_tables])
+    check(_lib.lib().vh_embed_nar_packed(
+        *ids, ptr(_f32(text_table, 'text table')), int(text_table.shape[0]), arr, vocab, n, n_rest,
+        ptr(_f32(pe_text, 'pe')), int(pe_text.shape[0]), ptr(_f32(pe_audio, 'pe')), int(pe_audio.shape[0]),
+        ptr(layout.seg_start), ptr(layout.x_len), ptr(layout.a_len), ptr(layout.prefix), layout.n_seg, layout.max_x_len,
+        layout.max_a_len, ptr(_f32(out, 'out')), layout.rows, d, ptr(_lib.err_flag(out.device)), _drop_ref(drop_text),
+        _drop_ref(drop_audio), stream()), 'vh_embed_nar_packed')
+    return out
+
+
+def embed_nar_packed_bwd(tokens, codes, dout, dtext_table, dcode_tables, text_vocab, code_vocab, n_rest, pe_text_rows,
+                         pe_audio_rows, layout, drop_text=None, drop_audio=None):
+    """The backward of `embed_nar_packed` in ONE launch (vh_embed_nar_packed_bwd): dout (M, d), multiplied by the regenerated
+    fields, is ADDED into dtext_table (text_vocab, d) and dcode_tables[j] (code_vocab[j], d) — fp32, zeroed or holding what
+    the sums should start from; None: skipped — at the rows the ids name, each gradient row read once for all its tables.
+    fp32 atomics, no promise of order."""
+    n = len(dcode_tables)
+    if len(code_vocab) != n:
+        raise _lib.VhError(f'embed_nar_packed_bwd: {n} gradient tables, {len(code_vocab)} row counts')
+    for t, v in zip([dtext_table, *dcode_tables], [text_vocab, *code_vocab]):
+        if t is not None and (t.dim() != 2 or t.shape[0] != v or not t.is_contiguous()):
+            raise _lib.VhError(f'embed_nar_packed_bwd: a gradient table {tuple(t.shape)} for {v} rows')
+    d, ids = _nar_packed_args('embed_nar_packed_bwd', tokens, codes, dout, dcode_tables, n_rest, layout, dout)
+    arr = (C.c_void_p * n)(*[None if t is None else ptr(_f32(t, 'table gradient')) for t in dcode_tables])
+    vocab = (C.c_int32 * n)(*[int(v) for v in code_vocab])
+    check(_lib.lib().vh_embed_nar_packed_bwd(
+        *ids, ptr(_f32(dout, 'dout')), None if dtext_table is None else ptr(_f32(dtext_table, 'table gradient')),
+        int(text_vocab), arr, vocab, n, n_rest, int(pe_text_rows), int(pe_audio_rows), ptr(layout.seg_start),
+        ptr(layout.x_len), ptr(layout.a_len), ptr(layout.prefix), layout.n_seg, layout.max_x_len, layout.max_a_len, layout.rows,
+        d, ptr(_lib.err_flag(dout.device)), _drop_ref(drop_text), _drop_ref(drop_audio), stream()), 'vh_embed_nar_packed_bwd')
+
+
 def ids_to_device(ids, device, vocab, what):
     """Token ids → `device`.  Ids still on the host are range-checked here, before they travel (the
     reference's nn.Embedding raises IndexError); device-resident ids are checked by the kernels

@@ -54,9 +54,9 @@ def train(hparams_fp: Path, model_name: str, batches=None, device=None, log=prin
     accum = max(1, config.grad_accum)
     if batches is None:
         batches = synthetic_batches(model_name, config, rank, world, config.max_steps * accum)
-    # VALLE2_TRAIN_PACKED=1 (opt-in): the AR model's steps run over packed rows, no padding (ValleAR.training_step_packed);
-    # read here, per call, like the project's other environment opt-ins
-    packed = os.environ.get('VALLE2_TRAIN_PACKED') == '1' and model_name == 'ValleAR'
+    # VALLE2_TRAIN_PACKED=1 (opt-in): the steps run over packed rows, no padding (ValleAR.training_step_packed,
+    # ValleNAR.training_step_packed); read here, per call, like the project's other environment opt-ins
+    packed = os.environ.get('VALLE2_TRAIN_PACKED') == '1' and model_name in ('ValleAR', 'ValleNAR')
     step, t0, losses = 0, time.perf_counter(), []
     optimizer.zero_grad()
     one_shot = iter(batches) is batches                  # a generator: a single epoch, then stop

@@ -216,6 +216,86 @@ class ValleNAR(_Base):
         rows = logits.shape[0] * logits.shape[1]
         return A.CrossEntropyFn.apply(logits.reshape(rows, -1), target.reshape(rows))
 
+    def training_step_packed(self, batch, **kwargs):
+        """`training_step` of a ragged batch WITHOUT its padding (extension, opt-in; `training_step` is untouched).  The same
+        collated batch; utterance b contributes the rows [tokens[b, :tokens_lens[b]] | codes[b, :codes_lens[b]]], the
+        utterances lie back to back in one (M, d) buffer, positions restart at 0 for each stream of each utterance, and every
+        utterance attends its own rows only, under the full mask (`vh_attn_rows_packed_lse` / `vh_attn_rows_bwd_packed`;
+        AdaptiveLayerNorm's scale and shift are one vector per stage, so it and every other kernel is the row-wise one over M
+        rows).  The acoustic prefix of utterance b is p_b = prefix_len_of(codes_lens[b]) — a third of ITS OWN frames, capped
+        at 3 s — where `training_step` takes it from the padded width: frames below p_b carry all Q codebooks, the rest the
+        codebooks below the stage (`vh_embed_nar_packed`, one launch; one backward launch), and the head runs over the
+        sum(codes_lens[b] - p_b) target frames only.  The loss is the mean cross entropy over those frames against
+        codes[b, p_b:codes_lens[b], stage]: the intended `training_step` on each utterance alone (B = 1, nothing padded), the
+        per-utterance losses combined token-weighted.  It differs from `training_step` on a ragged batch — that one trains
+        short utterances with the long ones' prefix length, attends padding keys (D6) and averages over padded frames — and
+        equals it when all lengths are equal and nothing is padded.  `stage=` pins the stage, drawn as in `training_step`
+        otherwise.  Dropout as in training_step, the fields keyed on the packed row.  Head width 64; under no_grad the same
+        value without a graph."""
+        cfg = self.config
+        q = cfg.num_quantizers
+        stage = kwargs.get('stage')
+        if stage is None:
+            stage = random.randint(1, q - 1)
+        if cfg.d_model != kernels.HEAD_DIM * cfg.n_heads:
+            raise ValueError(f'training_step_packed: head width {cfg.d_model // cfg.n_heads} (d_model={cfg.d_model}, '
+                             f'n_heads={cfg.n_heads}): the packed attention serves width {kernels.HEAD_DIM} only — '
+                             'training_step serves the others')
+        if isinstance(stage, bool) or not isinstance(stage, int) or not 1 <= stage <= q - 1:
+            raise ValueError(f'training_step_packed: stage={stage!r} is outside 1 .. {q - 1} (num_quantizers - 1)')
+        tokens, codes = batch['tokens'], batch['codes']
+        txs, tys = [int(v) for v in batch['tokens_lens']], [int(v) for v in batch['codes_lens']]
+        n = tokens.shape[0]
+        if len(txs) != n or len(tys) != n or codes.shape[0] != n:
+            raise ValueError(f'training_step_packed: {n} rows of tokens, {codes.shape[0]} of codes, {len(txs)} tokens_lens, '
+                             f'{len(tys)} codes_lens')
+        if tokens.dim() != 2 or codes.dim() != 3 or codes.shape[2] != q:
+            raise ValueError(f'training_step_packed: expected tokens (B, Tx) and codes (B, T, {q}), got {tuple(tokens.shape)} and '
+                             f'{tuple(codes.shape)}')
+        for what, lens, width in (('tokens_lens', txs, tokens.shape[1]), ('codes_lens', tys, codes.shape[1])):
+            bad = [v for v in lens if not 1 <= v <= width]
+            if bad:
+                raise ValueError(f'training_step_packed: {what} entry {bad[0]} is outside 1 .. {width} (the batch\'s padded width)')
+        if max(txs) > self.tokens_position_emb.pe.shape[0] or max(tys) > self.audio_position_emb.pe.shape[0]:
+            raise ValueError(f'training_step_packed: a stream of {max(txs)} text ids / {max(tys)} frames exceeds the positional table')
+        ids = {'tokens': tokens, 'codes': codes}
+        if not torch.is_grad_enabled():
+            with torch.no_grad():
+                return self._packed_loss_on_device(ids, txs, tys, stage)
+        if self.device.type != 'cuda':
+            raise _lib.VhError('ValleNAR.training_step_packed with gradients needs the model on its HIP device '
+                               '(model.to("cuda")): gradients cannot flow into a CPU copy of the parameters')
+        return self._packed_loss(ids, txs, tys, stage)
+
+    @_on_device
+    def _packed_loss_on_device(self, ids, txs, tys, stage):
+        return self._packed_loss(ids, txs, tys, stage)
+
+    def _packed_loss(self, ids, txs, tys, stage):
+        from . import autograd as A
+        from .engine import NarTrainLayout
+        dev, cfg = self.device, self.config
+        d, q = cfg.d_model, cfg.num_quantizers
+        tokens = kernels.ids_to_device(ids['tokens'], dev, cfg.vocab_size, 'tokens')
+        codes = kernels.ids_to_device(ids['codes'], dev, cfg.num_audio_tokens, 'codes (EOS/BOS have no codebook row)')
+        layout = NarTrainLayout(txs, tys, [self.prefix_len_of(t) for t in tys], codes.shape[1], dev)
+        M = layout.rows
+        # PE dropout as in training_step (live in train mode whatever config.dropout says, D9): the fields of both streams are
+        # keyed on the row of the packed buffer
+        seed = dropout.seed_if(dropout.live(self.tokens_position_emb.dropout), dropout.live(self.audio_position_emb.dropout))
+        dr_t = dropout.spec(seed, dropout.site(dropout.PE_TEXT), dropout.live(self.tokens_position_emb.dropout))
+        dr_a = dropout.spec(seed, dropout.site(dropout.PE_AUDIO), dropout.live(self.audio_position_emb.dropout))
+        dropout.record('tokens_position_emb.dropout', dr_t, M, d)
+        dropout.record('audio_position_emb.dropout', dr_a, M, d)
+        x = A.EmbedNarPackedFn.apply(tokens, codes, layout, max(1, min(stage, q)), self.tokens_position_emb.pe,
+                                     self.audio_position_emb.pe, dr_t, dr_a, self.tokens_emb.weight,
+                                     *[e.weight for e in self.codes_embs])
+        x = A.transformer_train(self.transformer, x, 1, M, dict(mode=kernels.MASK_FULL, rows=layout.packed),
+                                embedding=self.stage_embs[stage - 1].weight)
+        logits = A.linear(x.index_select(0, layout.target_rows), self.proj_layers[stage - 1].weight)
+        target = codes[:, :, stage].reshape(-1).index_select(0, layout.target_index)
+        return A.CrossEntropyFn.apply(logits, target)
+
     def configure_optimizers(self):
         """The reference's ValleNAR has no configure_optimizers; same recipe as AR."""
         from torch import optim
