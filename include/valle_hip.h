@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 144            /* 0.2.20: packed NAR training — vh_embed_nar_packed and vh_embed_nar_packed_bwd (the NAR model input over packed rows: text rows and audio rows of every segment in one launch, the codebook count changing at each segment's own prefix boundary; the backward reads every gradient row once for all its tables); nothing earlier changes; 0.2.19: packed AR training — vh_attn_rows_packed_lse (vh_attn_rows_packed with a mask mode, per-segment text lengths and lse2), vh_attn_rows_bwd_packed + vh_attn_rows_bwd_packed_ws_bytes (the five-product backward over segments); nothing earlier changes; 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 145            /* 0.2.21: packed AR prompt pass — vh_transformer_forward_packed_lm (vh_transformer_forward_packed under the prefix-LM mask of every segment, seg_x_len and a scratch lse2) and vh_kv_unpack (the K/V rows of a packed stream copied bit for bit to rows of a per-row or grouped cache, all layers and both of K and V in one launch); nothing earlier changes; 0.2.20: packed NAR training — vh_embed_nar_packed and vh_embed_nar_packed_bwd (the NAR model input over packed rows: text rows and audio rows of every segment in one launch, the codebook count changing at each segment's own prefix boundary; the backward reads every gradient row once for all its tables); nothing earlier changes; 0.2.19: packed AR training — vh_attn_rows_packed_lse (vh_attn_rows_packed with a mask mode, per-segment text lengths and lse2), vh_attn_rows_bwd_packed + vh_attn_rows_bwd_packed_ws_bytes (the five-product backward over segments); nothing earlier changes; 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -1062,6 +1062,23 @@ int vh_transformer_forward(const vh_forward_desc* desc, void* stream);
  * vh_attn_rows_packed for vh_attn_rows; the segment and block arrays are its arguments, under its contract. */
 int vh_transformer_forward_packed(const vh_forward_desc* desc, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
                                   const int32_t* blocks, int n_blocks, void* stream);
+/* vh_transformer_forward_packed under the PREFIX-LM mask (the AR prompt pass of a ragged batch): desc->mode = VH_MASK_PREFIX,
+ * segment s attends under the prefix mask of its own text length seg_x_len[s] (clamped to 0 .. seg_len[s]) — the attention is
+ * vh_attn_rows_packed_lse, so the caller lends lse2, (n_heads, T) floats it need not read.  fp32, head width 64, LayerNorm
+ * (desc->ada NULL); B != 1 and bad dimensions are VH_EINVAL, another mode, the mask fields, ada or another head width
+ * VH_EUNSUPPORTED, a misaligned q / attn / lse2 / cache VH_EALIGN — all before any launch. */
+int vh_transformer_forward_packed_lm(const vh_forward_desc* desc, const int32_t* seg_start, const int32_t* seg_len,
+                                     const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks, float* lse2,
+                                     void* stream);
+/* The K/V rows of packed streams to the rows of a cache: src (n_streams, n_heads, S_src, 64) fp32 — n_streams = layers x 2,
+ * what a packed forward wrote — dst (n_streams, B_dst, n_heads, S_dst, 64) fp32.  Rows seg_start[s] .. + seg_len[s] - 1 of
+ * every (stream, head) go to positions 0 .. seg_len[s] - 1 of row dst_row[s], bit for bit (16-byte loads and stores); nothing
+ * else of dst is written.  seg_start / seg_len / dst_row: device int32 (n_seg).  A segment reaching past S_src is cut there, a
+ * length beyond S_dst is cut there, a segment that starts outside [0, S_src) or names a row outside [0, B_dst) writes nothing.
+ * Refused before the launch: null pointers, non-positive dimensions or n_seg (VH_EINVAL), src / dst not 16-byte aligned
+ * (VH_EALIGN), n_seg > 65535 or more than 2^26 rows per stream (VH_EUNSUPPORTED). */
+int vh_kv_unpack(const float* src, float* dst, int n_streams, int n_heads, int S_src, int B_dst, int S_dst,
+                 const int32_t* seg_start, const int32_t* seg_len, const int32_t* dst_row, int n_seg, void* stream);
 
 /* ---- perf mode of the MFMA-bound legs: bf16 operands, fp32 accumulate (opt-in; never the parity path) ------------
  * SURVEY.md section 7's "perf mode" for the prompt pass (valle/models/valle_ar.py:141-158 at kv_cache=None) and the NAR

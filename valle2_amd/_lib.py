@@ -314,6 +314,11 @@ SIGNATURES = {
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
                                           c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p,
                                           c_dropp, c_dropp, C.c_void_p]),
+    # packed AR prompt pass: the prefix-LM composite over segments and the K/V rows back to per-row caches (ABI 145)
+    'vh_transformer_forward_packed_lm': (C.c_int, [C.POINTER(VhForwardDesc), c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int,
+                                                   c_f32p, C.c_void_p]),
+    'vh_kv_unpack': (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, C.c_int,
+                               C.c_void_p]),
 }
 
 _lib = None

@@ -1418,3 +1418,63 @@ extern "C" int vh_decode_group_reset(int64_t* codes, int64_t codes_stride, int c
     VH_CHECK_LAUNCH("vh_decode_group_reset");
     return VH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// vh_kv_unpack: the K/V rows a packed forward left in ONE (1, h, S_src, 64) stream per (layer, K|V) go to the per-row caches
+// the decoder reads, all layers and both of K and V in one launch.  Segment s of a (stream, head) is one contiguous run of
+// seg_len[s] x 256 bytes on both sides, so the whole kernel is n_streams x h x n_seg straight copies: workgroup (x = stream x
+// head, y = segment, z) takes the 64-row pieces z, z + gridDim.z, ... of its run, a thread four 16-byte loads in flight and
+// then their four stores (16 KiB per workgroup per trip, consecutive lanes on consecutive 16 bytes).  Plain loads and stores:
+// the rows are read again by the first decode steps, and whether a non-temporal form helps has not been measured.
+// Guards as in attn_rows_packed_kernel (workgroup-uniform): a segment that starts outside the stream or names a row outside
+// [0, B_dst) copies nothing; one that reaches past S_src, or is longer than S_dst, is cut there.
+// ---------------------------------------------------------------------------------------------
+#define KVU_ROWS 64                  // rows per workgroup trip: 256 threads x 4 float4 = 64 rows of 64 floats
+__global__ __launch_bounds__(256) void kv_unpack_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                        const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_len,
+                                                        const int32_t* __restrict__ dst_row, int n_heads, int S_src, int B_dst,
+                                                        int S_dst) {
+    const int sh = blockIdx.x, strm = sh / n_heads, head = sh - strm * n_heads;
+    const int s = blockIdx.y;
+    const int s0 = seg_start[s], row = dst_row[s];
+    if (s0 < 0 || s0 >= S_src || row < 0 || row >= B_dst) return;
+    const int len = min(min(seg_len[s], S_src - s0), S_dst);
+    if (len <= 0) return;
+    const float* from = src + ((int64_t)sh * S_src + s0) * VH_HEAD_DIM;
+    float* to = dst + (((int64_t)strm * B_dst + row) * n_heads + head) * (int64_t)S_dst * VH_HEAD_DIM;
+    const int n4 = len * (VH_HEAD_DIM / 4);                       // float4s of the run (S_dst x 16 < 2^31: checked by the host)
+    for (int i0 = blockIdx.z * (KVU_ROWS * 16) + threadIdx.x; i0 < n4; i0 += gridDim.z * (KVU_ROWS * 16)) {
+        f32x4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (i0 + 256 * j < n4) v[j] = ld4(from + 4 * (int64_t)(i0 + 256 * j));
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (i0 + 256 * j < n4) st4(to + 4 * (int64_t)(i0 + 256 * j), v[j]);
+    }
+}
+
+extern "C" int vh_kv_unpack(const float* src, float* dst, int n_streams, int n_heads, int S_src, int B_dst, int S_dst,
+                            const int32_t* seg_start, const int32_t* seg_len, const int32_t* dst_row, int n_seg, void* stream) {
+    VH_REQUIRE(src && dst, VH_EINVAL, "vh_kv_unpack: null pointer (src or dst)");
+    VH_REQUIRE(seg_start && seg_len && dst_row, VH_EINVAL, "vh_kv_unpack: null pointer (seg_start, seg_len or dst_row)");
+    VH_REQUIRE(n_streams > 0 && n_heads > 0 && S_src > 0 && B_dst > 0 && S_dst > 0, VH_EINVAL,
+               "vh_kv_unpack: bad dims n_streams=%d n_heads=%d S_src=%d B_dst=%d S_dst=%d", n_streams, n_heads, S_src, B_dst, S_dst);
+    VH_REQUIRE(n_seg > 0, VH_EINVAL, "vh_kv_unpack: n_seg=%d", n_seg);
+    VH_REQUIRE(vh_aligned16(src) && vh_aligned16(dst), VH_EALIGN, "vh_kv_unpack: src and dst must be 16-byte aligned");
+    VH_REQUIRE(((reinterpret_cast<uintptr_t>(seg_start) | reinterpret_cast<uintptr_t>(seg_len) | reinterpret_cast<uintptr_t>(dst_row)) & 3u) == 0,
+               VH_EALIGN, "vh_kv_unpack: seg_start, seg_len and dst_row must be 4-byte aligned");
+    VH_REQUIRE((int64_t)n_streams * n_heads <= 0x7fffffffLL && n_seg <= 65535, VH_EUNSUPPORTED,
+               "vh_kv_unpack: n_streams=%d x n_heads=%d, n_seg=%d workgroups (x <= 2^31 - 1, y <= 65535)", n_streams, n_heads, n_seg);
+    VH_REQUIRE(S_src <= (1 << 26) && S_dst <= (1 << 26), VH_EUNSUPPORTED, "vh_kv_unpack: S_src=%d S_dst=%d (at most 2^26 rows per stream)",
+               S_src, S_dst);
+    // pieces of a run share the segment's workgroups over z until the launch has ~2048 workgroups (8 per CU) or a workgroup per
+    // 64 rows of the longest possible run
+    const int64_t runs = (int64_t)n_streams * n_heads * n_seg;
+    const int trips = (min(S_src, S_dst) + KVU_ROWS - 1) / KVU_ROWS;
+    const int gz = (int)max((int64_t)1, min((int64_t)min(trips, 64), (2048 + runs - 1) / runs));
+    hipLaunchKernelGGL(kv_unpack_kernel, dim3(n_streams * n_heads, n_seg, gz), dim3(256), 0, (hipStream_t)stream, src, dst, seg_start,
+                       seg_len, dst_row, n_heads, S_src, B_dst, S_dst);
+    VH_CHECK_LAUNCH("vh_kv_unpack");
+    return VH_OK;
+}

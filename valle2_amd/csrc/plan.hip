@@ -433,10 +433,13 @@ extern "C" int vh_ar_decoder_profile_attn(vh_ar_decoder* dec, int n_steps, void*
 // ---------------------------------------------------------------------------------------------
 // full-sequence forward (prefill / NAR stage / training forward)
 // ---------------------------------------------------------------------------------------------
-// the segments of a packed forward (vh_transformer_forward_packed); null: the padded (B, T) layout
+// the segments of a packed forward (vh_transformer_forward_packed); null: the padded (B, T) layout.  seg_x_len set: the
+// prefix-LM form (vh_transformer_forward_packed_lm), each segment's text length and the lse2 rows its attention kernel writes
 struct packed_rows {
     const int32_t *seg_start, *seg_len, *blocks;
     int n_seg, n_blocks;
+    const int32_t* seg_x_len;
+    float* lse2;
 };
 
 // the layers of both forwards: the same launches in the same order, the packed one with vh_attn_rows_packed for vh_attn_rows
@@ -450,7 +453,11 @@ static int forward_layers(const vh_forward_desc* f, const packed_rows* pk, void*
                          stream));
         TRY(vh_linear_qkv(f->xn, D, L.wqkv, f->q, D, L.kcache, L.vcache, nullptr, B, T, D, f->n_heads,
                           f->S_max, nullptr, nullptr, nullptr, nullptr, 0.f, stream));
-        if (pk)
+        if (pk && pk->seg_x_len)
+            TRY(vh_attn_rows_packed_lse(f->q, D, L.kcache, L.vcache, f->attn, D, f->n_heads, T, f->S_max, VH_MASK_PREFIX,
+                                        pk->seg_start, pk->seg_len, pk->seg_x_len, pk->n_seg, pk->blocks, pk->n_blocks, pk->lse2,
+                                        stream));
+        else if (pk)
             TRY(vh_attn_rows_packed(f->q, D, L.kcache, L.vcache, f->attn, D, f->n_heads, f->S_max, pk->seg_start, pk->seg_len,
                                     pk->n_seg, pk->blocks, pk->n_blocks, stream));
         else
@@ -508,6 +515,48 @@ extern "C" int vh_transformer_forward_packed(const vh_forward_desc* f, const int
         VH_REQUIRE(vh_aligned16(f->layers[i].kcache) && vh_aligned16(f->layers[i].vcache), VH_EALIGN,
                    "vh_transformer_forward_packed: kcache and vcache must be 16-byte aligned (layer %d)", i);
     }
-    const packed_rows pk{seg_start, seg_len, blocks, n_seg, n_blocks};
+    const packed_rows pk{seg_start, seg_len, blocks, n_seg, n_blocks, nullptr, nullptr};
+    return forward_layers(f, &pk, stream);
+}
+
+// The prompt pass of a ragged batch over packed rows: vh_transformer_forward_packed's launches under the prefix-LM mask of
+// every segment.  The attention is the packed TRAINING forward (attn_rows_packed_lse_kernel: attn_rows_body.inc takes the mask
+// mode and seg_x_len only in the instantiation that also writes lse2), so the caller lends an (n_heads, T) lse2 it never reads.
+extern "C" int vh_transformer_forward_packed_lm(const vh_forward_desc* f, const int32_t* seg_start, const int32_t* seg_len,
+                                                const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks,
+                                                float* lse2, void* stream) {
+    VH_REQUIRE(f && f->layers && f->x && f->xn && f->q && f->attn && f->hidden, VH_EINVAL,
+               "vh_transformer_forward_packed_lm: null pointer in desc");
+    VH_REQUIRE(seg_start && seg_len && seg_x_len && blocks, VH_EINVAL,
+               "vh_transformer_forward_packed_lm: null pointer (seg_start, seg_len, seg_x_len or blocks)");
+    VH_REQUIRE(lse2, VH_EINVAL, "vh_transformer_forward_packed_lm: null pointer (lse2: (n_heads, T) floats of scratch)");
+    VH_REQUIRE(f->B == 1, VH_EINVAL, "vh_transformer_forward_packed_lm: B=%d (the packed rows are ONE row stream: B = 1, T = the "
+               "sum of the segment lengths)", f->B);
+    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "vh_transformer_forward_packed_lm: bad dims T=%d L=%d", f->T, f->n_layers);
+    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "vh_transformer_forward_packed_lm: S_max=%d < T=%d", f->S_max, f->T);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_transformer_forward_packed_lm: n_seg=%d", n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_transformer_forward_packed_lm: n_blocks=%d", n_blocks);
+    VH_REQUIRE(f->mode == VH_MASK_PREFIX, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed_lm: mode=%d (segments attend under their prefix-LM masks: VH_MASK_PREFIX)", f->mode);
+    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: kv_len is set (a segment's length is its key length)");
+    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: x_len_dev is set (the text lengths are seg_x_len)");
+    VH_REQUIRE(!f->mask, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: mask is set (no explicit mask over segments)");
+    VH_REQUIRE(!f->pad, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: pad is set (packed rows have no padding)");
+    VH_REQUIRE(!f->ada, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: ada is set (LayerNorm stacks only)");
+    VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed_lm: d_model=%d != n_heads=%d x 64", f->d_model, f->n_heads);
+    // what vh_attn_rows_packed_lse would refuse inside layer 0, said before anything is launched
+    VH_REQUIRE(vh_aligned16(f->q), VH_EALIGN, "vh_transformer_forward_packed_lm: q must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(f->attn), VH_EALIGN, "vh_transformer_forward_packed_lm: attn must be 16-byte aligned");
+    VH_REQUIRE((reinterpret_cast<uintptr_t>(lse2) & 3u) == 0, VH_EALIGN, "vh_transformer_forward_packed_lm: lse2 must be 4-byte aligned");
+    VH_REQUIRE((int64_t)n_blocks * f->n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed_lm: n_blocks=%d x n_heads=%d workgroups", n_blocks, f->n_heads);
+    for (int i = 0; i < f->n_layers; ++i) {
+        VH_REQUIRE(f->layers[i].kcache && f->layers[i].vcache, VH_EINVAL,
+                   "vh_transformer_forward_packed_lm: null kcache / vcache (layer %d)", i);
+        VH_REQUIRE(vh_aligned16(f->layers[i].kcache) && vh_aligned16(f->layers[i].vcache), VH_EALIGN,
+                   "vh_transformer_forward_packed_lm: kcache and vcache must be 16-byte aligned (layer %d)", i);
+    }
+    const packed_rows pk{seg_start, seg_len, blocks, n_seg, n_blocks, seg_x_len, lse2};
     return forward_layers(f, &pk, stream);
 }

@@ -73,6 +73,17 @@ class KVCache:
         view.n_layers, view.batch, view.n_heads, view.s_max, view.head_dim = self.n_layers, 1, self.n_heads, self.s_max, self.head_dim
         return view
 
+    def unpack_into(self, dst: 'KVCache', seg_start, seg_len, dst_row):
+        """The rows a packed forward left in this ONE-ROW cache, to rows of `dst` (a row cache or a grouped prefix cache of the
+        same layers and heads): rows seg_start[s] .. + seg_len[s] - 1 of every (layer, K|V, head) go to positions 0 ..
+        seg_len[s] - 1 of dst's row dst_row[s], in one launch and bit for bit (`kernels.kv_unpack`); the tables are device
+        int32 tensors of one entry per segment.  Nothing else of dst is written."""
+        if self.batch != 1 or self.bf16 or dst.bf16 or self.head_dim != HEAD_DIM or \
+                (dst.n_layers, dst.n_heads, dst.head_dim) != (self.n_layers, self.n_heads, self.head_dim):
+            raise _lib.VhError('KVCache.unpack_into: a one-row fp32 width-64 cache into an fp32 cache of the same layers and heads')
+        kernels.kv_unpack(self.buf, dst.buf, seg_start, seg_len, dst_row)
+        return dst
+
     def k(self, i):
         return self.buf[i, 0]
 
@@ -652,6 +663,63 @@ def transformer_forward_packed(transformer, x, cache: KVCache, rows: PackedRows,
     check(_lib.lib().vh_transformer_forward_packed(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg,
                                                    ptr(rows.blocks), rows.n_blocks, stream()),
           'vh_transformer_forward_packed')
+    return x
+
+
+class PromptRows:
+    """The packed layout of a ragged AR prompt pass (generation.prompt_pass), uploaded in ONE copy: utterance g's rows
+    [txs[g] text | pls[g] BOS + prompt] lie back to back as `pack_plan` lays them out.  It stands for a `PackedRows` with text
+    lengths (what `transformer_forward_packed_lm` takes) and for the segment tables of `kernels.embed_nar_packed` (x_len, a_len,
+    prefix = 0: one codebook everywhere), and carries dst_row (the cache row each segment's K/V go to, `KVCache.unpack_into`)
+    and last_rows (the packed row of each utterance's last position: where decoding starts from)."""
+
+    def __init__(self, txs, pls, dst_rows, device):
+        self.x_lens, a_lens, dst_rows = [int(t) for t in txs], [int(p) for p in pls], [int(r) for r in dst_rows]
+        if not self.x_lens or len(a_lens) != len(self.x_lens) or len(dst_rows) != len(self.x_lens) or min(self.x_lens) < 0 or min(a_lens) < 1:
+            raise ValueError('PromptRows: one text length >= 0, one BOS + prompt length >= 1 and one cache row per utterance')
+        self.lengths = [t + p for t, p in zip(self.x_lens, a_lens)]
+        self.starts, self.rows, blocks = pack_plan(self.lengths)
+        n = self.n_seg = len(self.lengths)
+        self.n_blocks = len(blocks)
+        self.max_x_len, self.max_a_len = max(self.x_lens), max(a_lens)
+        table = [self.starts, self.lengths, self.x_lens, a_lens, [0] * n, dst_rows,
+                 [s + c - 1 for s, c in zip(self.starts, self.lengths)]]
+        dev = _lib.to_device_async(torch.tensor([v for row in table for v in row] + [v for b in blocks for v in b],
+                                                dtype=torch.int32), device)
+        (self.seg_start, self.seg_len, self.seg_x_len, self.a_len, self.prefix, self.dst_row,
+         self.last_rows) = (dev[i * n:(i + 1) * n] for i in range(7))
+        self.x_len = self.seg_x_len
+        self.blocks = dev[7 * n:].view(-1, 2)
+
+
+def transformer_forward_packed_lm(transformer, x, cache: KVCache, rows, scratch=None, lse2=None):
+    """`transformer_forward(mode=MASK_PREFIX)` of a ragged batch over PACKED rows, forward only: x (M, d) holds utterance b at
+    rows rows.starts[b] .. + rows.lengths[b] - 1 and is updated in place; each utterance attends its own rows only, under the
+    prefix-LM mask of its own text length rows.x_lens[b] (the packed training forward's kernel, `vh_attn_rows_packed_lse`: it
+    writes the (n_heads, M) `lse2`, scratch nobody reads here); every other launch is the row-wise one over M rows.  `rows`: a
+    `PackedRows` built with x_lens, or a `PromptRows`.  `cache`: a one-row fp32 KVCache of s_max >= M; each layer's K/V land at
+    the packed rows (`KVCache.unpack_into` moves them to per-row caches).  fp32, head width 64, LayerNorm.  Returns x."""
+    cfg = transformer.hparams
+    if x.dim() != 2:
+        raise _lib.VhError(f'transformer_forward_packed_lm: x must be (M, d), got {tuple(x.shape)}')
+    M, d = x.shape
+    if d != cfg.n_heads * HEAD_DIM:
+        raise _lib.VhError(f'transformer_forward_packed_lm: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
+    if cfg.norm != 'LayerNorm':
+        raise _lib.VhError(f'transformer_forward_packed_lm: norm={cfg.norm!r} (LayerNorm stacks only)')
+    if M != rows.rows:
+        raise _lib.VhError(f'transformer_forward_packed_lm: x has {M} rows, the packed rows {rows.rows}')
+    if rows.seg_x_len is None:
+        raise _lib.VhError('transformer_forward_packed_lm: the prefix mask needs PackedRows(lengths, device, x_lens)')
+    if lse2 is None:
+        lse2 = torch.empty(cfg.n_heads, M, device=x.device, dtype=torch.float32)
+    elif tuple(lse2.shape) != (cfg.n_heads, M) or lse2.dtype != torch.float32 or not lse2.is_contiguous():
+        raise _lib.VhError('transformer_forward_packed_lm: lse2 must be contiguous float32 (n_heads, M)')
+    scratch, common = _forward_front(transformer, x, 1, M, cache, None, scratch, bf16=False)
+    desc = VhForwardDesc(mode=kernels.MASK_PREFIX, x_len=0, **_fp32_scratch_fields(scratch), **common)
+    check(_lib.lib().vh_transformer_forward_packed_lm(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), ptr(rows.seg_x_len),
+                                                      rows.n_seg, ptr(rows.blocks), rows.n_blocks, ptr(lse2), stream()),
+          'vh_transformer_forward_packed_lm')
     return x
 
 

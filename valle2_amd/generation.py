@@ -12,9 +12,9 @@ import torch
 
 from . import _lib, kernels
 from . import sampling as _sampling
-from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, QueueSchedule, StepSampler,
+from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, PromptRows, QueueSchedule, StepSampler,
                      cached_decode_supported, ffn_fused_width, group_prefix_cap, grouped_prompts_fit, perf_forward_supported,
-                     queue_steps_cap, transformer_forward, transformer_forward_bf16)
+                     queue_steps_cap, transformer_forward, transformer_forward_bf16, transformer_forward_packed_lm)
 from .utils import get_best_beam
 
 EOS_POLL = 32
@@ -249,6 +249,7 @@ class DecodeState:
         self.row_sampling = None                                          # (B, 32) uint8: vh_row_sampling records of a call with Sampling
         self.row_limits = None                                            # (B, 8) uint8 beside them when a request carries a bound: vh_row_limits (zeros: none)
         self.cache = self.prefix = self.dec = None
+        self.prompt_rows = (False, 0)                                     # the last prompt pass: (packed, rows it computed)
         self.reused = self.busy = False
         self.uses = 0
 
@@ -377,16 +378,79 @@ def best_beam_tokens(model, rows, sum_logprobs, prompt_len):
 
 
 # ---- the prompt pass and the decode loops -----------------------------------------------------------------------------------
-def prompt_pass(model, plan, state, texts, first_codes):
+def packed_prompt_on(model):
+    """The switch of the packed prompt pass: `model.packed_prompt` (ValleAR's class attribute; True / False), or, while that
+    is None, VALLE2_PACKED_PROMPT=1 in the environment of the call."""
+    switch = getattr(model, 'packed_prompt', None)
+    return os.environ.get('VALLE2_PACKED_PROMPT', '0') == '1' if switch is None else bool(switch)
+
+
+def packed_prompt_qualifies(kind, perf_mode, head_dim, forced, ragged, no_cache=False):
+    """Whether a call's prompt pass may run over packed rows (pure: no model, no device): utterances of different lengths
+    (equal ones have no padding to drop), the fp32 parity path, head width 64, cached decoding on rows or grouped prefixes of
+    their own (SHARED has a single row) and no teacher forcing.  Every other call runs the padded pass."""
+    return bool(ragged) and not perf_mode and head_dim == kernels.HEAD_DIM and not no_cache and not forced and kind in (ROWS, GROUPED)
+
+
+def _write_prompts(codes, first_codes, n):
+    """codes[g * n:(g + 1) * n, 1:1 + len(first_codes[g])] = first_codes[g] for every utterance in one scatter (the padded pass
+    writes them utterance by utterance)."""
+    lens = torch.tensor([int(c.shape[0]) for c in first_codes], dtype=torch.int64)
+    total = int(lens.sum())
+    if total == 0:
+        return
+    g = torch.repeat_interleave(torch.arange(len(first_codes)), lens)
+    t = torch.arange(total) - torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens)
+    dest = (g * n * codes.shape[1] + 1 + t).unsqueeze(0) + (torch.arange(n) * codes.shape[1]).unsqueeze(1)
+    codes.view(-1).index_copy_(0, _lib.to_device_async(dest.reshape(-1), codes.device), torch.cat(first_codes).repeat(n))
+
+
+def packed_pass(model, texts, txs, pls, codes, into, dst_rows):
+    """The prompt pass of several utterances over PACKED rows: one embed launch (`vh_embed_nar_packed` with one codebook: text
+    rows, then BOS + prompt rows, positions restarting per stream), one packed prefix-LM forward into a transient one-row
+    cache of sum(ctx) rows and one `vh_kv_unpack` into rows `dst_rows` of `into` (a row cache or a grouped prefix cache).
+    codes (G, >= max(pls)): row g holds BOS + prompt g.  Returns the (G, d) hidden rows of the utterances' last positions."""
+    cfg, dev, d = model.config, model.device, model.config.d_model
+    rows = PromptRows(txs, pls, dst_rows, dev)
+    G, width = rows.n_seg, max(rows.max_x_len, 1)
+    flat = torch.cat(texts)
+    if flat.numel():
+        # the text ids as the (G, longest text) rows the embed kernel indexes: one gather of the concatenated ids
+        lens = torch.tensor(rows.x_lens, dtype=torch.int64)
+        idx = (torch.cumsum(lens, 0) - lens).unsqueeze(1) + torch.minimum(torch.arange(width).unsqueeze(0), (lens - 1).clamp(min=0).unsqueeze(1))
+        tokens = flat.index_select(0, _lib.to_device_async(idx.clamp(max=flat.numel() - 1).reshape(-1), dev)).view(G, width)
+    else:
+        tokens = torch.zeros(G, width, device=dev, dtype=torch.int64)
+    x = torch.empty(rows.rows, d, device=dev, dtype=torch.float32)
+    kernels.embed_nar_packed(tokens, codes.unsqueeze(-1), model.tokens_emb.weight.detach(), [model.audio_emb.weight.detach()], 1,
+                             model.tokens_position_emb.pe, model.audio_position_emb.pe, rows, x)
+    stream_cache = KVCache(cfg.num_layers, 1, cfg.n_heads, rows.rows, dev)
+    transformer_forward_packed_lm(model.transformer, x, stream_cache, rows,
+                                  scratch=ForwardScratch(rows.rows, d, cfg.dim_feedforward, dev))
+    stream_cache.unpack_into(into, rows.seg_start, rows.seg_len, rows.dst_row)
+    return x.index_select(0, rows.last_rows)
+
+
+def prompt_pass(model, plan, state, texts, first_codes, forced=False):
     """Step 0 (valle_ar.py:143-155 at kv_cache=None): embed and run the whole prompt into the armed state's caches.  Row b is
     laid out [text_b | BOS + prompt_b | padding]; the prefix-LM mask takes per-row lengths.  Returns the last hidden row of
     every decode row, the length arguments of the pass and the stacked text ids of equal-length rows (the recompute steps
-    run the same pass again)."""
+    run the same pass again).  With the packed switch on (`packed_prompt_on`) a call that qualifies
+    (`packed_prompt_qualifies`) runs `packed_pass` instead: no padding row is computed; `state.prompt_rows` says which."""
     cfg, dev, d = model.config, model.device, model.config.d_model
     B, s0, n, codes = plan.B, plan.s0, plan.beams, state.codes
     i32 = dict(device=dev, dtype=torch.int32)
     rows = 1 if plan.kind == SHARED else plan.G
     text_ids = None
+    state.prompt_rows = (False, rows * s0)
+    if packed_prompt_on(model) and packed_prompt_qualifies(plan.kind, plan.perf_mode, d // cfg.n_heads, forced, plan.ragged, plan.no_cache):
+        _write_prompts(codes, first_codes, n)
+        last = packed_pass(model, texts, plan.txs, plan.pls, codes[:plan.G * n:n], state.cache if state.prefix is None else state.prefix,
+                           range(plan.G))
+        state.prompt_rows = (True, sum(plan.ctx))
+        if plan.kind == GROUPED:
+            last = last.repeat_interleave(n, 0)       # every beam starts from its utterance's last hidden row
+        return last.contiguous(), {}, None
     if not plan.ragged:
         text_ids = torch.stack(texts[:rows])
         codes[:, 1:plan.pl_max] = torch.stack(first_codes).repeat_interleave(n, 0) if plan.kind == GROUPED else torch.stack(first_codes)
@@ -516,6 +580,9 @@ def _generate_in_groups(model, texts, first_codes, max_new, use_graph, perf_mode
     merged['groups'] = sum(st['groups'] for st in stats)
     merged['repetition_aware'] = any(st['repetition_aware'] for st in stats)
     merged['bounded'] = any(st['bounded'] for st in stats)
+    merged['packed_prompt'] = any(st['packed_prompt'] for st in stats)
+    merged['prompt_rows'] = sum(st['prompt_rows'] for st in stats)
+    merged['padded_prompt_rows'] = sum(st['padded_prompt_rows'] for st in stats)
     model.last_generate_stats = merged
     return out
 
@@ -568,7 +635,7 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
             raise ValueError('shared_prompt: every row must carry the same text and prompt ids')
         seed = state.arm(model, plan, sampling)
         t_host1 = time.perf_counter()
-        last, fwd, text_ids = prompt_pass(model, plan, state, texts, first_codes)
+        last, fwd, text_ids = prompt_pass(model, plan, state, texts, first_codes, forced=forced is not None)
         t_host2 = time.perf_counter()
         dec = state.decoder(model, plan, seed)
         dec.capture()                                 # (a no-op without a graph: the no-cache path only borrows the sampler)
@@ -610,7 +677,10 @@ def generate_batch(model, texts, first_codes, max_new, use_graph, profile_attn, 
             # has finished
             'decoder_reused': state.reused, 'slot_uses': state.uses if state.busy else 0,
             'host_setup_ms': (t_host1 - t_host0) * 1e3, 'host_decoder_ms': (t_host3 - t_host2) * 1e3,
-            'kv_cache': not plan.no_cache}
+            'kv_cache': not plan.no_cache,
+            # the prompt pass: over packed rows or padded ones, the rows it computed and the rows the padded pass computes
+            'packed_prompt': state.prompt_rows[0], 'prompt_rows': state.prompt_rows[1],
+            'padded_prompt_rows': (1 if plan.kind == SHARED else G) * plan.s0}
         out_codes = state.codes[:, : plan.pl_max + n_new].clone()
         stats['host_tail_ms'] = (time.perf_counter() - t_host4) * 1e3
         stats['host_outside_ms'] = stats['host_setup_ms'] + stats['host_decoder_ms'] + stats['host_tail_ms']
@@ -679,6 +749,37 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
         live_cl, live_ap = 0, plan.pl_max + 1                              # the fresh rows the first sample leaves
         gap_s, t_gap = 0.0, None
         p = 0
+        # the packed switch: a poll's refills wait until all its groups are re-armed and, two or more, run as one packed pass
+        pack_refills = packed_prompt_on(model)
+        refills, packed_refills = [], 0
+
+        def refill_pass(g, nxt):
+            """The one-row prompt pass of utterance nxt into group g's region of the prefix cache; its last hidden row (1, d)."""
+            nonlocal scratch
+            x = torch.empty(1, ctx[nxt], d, device=dev, dtype=torch.float32)
+            model._embed_rows(texts[nxt].unsqueeze(0), codes[g * beams:g * beams + 1, :pls[nxt]], x)
+            if scratch is None:
+                scratch = ForwardScratch(max(ctx), d, cfg.dim_feedforward, dev)
+            transformer_forward(model.transformer, x, prefix.group_view(g), mode=kernels.MASK_PREFIX,
+                                scratch=scratch.fit(ctx[nxt]), x_len=txs[nxt])
+            return x[:, -1]
+
+        def first_sample(g, nxt, last):
+            """Group g's rows take utterance nxt's records and draw its first token from its last prompt row (1, d)."""
+            nonlocal live_cl, live_ap
+            rows = slice(g * beams, (g + 1) * beams)
+            if waiting is not None:
+                # the group's rows take the new utterance's seed, keys 0 .. beams - 1 and filter: a stream-ordered write
+                # between replays (the captured steps hold the pointer), before the first sample reads them; its length
+                # bounds travel with them
+                state.row_sampling[rows].copy_(waiting[(nxt - slots) * beams:(nxt - slots + 1) * beams])
+                if waiting_limits is not None:
+                    state.row_limits[rows].copy_(waiting_limits[(nxt - slots) * beams:(nxt - slots + 1) * beams])
+            # (first_len stands in for cache_len: the first sample appends no K/V row, and vh_decode_group_reset left
+            # cache_len where the first step appends)
+            dec.sample_from(last.expand(beams, d).contiguous(), rows, state.first_len)
+            live_cl, live_ap = max(live_cl, 0), max(live_ap, pls[nxt] + 1)
+
         while not sched.finished:
             # the rows that step on stand at most here; every other row was re-armed or rewound to a fresh row below
             if live_cl + poll > s_suf or live_ap + poll > width:
@@ -729,29 +830,32 @@ def generate_queued(model, utterances, beams, slots, use_graph=True):
                 # refill: re-arm the rows, one-row prompt pass into the group's region of the prefix cache, first sample
                 kernels.decode_group_reset(codes, g, beams, firsts[nxt], ctx[nxt], model.bos_token, model.eos_token, cache_len,
                                            audio_pos, pos_base, dec.sum_logprobs, group_len)
-                x = torch.empty(1, ctx[nxt], d, device=dev, dtype=torch.float32)
-                model._embed_rows(texts[nxt].unsqueeze(0), codes[g * beams:g * beams + 1, :pls[nxt]], x)
-                if scratch is None:
-                    scratch = ForwardScratch(max(ctx), d, cfg.dim_feedforward, dev)
-                transformer_forward(model.transformer, x, prefix.group_view(g), mode=kernels.MASK_PREFIX,
-                                    scratch=scratch.fit(ctx[nxt]), x_len=txs[nxt])
-                if waiting is not None:
-                    # the group's rows take the new utterance's seed, keys 0 .. beams - 1 and filter: a stream-ordered write
-                    # between replays (the captured steps hold the pointer), before the first sample reads them; its length
-                    # bounds travel with them
-                    state.row_sampling[rows].copy_(waiting[(nxt - slots) * beams:(nxt - slots + 1) * beams])
-                    if waiting_limits is not None:
-                        state.row_limits[rows].copy_(waiting_limits[(nxt - slots) * beams:(nxt - slots + 1) * beams])
-                # (first_len stands in for cache_len: the first sample appends no K/V row, and vh_decode_group_reset left
-                # cache_len where the first step appends)
-                dec.sample_from(x[:, -1].expand(beams, d).contiguous(), rows, state.first_len)
-                live_cl, live_ap = max(live_cl, 0), max(live_ap, pls[nxt] + 1)
+                if pack_refills:
+                    refills.append((g, nxt))              # (their passes run together once every group of the poll is re-armed)
+                else:
+                    first_sample(g, nxt, refill_pass(g, nxt))
+            if len(refills) >= 2:
+                # the refills of this poll as ONE packed pass: the groups' prompt rows back to back, their K/V unpacked into
+                # the groups' regions of the prefix cache
+                gs = [g for g, _ in refills]
+                head_rows = _lib.to_device_async(torch.tensor([g * beams for g in gs], dtype=torch.int64), dev)
+                lasts = packed_pass(model, [texts[u] for _, u in refills], [txs[u] for _, u in refills], [pls[u] for _, u in refills],
+                                    codes.index_select(0, head_rows)[:, :max(pls[u] for _, u in refills)], prefix, gs)
+                packed_refills += len(refills)
+                for i, (g, nxt) in enumerate(refills):
+                    first_sample(g, nxt, lasts[i:i + 1])
+            elif refills:
+                first_sample(*refills[0], refill_pass(*refills[0]))
+            refills.clear()
         done_mark = torch.cuda.Event(enable_timing=True)
         done_mark.record()
         done_mark.synchronize()
         _lib.raise_device_errors(dev)
         model.last_generate_stats = {
             'queued': True, 'slots': slots, 'beams': beams, 'groups': n, 'refills': sched.refills, 'polls': polls,
+            # the starting prompt pass (packed or padded, and the rows it computed) and the refills that ran in packed passes
+            'packed_prompt': state.prompt_rows[0], 'prompt_rows': state.prompt_rows[1], 'padded_prompt_rows': slots * plan.s0,
+            'packed_refills': packed_refills,
             'steps': steps, 'parked_group_steps': parked_steps, 'max_cache_len': max_cl, 'max_audio_pos': max_ap,
             's_suf': s_suf, 'codes_width': width, 'prefix_cap': cap, 'intervals': sched.intervals(),
             'sum_logprobs': torch.cat([saved[u][1] for u in range(n)]), 'prompt_lens': [pl for pl in pls for _ in range(beams)],

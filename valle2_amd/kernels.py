@@ -591,6 +591,35 @@ def kv_store(qkv, kcache, vcache, B, T):
     return kcache, vcache
 
 
+def kv_unpack(src, dst, seg_start, seg_len, dst_row):
+    """The K/V rows a packed forward wrote, to the rows of a cache, all layers and both of K and V in ONE launch (vh_kv_unpack;
+    a bit-exact copy).  src (..., h, S_src, 64) and dst (..., B_dst, h, S_dst, 64): contiguous fp32 with the same leading
+    streams (a one-row `KVCache.buf` (L, 2, 1, h, S_src, 64) and a cache's (L, 2, B_dst, h, S_dst, 64)).  seg_start / seg_len /
+    dst_row: device int32 (n_seg) — rows seg_start[s] .. + seg_len[s] - 1 of every (stream, head) go to positions 0 ..
+    seg_len[s] - 1 of row dst_row[s]; nothing else of dst is written.  A segment past S_src or longer than S_dst is cut there, a
+    row outside [0, B_dst) writes nothing."""
+    if src.dtype != torch.float32 or dst.dtype != torch.float32 or not src.is_contiguous() or not dst.is_contiguous():
+        raise _lib.VhError('kv_unpack: src and dst must be contiguous float32')
+    if not src.is_cuda or not dst.is_cuda:
+        raise _lib.VhError('kv_unpack: src and dst must be on the HIP device')
+    if src.dim() < 4 or dst.dim() < 5 or src.shape[-1] != HEAD_DIM or dst.shape[-1] != HEAD_DIM:
+        raise _lib.VhError(f'kv_unpack: src {tuple(src.shape)} / dst {tuple(dst.shape)}: (streams, h, S_src, 64) and (streams, B_dst, h, S_dst, 64)')
+    n_heads, S_src = src.shape[-3], src.shape[-2]
+    B_dst, S_dst = dst.shape[-4], dst.shape[-2]
+    if min(n_heads, S_src, B_dst, S_dst) < 1 or dst.shape[-3] != n_heads:
+        raise _lib.VhError(f'kv_unpack: src {tuple(src.shape)} / dst {tuple(dst.shape)}: the same heads, every dimension >= 1')
+    n_streams = src.numel() // (n_heads * S_src * HEAD_DIM)
+    if (src.dim() == 6 and src.shape[2] != 1) or dst.numel() != n_streams * B_dst * n_heads * S_dst * HEAD_DIM:
+        raise _lib.VhError(f'kv_unpack: src {tuple(src.shape)} holds {n_streams} one-row streams, dst {tuple(dst.shape)} does not match')
+    n_seg = seg_start.numel()
+    for t_ in (seg_start, seg_len, dst_row):
+        if t_.dtype != torch.int32 or t_.numel() != n_seg or not t_.is_cuda or not t_.is_contiguous() or n_seg < 1:
+            raise _lib.VhError('kv_unpack: seg_start / seg_len / dst_row must be device int32 tensors of the same n_seg >= 1 entries')
+    check(_lib.lib().vh_kv_unpack(ptr(src), ptr(dst), n_streams, n_heads, S_src, B_dst, S_dst, ptr(seg_start), ptr(seg_len),
+                                  ptr(dst_row), n_seg, stream()), 'vh_kv_unpack')
+    return dst
+
+
 def attn_decode_shared_ws(B, n_heads, prefix_len, n_split, device):
     """Record workspace of `attn_decode_shared` (vh_attn_decode_shared_ws_bytes), as a float32 tensor."""
     n = _lib.lib().vh_attn_decode_shared_ws_bytes(B, n_heads, prefix_len, n_split)

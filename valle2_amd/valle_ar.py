@@ -69,6 +69,16 @@ def _sampling_refused_early(fn):
 
 
 class ValleAR(_Base):
+    # The prompt pass of ragged generate calls over PACKED rows (generation.packed_pass: no padding row is computed; one embed
+    # launch, one packed prefix-LM forward, one vh_kv_unpack into the decoder's caches).  None: on when VALLE2_PACKED_PROMPT=1
+    # is in the environment of the call, else off; True / False (on the class or on a model) override.  The only switch — the
+    # signatures of generate, generate_many, generate_queued, generate_batch and codec_io.* do not change — and it reaches all
+    # of them.  It takes effect where the call qualifies (generation.packed_prompt_qualifies: utterances of different lengths,
+    # fp32, head width 64, cached decoding, no `forced`, not shared_prompt); every other call runs the padded pass as ever.
+    # (A model that lives on the CPU computes through a cached device copy: set the switch on the class, or before the first
+    # call.)
+    packed_prompt = None
+
     def __init__(self, config):
         super().__init__()
         self.config = config
@@ -340,7 +350,9 @@ class ValleAR(_Base):
         / max_audio_pos (largest values any row reached) beside s_suf / codes_width (what they must stay within), intervals
         ((slot, start poll, end poll) per utterance), sum_logprobs and prompt_lens per row in utterance order, rows (per
         utterance in input order, the saved (beams, length) int64 tokens its best beam was chosen from: BOS + prompt + what was
-        generated, cut at max_audio_len; a call that fell back to generate_many records none)."""
+        generated, cut at max_audio_len; a call that fell back to generate_many records none), packed_prompt / prompt_rows /
+        padded_prompt_rows (the starting prompt pass, as generate_batch reports them) and packed_refills (the refills that ran in
+        packed passes: with `packed_prompt` on, a poll that retires two or more groups refills them in one)."""
         beams = self.config.num_beams if beams is None else beams
         generation.check_queued(self.config, beams, slots)
         _sampling.of_utterances('generate_queued', utterances, self.config)
@@ -394,7 +406,10 @@ class ValleAR(_Base):
         sampling (keyword-only): a list with one valle2_amd.Sampling per entry of texts (every entry or None).  Row g * beams +
         j then draws from (sampling[g].seed, j, audio position) through sampling[g]'s own top_k / tok_p / temperature (None:
         the config's) — on every kind of decode, graph or eager — and no seed is drawn from torch's generator;
-        `last_generate_stats['sampling']` is 'rows' ('call' without).  Refused with forced."""
+        `last_generate_stats['sampling']` is 'rows' ('call' without).  Refused with forced.
+        The prompt pass (`packed_prompt`, above the constructor): `last_generate_stats['packed_prompt']` says whether it ran over
+        packed rows, `prompt_rows` how many rows it computed (the sum of the contexts when packed) and `padded_prompt_rows` how
+        many the padded pass computes (pass rows x the longest context; one row under shared_prompt)."""
         return generation.generate_batch(self, texts, first_codes, max_new, use_graph, profile_attn, perf_mode, forced, keep_logits,
                                          shared_prompt, beams, sampling)
 
