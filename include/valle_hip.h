@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VH_VERSION 145            /* 0.2.21: packed AR prompt pass — vh_transformer_forward_packed_lm (vh_transformer_forward_packed under the prefix-LM mask of every segment, seg_x_len and a scratch lse2) and vh_kv_unpack (the K/V rows of a packed stream copied bit for bit to rows of a per-row or grouped cache, all layers and both of K and V in one launch); nothing earlier changes; 0.2.20: packed NAR training — vh_embed_nar_packed and vh_embed_nar_packed_bwd (the NAR model input over packed rows: text rows and audio rows of every segment in one launch, the codebook count changing at each segment's own prefix boundary; the backward reads every gradient row once for all its tables); nothing earlier changes; 0.2.19: packed AR training — vh_attn_rows_packed_lse (vh_attn_rows_packed with a mask mode, per-segment text lengths and lse2), vh_attn_rows_bwd_packed + vh_attn_rows_bwd_packed_ws_bytes (the five-product backward over segments); nothing earlier changes; 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
+#define VH_VERSION 146            /* 0.2.22: packed AR prompt pass in perf mode — vh_attn_rows_packed_lm_bf16 (vh_attn_rows_packed_bf16 under the prefix-LM mask of every segment, seg_x_len), vh_transformer_forward_packed_lm_bf16 (the perf-mode prompt pass of a ragged batch with no padding rows) and vh_kv_unpack_bf16 (vh_kv_unpack for 16-bit streams); nothing earlier changes; 0.2.21: packed AR prompt pass — vh_transformer_forward_packed_lm (vh_transformer_forward_packed under the prefix-LM mask of every segment, seg_x_len and a scratch lse2) and vh_kv_unpack (the K/V rows of a packed stream copied bit for bit to rows of a per-row or grouped cache, all layers and both of K and V in one launch); nothing earlier changes; 0.2.20: packed NAR training — vh_embed_nar_packed and vh_embed_nar_packed_bwd (the NAR model input over packed rows: text rows and audio rows of every segment in one launch, the codebook count changing at each segment's own prefix boundary; the backward reads every gradient row once for all its tables); nothing earlier changes; 0.2.19: packed AR training — vh_attn_rows_packed_lse (vh_attn_rows_packed with a mask mode, per-segment text lengths and lse2), vh_attn_rows_bwd_packed + vh_attn_rows_bwd_packed_ws_bytes (the five-product backward over segments); nothing earlier changes; 0.2.18: per-row length bounds for AR decoding — vh_row_limits records of (min_new, max_new), vh_sample_step_rows_bounded / vh_sample_step_wide_rows_bounded and vh_ar_decoder_set_row_limits (EOS outside the support below min_new, forced at max_new; NULL or zero records: bit for bit as before); 0.2.17: repetition-aware sampling per row — the two reserved words of vh_row_sampling are read as (window, max_repeats) by vh_sample_step_rows / vh_sample_step_wide_rows and the decoder's row_sampling (zeros: off, bit for bit as before; no new symbol, no new field); 0.2.16: packed NAR decoding in perf mode — vh_attn_rows_packed_bf16 (the 16-bit many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed_bf16 (the perf-mode stage forward of a ragged batch with no padding rows); 0.2.15: vh_attn_decode_form — which kernels a decode-attention call launches for a shape, or the entry point's refusal (read-only; one call record, one check, one plan and one launcher behind the seven vh_attn_decode* entries); 0.2.14: vh_linear_form and vh_linear_form_row — which compiled form a decode GEMM takes for a shape, or the entry point's refusal (read-only; one dispatch plan and one table of compiled forms behind every vh_linear* entry); 0.2.13: NAR decoding over packed rows — vh_attn_rows_packed (many-row attention over the segments of one K/V stream) and vh_transformer_forward_packed (the stage forward of a ragged batch with no padding rows); 0.2.12: per-request NAR sampling — vh_categorical_rows_keyed (the stage sampler keyed on (request, frame) with one vh_row_sampling record per request, tokens stored straight into the codes tensor); 0.2.11: per-row sampling — vh_row_sampling, vh_sample_step_rows and vh_sample_step_wide_rows (seed, draw key, top-k, top-p and temperature per row), vh_ar_decoder_desc gains row_sampling at its end; 0.2.10: queued decoding — vh_decode_groups_poll and vh_decode_group_reset (a finished group's rows go to a waiting utterance between graph replays), and vh_attn_decode_shared_groups takes prefix_len[g] == 0 as a PARKED group (no K/V read, rows exactly 0.0); 0.2.9: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded, vh_linear_qkv_folded_kv16) and vh_ffn_decode also serve K = d_model in {640, 768, 896} (10, 12 and 14 heads of width 64): accepted shapes of existing symbols only; 0.2.8: grouped shared-prompt decode attention (vh_attn_decode_shared_groups: the beams of several utterances, each group over its own prompt; vh_ar_decoder_desc gains n_groups, beams_per_group, prefix_cap, prefix_lens at its end); 0.2.7: perf mode of the decode step with key splits and with a shared prompt (vh_attn_decode_kv16_split, vh_attn_decode_shared_kv16; vh_ar_decoder takes kv_bf16 with n_split > 1 and with prefix_len > 0); 0.2.6: the folded-LayerNorm decode GEMMs (vh_linear_folded, vh_linear_qkv_folded) take K in {1280, 1536, 1792, 2048, 2560, 3072, 3584, 4096} and vh_ar_decoder serves d_model <= 4096 at head width 64; 0.2.5: up to 32 codebooks in vh_embed_sum_pe (VH_MAX_TABLES) and vh_sample_step_wide for vocabularies up to VH_SAMPLE_MAX_V (the decoder samples through it when V > 2048); 0.2.4: KV-cached decoding at head widths other than 64 (vh_attn_decode_hd, vh_linear_qkv[_folded]_hd, vh_kv_store; the decoder derives the width from d_model / n_heads); 0.2.3: perf-mode q is PRE-SCALED by 1/sqrt(64) log2(e) between vh_linear_qkv_bf16 and vh_attn_rows_bf16; 0.2.2: head + greedy step in one launch (vh_head_greedy, opt-in: vh_ar_decoder_desc.head_ws); 0.2.1: shared-prompt decode attention (vh_attn_decode_shared); 0.2.0: bf16-MFMA perf mode of the prompt pass / NAR stage (vh_*_bf16); 0.1.2: five-product attention backward (vh_attn_rows_bwd_ws); 0.1.1: dropout fields (vh_dropout_spec) */
 #define VH_MAX_TABLES 32          /* EnCodec: 8 codebooks at 6 kbps (valle/config.py:15-17), 16 at 12 kbps, 32 at 24 kbps */
 #define VH_SAMPLE_MAX_V 16384     /* widest row vh_sample_step_wide takes (num_audio_tokens <= 16383); vh_sample_step: 2048 */
 #define VH_HEAD_DIM 64            /* every configuration of the path has d_model/n_heads = 64 */
@@ -1160,6 +1160,30 @@ int vh_attn_rows_packed_bf16(const uint16_t* q, int ldq, const uint16_t* kcache1
  * either layer table is refused here, before any launch, not by the launch that would meet it. */
 int vh_transformer_forward_packed_bf16(const vh_forward16_desc* desc, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
                                        const int32_t* blocks, int n_blocks, void* stream);
+/* vh_attn_rows_packed_bf16 under the PREFIX-LM mask (ABI 146): segment s attends under the prefix mask of its own text length
+ * seg_x_len[s], clamped to 0 .. seg_len[s] — query i sees key j iff j < x_len or (i >= x_len and j <= i).  Per segment the
+ * output is bit for bit vh_attn_rows_bf16(B = 1, Tq = Tk = seg_len[s], VH_MASK_PREFIX, x_len = seg_x_len[s]) on that segment
+ * alone: the same body over the same keys in the same tile order.  Layout, alignment, the tail-tile clamp and the refusals are
+ * vh_attn_rows_packed_bf16's, plus a null seg_x_len (VH_EINVAL); seg_x_len is a DEVICE int32 array of n_seg entries, and the
+ * caller vouches for the segment and block arrays exactly as there: the segments disjoint and inside [0, M), every block
+ * naming a segment < n_seg and a first query 0 <= q0 < seg_len, the blocks covering every query once.  Workgroups run in table
+ * order: under this mask a segment's LAST query block visits the most key tiles. */
+int vh_attn_rows_packed_lm_bf16(const uint16_t* q, int ldq, const uint16_t* kcache16, const uint16_t* vcache16, uint16_t* out,
+                                int ldo, int n_heads, int S_max, const int32_t* seg_start, const int32_t* seg_len,
+                                const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks, void* stream);
+/* vh_transformer_forward_packed_bf16 under the PREFIX-LM mask (the perf-mode AR prompt pass of a ragged batch, ABI 146):
+ * desc->mode = VH_MASK_PREFIX, segment s attends under the prefix mask of its own text length seg_x_len[s] — the launches of
+ * vh_transformer_forward_bf16 with vh_attn_rows_packed_lm_bf16 for vh_attn_rows_bf16.  LayerNorm stacks (desc->ada NULL).
+ * B != 1, S_max < T and bad dimensions are VH_EINVAL; another mode, kv_len, x_len_dev, ada, or a d_model / dff
+ * vh_transformer_forward_bf16 does not take VH_EUNSUPPORTED; null or misaligned pointers in the descriptor or in either layer
+ * table VH_EINVAL / VH_EALIGN — all before any launch. */
+int vh_transformer_forward_packed_lm_bf16(const vh_forward16_desc* desc, const int32_t* seg_start, const int32_t* seg_len,
+                                          const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks, void* stream);
+/* vh_kv_unpack for 16-bit streams (ABI 146): src (n_streams, n_heads, S_src, 64) and dst (n_streams, B_dst, n_heads, S_dst, 64)
+ * uint16_t (a row is 128 bytes, moved with 16-byte loads and stores).  The same tables, the same cuts and the same refusals as
+ * vh_kv_unpack; the copy is bit for bit and nothing else of dst is written. */
+int vh_kv_unpack_bf16(const uint16_t* src, uint16_t* dst, int n_streams, int n_heads, int S_src, int B_dst, int S_dst,
+                      const int32_t* seg_start, const int32_t* seg_len, const int32_t* dst_row, int n_seg, void* stream);
 
 #ifdef __cplusplus
 }

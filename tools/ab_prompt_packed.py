@@ -18,7 +18,16 @@ Both arms are warm (one untimed call each per set), the timed calls alternate of
 too: they run other GEMM row counts, so they agree to summation order and a token may flip where the two leading logits are
 closer than that (and every later token of that row with it).
 
+--perf-mode True | kv measures the PERF-MODE prompt pass instead (`ValleAR.packed_prompt_perf`; section 1 only: queued and
+grouped calls refuse perf_mode): `generate_batch(..., perf_mode=True)` runs the 16-bit packed pass against the 16-bit padded
+one, `perf_mode='kv'` the fp32 packed pass against the fp32 padded one, both narrowed once.
+
+--padded-only times the padded arm alone and never touches a switch, and --package-root DIR imports `valle2_amd` from another
+checkout (built there): together they measure the PARENT commit's padded pass with this tool, the control that shows the padded
+route has not moved.
+
     python tools/ab_prompt_packed.py [--utterances 32] [--reps 7] [--max-len 1024] [--max-new 512] [--skip-queued]
+                                     [--perf-mode {True,kv}] [--padded-only] [--package-root DIR]
     (one JSON line per set and section)
 """
 from __future__ import annotations
@@ -31,8 +40,6 @@ import sys
 import tempfile
 import time
 from pathlib import Path
-
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 
 def length_sets(n, lmax):
@@ -56,7 +63,12 @@ def main():
     ap.add_argument('--queue-slots', type=int, default=16)
     ap.add_argument('--queue-max-new', type=int, default=256, help='max_audio_len of the queued section')
     ap.add_argument('--skip-queued', action='store_true')
+    ap.add_argument('--perf-mode', choices=['True', 'kv'], default=None,
+                    help='measure generate_batch(perf_mode=...) under ValleAR.packed_prompt_perf (section 1 only)')
+    ap.add_argument('--padded-only', action='store_true', help='time the padded arm alone; no switch is set')
+    ap.add_argument('--package-root', default=None, help='import valle2_amd from this checkout instead of the tool\'s own')
     args = ap.parse_args()
+    sys.path.insert(0, str(Path(args.package_root).resolve() if args.package_root else Path(__file__).resolve().parents[1]))
     os.chdir(tempfile.mkdtemp(prefix='ab_prompt_packed_'))      # ConfigValle() mkdirs under the CWD
     import torch
 
@@ -87,13 +99,17 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3, out
 
+    perf_mode = {None: False, 'True': True, 'kv': 'kv'}[args.perf_mode]
+    switch = 'packed_prompt_perf' if perf_mode else 'packed_prompt'
+
     def compare(m, section, name, lengths, call, flat, extra):
         """Alternate the switch off / on around `call`; one JSON line."""
         def arm(on):
-            m.packed_prompt = on
+            if not args.padded_only:
+                setattr(m, switch, on)
             ms, out = timed(call)
             return ms, out, dict(m.last_generate_stats)
-        arms = {'padded': False, 'packed': True}
+        arms = {'padded': False} if args.padded_only else {'padded': False, 'packed': True}
         outs = {k: arm(on)[1:] for k, on in arms.items()}        # warm-up of every shape the timed calls use
         wall, prefill = {k: [] for k in arms}, {k: [] for k in arms}
         for _ in range(args.reps):
@@ -101,25 +117,27 @@ def main():
                 ms, _, st = arm(on)
                 wall[k].append(ms)
                 prefill[k].append(st['prefill_ms'])
-        a, b = flat(outs['padded'][0]), flat(outs['packed'][0])
+        a, b = flat(outs['padded'][0]), flat(outs[list(arms)[-1]][0])
         lmax, total = max(lengths), sum(lengths)
-        report = dict(section=section, set=name, utterances=len(lengths), reps=args.reps, rows_padded=lmax * len(lengths),
+        report = dict(section=section, perf_mode=perf_mode, package=str(Path(sys.modules['valle2_amd'].__file__).parent.parent.name)
+                      if args.package_root else 'this checkout', set=name, utterances=len(lengths), reps=args.reps, rows_padded=lmax * len(lengths),
                       rows_packed=total, row_share=round(total / (lmax * len(lengths)), 3),
                       key_tile_share=round(sum(n * n for n in lengths) / (lmax * total), 3),
                       tokens=int(a.numel()), tokens_equal_share=round(float((a == b).float().mean()), 6))
         for k in arms:
             st = outs[k][1]
-            report[k] = dict(packed_prompt=st['packed_prompt'], prompt_rows=st['prompt_rows'], prefill_ms=summary(prefill[k]),
+            report[k] = dict(packed_prompt=st.get('packed_prompt'), prompt_rows=st.get('prompt_rows'), prefill_ms=summary(prefill[k]),
                              wall_ms=summary(wall[k]), **{key: st.get(key) for key in extra})
-        for fig, src in (('prefill', prefill), ('wall', wall)):
+        for fig, src in (('prefill', prefill), ('wall', wall)) if not args.padded_only else ():
             report[f'{fig}_packed_over_padded'] = round(statistics.median(src['packed']) / statistics.median(src['padded']), 3)
         print(json.dumps(report), flush=True)
 
     cfg, m = model(args.max_new)
     for name, lengths in length_sets(args.utterances, args.max_len).items():
         texts, firsts = ids(cfg, lengths)
-        compare(m, 'generate_batch', name, lengths, lambda: m.generate_batch(texts, firsts), lambda rows: rows, ())
-    if args.skip_queued:
+        compare(m, 'generate_batch', name, lengths, lambda: m.generate_batch(texts, firsts, perf_mode=perf_mode), lambda rows: rows,
+                ('prefill_bf16', 'kv_bf16') if perf_mode else ())
+    if args.skip_queued or perf_mode:
         return
     m.release_decoders()
     del m

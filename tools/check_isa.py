@@ -18,7 +18,8 @@ REPO = Path(__file__).resolve().parent.parent
 HIPCC = '/opt/rocm/bin/hipcc'
 ATTN_WAIT_KERNELS = ['_Z21attn_bwd_fused_kernelILi8EEv7BwdArgs', '_Z21attn_bwd_fused_kernelILi4EEv7BwdArgs', '_Z19attn_bwd_dkv_kernel7BwdArgs',
                      '_Z16attn_rows_kernel8RowsArgs']
-BF16_WAIT_KERNELS = ['_Z13attn16_kernel10Attn16Args', '_Z20attn16_packed_kernel10Attn16Args12Packed16Segs']
+BF16_WAIT_KERNELS = ['_Z13attn16_kernel10Attn16Args', '_Z20attn16_packed_kernel10Attn16Args12Packed16Segs',
+                     '_Z23attn16_packed_lm_kernel10Attn16Args14Packed16LmSegs']
 
 
 def compile_asm():

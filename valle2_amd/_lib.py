@@ -319,6 +319,13 @@ SIGNATURES = {
                                                    c_f32p, C.c_void_p]),
     'vh_kv_unpack': (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, C.c_int,
                                C.c_void_p]),
+    # packed AR prompt pass in perf mode: the same three in the 16-bit operand format (ABI 146)
+    'vh_attn_rows_packed_lm_bf16': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                              c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.c_void_p]),
+    'vh_transformer_forward_packed_lm_bf16': (C.c_int, [C.POINTER(VhForward16Desc), c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int,
+                                                        C.c_void_p]),
+    'vh_kv_unpack_bf16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p,
+                                    C.c_int, C.c_void_p]),
 }
 
 _lib = None

@@ -1,15 +1,18 @@
 // The body of the 16-bit many-row attention kernels, included by bf16.hip once per kernel (ATTN16_PACKED 0: attn16_kernel,
-// 1: attn16_packed_kernel), as attn_rows_body.inc is by attention.hip and for its reason: stamped out as the kernel itself
-// the text compiles for attn16_kernel to the instructions it had before the packed kernel existed.  What differs between
-// the two — the sequence's lengths, its first row, its K/V base and the workgroup's first query — is spelt by the A16_*
-// macros below, which expand to attn16_kernel's own expressions.
+// 1: attn16_packed_kernel, 2: attn16_packed_lm_kernel), as attn_rows_body.inc is by attention.hip and for its reason: stamped
+// out as the kernel itself the text compiles for attn16_kernel to the instructions it had before the packed kernels existed.
+// What differs between them — the sequence's lengths, its first row, its K/V base and the workgroup's first query — is spelt
+// by the A16_* macros below, which expand to attn16_kernel's own expressions.
 //
 // One workgroup = 128 queries (4 waves x 32) of one (sequence, head) over that sequence's keys in 64-key tiles.  The sequence
 // is batch row b of a padded (B, Tq, ·) layout (attn16_kernel, FULL / PREFIX mask) or one segment of a packed row stream
-// (attn16_packed_kernel, full mask): there Tq = Tk = kvl = the segment's length, row 0 of the sequence is row seg_start of
+// (attn16_packed_kernel, full mask; attn16_packed_lm_kernel, the prefix-LM mask of the segment's own text length
+// seg_x_len[seg]): there Tq = Tk = kvl = the segment's length, row 0 of the sequence is row seg_start of
 // q / out / the one K/V stream, and everything below — the ring of three images, the clamp of a tail tile to the
 // sequence's own last row, the waits, the arithmetic and the epilogue — is the same code.
-#if ATTN16_PACKED
+#if ATTN16_PACKED == 2
+__global__ __launch_bounds__(256, 2) void attn16_packed_lm_kernel(Attn16Args a, Packed16LmSegs ps) {
+#elif ATTN16_PACKED
 __global__ __launch_bounds__(256, 2) void attn16_packed_kernel(Attn16Args a, Packed16Segs ps) {
 #else
 __global__ __launch_bounds__(256, 2) void attn16_kernel(Attn16Args a) {
@@ -29,8 +32,14 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(Attn16Args a) {
     if (s0 < 0 || s0 >= a.S_max) return;
     const int len = min(ps.seg_len[seg], a.S_max - s0);       // never a cache row at or beyond S_max, whatever the table says
     if (bq0 < 0 || bq0 >= len) return;                        // (all of these before the first DMA and the first barrier)
+#if ATTN16_PACKED == 2
+    // the segment's text length, clamped to 0 .. len (a text length beyond the segment is full visibility, as in attn16_kernel)
+    const int q_off = 0, kvl = len, xl = min(max(ps.seg_x_len[seg], 0), len);
+    const bool prefix = true;
+#else
     const int q_off = 0, kvl = len, xl = 0;
     const bool prefix = false;
+#endif
 #define A16_TQ len                                            /* queries = keys = the segment's rows */
 #define A16_TK len
 #define A16_QBLK0 bq0                                         /* the workgroup's first query inside the sequence */

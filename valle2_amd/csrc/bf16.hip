@@ -12,6 +12,8 @@
 //                        a k-step in accumulator order), V^T fragments by ds_read_b64_tr_b16 from the row-major V tile.
 //   attn16_packed_kernel the same body (attn16_body.inc) over the SEGMENTS of one packed row stream under the full mask:
 //                        the NAR stage of a ragged batch with no padding rows (vh_attn_rows_packed_bf16).
+//   attn16_packed_lm_kernel  the same over segments under the prefix-LM mask of each segment's own text length: the AR
+//                        prompt pass of a ragged batch with no padding rows (vh_attn_rows_packed_lm_bf16).
 //   layernorm16_kernel   LayerNorm / AdaptiveLayerNorm of the fp32 residual stream written as bf16.
 //
 // MFMA operand maps (cdna_hip_programming.md section 3), lane l: r = l & 31, h = l >> 5:
@@ -620,11 +622,21 @@ struct Packed16Segs {
     int n_seg;
 };
 
+// The same segments with each one's text length for the prefix-LM mask (vh_attn_rows_packed_lm_bf16).  A struct of its own:
+// attn16_packed_kernel keeps its arguments, and with them its compiled text.
+struct Packed16LmSegs {
+    const int32_t* seg_start; const int32_t* seg_len; const int32_t* blocks; const int32_t* seg_x_len;
+    int n_seg;
+};
+
 #define ATTN16_PACKED 0
 #include "attn16_body.inc"          // attn16_kernel(Attn16Args)
 #undef ATTN16_PACKED
 #define ATTN16_PACKED 1
 #include "attn16_body.inc"          // attn16_packed_kernel(Attn16Args, Packed16Segs)
+#undef ATTN16_PACKED
+#define ATTN16_PACKED 2
+#include "attn16_body.inc"          // attn16_packed_lm_kernel(Attn16Args, Packed16LmSegs)
 #undef ATTN16_PACKED
 
 extern "C" int vh_attn_rows_bf16(const uint16_t* q, int ldq_, const uint16_t* kcache16, const uint16_t* vcache16, uint16_t* out,
@@ -672,15 +684,43 @@ extern "C" int vh_attn_rows_packed_bf16(const uint16_t* q, int ldq_, const uint1
     return VH_OK;
 }
 
+extern "C" int vh_attn_rows_packed_lm_bf16(const uint16_t* q, int ldq_, const uint16_t* kcache16, const uint16_t* vcache16,
+                                           uint16_t* out, int ldo, int n_heads, int S_max, const int32_t* seg_start,
+                                           const int32_t* seg_len, const int32_t* seg_x_len, int n_seg, const int32_t* blocks,
+                                           int n_blocks, void* stream) {
+    VH_REQUIRE(q && kcache16 && vcache16 && out, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: null pointer (q, kcache16, vcache16 or out)");
+    VH_REQUIRE(seg_start && seg_len && seg_x_len && blocks, VH_EINVAL,
+               "vh_attn_rows_packed_lm_bf16: null pointer (seg_start, seg_len, seg_x_len or blocks)");
+    VH_REQUIRE(n_heads > 0 && S_max >= 1, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: bad dims n_heads=%d S_max=%d", n_heads, S_max);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: n_seg=%d", n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: n_blocks=%d", n_blocks);
+    VH_REQUIRE(ldq_ % 8 == 0 && ldq_ >= n_heads * VH_HEAD_DIM, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: ldq=%d", ldq_);
+    VH_REQUIRE(ldo % 8 == 0 && ldo >= n_heads * VH_HEAD_DIM, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: ldo=%d", ldo);
+    VH_REQUIRE(vh_aligned16(q), VH_EALIGN, "vh_attn_rows_packed_lm_bf16: q must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(out), VH_EALIGN, "vh_attn_rows_packed_lm_bf16: out must be 16-byte aligned");
+    VH_REQUIRE(vh_aligned16(kcache16) && vh_aligned16(vcache16), VH_EALIGN,
+               "vh_attn_rows_packed_lm_bf16: kcache16 and vcache16 must be 16-byte aligned");
+    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
+               "vh_attn_rows_packed_lm_bf16: n_blocks=%d x n_heads=%d workgroups", n_blocks, n_heads);
+    // (as in vh_attn_rows_packed_bf16: the kernel reads the lengths and the text lengths from the segment table)
+    Attn16Args a{q, ldq_, kcache16, vcache16, out, ldo, 1, n_heads, 0, 0, S_max, VH_MASK_PREFIX, 0, nullptr, nullptr, 0};
+    Packed16LmSegs ps{seg_start, seg_len, blocks, seg_x_len, n_seg};
+    hipLaunchKernelGGL(attn16_packed_lm_kernel, dim3((unsigned)(n_blocks * n_heads)), dim3(256), 0, (hipStream_t)stream, a, ps);
+    VH_CHECK_LAUNCH("vh_attn_rows_packed_lm_bf16");
+    return VH_OK;
+}
+
 // =============================================================================================
 // composite: the full-sequence forward of vh_transformer_forward with bf16 operands
 // =============================================================================================
 #define TRY16(call) do { int rc_ = (call); if (rc_ != VH_OK) return rc_; } while (0)
 
-// the segments of a packed forward (vh_transformer_forward_packed_bf16); null: the padded (B, T) layout
+// the segments of a packed forward (vh_transformer_forward_packed_bf16, or with seg_x_len vh_transformer_forward_packed_lm_bf16);
+// null: the padded (B, T) layout
 struct packed_rows16 {
     const int32_t *seg_start, *seg_len, *blocks;
     int n_seg, n_blocks;
+    const int32_t* seg_x_len;         // the text length inside each segment: the prefix-LM mask; null: the full mask
 };
 
 // every layer's 16-bit matrices and caches are there, said before the first layer is launched (`name`: the entry point
@@ -694,8 +734,8 @@ static int layers16_complete(const vh_forward16_desc* f, const char* name) {
     return VH_OK;
 }
 
-// the layers of both forwards: the same launches in the same order, the packed one with vh_attn_rows_packed_bf16 for
-// vh_attn_rows_bf16
+// the layers of the three forwards: the same launches in the same order, the packed ones with vh_attn_rows_packed_bf16 or
+// vh_attn_rows_packed_lm_bf16 for vh_attn_rows_bf16
 static int forward16_layers(const vh_forward16_desc* f, const packed_rows16* pk, void* stream) {
     const int B = f->B, T = f->T, D = f->d_model, M = B * T;
     for (int i = 0; i < f->n_layers; ++i) {
@@ -706,7 +746,10 @@ static int forward16_layers(const vh_forward16_desc* f, const packed_rows16* pk,
         TRY16(vh_layernorm_bf16(src, L.ln1_g, L.ln1_b, ada, ada ? ada + D : nullptr, f->xn16, M, D, f->ln_eps, stream));
         TRY16(vh_linear_qkv_bf16(f->xn16, D, H.wqkv, f->q16, D, H.kcache16, H.vcache16, nullptr, B, T, D, f->n_heads,
                                  f->S_max, stream));
-        if (pk)
+        if (pk && pk->seg_x_len)
+            TRY16(vh_attn_rows_packed_lm_bf16(f->q16, D, H.kcache16, H.vcache16, f->attn16, D, f->n_heads, f->S_max, pk->seg_start,
+                                              pk->seg_len, pk->seg_x_len, pk->n_seg, pk->blocks, pk->n_blocks, stream));
+        else if (pk)
             TRY16(vh_attn_rows_packed_bf16(f->q16, D, H.kcache16, H.vcache16, f->attn16, D, f->n_heads, f->S_max, pk->seg_start,
                                            pk->seg_len, pk->n_seg, pk->blocks, pk->n_blocks, stream));
         else
@@ -734,48 +777,79 @@ extern "C" int vh_transformer_forward_bf16(const vh_forward16_desc* f, void* str
     return forward16_layers(f, nullptr, stream);
 }
 
-extern "C" int vh_transformer_forward_packed_bf16(const vh_forward16_desc* f, const int32_t* seg_start, const int32_t* seg_len,
-                                                  int n_seg, const int32_t* blocks, int n_blocks, void* stream) {
+// what both packed composites refuse alike, under the name of the entry point that was called: the descriptor and the segment
+// arguments (packed16_front, before the mask fields are looked at) ...
+static int packed16_front(const char* name, const vh_forward16_desc* f, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
+                          const int32_t* blocks, int n_blocks) {
     VH_REQUIRE(f && f->layers && f->layers16 && f->x && f->xn16 && f->q16 && f->attn16 && f->hidden16, VH_EINVAL,
-               "vh_transformer_forward_packed_bf16: null pointer in desc");
+               "%s: null pointer in desc", name);
     VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL,
-               "vh_transformer_forward_packed_bf16: null pointer (seg_start, seg_len or blocks)");
-    VH_REQUIRE(f->B == 1, VH_EINVAL, "vh_transformer_forward_packed_bf16: B=%d (the packed rows are ONE row stream: B = 1, T = the "
-               "sum of the segment lengths)", f->B);
-    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "vh_transformer_forward_packed_bf16: bad dims T=%d L=%d", f->T, f->n_layers);
-    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "vh_transformer_forward_packed_bf16: S_max=%d < T=%d", f->S_max, f->T);
-    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_transformer_forward_packed_bf16: n_seg=%d", n_seg);
-    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_transformer_forward_packed_bf16: n_blocks=%d", n_blocks);
-    VH_REQUIRE(f->mode == VH_MASK_FULL, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed_bf16: mode=%d (segments attend under the full mask only)", f->mode);
-    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: kv_len is set (a segment's length is its key length)");
-    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: x_len_dev is set (no prefix mask over segments)");
+               "%s: null pointer (seg_start, seg_len or blocks)", name);
+    VH_REQUIRE(f->B == 1, VH_EINVAL, "%s: B=%d (the packed rows are ONE row stream: B = 1, T = the "
+               "sum of the segment lengths)", name, f->B);
+    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "%s: bad dims T=%d L=%d", name, f->T, f->n_layers);
+    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "%s: S_max=%d < T=%d", name, f->S_max, f->T);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "%s: n_seg=%d", name, n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "%s: n_blocks=%d", name, n_blocks);
+    return VH_OK;
+}
+
+// ... and the shapes the 16-bit stack takes, and every pointer of the descriptor and of both layer tables (packed16_back)
+static int packed16_back(const char* name, const vh_forward16_desc* f, int n_blocks) {
     VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM && f->d_model % 128 == 0 && f->dff % 128 == 0, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed_bf16: d_model=%d dff=%d (n_heads x 64, multiples of 128)", f->d_model, f->dff);
-    VH_REQUIRE(f->d_model <= 4096, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: d_model=%d (vh_layernorm_bf16 serves <= 4096)",
+               "%s: d_model=%d dff=%d (n_heads x 64, multiples of 128)", name, f->d_model, f->dff);
+    VH_REQUIRE(f->d_model <= 4096, VH_EUNSUPPORTED, "%s: d_model=%d (vh_layernorm_bf16 serves <= 4096)", name,
                f->d_model);
     VH_REQUIRE((int64_t)n_blocks * f->n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed_bf16: n_blocks=%d x n_heads=%d workgroups", n_blocks, f->n_heads);
+               "%s: n_blocks=%d x n_heads=%d workgroups", name, n_blocks, f->n_heads);
     // what the launches of any layer would refuse for a pointer — null or not 16-byte aligned — said here, under this entry
     // point's name, before anything is launched
     VH_REQUIRE(vh_aligned16(f->x) && vh_aligned16(f->x_in) && vh_aligned16(f->ada), VH_EALIGN,
-               "vh_transformer_forward_packed_bf16: x, x_in and ada must be 16-byte aligned");
+               "%s: x, x_in and ada must be 16-byte aligned", name);
     VH_REQUIRE(vh_aligned16(f->xn16) && vh_aligned16(f->q16) && vh_aligned16(f->attn16) && vh_aligned16(f->hidden16), VH_EALIGN,
-               "vh_transformer_forward_packed_bf16: xn16, q16, attn16 and hidden16 must be 16-byte aligned");
-    TRY16(layers16_complete(f, "vh_transformer_forward_packed_bf16"));
+               "%s: xn16, q16, attn16 and hidden16 must be 16-byte aligned", name);
+    TRY16(layers16_complete(f, name));
     for (int i = 0; i < f->n_layers; ++i) {
         const vh_layer& L = f->layers[i];
         const vh_layer16& H = f->layers16[i];
         VH_REQUIRE(vh_aligned16(H.kcache16) && vh_aligned16(H.vcache16), VH_EALIGN,
-                   "vh_transformer_forward_packed_bf16: kcache16 and vcache16 must be 16-byte aligned (layer %d)", i);
+                   "%s: kcache16 and vcache16 must be 16-byte aligned (layer %d)", name, i);
         VH_REQUIRE(vh_aligned16(H.wqkv) && vh_aligned16(H.wo) && vh_aligned16(H.w1) && vh_aligned16(H.w2), VH_EALIGN,
-                   "vh_transformer_forward_packed_bf16: wqkv, wo, w1 and w2 must be 16-byte aligned (layer %d)", i);
+                   "%s: wqkv, wo, w1 and w2 must be 16-byte aligned (layer %d)", name, i);
         VH_REQUIRE(L.ln1_g && L.ln1_b && L.ln2_g && L.ln2_b, VH_EINVAL,
-                   "vh_transformer_forward_packed_bf16: layer %d has a null LayerNorm parameter", i);
+                   "%s: layer %d has a null LayerNorm parameter", name, i);
         VH_REQUIRE(vh_aligned16(L.ln1_g) && vh_aligned16(L.ln1_b) && vh_aligned16(L.ln2_g) && vh_aligned16(L.ln2_b) &&
                        vh_aligned16(L.bo) && vh_aligned16(L.b1) && vh_aligned16(L.b2), VH_EALIGN,
-                   "vh_transformer_forward_packed_bf16: LayerNorm parameters and biases must be 16-byte aligned (layer %d)", i);
+                   "%s: LayerNorm parameters and biases must be 16-byte aligned (layer %d)", name, i);
     }
-    const packed_rows16 pk{seg_start, seg_len, blocks, n_seg, n_blocks};
+    return VH_OK;
+}
+
+extern "C" int vh_transformer_forward_packed_bf16(const vh_forward16_desc* f, const int32_t* seg_start, const int32_t* seg_len,
+                                                  int n_seg, const int32_t* blocks, int n_blocks, void* stream) {
+    const char* name = "vh_transformer_forward_packed_bf16";
+    TRY16(packed16_front(name, f, seg_start, seg_len, n_seg, blocks, n_blocks));
+    VH_REQUIRE(f->mode == VH_MASK_FULL, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed_bf16: mode=%d (segments attend under the full mask only)", f->mode);
+    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: kv_len is set (a segment's length is its key length)");
+    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: x_len_dev is set (no prefix mask over segments)");
+    TRY16(packed16_back(name, f, n_blocks));
+    const packed_rows16 pk{seg_start, seg_len, blocks, n_seg, n_blocks, nullptr};
+    return forward16_layers(f, &pk, stream);
+}
+
+extern "C" int vh_transformer_forward_packed_lm_bf16(const vh_forward16_desc* f, const int32_t* seg_start, const int32_t* seg_len,
+                                                     const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks,
+                                                     void* stream) {
+    const char* name = "vh_transformer_forward_packed_lm_bf16";
+    TRY16(packed16_front(name, f, seg_start, seg_len, n_seg, blocks, n_blocks));
+    VH_REQUIRE(seg_x_len, VH_EINVAL, "vh_transformer_forward_packed_lm_bf16: null pointer (seg_x_len)");
+    VH_REQUIRE(f->mode == VH_MASK_PREFIX, VH_EUNSUPPORTED,
+               "vh_transformer_forward_packed_lm_bf16: mode=%d (segments attend under their prefix-LM masks: VH_MASK_PREFIX)", f->mode);
+    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm_bf16: kv_len is set (a segment's length is its key length)");
+    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm_bf16: x_len_dev is set (the text lengths are seg_x_len)");
+    VH_REQUIRE(!f->ada, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm_bf16: ada is set (LayerNorm stacks only)");
+    TRY16(packed16_back(name, f, n_blocks));
+    const packed_rows16 pk{seg_start, seg_len, blocks, n_seg, n_blocks, seg_x_len};
     return forward16_layers(f, &pk, stream);
 }

@@ -1429,52 +1429,71 @@ extern "C" int vh_decode_group_reset(int64_t* codes, int64_t codes_stride, int c
 // Guards as in attn_rows_packed_kernel (workgroup-uniform): a segment that starts outside the stream or names a row outside
 // [0, B_dst) copies nothing; one that reaches past S_src, or is longer than S_dst, is cut there.
 // ---------------------------------------------------------------------------------------------
-#define KVU_ROWS 64                  // rows per workgroup trip: 256 threads x 4 float4 = 64 rows of 64 floats
-__global__ __launch_bounds__(256) void kv_unpack_kernel(const float* __restrict__ src, float* __restrict__ dst,
+#define KVU_ROWS 64                  // fp32 rows per workgroup trip: 256 threads x 4 x 16 bytes = 64 rows of 64 floats (128 rows of 64 halves)
+// One kernel for both element widths (T = float: vh_kv_unpack, T = uint16_t: vh_kv_unpack_bf16, a row is then 128 bytes): only
+// the number of 16-byte units per row depends on T, the copy itself moves 16 bytes at a time whatever they hold.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_unpack_kernel(const T* __restrict__ src, T* __restrict__ dst,
                                                         const int32_t* __restrict__ seg_start, const int32_t* __restrict__ seg_len,
                                                         const int32_t* __restrict__ dst_row, int n_heads, int S_src, int B_dst,
                                                         int S_dst) {
+    constexpr int E = 16 / (int)sizeof(T);                        // elements of a 16-byte unit
     const int sh = blockIdx.x, strm = sh / n_heads, head = sh - strm * n_heads;
     const int s = blockIdx.y;
     const int s0 = seg_start[s], row = dst_row[s];
     if (s0 < 0 || s0 >= S_src || row < 0 || row >= B_dst) return;
     const int len = min(min(seg_len[s], S_src - s0), S_dst);
     if (len <= 0) return;
-    const float* from = src + ((int64_t)sh * S_src + s0) * VH_HEAD_DIM;
-    float* to = dst + (((int64_t)strm * B_dst + row) * n_heads + head) * (int64_t)S_dst * VH_HEAD_DIM;
-    const int n4 = len * (VH_HEAD_DIM / 4);                       // float4s of the run (S_dst x 16 < 2^31: checked by the host)
+    const T* from = src + ((int64_t)sh * S_src + s0) * VH_HEAD_DIM;
+    T* to = dst + (((int64_t)strm * B_dst + row) * n_heads + head) * (int64_t)S_dst * VH_HEAD_DIM;
+    const int n4 = len * (VH_HEAD_DIM / E);                       // 16-byte units of the run (S_dst x 16 < 2^31: checked by the host)
     for (int i0 = blockIdx.z * (KVU_ROWS * 16) + threadIdx.x; i0 < n4; i0 += gridDim.z * (KVU_ROWS * 16)) {
         f32x4 v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (i0 + 256 * j < n4) v[j] = ld4(from + 4 * (int64_t)(i0 + 256 * j));
+            if (i0 + 256 * j < n4) v[j] = ld4(reinterpret_cast<const float*>(from + E * (int64_t)(i0 + 256 * j)));
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (i0 + 256 * j < n4) st4(to + 4 * (int64_t)(i0 + 256 * j), v[j]);
+            if (i0 + 256 * j < n4) st4(reinterpret_cast<float*>(to + E * (int64_t)(i0 + 256 * j)), v[j]);
     }
+}
+
+// the checks and the launch of both entry points (`name`: the one the refusal is reported under)
+template <typename T>
+static int kv_unpack_launch(const char* name, const T* src, T* dst, int n_streams, int n_heads, int S_src, int B_dst, int S_dst,
+                            const int32_t* seg_start, const int32_t* seg_len, const int32_t* dst_row, int n_seg, void* stream) {
+    VH_REQUIRE(src && dst, VH_EINVAL, "%s: null pointer (src or dst)", name);
+    VH_REQUIRE(seg_start && seg_len && dst_row, VH_EINVAL, "%s: null pointer (seg_start, seg_len or dst_row)", name);
+    VH_REQUIRE(n_streams > 0 && n_heads > 0 && S_src > 0 && B_dst > 0 && S_dst > 0, VH_EINVAL,
+               "%s: bad dims n_streams=%d n_heads=%d S_src=%d B_dst=%d S_dst=%d", name, n_streams, n_heads, S_src, B_dst, S_dst);
+    VH_REQUIRE(n_seg > 0, VH_EINVAL, "%s: n_seg=%d", name, n_seg);
+    VH_REQUIRE(vh_aligned16(src) && vh_aligned16(dst), VH_EALIGN, "%s: src and dst must be 16-byte aligned", name);
+    VH_REQUIRE(((reinterpret_cast<uintptr_t>(seg_start) | reinterpret_cast<uintptr_t>(seg_len) | reinterpret_cast<uintptr_t>(dst_row)) & 3u) == 0,
+               VH_EALIGN, "%s: seg_start, seg_len and dst_row must be 4-byte aligned", name);
+    VH_REQUIRE((int64_t)n_streams * n_heads <= 0x7fffffffLL && n_seg <= 65535, VH_EUNSUPPORTED,
+               "%s: n_streams=%d x n_heads=%d, n_seg=%d workgroups (x <= 2^31 - 1, y <= 65535)", name, n_streams, n_heads, n_seg);
+    VH_REQUIRE(S_src <= (1 << 26) && S_dst <= (1 << 26), VH_EUNSUPPORTED, "%s: S_src=%d S_dst=%d (at most 2^26 rows per stream)", name,
+               S_src, S_dst);
+    // pieces of a run share the segment's workgroups over z until the launch has ~2048 workgroups (8 per CU) or a workgroup per
+    // trip (64 fp32 rows, 128 16-bit rows) of the longest possible run
+    const int64_t runs = (int64_t)n_streams * n_heads * n_seg;
+    const int trip_rows = KVU_ROWS * 4 / (int)sizeof(T);
+    const int trips = (min(S_src, S_dst) + trip_rows - 1) / trip_rows;
+    const int gz = (int)max((int64_t)1, min((int64_t)min(trips, 64), (2048 + runs - 1) / runs));
+    hipLaunchKernelGGL(kv_unpack_kernel<T>, dim3(n_streams * n_heads, n_seg, gz), dim3(256), 0, (hipStream_t)stream, src, dst, seg_start,
+                       seg_len, dst_row, n_heads, S_src, B_dst, S_dst);
+    VH_CHECK_LAUNCH(name);
+    return VH_OK;
 }
 
 extern "C" int vh_kv_unpack(const float* src, float* dst, int n_streams, int n_heads, int S_src, int B_dst, int S_dst,
                             const int32_t* seg_start, const int32_t* seg_len, const int32_t* dst_row, int n_seg, void* stream) {
-    VH_REQUIRE(src && dst, VH_EINVAL, "vh_kv_unpack: null pointer (src or dst)");
-    VH_REQUIRE(seg_start && seg_len && dst_row, VH_EINVAL, "vh_kv_unpack: null pointer (seg_start, seg_len or dst_row)");
-    VH_REQUIRE(n_streams > 0 && n_heads > 0 && S_src > 0 && B_dst > 0 && S_dst > 0, VH_EINVAL,
-               "vh_kv_unpack: bad dims n_streams=%d n_heads=%d S_src=%d B_dst=%d S_dst=%d", n_streams, n_heads, S_src, B_dst, S_dst);
-    VH_REQUIRE(n_seg > 0, VH_EINVAL, "vh_kv_unpack: n_seg=%d", n_seg);
-    VH_REQUIRE(vh_aligned16(src) && vh_aligned16(dst), VH_EALIGN, "vh_kv_unpack: src and dst must be 16-byte aligned");
-    VH_REQUIRE(((reinterpret_cast<uintptr_t>(seg_start) | reinterpret_cast<uintptr_t>(seg_len) | reinterpret_cast<uintptr_t>(dst_row)) & 3u) == 0,
-               VH_EALIGN, "vh_kv_unpack: seg_start, seg_len and dst_row must be 4-byte aligned");
-    VH_REQUIRE((int64_t)n_streams * n_heads <= 0x7fffffffLL && n_seg <= 65535, VH_EUNSUPPORTED,
-               "vh_kv_unpack: n_streams=%d x n_heads=%d, n_seg=%d workgroups (x <= 2^31 - 1, y <= 65535)", n_streams, n_heads, n_seg);
-    VH_REQUIRE(S_src <= (1 << 26) && S_dst <= (1 << 26), VH_EUNSUPPORTED, "vh_kv_unpack: S_src=%d S_dst=%d (at most 2^26 rows per stream)",
-               S_src, S_dst);
-    // pieces of a run share the segment's workgroups over z until the launch has ~2048 workgroups (8 per CU) or a workgroup per
-    // 64 rows of the longest possible run
-    const int64_t runs = (int64_t)n_streams * n_heads * n_seg;
-    const int trips = (min(S_src, S_dst) + KVU_ROWS - 1) / KVU_ROWS;
-    const int gz = (int)max((int64_t)1, min((int64_t)min(trips, 64), (2048 + runs - 1) / runs));
-    hipLaunchKernelGGL(kv_unpack_kernel, dim3(n_streams * n_heads, n_seg, gz), dim3(256), 0, (hipStream_t)stream, src, dst, seg_start,
-                       seg_len, dst_row, n_heads, S_src, B_dst, S_dst);
-    VH_CHECK_LAUNCH("vh_kv_unpack");
-    return VH_OK;
+    return kv_unpack_launch<float>("vh_kv_unpack", src, dst, n_streams, n_heads, S_src, B_dst, S_dst, seg_start, seg_len, dst_row, n_seg,
+                                   stream);
+}
+
+extern "C" int vh_kv_unpack_bf16(const uint16_t* src, uint16_t* dst, int n_streams, int n_heads, int S_src, int B_dst, int S_dst,
+                                 const int32_t* seg_start, const int32_t* seg_len, const int32_t* dst_row, int n_seg, void* stream) {
+    return kv_unpack_launch<uint16_t>("vh_kv_unpack_bf16", src, dst, n_streams, n_heads, S_src, B_dst, S_dst, seg_start, seg_len, dst_row,
+                                      n_seg, stream);
 }

@@ -76,12 +76,16 @@ class KVCache:
     def unpack_into(self, dst: 'KVCache', seg_start, seg_len, dst_row):
         """The rows a packed forward left in this ONE-ROW cache, to rows of `dst` (a row cache or a grouped prefix cache of the
         same layers and heads): rows seg_start[s] .. + seg_len[s] - 1 of every (layer, K|V, head) go to positions 0 ..
-        seg_len[s] - 1 of dst's row dst_row[s], in one launch and bit for bit (`kernels.kv_unpack`); the tables are device
-        int32 tensors of one entry per segment.  Nothing else of dst is written."""
-        if self.batch != 1 or self.bf16 or dst.bf16 or self.head_dim != HEAD_DIM or \
+        seg_len[s] - 1 of dst's row dst_row[s], in one launch and bit for bit (`kernels.kv_unpack`; a 16-bit cache into a
+        16-bit cache: `kernels.kv_unpack_bf16`); the tables are device int32 tensors of one entry per segment.  Nothing else
+        of dst is written."""
+        if self.bf16 != dst.bf16:
+            raise _lib.VhError('KVCache.unpack_into: mixed dtypes (an fp32 cache into an fp32 cache, a 16-bit cache into a 16-bit cache)')
+        if self.batch != 1 or self.head_dim != HEAD_DIM or \
                 (dst.n_layers, dst.n_heads, dst.head_dim) != (self.n_layers, self.n_heads, self.head_dim):
-            raise _lib.VhError('KVCache.unpack_into: a one-row fp32 width-64 cache into an fp32 cache of the same layers and heads')
-        kernels.kv_unpack(self.buf, dst.buf, seg_start, seg_len, dst_row)
+            raise _lib.VhError('KVCache.unpack_into: a one-row fp32 width-64 cache into an fp32 cache of the same layers and heads '
+                               '(or both 16-bit)')
+        (kernels.kv_unpack_bf16 if self.bf16 else kernels.kv_unpack)(self.buf, dst.buf, seg_start, seg_len, dst_row)
         return dst
 
     def k(self, i):
@@ -742,6 +746,34 @@ def transformer_forward_packed_bf16(transformer, x, cache: KVCache, rows: Packed
     check(_lib.lib().vh_transformer_forward_packed_bf16(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg,
                                                         ptr(rows.blocks), rows.n_blocks, stream()),
           'vh_transformer_forward_packed_bf16')
+    return x
+
+
+def transformer_forward_packed_lm_bf16(transformer, x, cache: KVCache, rows, scratch=None):
+    """`transformer_forward_packed_lm` in PERF MODE: `transformer_forward_bf16(mode=MASK_PREFIX)` of a ragged batch over packed
+    rows, forward only.  x (M, d) fp32 holds utterance b at rows rows.starts[b] .. + rows.lengths[b] - 1 and is updated in place;
+    each utterance attends its own rows only, under the prefix-LM mask of its own text length (`vh_attn_rows_packed_lm_bf16`),
+    every other launch is the row-wise 16-bit one over M rows.  `rows`: a `PackedRows` built with x_lens, or a `PromptRows`.
+    `cache`: a one-row 16-bit KVCache of s_max >= M (`KVCache.unpack_into` moves its rows to a 16-bit row cache); `scratch`: a
+    ForwardScratch16.  Head width 64, LayerNorm, the shapes of `perf_forward_supported`.  Returns x."""
+    cfg = transformer.hparams
+    if x.dim() != 2:
+        raise _lib.VhError(f'transformer_forward_packed_lm_bf16: x must be (M, d), got {tuple(x.shape)}')
+    M, d = x.shape
+    if d != cfg.n_heads * HEAD_DIM:
+        raise _lib.VhError(f'transformer_forward_packed_lm_bf16: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
+    if cfg.norm != 'LayerNorm':
+        raise _lib.VhError(f'transformer_forward_packed_lm_bf16: norm={cfg.norm!r} (LayerNorm stacks only)')
+    if M != rows.rows:
+        raise _lib.VhError(f'transformer_forward_packed_lm_bf16: x has {M} rows, the packed rows {rows.rows}')
+    if rows.seg_x_len is None:
+        raise _lib.VhError('transformer_forward_packed_lm_bf16: the prefix mask needs PackedRows(lengths, device, x_lens)')
+    _refuse_unless_perf_forward(cfg)
+    scratch, common = _forward_front(transformer, x, 1, M, cache, None, scratch, bf16=True)
+    desc = _forward16_desc(transformer, cache, scratch, common, mode=kernels.MASK_PREFIX, x_len=0)
+    check(_lib.lib().vh_transformer_forward_packed_lm_bf16(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), ptr(rows.seg_x_len),
+                                                           rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()),
+          'vh_transformer_forward_packed_lm_bf16')
     return x
 
 

@@ -14,7 +14,8 @@ from . import _lib, kernels
 from . import sampling as _sampling
 from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, PromptRows, QueueSchedule, StepSampler,
                      cached_decode_supported, ffn_fused_width, group_prefix_cap, grouped_prompts_fit, perf_forward_supported,
-                     queue_steps_cap, transformer_forward, transformer_forward_bf16, transformer_forward_packed_lm)
+                     queue_steps_cap, transformer_forward, transformer_forward_bf16, transformer_forward_packed_lm,
+                     transformer_forward_packed_lm_bf16)
 from .utils import get_best_beam
 
 EOS_POLL = 32
@@ -392,6 +393,23 @@ def packed_prompt_qualifies(kind, perf_mode, head_dim, forced, ragged, no_cache=
     return bool(ragged) and not perf_mode and head_dim == kernels.HEAD_DIM and not no_cache and not forced and kind in (ROWS, GROUPED)
 
 
+def packed_prompt_perf_on(model):
+    """The switch of the packed prompt pass in PERF MODE, a switch of its own beside `packed_prompt_on`:
+    `model.packed_prompt_perf` (ValleAR's class attribute; True / False), or, while that is None, VALLE2_PACKED_PROMPT_PERF=1 in
+    the environment of the call."""
+    switch = getattr(model, 'packed_prompt_perf', None)
+    return os.environ.get('VALLE2_PACKED_PROMPT_PERF', '0') == '1' if switch is None else bool(switch)
+
+
+def packed_prompt_perf_qualifies(kind, perf_mode, head_dim, forced, ragged, no_cache=False):
+    """`packed_prompt_qualifies` for perf mode (pure: no model, no device): utterances of different lengths, perf_mode True or
+    'kv', head width 64, cached decoding on independent rows — ROWS_PERF_PREFILL (the 16-bit packed pass into the 16-bit row
+    cache) or ROWS ('kv', or a shape the 16-bit stack does not take: the fp32 packed pass, narrowed once) — and no teacher
+    forcing.  SHARED has a single row, grouped and queued calls refuse perf_mode; every other call runs the padded pass."""
+    return (bool(ragged) and bool(perf_mode) and head_dim == kernels.HEAD_DIM and not no_cache and not forced
+            and kind in (ROWS_PERF_PREFILL, ROWS))
+
+
 def _write_prompts(codes, first_codes, n):
     """codes[g * n:(g + 1) * n, 1:1 + len(first_codes[g])] = first_codes[g] for every utterance in one scatter (the padded pass
     writes them utterance by utterance)."""
@@ -409,6 +427,8 @@ def packed_pass(model, texts, txs, pls, codes, into, dst_rows):
     """The prompt pass of several utterances over PACKED rows: one embed launch (`vh_embed_nar_packed` with one codebook: text
     rows, then BOS + prompt rows, positions restarting per stream), one packed prefix-LM forward into a transient one-row
     cache of sum(ctx) rows and one `vh_kv_unpack` into rows `dst_rows` of `into` (a row cache or a grouped prefix cache).
+    A 16-bit `into` (perf mode's row cache) takes the 16-bit forms of the last two: `transformer_forward_packed_lm_bf16` into a
+    transient 16-bit stream and `vh_kv_unpack_bf16`.
     codes (G, >= max(pls)): row g holds BOS + prompt g.  Returns the (G, d) hidden rows of the utterances' last positions."""
     cfg, dev, d = model.config, model.device, model.config.d_model
     rows = PromptRows(txs, pls, dst_rows, dev)
@@ -424,9 +444,14 @@ def packed_pass(model, texts, txs, pls, codes, into, dst_rows):
     x = torch.empty(rows.rows, d, device=dev, dtype=torch.float32)
     kernels.embed_nar_packed(tokens, codes.unsqueeze(-1), model.tokens_emb.weight.detach(), [model.audio_emb.weight.detach()], 1,
                              model.tokens_position_emb.pe, model.audio_position_emb.pe, rows, x)
-    stream_cache = KVCache(cfg.num_layers, 1, cfg.n_heads, rows.rows, dev)
-    transformer_forward_packed_lm(model.transformer, x, stream_cache, rows,
-                                  scratch=ForwardScratch(rows.rows, d, cfg.dim_feedforward, dev))
+    if into.bf16:
+        stream_cache = KVCache(cfg.num_layers, 1, cfg.n_heads, rows.rows, dev, dtype=kernels.H16)
+        transformer_forward_packed_lm_bf16(model.transformer, x, stream_cache, rows,
+                                           scratch=ForwardScratch16(rows.rows, d, cfg.dim_feedforward, dev))
+    else:
+        stream_cache = KVCache(cfg.num_layers, 1, cfg.n_heads, rows.rows, dev)
+        transformer_forward_packed_lm(model.transformer, x, stream_cache, rows,
+                                      scratch=ForwardScratch(rows.rows, d, cfg.dim_feedforward, dev))
     stream_cache.unpack_into(into, rows.seg_start, rows.seg_len, rows.dst_row)
     return x.index_select(0, rows.last_rows)
 
@@ -436,7 +461,10 @@ def prompt_pass(model, plan, state, texts, first_codes, forced=False):
     laid out [text_b | BOS + prompt_b | padding]; the prefix-LM mask takes per-row lengths.  Returns the last hidden row of
     every decode row, the length arguments of the pass and the stacked text ids of equal-length rows (the recompute steps
     run the same pass again).  With the packed switch on (`packed_prompt_on`) a call that qualifies
-    (`packed_prompt_qualifies`) runs `packed_pass` instead: no padding row is computed; `state.prompt_rows` says which."""
+    (`packed_prompt_qualifies`) runs `packed_pass` instead: no padding row is computed; `state.prompt_rows` says which.  Perf
+    mode has a switch of its own (`packed_prompt_perf_on`, `packed_prompt_perf_qualifies`): ROWS_PERF_PREFILL runs the 16-bit
+    packed pass straight into the 16-bit row cache, ROWS the fp32 packed pass into the fp32 cache of s0 keys, narrowed once as
+    after the padded pass."""
     cfg, dev, d = model.config, model.device, model.config.d_model
     B, s0, n, codes = plan.B, plan.s0, plan.beams, state.codes
     i32 = dict(device=dev, dtype=torch.int32)
@@ -450,6 +478,14 @@ def prompt_pass(model, plan, state, texts, first_codes, forced=False):
         state.prompt_rows = (True, sum(plan.ctx))
         if plan.kind == GROUPED:
             last = last.repeat_interleave(n, 0)       # every beam starts from its utterance's last hidden row
+        return last.contiguous(), {}, None
+    if packed_prompt_perf_on(model) and packed_prompt_perf_qualifies(plan.kind, plan.perf_mode, d // cfg.n_heads, forced, plan.ragged,
+                                                                     plan.no_cache):
+        _write_prompts(codes, first_codes, n)
+        last = packed_pass(model, texts, plan.txs, plan.pls, codes[:plan.G], state.cache, range(plan.G))
+        state.prompt_rows = (True, sum(plan.ctx))
+        if plan.kind == ROWS:
+            state.cache = state.cache.narrowed(plan.s_max)    # fp32 prompt K/V -> the bf16 cache of the decode steps
         return last.contiguous(), {}, None
     if not plan.ragged:
         text_ids = torch.stack(texts[:rows])

@@ -600,23 +600,28 @@ def kv_unpack(src, dst, seg_start, seg_len, dst_row):
     row outside [0, B_dst) writes nothing."""
     if src.dtype != torch.float32 or dst.dtype != torch.float32 or not src.is_contiguous() or not dst.is_contiguous():
         raise _lib.VhError('kv_unpack: src and dst must be contiguous float32')
+    return _kv_unpack('kv_unpack', _lib.lib().vh_kv_unpack, src, dst, seg_start, seg_len, dst_row)
+
+
+def _kv_unpack(what, entry, src, dst, seg_start, seg_len, dst_row):
+    """The shape checks and the call of `kv_unpack` and `kv_unpack_bf16` (the dtype is the caller's check)."""
     if not src.is_cuda or not dst.is_cuda:
-        raise _lib.VhError('kv_unpack: src and dst must be on the HIP device')
+        raise _lib.VhError(f'{what}: src and dst must be on the HIP device')
     if src.dim() < 4 or dst.dim() < 5 or src.shape[-1] != HEAD_DIM or dst.shape[-1] != HEAD_DIM:
-        raise _lib.VhError(f'kv_unpack: src {tuple(src.shape)} / dst {tuple(dst.shape)}: (streams, h, S_src, 64) and (streams, B_dst, h, S_dst, 64)')
+        raise _lib.VhError(f'{what}: src {tuple(src.shape)} / dst {tuple(dst.shape)}: (streams, h, S_src, 64) and (streams, B_dst, h, S_dst, 64)')
     n_heads, S_src = src.shape[-3], src.shape[-2]
     B_dst, S_dst = dst.shape[-4], dst.shape[-2]
     if min(n_heads, S_src, B_dst, S_dst) < 1 or dst.shape[-3] != n_heads:
-        raise _lib.VhError(f'kv_unpack: src {tuple(src.shape)} / dst {tuple(dst.shape)}: the same heads, every dimension >= 1')
+        raise _lib.VhError(f'{what}: src {tuple(src.shape)} / dst {tuple(dst.shape)}: the same heads, every dimension >= 1')
     n_streams = src.numel() // (n_heads * S_src * HEAD_DIM)
     if (src.dim() == 6 and src.shape[2] != 1) or dst.numel() != n_streams * B_dst * n_heads * S_dst * HEAD_DIM:
-        raise _lib.VhError(f'kv_unpack: src {tuple(src.shape)} holds {n_streams} one-row streams, dst {tuple(dst.shape)} does not match')
+        raise _lib.VhError(f'{what}: src {tuple(src.shape)} holds {n_streams} one-row streams, dst {tuple(dst.shape)} does not match')
     n_seg = seg_start.numel()
     for t_ in (seg_start, seg_len, dst_row):
         if t_.dtype != torch.int32 or t_.numel() != n_seg or not t_.is_cuda or not t_.is_contiguous() or n_seg < 1:
-            raise _lib.VhError('kv_unpack: seg_start / seg_len / dst_row must be device int32 tensors of the same n_seg >= 1 entries')
-    check(_lib.lib().vh_kv_unpack(ptr(src), ptr(dst), n_streams, n_heads, S_src, B_dst, S_dst, ptr(seg_start), ptr(seg_len),
-                                  ptr(dst_row), n_seg, stream()), 'vh_kv_unpack')
+            raise _lib.VhError(f'{what}: seg_start / seg_len / dst_row must be device int32 tensors of the same n_seg >= 1 entries')
+    check(entry(ptr(src), ptr(dst), n_streams, n_heads, S_src, B_dst, S_dst, ptr(seg_start), ptr(seg_len), ptr(dst_row), n_seg,
+                stream()), 'vh_' + what)
     return dst
 
 
@@ -839,6 +844,34 @@ def attn_rows_packed_bf16(q, kcache, vcache, out, n_heads, rows):
         S_max, ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()),
         'vh_attn_rows_packed_bf16')
     return out
+
+
+def attn_rows_packed_lm_bf16(q, kcache, vcache, out, n_heads, rows):
+    """`attn_rows_packed_bf16` under the PREFIX-LM mask: every segment of `rows` (an engine.PackedRows built with x_lens, or an
+    engine.PromptRows) attends its own rows of ONE 16-bit K/V stream under the prefix mask of its own text length — per segment
+    the bits of `attn_rows_bf16(B=1, Tq=Tk=len, MASK_PREFIX, x_len)` on it alone (vh_attn_rows_packed_lm_bf16).  Operands as for
+    `attn_rows_packed_bf16`."""
+    S_max = kcache.shape[2]
+    M = rows.rows
+    if tuple(kcache.shape) != (1, n_heads, S_max, HEAD_DIM) or kcache.shape != vcache.shape or M > S_max:
+        raise _lib.VhError(f'attn_rows_packed_lm_bf16: cache {tuple(kcache.shape)} M={M}')
+    if q.shape[0] != M or out.shape[0] != M:
+        raise _lib.VhError('attn_rows_packed_lm_bf16: q/out rows')
+    if rows.seg_x_len is None:
+        raise _lib.VhError('attn_rows_packed_lm_bf16: the prefix mask needs PackedRows(lengths, device, x_lens)')
+    check(_lib.lib().vh_attn_rows_packed_lm_bf16(
+        _bf16(q, 'q'), q.stride(0), _bf16(kcache, 'kcache'), _bf16(vcache, 'vcache'), _bf16(out, 'out'), out.stride(0), n_heads,
+        S_max, ptr(rows.seg_start), ptr(rows.seg_len), ptr(rows.seg_x_len), rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()),
+        'vh_attn_rows_packed_lm_bf16')
+    return out
+
+
+def kv_unpack_bf16(src, dst, seg_start, seg_len, dst_row):
+    """`kv_unpack` for 16-bit streams (vh_kv_unpack_bf16): src (..., h, S_src, 64) and dst (..., B_dst, h, S_dst, 64) contiguous
+    H16 with the same leading streams; the same tables, the same cuts, a bit-exact copy and nothing else of dst written."""
+    if src.dtype != H16 or dst.dtype != H16 or not src.is_contiguous() or not dst.is_contiguous():
+        raise _lib.VhError(f'kv_unpack_bf16: src and dst must be contiguous {H16}')
+    return _kv_unpack('kv_unpack_bf16', _lib.lib().vh_kv_unpack_bf16, src, dst, seg_start, seg_len, dst_row)
 
 
 def greedy_step(logits, V, eos, codes, eos_count, audio_emb, pe, audio_pos, cache_len, x_next,

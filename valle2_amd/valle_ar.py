@@ -78,6 +78,12 @@ class ValleAR(_Base):
     # (A model that lives on the CPU computes through a cached device copy: set the switch on the class, or before the first
     # call.)
     packed_prompt = None
+    # The same for PERF MODE, a switch of its own (`packed_prompt` leaves perf-mode calls on the padded pass): None: on when
+    # VALLE2_PACKED_PROMPT_PERF=1 is in the environment of the call, else off; True / False override.  It takes effect where the
+    # call qualifies (generation.packed_prompt_perf_qualifies: utterances of different lengths, perf_mode True or 'kv', head
+    # width 64, independent cached rows, no `forced`): perf_mode=True runs the 16-bit packed pass into the 16-bit row cache,
+    # 'kv' (or a shape the 16-bit stack does not take) the fp32 packed pass, narrowed once; every other call runs the padded pass.
+    packed_prompt_perf = None
 
     def __init__(self, config):
         super().__init__()
