@@ -466,6 +466,37 @@ int vh_attn_decode_hd(const float* q, int ldq, const float* kcache, const float*
                       const int32_t* cache_len, int len_bias, int B, int n_heads, int head_dim, int S_max, float scale,
                       int n_split, void* partial, size_t partial_bytes, void* stream);
 
+/* ---- many-row attention (forward) at a head width other than 64 ------------------------------------------------------
+ * vh_attn_rows without a cache layout: one flash kernel over fp32 q (B, h, Tq, head_dim), k / v (B, h, Tk, head_dim) and
+ * out (B, h, Tq, head_dim) given as STRIDED VIEWS with unit stride in the last dimension — element (b, head, row, c) of an
+ * operand lies at base + b * sb + head * sh + row * sr + c (strides in floats) — so the per-head column blocks of a
+ * (rows, 3 d) QKV projection are read in place and out is the per-head columns of a (rows, d) buffer: no transposition
+ * pass, no staging copy, and no (B, h, Tq, Tk) score map (scores live in registers, K / V tiles in LDS).
+ * scale is the softmax scale (callers pass (float)(1 / sqrt((double)head_dim))).  A pure addition of ABI 146: no earlier
+ * symbol, struct or behaviour changes, and VH_VERSION stays.
+ * Masks: the analytic modes of vh_attn_rows with its exact semantics — query row i sits at key position q_off + i,
+ * q_off = Tk - Tq; kvl(b) = kv_len ? min(kv_len[b], Tk) : Tk; xl(b) = x_len_dev ? x_len_dev[b] : x_len;
+ *   VH_MASK_FULL   : key j visible iff j < kvl(b)
+ *   VH_MASK_PREFIX : key j visible iff j < kvl(b) && (j < xl(b) || (q_off+i >= xl(b) && j <= q_off+i))   (causal: x_len = 0)
+ *   VH_MASK_EXPLICIT is refused (VH_EUNSUPPORTED): caller-supplied masks keep the materialised route.
+ * A row with kv_len[b] <= 0 has no visible key: its workgroups load no key tile and every query of the row gets NaN in all
+ * its head_dim outputs (0 / 0 — what vh_attn_rows at width 64 and SDPA give for a fully masked row); with kv_len[b] >= 1
+ * every query sees key 0 in either mode.  Keys kvl(b) .. Tk - 1 are read (they meet weight 0) and must be finite, as for
+ * vh_attn_rows.
+ * head_dim: a multiple of 4 from 16 to 128 (64 included, for comparisons); anything else — 132..256 too, which the decode
+ * kernel takes — is VH_EUNSUPPORTED.  One body compiled for NB = ceil(head_dim / 32) in {1, 2, 3, 4}; columns head_dim ..
+ * 32 NB - 1 are zero-filled on chip and never loaded or stored: nothing outside the operands' head_dim columns is touched.
+ * All checks run before any launch: a null q / k / v / out, a mode that is not one of the three, B / n_heads / Tq <= 0 or
+ * Tq > Tk, a stride that is not a multiple of 4 floats (rows must stay 16-byte aligned) -> VH_EINVAL; a q / k / v / out that
+ * is not 16-byte aligned -> VH_EALIGN; a negative k / v row stride, or one that puts key row Tk - 1 more than 2^30 floats
+ * after row 0 (the kernel's key offsets are 32-bit) -> VH_EUNSUPPORTED.  Deterministic (no atomics). */
+int vh_attn_rows_hd(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sr,
+                    const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sr,
+                    const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sr,
+                    float* out, int64_t o_sb, int64_t o_sh, int64_t o_sr,
+                    int B, int n_heads, int head_dim, int Tq, int Tk, float scale,
+                    int mode, int x_len, const int32_t* x_len_dev, const int32_t* kv_len, void* stream);
+
 /* ---- perf mode of the decode step: bf16 K/V cache (opt-in; never the parity path) ---------------
  * SURVEY.md section 7's "perf mode": the K/V cache — 93 % of the bytes a decode step reads at configs[1] — stored
  * as bf16 (B, h, S_max, 64), everything else (weights, q, softmax, accumulators, residual stream) fp32 as in the parity

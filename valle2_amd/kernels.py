@@ -7,6 +7,7 @@ Nothing here computes on the CPU.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -485,6 +486,7 @@ def attn_generic(q, k, v, out, scale, **spec):
     place).  Returns P (B, h, Tq, Tk) for a backward that wants it."""
     B, h, Tq, hd = q.shape
     Tk = k.shape[2]
+    ATTN_HD_CALLS['materialized'] += 1
     tp = (Tk + 3) // 4 * 4
     P = torch.empty(B, h, Tq, tp, device=q.device, dtype=torch.float32)[..., :Tk]
     gemm(q, k, P)                                               # raw scores
@@ -498,6 +500,59 @@ def attn_generic(q, k, v, out, scale, **spec):
         softmax_rows(P, tp, B, h, Tq, Tk, scale, **spec)
     gemm(P, v, out, b_kmajor=True)
     return P
+
+
+# The flash route of the many-row attention at head widths other than 64 (vh_attn_rows_hd).  None: the environment variable
+# VALLE2_ATTN_HD_FLASH=1 decides; True / False: this value does.  Default OFF.  attn_hd_route answers for callers that pick
+# a route per call (tools/ab_attn_hd.py); the stack (engine._transformer_forward_generic) does not ask it yet and always
+# takes attn_generic: the same kernels, launches and bits as before (DESIGN.md section 3.17 says why).
+ATTN_HD_FLASH = None
+ATTN_HD_CALLS = {'flash': 0, 'materialized': 0}     # calls of attn_rows_hd / attn_generic since reset_attn_hd_calls()
+
+
+def reset_attn_hd_calls():
+    for key in ATTN_HD_CALLS:
+        ATTN_HD_CALLS[key] = 0
+
+
+def attn_hd_route(hd, spec):
+    """Which many-row attention a head width and a mask spec take: 'flash' (attn_rows_hd) when the switch is on, hd is a
+    multiple of 4 from 16 to 128 other than 64 (which has attention.hip's kernels) and `spec` carries no caller-supplied
+    `mask` / `pad`; 'materialized' (attn_generic) otherwise.  Pure: no device, no library call."""
+    on = ATTN_HD_FLASH if ATTN_HD_FLASH is not None else os.environ.get('VALLE2_ATTN_HD_FLASH') == '1'
+    if not on or hd == HEAD_DIM or hd % 4 or not 16 <= hd <= 128:
+        return 'materialized'
+    if spec.get('mask') is not None or spec.get('pad') is not None or spec.get('mode', MASK_FULL) == MASK_EXPLICIT:
+        return 'materialized'
+    return 'flash'
+
+
+def attn_rows_hd(q, k, v, out, scale, **spec):
+    """`attn_generic` without the score map: one flash kernel (vh_attn_rows_hd) over the same views — q (B, h, Tq, hd),
+    k / v (B, h, Tk, hd), out (B, h, Tq, hd) with unit stride in the last dimension, the per-head column blocks of a
+    (rows, 3 d) projection read in place — for hd a multiple of 4 from 16 to 128 and the analytic masks of `spec` (mode,
+    x_len, x_len_dev, kv_len; a `mask` or `pad` is refused: those keep attn_generic).  Nothing is returned: no P exists."""
+    if spec.get('mask') is not None or spec.get('pad') is not None:
+        raise _lib.VhError('attn_rows_hd: caller-supplied masks take attn_generic')
+    if q.dim() != 4 or out.shape != q.shape or k.shape != v.shape or k.dim() != 4 or k.shape[:2] != q.shape[:2] \
+            or k.shape[3] != q.shape[3]:
+        raise _lib.VhError(f'attn_rows_hd: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} out {tuple(out.shape)}')
+    for t, name in ((q, 'q'), (k, 'k'), (v, 'v'), (out, 'out')):
+        _f32(t, name)
+        if not t.is_cuda or t.stride(3) != 1:
+            raise _lib.VhError(f'attn_rows_hd: {name} must be a device view with unit stride in the last dimension')
+    B, h, Tq, hd = q.shape
+    Tk = k.shape[2]
+    for t_, name in ((spec.get('x_len_dev'), 'x_len_dev'), (spec.get('kv_len'), 'kv_len')):
+        if t_ is not None and (t_.dtype != torch.int32 or t_.numel() < B or not t_.is_cuda or not t_.is_contiguous()):
+            raise _lib.VhError(f'attn_rows_hd: {name} must be a contiguous device int32 tensor of B entries')
+    ATTN_HD_CALLS['flash'] += 1
+    check(_lib.lib().vh_attn_rows_hd(
+        q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
+        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), out.data_ptr(), out.stride(0), out.stride(1), out.stride(2),
+        B, h, hd, Tq, Tk, float(scale), spec.get('mode', MASK_FULL), int(spec.get('x_len', 0)), ptr(spec.get('x_len_dev')),
+        ptr(spec.get('kv_len')), stream()), 'vh_attn_rows_hd')
+    return out
 
 
 def attn_decode_ws(B, n_heads, n_split, device):
