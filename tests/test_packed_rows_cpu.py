@@ -183,6 +183,8 @@ def test_forward_packed_refuses_a_bad_descriptor(L, kw, code, text):
     ((I32, I32, 3, None, 4), EINVAL, 'blocks'),
     ((I32, I32, 0, I32, 4), EINVAL, 'n_seg=0'),
     ((I32, I32, 3, I32, 0), EINVAL, 'n_blocks=0'),
+    # under the composite's own name, before anything is launched (it used to come from vh_attn_rows_packed inside layer 0)
+    ((I32, I32, 3, I32, 1 << 30), EUNSUPPORTED, 'vh_transformer_forward_packed: n_blocks=1073741824 x n_heads=2 workgroups'),
 ])
 def test_forward_packed_refuses_bad_segment_arguments(L, args, code, text):
     layers = _layers()

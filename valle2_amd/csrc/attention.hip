@@ -567,16 +567,12 @@ extern "C" int vh_attn_rows_packed(const float* q, int ldq, const float* kcache,
     VH_REQUIRE(q && kcache && vcache && out, VH_EINVAL, "vh_attn_rows_packed: null pointer (q, kcache, vcache or out)");
     VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL, "vh_attn_rows_packed: null pointer (seg_start, seg_len or blocks)");
     VH_REQUIRE(n_heads > 0 && S_max >= 1, VH_EINVAL, "vh_attn_rows_packed: bad dims n_heads=%d S_max=%d", n_heads, S_max);
-    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_packed: n_seg=%d", n_seg);
-    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_attn_rows_packed: n_blocks=%d", n_blocks);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD, VH_EINVAL, "vh_attn_rows_packed: ldq=%d", ldq);
-    VH_REQUIRE(ldo % 4 == 0 && ldo >= n_heads * HD, VH_EINVAL, "vh_attn_rows_packed: ldo=%d", ldo);
+    VH_TRY(vh_packed_attn_sizes("vh_attn_rows_packed", n_heads, n_seg, n_blocks, ldq, ldo, 4));
     VH_REQUIRE(vh_aligned16(q), VH_EALIGN, "vh_attn_rows_packed: q must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(out), VH_EALIGN, "vh_attn_rows_packed: out must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(kcache) && vh_aligned16(vcache), VH_EALIGN,
                "vh_attn_rows_packed: kcache and vcache must be 16-byte aligned");
-    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED, "vh_attn_rows_packed: n_blocks=%d x n_heads=%d workgroups",
-               n_blocks, n_heads);
+    VH_TRY(vh_packed_workgroups("vh_attn_rows_packed", n_blocks, n_heads));
     RowsArgs a{q, ldq, kcache, vcache, out, ldo, n_heads, 0, 0, S_max, VH_MASK_FULL, 0,
                nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0};
     PackedSegs ps{seg_start, seg_len, blocks, n_seg, S_max};
@@ -1784,16 +1780,12 @@ extern "C" int vh_attn_rows_packed_lse(const float* q, int ldq, const float* kca
     VH_REQUIRE(mode == VH_MASK_FULL || mode == VH_MASK_PREFIX, VH_EINVAL, "vh_attn_rows_packed_lse: mode=%d (full or prefix)", mode);
     VH_REQUIRE(mode != VH_MASK_PREFIX || seg_x_len, VH_EINVAL, "vh_attn_rows_packed_lse: the prefix mask needs seg_x_len");
     VH_REQUIRE(n_heads > 0 && M >= 1 && S_max >= M, VH_EINVAL, "vh_attn_rows_packed_lse: bad dims n_heads=%d M=%d S_max=%d", n_heads, M, S_max);
-    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_packed_lse: n_seg=%d", n_seg);
-    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_attn_rows_packed_lse: n_blocks=%d", n_blocks);
-    VH_REQUIRE(ldq % 4 == 0 && ldq >= n_heads * HD, VH_EINVAL, "vh_attn_rows_packed_lse: ldq=%d", ldq);
-    VH_REQUIRE(ldo % 4 == 0 && ldo >= n_heads * HD, VH_EINVAL, "vh_attn_rows_packed_lse: ldo=%d", ldo);
+    VH_TRY(vh_packed_attn_sizes("vh_attn_rows_packed_lse", n_heads, n_seg, n_blocks, ldq, ldo, 4));
     VH_REQUIRE(vh_aligned16(q) && vh_aligned16(out), VH_EALIGN, "vh_attn_rows_packed_lse: q and out must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(kcache) && vh_aligned16(vcache), VH_EALIGN,
                "vh_attn_rows_packed_lse: kcache and vcache must be 16-byte aligned");
     VH_REQUIRE(((uintptr_t)lse2 & 3) == 0, VH_EALIGN, "vh_attn_rows_packed_lse: lse2 must be 4-byte aligned");
-    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED, "vh_attn_rows_packed_lse: n_blocks=%d x n_heads=%d workgroups",
-               n_blocks, n_heads);
+    VH_TRY(vh_packed_workgroups("vh_attn_rows_packed_lse", n_blocks, n_heads));
     RowsArgs a{q, ldq, kcache, vcache, out, ldo, n_heads, M, 0, S_max, mode, 0,
                nullptr, nullptr, nullptr, nullptr, 0, lse2, 0};
     PackedSegs ps{seg_start, seg_len, blocks, n_seg, M};        // n_rows = M: a segment reaching past it is cut (lse2 has M rows)

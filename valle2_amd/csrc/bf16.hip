@@ -666,16 +666,12 @@ extern "C" int vh_attn_rows_packed_bf16(const uint16_t* q, int ldq_, const uint1
     VH_REQUIRE(q && kcache16 && vcache16 && out, VH_EINVAL, "vh_attn_rows_packed_bf16: null pointer (q, kcache16, vcache16 or out)");
     VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL, "vh_attn_rows_packed_bf16: null pointer (seg_start, seg_len or blocks)");
     VH_REQUIRE(n_heads > 0 && S_max >= 1, VH_EINVAL, "vh_attn_rows_packed_bf16: bad dims n_heads=%d S_max=%d", n_heads, S_max);
-    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_packed_bf16: n_seg=%d", n_seg);
-    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_attn_rows_packed_bf16: n_blocks=%d", n_blocks);
-    VH_REQUIRE(ldq_ % 8 == 0 && ldq_ >= n_heads * VH_HEAD_DIM, VH_EINVAL, "vh_attn_rows_packed_bf16: ldq=%d", ldq_);
-    VH_REQUIRE(ldo % 8 == 0 && ldo >= n_heads * VH_HEAD_DIM, VH_EINVAL, "vh_attn_rows_packed_bf16: ldo=%d", ldo);
+    VH_TRY(vh_packed_attn_sizes("vh_attn_rows_packed_bf16", n_heads, n_seg, n_blocks, ldq_, ldo, 8));
     VH_REQUIRE(vh_aligned16(q), VH_EALIGN, "vh_attn_rows_packed_bf16: q must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(out), VH_EALIGN, "vh_attn_rows_packed_bf16: out must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(kcache16) && vh_aligned16(vcache16), VH_EALIGN,
                "vh_attn_rows_packed_bf16: kcache16 and vcache16 must be 16-byte aligned");
-    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
-               "vh_attn_rows_packed_bf16: n_blocks=%d x n_heads=%d workgroups", n_blocks, n_heads);
+    VH_TRY(vh_packed_workgroups("vh_attn_rows_packed_bf16", n_blocks, n_heads));
     // (B, Tq, Tk, the mask fields and n_qb are the padded kernel's: the packed one reads them from the segment table)
     Attn16Args a{q, ldq_, kcache16, vcache16, out, ldo, 1, n_heads, 0, 0, S_max, VH_MASK_FULL, 0, nullptr, nullptr, 0};
     Packed16Segs ps{seg_start, seg_len, blocks, n_seg};
@@ -692,16 +688,12 @@ extern "C" int vh_attn_rows_packed_lm_bf16(const uint16_t* q, int ldq_, const ui
     VH_REQUIRE(seg_start && seg_len && seg_x_len && blocks, VH_EINVAL,
                "vh_attn_rows_packed_lm_bf16: null pointer (seg_start, seg_len, seg_x_len or blocks)");
     VH_REQUIRE(n_heads > 0 && S_max >= 1, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: bad dims n_heads=%d S_max=%d", n_heads, S_max);
-    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: n_seg=%d", n_seg);
-    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: n_blocks=%d", n_blocks);
-    VH_REQUIRE(ldq_ % 8 == 0 && ldq_ >= n_heads * VH_HEAD_DIM, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: ldq=%d", ldq_);
-    VH_REQUIRE(ldo % 8 == 0 && ldo >= n_heads * VH_HEAD_DIM, VH_EINVAL, "vh_attn_rows_packed_lm_bf16: ldo=%d", ldo);
+    VH_TRY(vh_packed_attn_sizes("vh_attn_rows_packed_lm_bf16", n_heads, n_seg, n_blocks, ldq_, ldo, 8));
     VH_REQUIRE(vh_aligned16(q), VH_EALIGN, "vh_attn_rows_packed_lm_bf16: q must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(out), VH_EALIGN, "vh_attn_rows_packed_lm_bf16: out must be 16-byte aligned");
     VH_REQUIRE(vh_aligned16(kcache16) && vh_aligned16(vcache16), VH_EALIGN,
                "vh_attn_rows_packed_lm_bf16: kcache16 and vcache16 must be 16-byte aligned");
-    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
-               "vh_attn_rows_packed_lm_bf16: n_blocks=%d x n_heads=%d workgroups", n_blocks, n_heads);
+    VH_TRY(vh_packed_workgroups("vh_attn_rows_packed_lm_bf16", n_blocks, n_heads));
     // (as in vh_attn_rows_packed_bf16: the kernel reads the lengths and the text lengths from the segment table)
     Attn16Args a{q, ldq_, kcache16, vcache16, out, ldo, 1, n_heads, 0, 0, S_max, VH_MASK_PREFIX, 0, nullptr, nullptr, 0};
     Packed16LmSegs ps{seg_start, seg_len, blocks, seg_x_len, n_seg};
@@ -713,15 +705,7 @@ extern "C" int vh_attn_rows_packed_lm_bf16(const uint16_t* q, int ldq_, const ui
 // =============================================================================================
 // composite: the full-sequence forward of vh_transformer_forward with bf16 operands
 // =============================================================================================
-#define TRY16(call) do { int rc_ = (call); if (rc_ != VH_OK) return rc_; } while (0)
-
-// the segments of a packed forward (vh_transformer_forward_packed_bf16, or with seg_x_len vh_transformer_forward_packed_lm_bf16);
-// null: the padded (B, T) layout
-struct packed_rows16 {
-    const int32_t *seg_start, *seg_len, *blocks;
-    int n_seg, n_blocks;
-    const int32_t* seg_x_len;         // the text length inside each segment: the prefix-LM mask; null: the full mask
-};
+#define TRY16(call) VH_TRY(call)
 
 // every layer's 16-bit matrices and caches are there, said before the first layer is launched (`name`: the entry point
 // the refusal is reported under)
@@ -736,7 +720,7 @@ static int layers16_complete(const vh_forward16_desc* f, const char* name) {
 
 // the layers of the three forwards: the same launches in the same order, the packed ones with vh_attn_rows_packed_bf16 or
 // vh_attn_rows_packed_lm_bf16 for vh_attn_rows_bf16
-static int forward16_layers(const vh_forward16_desc* f, const packed_rows16* pk, void* stream) {
+static int forward16_layers(const vh_forward16_desc* f, const vh_segments* pk, void* stream) {
     const int B = f->B, T = f->T, D = f->d_model, M = B * T;
     for (int i = 0; i < f->n_layers; ++i) {
         const vh_layer& L = f->layers[i];
@@ -777,31 +761,14 @@ extern "C" int vh_transformer_forward_bf16(const vh_forward16_desc* f, void* str
     return forward16_layers(f, nullptr, stream);
 }
 
-// what both packed composites refuse alike, under the name of the entry point that was called: the descriptor and the segment
-// arguments (packed16_front, before the mask fields are looked at) ...
-static int packed16_front(const char* name, const vh_forward16_desc* f, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
-                          const int32_t* blocks, int n_blocks) {
-    VH_REQUIRE(f && f->layers && f->layers16 && f->x && f->xn16 && f->q16 && f->attn16 && f->hidden16, VH_EINVAL,
-               "%s: null pointer in desc", name);
-    VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL,
-               "%s: null pointer (seg_start, seg_len or blocks)", name);
-    VH_REQUIRE(f->B == 1, VH_EINVAL, "%s: B=%d (the packed rows are ONE row stream: B = 1, T = the "
-               "sum of the segment lengths)", name, f->B);
-    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "%s: bad dims T=%d L=%d", name, f->T, f->n_layers);
-    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "%s: S_max=%d < T=%d", name, f->S_max, f->T);
-    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "%s: n_seg=%d", name, n_seg);
-    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "%s: n_blocks=%d", name, n_blocks);
-    return VH_OK;
-}
-
-// ... and the shapes the 16-bit stack takes, and every pointer of the descriptor and of both layer tables (packed16_back)
+// what both packed composites refuse alike past vh_common.h's vh_packed_front / vh_packed_mask, under the name of the entry point
+// that was called: the shapes the 16-bit stack takes, and every pointer of the descriptor and of both layer tables
 static int packed16_back(const char* name, const vh_forward16_desc* f, int n_blocks) {
     VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM && f->d_model % 128 == 0 && f->dff % 128 == 0, VH_EUNSUPPORTED,
                "%s: d_model=%d dff=%d (n_heads x 64, multiples of 128)", name, f->d_model, f->dff);
     VH_REQUIRE(f->d_model <= 4096, VH_EUNSUPPORTED, "%s: d_model=%d (vh_layernorm_bf16 serves <= 4096)", name,
                f->d_model);
-    VH_REQUIRE((int64_t)n_blocks * f->n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
-               "%s: n_blocks=%d x n_heads=%d workgroups", name, n_blocks, f->n_heads);
+    TRY16(vh_packed_workgroups(name, n_blocks, f->n_heads));
     // what the launches of any layer would refuse for a pointer — null or not 16-byte aligned — said here, under this entry
     // point's name, before anything is launched
     VH_REQUIRE(vh_aligned16(f->x) && vh_aligned16(f->x_in) && vh_aligned16(f->ada), VH_EALIGN,
@@ -825,31 +792,29 @@ static int packed16_back(const char* name, const vh_forward16_desc* f, int n_blo
     return VH_OK;
 }
 
+static bool desc16_complete(const vh_forward16_desc* f) {
+    return f && f->layers && f->layers16 && f->x && f->xn16 && f->q16 && f->attn16 && f->hidden16;
+}
+
 extern "C" int vh_transformer_forward_packed_bf16(const vh_forward16_desc* f, const int32_t* seg_start, const int32_t* seg_len,
                                                   int n_seg, const int32_t* blocks, int n_blocks, void* stream) {
     const char* name = "vh_transformer_forward_packed_bf16";
-    TRY16(packed16_front(name, f, seg_start, seg_len, n_seg, blocks, n_blocks));
-    VH_REQUIRE(f->mode == VH_MASK_FULL, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed_bf16: mode=%d (segments attend under the full mask only)", f->mode);
-    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: kv_len is set (a segment's length is its key length)");
-    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed_bf16: x_len_dev is set (no prefix mask over segments)");
+    const vh_segments sg{seg_start, seg_len, blocks, n_seg, n_blocks, nullptr, nullptr};
+    TRY16(vh_packed_front(name, f, desc16_complete(f), sg));
+    TRY16(vh_packed_mask(name, f, false));
     TRY16(packed16_back(name, f, n_blocks));
-    const packed_rows16 pk{seg_start, seg_len, blocks, n_seg, n_blocks, nullptr};
-    return forward16_layers(f, &pk, stream);
+    return forward16_layers(f, &sg, stream);
 }
 
 extern "C" int vh_transformer_forward_packed_lm_bf16(const vh_forward16_desc* f, const int32_t* seg_start, const int32_t* seg_len,
                                                      const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks,
                                                      void* stream) {
     const char* name = "vh_transformer_forward_packed_lm_bf16";
-    TRY16(packed16_front(name, f, seg_start, seg_len, n_seg, blocks, n_blocks));
+    const vh_segments sg{seg_start, seg_len, blocks, n_seg, n_blocks, seg_x_len, nullptr};
+    TRY16(vh_packed_front(name, f, desc16_complete(f), sg));
     VH_REQUIRE(seg_x_len, VH_EINVAL, "vh_transformer_forward_packed_lm_bf16: null pointer (seg_x_len)");
-    VH_REQUIRE(f->mode == VH_MASK_PREFIX, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed_lm_bf16: mode=%d (segments attend under their prefix-LM masks: VH_MASK_PREFIX)", f->mode);
-    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm_bf16: kv_len is set (a segment's length is its key length)");
-    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm_bf16: x_len_dev is set (the text lengths are seg_x_len)");
+    TRY16(vh_packed_mask(name, f, true));
     VH_REQUIRE(!f->ada, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm_bf16: ada is set (LayerNorm stacks only)");
     TRY16(packed16_back(name, f, n_blocks));
-    const packed_rows16 pk{seg_start, seg_len, blocks, n_seg, n_blocks, seg_x_len};
-    return forward16_layers(f, &pk, stream);
+    return forward16_layers(f, &sg, stream);
 }

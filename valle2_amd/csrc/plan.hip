@@ -34,11 +34,7 @@ extern "C" int vh_version(void) { return VH_VERSION; }
         VH_REQUIRE(e_ == hipSuccess, VH_ELAUNCH, #call ": %s", hipGetErrorString(e_)); \
     } while (0)
 
-#define TRY(call)                \
-    do {                         \
-        int rc_ = (call);        \
-        if (rc_ != VH_OK) return rc_; \
-    } while (0)
+#define TRY(call) VH_TRY(call)
 
 // ---------------------------------------------------------------------------------------------
 // AR decoder
@@ -433,17 +429,8 @@ extern "C" int vh_ar_decoder_profile_attn(vh_ar_decoder* dec, int n_steps, void*
 // ---------------------------------------------------------------------------------------------
 // full-sequence forward (prefill / NAR stage / training forward)
 // ---------------------------------------------------------------------------------------------
-// the segments of a packed forward (vh_transformer_forward_packed); null: the padded (B, T) layout.  seg_x_len set: the
-// prefix-LM form (vh_transformer_forward_packed_lm), each segment's text length and the lse2 rows its attention kernel writes
-struct packed_rows {
-    const int32_t *seg_start, *seg_len, *blocks;
-    int n_seg, n_blocks;
-    const int32_t* seg_x_len;
-    float* lse2;
-};
-
 // the layers of both forwards: the same launches in the same order, the packed one with vh_attn_rows_packed for vh_attn_rows
-static int forward_layers(const vh_forward_desc* f, const packed_rows* pk, void* stream) {
+static int forward_layers(const vh_forward_desc* f, const vh_segments* pk, void* stream) {
     const int B = f->B, T = f->T, D = f->d_model, M = B * T;
     for (int i = 0; i < f->n_layers; ++i) {
         const vh_layer& L = f->layers[i];
@@ -486,37 +473,42 @@ extern "C" int vh_transformer_forward(const vh_forward_desc* f, void* stream) {
     return forward_layers(f, nullptr, stream);
 }
 
+// What both packed forwards refuse alike past vh_common.h's vh_packed_front / vh_packed_stream / vh_packed_mask, under the name of
+// the entry point that was called: the masks of the padded forward (packed_no_masks) ...
+static int packed_no_masks(const char* name, const vh_forward_desc* f) {
+    VH_REQUIRE(!f->mask, VH_EUNSUPPORTED, "%s: mask is set (no explicit mask over segments)", name);
+    VH_REQUIRE(!f->pad, VH_EUNSUPPORTED, "%s: pad is set (packed rows have no padding)", name);
+    return VH_OK;
+}
+
+// ... and the head width, and what the packed attention would refuse inside layer 0 (lse2 where there is one), said before
+// anything is launched (packed_back)
+static int packed_back(const char* name, const vh_forward_desc* f, const vh_segments& sg) {
+    VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM, VH_EUNSUPPORTED, "%s: d_model=%d != n_heads=%d x 64", name, f->d_model,
+               f->n_heads);
+    VH_REQUIRE(vh_aligned16(f->q), VH_EALIGN, "%s: q must be 16-byte aligned", name);
+    VH_REQUIRE(vh_aligned16(f->attn), VH_EALIGN, "%s: attn must be 16-byte aligned", name);
+    VH_REQUIRE((reinterpret_cast<uintptr_t>(sg.lse2) & 3u) == 0, VH_EALIGN, "%s: lse2 must be 4-byte aligned", name);
+    TRY(vh_packed_workgroups(name, sg.n_blocks, f->n_heads));
+    for (int i = 0; i < f->n_layers; ++i) {
+        VH_REQUIRE(f->layers[i].kcache && f->layers[i].vcache, VH_EINVAL, "%s: null kcache / vcache (layer %d)", name, i);
+        VH_REQUIRE(vh_aligned16(f->layers[i].kcache) && vh_aligned16(f->layers[i].vcache), VH_EALIGN,
+                   "%s: kcache and vcache must be 16-byte aligned (layer %d)", name, i);
+    }
+    return VH_OK;
+}
+
+static bool desc_complete(const vh_forward_desc* f) { return f && f->layers && f->x && f->xn && f->q && f->attn && f->hidden; }
+
 extern "C" int vh_transformer_forward_packed(const vh_forward_desc* f, const int32_t* seg_start, const int32_t* seg_len, int n_seg,
                                              const int32_t* blocks, int n_blocks, void* stream) {
-    VH_REQUIRE(f && f->layers && f->x && f->xn && f->q && f->attn && f->hidden, VH_EINVAL,
-               "vh_transformer_forward_packed: null pointer in desc");
-    VH_REQUIRE(seg_start && seg_len && blocks, VH_EINVAL,
-               "vh_transformer_forward_packed: null pointer (seg_start, seg_len or blocks)");
-    VH_REQUIRE(f->B == 1, VH_EINVAL, "vh_transformer_forward_packed: B=%d (the packed rows are ONE row stream: B = 1, T = the sum "
-               "of the segment lengths)", f->B);
-    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "vh_transformer_forward_packed: bad dims T=%d L=%d", f->T, f->n_layers);
-    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "vh_transformer_forward_packed: S_max=%d < T=%d", f->S_max, f->T);
-    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_transformer_forward_packed: n_seg=%d", n_seg);
-    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_transformer_forward_packed: n_blocks=%d", n_blocks);
-    VH_REQUIRE(f->mode == VH_MASK_FULL, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed: mode=%d (segments attend under the full mask only)", f->mode);
-    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed: kv_len is set (a segment's length is its key length)");
-    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed: x_len_dev is set (no prefix mask over segments)");
-    VH_REQUIRE(!f->mask, VH_EUNSUPPORTED, "vh_transformer_forward_packed: mask is set (no explicit mask over segments)");
-    VH_REQUIRE(!f->pad, VH_EUNSUPPORTED, "vh_transformer_forward_packed: pad is set (packed rows have no padding)");
-    VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed: d_model=%d != n_heads=%d x 64", f->d_model, f->n_heads);
-    // what vh_attn_rows_packed would refuse inside layer 0, said before anything is launched
-    VH_REQUIRE(vh_aligned16(f->q), VH_EALIGN, "vh_transformer_forward_packed: q must be 16-byte aligned");
-    VH_REQUIRE(vh_aligned16(f->attn), VH_EALIGN, "vh_transformer_forward_packed: attn must be 16-byte aligned");
-    for (int i = 0; i < f->n_layers; ++i) {
-        VH_REQUIRE(f->layers[i].kcache && f->layers[i].vcache, VH_EINVAL,
-                   "vh_transformer_forward_packed: null kcache / vcache (layer %d)", i);
-        VH_REQUIRE(vh_aligned16(f->layers[i].kcache) && vh_aligned16(f->layers[i].vcache), VH_EALIGN,
-                   "vh_transformer_forward_packed: kcache and vcache must be 16-byte aligned (layer %d)", i);
-    }
-    const packed_rows pk{seg_start, seg_len, blocks, n_seg, n_blocks, nullptr, nullptr};
-    return forward_layers(f, &pk, stream);
+    const char* name = "vh_transformer_forward_packed";
+    const vh_segments sg{seg_start, seg_len, blocks, n_seg, n_blocks, nullptr, nullptr};
+    TRY(vh_packed_front(name, f, desc_complete(f), sg));
+    TRY(vh_packed_mask(name, f, false));
+    TRY(packed_no_masks(name, f));
+    TRY(packed_back(name, f, sg));
+    return forward_layers(f, &sg, stream);
 }
 
 // The prompt pass of a ragged batch over packed rows: vh_transformer_forward_packed's launches under the prefix-LM mask of
@@ -525,38 +517,16 @@ extern "C" int vh_transformer_forward_packed(const vh_forward_desc* f, const int
 extern "C" int vh_transformer_forward_packed_lm(const vh_forward_desc* f, const int32_t* seg_start, const int32_t* seg_len,
                                                 const int32_t* seg_x_len, int n_seg, const int32_t* blocks, int n_blocks,
                                                 float* lse2, void* stream) {
-    VH_REQUIRE(f && f->layers && f->x && f->xn && f->q && f->attn && f->hidden, VH_EINVAL,
-               "vh_transformer_forward_packed_lm: null pointer in desc");
+    const char* name = "vh_transformer_forward_packed_lm";
+    const vh_segments sg{seg_start, seg_len, blocks, n_seg, n_blocks, seg_x_len, lse2};
+    VH_REQUIRE(desc_complete(f), VH_EINVAL, "vh_transformer_forward_packed_lm: null pointer in desc");
     VH_REQUIRE(seg_start && seg_len && seg_x_len && blocks, VH_EINVAL,
                "vh_transformer_forward_packed_lm: null pointer (seg_start, seg_len, seg_x_len or blocks)");
     VH_REQUIRE(lse2, VH_EINVAL, "vh_transformer_forward_packed_lm: null pointer (lse2: (n_heads, T) floats of scratch)");
-    VH_REQUIRE(f->B == 1, VH_EINVAL, "vh_transformer_forward_packed_lm: B=%d (the packed rows are ONE row stream: B = 1, T = the "
-               "sum of the segment lengths)", f->B);
-    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "vh_transformer_forward_packed_lm: bad dims T=%d L=%d", f->T, f->n_layers);
-    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "vh_transformer_forward_packed_lm: S_max=%d < T=%d", f->S_max, f->T);
-    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "vh_transformer_forward_packed_lm: n_seg=%d", n_seg);
-    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "vh_transformer_forward_packed_lm: n_blocks=%d", n_blocks);
-    VH_REQUIRE(f->mode == VH_MASK_PREFIX, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed_lm: mode=%d (segments attend under their prefix-LM masks: VH_MASK_PREFIX)", f->mode);
-    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: kv_len is set (a segment's length is its key length)");
-    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: x_len_dev is set (the text lengths are seg_x_len)");
-    VH_REQUIRE(!f->mask, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: mask is set (no explicit mask over segments)");
-    VH_REQUIRE(!f->pad, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: pad is set (packed rows have no padding)");
+    TRY(vh_packed_stream(name, f, n_seg, n_blocks));
+    TRY(vh_packed_mask(name, f, true));
+    TRY(packed_no_masks(name, f));
     VH_REQUIRE(!f->ada, VH_EUNSUPPORTED, "vh_transformer_forward_packed_lm: ada is set (LayerNorm stacks only)");
-    VH_REQUIRE(f->d_model == f->n_heads * VH_HEAD_DIM, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed_lm: d_model=%d != n_heads=%d x 64", f->d_model, f->n_heads);
-    // what vh_attn_rows_packed_lse would refuse inside layer 0, said before anything is launched
-    VH_REQUIRE(vh_aligned16(f->q), VH_EALIGN, "vh_transformer_forward_packed_lm: q must be 16-byte aligned");
-    VH_REQUIRE(vh_aligned16(f->attn), VH_EALIGN, "vh_transformer_forward_packed_lm: attn must be 16-byte aligned");
-    VH_REQUIRE((reinterpret_cast<uintptr_t>(lse2) & 3u) == 0, VH_EALIGN, "vh_transformer_forward_packed_lm: lse2 must be 4-byte aligned");
-    VH_REQUIRE((int64_t)n_blocks * f->n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED,
-               "vh_transformer_forward_packed_lm: n_blocks=%d x n_heads=%d workgroups", n_blocks, f->n_heads);
-    for (int i = 0; i < f->n_layers; ++i) {
-        VH_REQUIRE(f->layers[i].kcache && f->layers[i].vcache, VH_EINVAL,
-                   "vh_transformer_forward_packed_lm: null kcache / vcache (layer %d)", i);
-        VH_REQUIRE(vh_aligned16(f->layers[i].kcache) && vh_aligned16(f->layers[i].vcache), VH_EALIGN,
-                   "vh_transformer_forward_packed_lm: kcache and vcache must be 16-byte aligned (layer %d)", i);
-    }
-    const packed_rows pk{seg_start, seg_len, blocks, n_seg, n_blocks, seg_x_len, lse2};
-    return forward_layers(f, &pk, stream);
+    TRY(packed_back(name, f, sg));
+    return forward_layers(f, &sg, stream);
 }

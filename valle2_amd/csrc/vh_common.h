@@ -84,6 +84,13 @@ void vh_set_error(const char* fmt, ...);
         }                                \
     } while (0)
 
+// a callee's refusal is the caller's: its code is returned, its message stays
+#define VH_TRY(call)                  \
+    do {                              \
+        int rc_ = (call);             \
+        if (rc_ != VH_OK) return rc_; \
+    } while (0)
+
 static inline bool vh_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 #define VH_CHECK_LAUNCH(name)                                                      \
@@ -126,6 +133,64 @@ struct DecodeAttnCall {
 int vh_internal_attn_decode_check(const DecodeAttnCall& c, bool pointers);
 // check -> plan -> launch
 int vh_internal_attn_decode(const DecodeAttnCall& c);
+
+// ---- packed rows: the segments of one row stream, and what every entry that takes them refuses alike ----
+// The segment arguments of a packed forward (vh_transformer_forward_packed[_lm][_bf16]) on their way through the layer loops
+// (plan.hip: forward_layers, bf16.hip: forward16_layers), where null means the padded (B, T) layout.  seg_x_len set: the
+// prefix-LM forms, each segment's text length; lse2: the rows the fp32 prefix-LM attention writes.  Null where unused.
+struct vh_segments {
+    const int32_t *seg_start, *seg_len, *blocks;
+    int n_seg, n_blocks;
+    const int32_t* seg_x_len;
+    float* lse2;
+};
+
+// The refusals below are reported under `name`, the entry point that was called, and stand in every caller where that
+// entry's own checks leave them in its order of checks (tests/golden/packed_refusals.txt pins the order).
+// one workgroup per (block, head): the four packed attention entries and, before any launch, the four composites
+static inline int vh_packed_workgroups(const char* name, int n_blocks, int n_heads) {
+    VH_REQUIRE((int64_t)n_blocks * n_heads <= 0x7fffffffLL, VH_EUNSUPPORTED, "%s: n_blocks=%d x n_heads=%d workgroups", name,
+               n_blocks, n_heads);
+    return VH_OK;
+}
+// the table sizes and the leading dimensions of the four packed attention entries; ld_mod: the elements of 16 bytes
+static inline int vh_packed_attn_sizes(const char* name, int n_heads, int n_seg, int n_blocks, int ldq, int ldo, int ld_mod) {
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "%s: n_seg=%d", name, n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "%s: n_blocks=%d", name, n_blocks);
+    VH_REQUIRE(ldq % ld_mod == 0 && ldq >= n_heads * VH_HEAD_DIM, VH_EINVAL, "%s: ldq=%d", name, ldq);
+    VH_REQUIRE(ldo % ld_mod == 0 && ldo >= n_heads * VH_HEAD_DIM, VH_EINVAL, "%s: ldo=%d", name, ldo);
+    return VH_OK;
+}
+// the row stream of the four packed composites (Desc: vh_forward_desc or vh_forward16_desc) ...
+template <class Desc>
+static inline int vh_packed_stream(const char* name, const Desc* f, int n_seg, int n_blocks) {
+    VH_REQUIRE(f->B == 1, VH_EINVAL, "%s: B=%d (the packed rows are ONE row stream: B = 1, T = the sum of the segment lengths)",
+               name, f->B);
+    VH_REQUIRE(f->T > 0 && f->n_layers > 0, VH_EINVAL, "%s: bad dims T=%d L=%d", name, f->T, f->n_layers);
+    VH_REQUIRE(f->S_max >= f->T, VH_EINVAL, "%s: S_max=%d < T=%d", name, f->S_max, f->T);
+    VH_REQUIRE(n_seg >= 1, VH_EINVAL, "%s: n_seg=%d", name, n_seg);
+    VH_REQUIRE(n_blocks >= 1, VH_EINVAL, "%s: n_blocks=%d", name, n_blocks);
+    return VH_OK;
+}
+// ... behind its pointers (desc_complete: the descriptor and every pointer the entry needs in it), for the three entries
+// that word the segment pointers alike ...
+template <class Desc>
+static inline int vh_packed_front(const char* name, const Desc* f, bool desc_complete, const vh_segments& sg) {
+    VH_REQUIRE(desc_complete, VH_EINVAL, "%s: null pointer in desc", name);
+    VH_REQUIRE(sg.seg_start && sg.seg_len && sg.blocks, VH_EINVAL, "%s: null pointer (seg_start, seg_len or blocks)", name);
+    return vh_packed_stream(name, f, sg.n_seg, sg.n_blocks);
+}
+// ... and the mask fields: the one mode the form serves (lm: the prefix-LM mask of every segment; otherwise the full mask),
+// and neither key lengths nor device text lengths beside the segment table
+template <class Desc>
+static inline int vh_packed_mask(const char* name, const Desc* f, bool lm) {
+    VH_REQUIRE(f->mode == (lm ? VH_MASK_PREFIX : VH_MASK_FULL), VH_EUNSUPPORTED, "%s: mode=%d (%s)", name, f->mode,
+               lm ? "segments attend under their prefix-LM masks: VH_MASK_PREFIX" : "segments attend under the full mask only");
+    VH_REQUIRE(!f->kv_len, VH_EUNSUPPORTED, "%s: kv_len is set (a segment's length is its key length)", name);
+    VH_REQUIRE(!f->x_len_dev, VH_EUNSUPPORTED, "%s: x_len_dev is set (%s)", name,
+               lm ? "the text lengths are seg_x_len" : "no prefix mask over segments");
+    return VH_OK;
+}
 
 // ---- device side -----------------------------------------------------------------------------
 // Cross-lane reductions on DPP (data-parallel primitives): one VALU instruction per step and no

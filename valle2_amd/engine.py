@@ -479,6 +479,17 @@ def pack_plan(lengths):
 PACK_BWD_CHUNK_KEYS = 256         # keys one workgroup of vh_attn_rows_bwd_packed takes (attention.hip FKMAX: the eight-wave kernel)
 
 
+def _text_lengths(what, x_lens, lengths):
+    """The text length inside each segment as ints (None stays None: the full mask), refused under the caller's name `what`
+    unless there is one per segment and it lies inside its segment."""
+    if x_lens is None:
+        return None
+    x_lens = [int(x) for x in x_lens]
+    if len(x_lens) != len(lengths) or any(not 0 <= x <= n for x, n in zip(x_lens, lengths)):
+        raise ValueError(f'{what}: one text length per segment, 0 <= x_len <= length')
+    return x_lens
+
+
 def pack_bwd_plan(lengths, chunk_keys=PACK_BWD_CHUNK_KEYS, x_lens=None):
     """The work items of the packed attention backward (pure Python, no device): every segment's keys in chunks of
     `chunk_keys` (a multiple of 32, at most 256; the last chunk of a segment may be short).  Returns (items, max_chunks):
@@ -494,10 +505,7 @@ def pack_bwd_plan(lengths, chunk_keys=PACK_BWD_CHUNK_KEYS, x_lens=None):
         raise ValueError(f'pack_bwd_plan: every length must be >= 1, got {min(lengths)}')
     if chunk_keys < 32 or chunk_keys > 256 or chunk_keys % 32:
         raise ValueError(f'pack_bwd_plan: chunk_keys={chunk_keys} must be a multiple of 32 in 32..256')
-    if x_lens is not None:
-        x_lens = [int(x) for x in x_lens]
-        if len(x_lens) != len(lengths) or any(not 0 <= x <= n for x, n in zip(x_lens, lengths)):
-            raise ValueError('pack_bwd_plan: one text length per segment, 0 <= x_len <= length')
+    x_lens = _text_lengths('pack_bwd_plan', x_lens, lengths)
     weighted = []
     for s, n in enumerate(lengths):
         tiles = (n + 31) // 32
@@ -520,9 +528,7 @@ class PackedRows:
         self.n_seg, self.n_blocks = len(self.lengths), len(blocks)
         i32 = self._i32 = lambda v: _lib.to_device_async(torch.tensor(v, dtype=torch.int32), device)   # noqa: E731
         self.seg_start, self.seg_len, self.blocks = i32(self.starts), i32(self.lengths), i32(blocks)
-        self.x_lens = None if x_lens is None else [int(x) for x in x_lens]
-        if self.x_lens is not None and (len(self.x_lens) != self.n_seg or any(not 0 <= x <= n for x, n in zip(self.x_lens, self.lengths))):
-            raise ValueError('PackedRows: one text length per segment, 0 <= x_len <= length')
+        self.x_lens = _text_lengths('PackedRows', x_lens, self.lengths)
         self.seg_x_len = None if x_lens is None else i32(self.x_lens)
         self._bwd = {}
 
@@ -642,8 +648,7 @@ class NarLayout:
     def forward(self, transformer, x, cache, scratch, embedding):
         """The stack under the full mask over x (rows, d) in place, every utterance attending its own rows."""
         if self.segments:
-            forward = transformer_forward_packed_bf16 if cache.bf16 else transformer_forward_packed
-            return forward(transformer, x, cache, self.segments, embedding=embedding, scratch=scratch)
+            return packed_forward_for(cache, lm=False)(transformer, x, cache, self.segments, embedding=embedding, scratch=scratch)
         forward = transformer_forward_bf16 if cache.bf16 else transformer_forward
         return forward(transformer, x.view(cache.batch, -1, x.shape[-1]), cache, mode=kernels.MASK_FULL, kv_len=self.kv_len,
                        embedding=embedding, scratch=scratch)
@@ -654,19 +659,38 @@ def transformer_forward_packed(transformer, x, cache: KVCache, rows: PackedRows,
     rows.starts[b] .. + rows.lengths[b] - 1 and is updated in place; each utterance attends its own rows only
     (`vh_attn_rows_packed`), every other launch is the row-wise one over M rows.  `cache`: a one-row KVCache of s_max >= M;
     each layer's K/V land at the packed rows.  Returns x."""
+    return _packed_forward('transformer_forward_packed', transformer, x, cache, rows, lm=False, bf16=False, embedding=embedding,
+                           scratch=scratch)
+
+
+def _packed_forward(what, transformer, x, cache, rows, *, lm, bf16, embedding=None, scratch=None, lse2=None):
+    """The four packed forwards (`what`: the one that was called, `vh_` + what its native entry): full mask or, lm, every
+    segment's prefix-LM mask; fp32 or, bf16, perf mode.  Their refusals in one order, the descriptor, the call."""
     cfg = transformer.hparams
     if x.dim() != 2:
-        raise _lib.VhError(f'transformer_forward_packed: x must be (M, d), got {tuple(x.shape)}')
+        raise _lib.VhError(f'{what}: x must be (M, d), got {tuple(x.shape)}')
     M, d = x.shape
     if d != cfg.n_heads * HEAD_DIM:
-        raise _lib.VhError(f'transformer_forward_packed: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
+        raise _lib.VhError(f'{what}: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
+    if lm and cfg.norm != 'LayerNorm':
+        raise _lib.VhError(f'{what}: norm={cfg.norm!r} (LayerNorm stacks only)')
     if M != rows.rows:
-        raise _lib.VhError(f'transformer_forward_packed: x has {M} rows, the packed rows {rows.rows}')
-    scratch, common = _forward_front(transformer, x, 1, M, cache, embedding, scratch, bf16=False)
-    desc = VhForwardDesc(mode=kernels.MASK_FULL, x_len=0, **_fp32_scratch_fields(scratch), **common)
-    check(_lib.lib().vh_transformer_forward_packed(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg,
-                                                   ptr(rows.blocks), rows.n_blocks, stream()),
-          'vh_transformer_forward_packed')
+        raise _lib.VhError(f'{what}: x has {M} rows, the packed rows {rows.rows}')
+    if lm:
+        kernels.needs_x_lens(what, rows)
+    if lm and not bf16:                     # the fp32 prefix-LM attention is the training forward's: it writes an lse2 nobody reads here
+        if lse2 is None:
+            lse2 = torch.empty(cfg.n_heads, M, device=x.device, dtype=torch.float32)
+        elif tuple(lse2.shape) != (cfg.n_heads, M) or lse2.dtype != torch.float32 or not lse2.is_contiguous():
+            raise _lib.VhError(f'{what}: lse2 must be contiguous float32 (n_heads, M)')
+    if bf16:
+        _refuse_unless_perf_forward(cfg)
+    scratch, common = _forward_front(transformer, x, 1, M, cache, embedding, scratch, bf16=bf16)
+    mode = dict(mode=kernels.MASK_PREFIX if lm else kernels.MASK_FULL, x_len=0)
+    desc = _forward16_desc(transformer, cache, scratch, common, **mode) if bf16 else \
+        VhForwardDesc(**mode, **_fp32_scratch_fields(scratch), **common)
+    segments = [ptr(rows.seg_start), ptr(rows.seg_len)] + [ptr(rows.seg_x_len)] * lm + [rows.n_seg, ptr(rows.blocks), rows.n_blocks]
+    check(getattr(_lib.lib(), 'vh_' + what)(C.byref(desc), *segments, *[ptr(lse2)] * (lm and not bf16), stream()), 'vh_' + what)
     return x
 
 
@@ -703,28 +727,7 @@ def transformer_forward_packed_lm(transformer, x, cache: KVCache, rows, scratch=
     writes the (n_heads, M) `lse2`, scratch nobody reads here); every other launch is the row-wise one over M rows.  `rows`: a
     `PackedRows` built with x_lens, or a `PromptRows`.  `cache`: a one-row fp32 KVCache of s_max >= M; each layer's K/V land at
     the packed rows (`KVCache.unpack_into` moves them to per-row caches).  fp32, head width 64, LayerNorm.  Returns x."""
-    cfg = transformer.hparams
-    if x.dim() != 2:
-        raise _lib.VhError(f'transformer_forward_packed_lm: x must be (M, d), got {tuple(x.shape)}')
-    M, d = x.shape
-    if d != cfg.n_heads * HEAD_DIM:
-        raise _lib.VhError(f'transformer_forward_packed_lm: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
-    if cfg.norm != 'LayerNorm':
-        raise _lib.VhError(f'transformer_forward_packed_lm: norm={cfg.norm!r} (LayerNorm stacks only)')
-    if M != rows.rows:
-        raise _lib.VhError(f'transformer_forward_packed_lm: x has {M} rows, the packed rows {rows.rows}')
-    if rows.seg_x_len is None:
-        raise _lib.VhError('transformer_forward_packed_lm: the prefix mask needs PackedRows(lengths, device, x_lens)')
-    if lse2 is None:
-        lse2 = torch.empty(cfg.n_heads, M, device=x.device, dtype=torch.float32)
-    elif tuple(lse2.shape) != (cfg.n_heads, M) or lse2.dtype != torch.float32 or not lse2.is_contiguous():
-        raise _lib.VhError('transformer_forward_packed_lm: lse2 must be contiguous float32 (n_heads, M)')
-    scratch, common = _forward_front(transformer, x, 1, M, cache, None, scratch, bf16=False)
-    desc = VhForwardDesc(mode=kernels.MASK_PREFIX, x_len=0, **_fp32_scratch_fields(scratch), **common)
-    check(_lib.lib().vh_transformer_forward_packed_lm(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), ptr(rows.seg_x_len),
-                                                      rows.n_seg, ptr(rows.blocks), rows.n_blocks, ptr(lse2), stream()),
-          'vh_transformer_forward_packed_lm')
-    return x
+    return _packed_forward('transformer_forward_packed_lm', transformer, x, cache, rows, lm=True, bf16=False, scratch=scratch, lse2=lse2)
 
 
 def transformer_forward_packed_bf16(transformer, x, cache: KVCache, rows: PackedRows, embedding=None, scratch=None):
@@ -732,21 +735,8 @@ def transformer_forward_packed_bf16(transformer, x, cache: KVCache, rows: Packed
     x (M, d) fp32 holds utterance b at rows rows.starts[b] .. + rows.lengths[b] - 1 and is updated in place; each utterance
     attends its own rows only (`vh_attn_rows_packed_bf16`), every other launch is the row-wise 16-bit one over M rows.
     `cache`: a one-row 16-bit KVCache of s_max >= M; `scratch`: a ForwardScratch16.  Returns x."""
-    cfg = transformer.hparams
-    if x.dim() != 2:
-        raise _lib.VhError(f'transformer_forward_packed_bf16: x must be (M, d), got {tuple(x.shape)}')
-    M, d = x.shape
-    if d != cfg.n_heads * HEAD_DIM:
-        raise _lib.VhError(f'transformer_forward_packed_bf16: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
-    if M != rows.rows:
-        raise _lib.VhError(f'transformer_forward_packed_bf16: x has {M} rows, the packed rows {rows.rows}')
-    _refuse_unless_perf_forward(cfg)
-    scratch, common = _forward_front(transformer, x, 1, M, cache, embedding, scratch, bf16=True)
-    desc = _forward16_desc(transformer, cache, scratch, common, mode=kernels.MASK_FULL, x_len=0)
-    check(_lib.lib().vh_transformer_forward_packed_bf16(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg,
-                                                        ptr(rows.blocks), rows.n_blocks, stream()),
-          'vh_transformer_forward_packed_bf16')
-    return x
+    return _packed_forward('transformer_forward_packed_bf16', transformer, x, cache, rows, lm=False, bf16=True, embedding=embedding,
+                           scratch=scratch)
 
 
 def transformer_forward_packed_lm_bf16(transformer, x, cache: KVCache, rows, scratch=None):
@@ -756,25 +746,13 @@ def transformer_forward_packed_lm_bf16(transformer, x, cache: KVCache, rows, scr
     every other launch is the row-wise 16-bit one over M rows.  `rows`: a `PackedRows` built with x_lens, or a `PromptRows`.
     `cache`: a one-row 16-bit KVCache of s_max >= M (`KVCache.unpack_into` moves its rows to a 16-bit row cache); `scratch`: a
     ForwardScratch16.  Head width 64, LayerNorm, the shapes of `perf_forward_supported`.  Returns x."""
-    cfg = transformer.hparams
-    if x.dim() != 2:
-        raise _lib.VhError(f'transformer_forward_packed_lm_bf16: x must be (M, d), got {tuple(x.shape)}')
-    M, d = x.shape
-    if d != cfg.n_heads * HEAD_DIM:
-        raise _lib.VhError(f'transformer_forward_packed_lm_bf16: head width {d // cfg.n_heads} (the packed attention is width 64 only)')
-    if cfg.norm != 'LayerNorm':
-        raise _lib.VhError(f'transformer_forward_packed_lm_bf16: norm={cfg.norm!r} (LayerNorm stacks only)')
-    if M != rows.rows:
-        raise _lib.VhError(f'transformer_forward_packed_lm_bf16: x has {M} rows, the packed rows {rows.rows}')
-    if rows.seg_x_len is None:
-        raise _lib.VhError('transformer_forward_packed_lm_bf16: the prefix mask needs PackedRows(lengths, device, x_lens)')
-    _refuse_unless_perf_forward(cfg)
-    scratch, common = _forward_front(transformer, x, 1, M, cache, None, scratch, bf16=True)
-    desc = _forward16_desc(transformer, cache, scratch, common, mode=kernels.MASK_PREFIX, x_len=0)
-    check(_lib.lib().vh_transformer_forward_packed_lm_bf16(C.byref(desc), ptr(rows.seg_start), ptr(rows.seg_len), ptr(rows.seg_x_len),
-                                                           rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()),
-          'vh_transformer_forward_packed_lm_bf16')
-    return x
+    return _packed_forward('transformer_forward_packed_lm_bf16', transformer, x, cache, rows, lm=True, bf16=True, scratch=scratch)
+
+
+def packed_forward_for(cache, lm):
+    """The packed forward that writes `cache`: 16-bit or fp32 by its storage; lm: under the prefix-LM masks, else the full mask."""
+    return {(False, False): transformer_forward_packed, (False, True): transformer_forward_packed_lm,
+            (True, False): transformer_forward_packed_bf16, (True, True): transformer_forward_packed_lm_bf16}[bool(cache.bf16), lm]
 
 
 def _transformer_forward_generic(transformer, x, *, mode, x_len, x_len_dev, kv_len, mask, pad, embedding, x_in, cache=None):

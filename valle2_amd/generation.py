@@ -14,8 +14,7 @@ from . import _lib, kernels
 from . import sampling as _sampling
 from .engine import (MAX_DECODE_D_MODEL, ArDecoder, ForwardScratch, ForwardScratch16, KVCache, PromptRows, QueueSchedule, StepSampler,
                      cached_decode_supported, ffn_fused_width, group_prefix_cap, grouped_prompts_fit, perf_forward_supported,
-                     queue_steps_cap, transformer_forward, transformer_forward_bf16, transformer_forward_packed_lm,
-                     transformer_forward_packed_lm_bf16)
+                     packed_forward_for, queue_steps_cap, transformer_forward, transformer_forward_bf16)
 from .utils import get_best_beam
 
 EOS_POLL = 32
@@ -379,11 +378,16 @@ def best_beam_tokens(model, rows, sum_logprobs, prompt_len):
 
 
 # ---- the prompt pass and the decode loops -----------------------------------------------------------------------------------
+def _switch(model, attribute, variable):
+    """A switch of the model: its attribute (True / False), or, while that is None, `variable`=1 in the environment of the call."""
+    switch = getattr(model, attribute, None)
+    return os.environ.get(variable, '0') == '1' if switch is None else bool(switch)
+
+
 def packed_prompt_on(model):
     """The switch of the packed prompt pass: `model.packed_prompt` (ValleAR's class attribute; True / False), or, while that
     is None, VALLE2_PACKED_PROMPT=1 in the environment of the call."""
-    switch = getattr(model, 'packed_prompt', None)
-    return os.environ.get('VALLE2_PACKED_PROMPT', '0') == '1' if switch is None else bool(switch)
+    return _switch(model, 'packed_prompt', 'VALLE2_PACKED_PROMPT')
 
 
 def packed_prompt_qualifies(kind, perf_mode, head_dim, forced, ragged, no_cache=False):
@@ -397,8 +401,7 @@ def packed_prompt_perf_on(model):
     """The switch of the packed prompt pass in PERF MODE, a switch of its own beside `packed_prompt_on`:
     `model.packed_prompt_perf` (ValleAR's class attribute; True / False), or, while that is None, VALLE2_PACKED_PROMPT_PERF=1 in
     the environment of the call."""
-    switch = getattr(model, 'packed_prompt_perf', None)
-    return os.environ.get('VALLE2_PACKED_PROMPT_PERF', '0') == '1' if switch is None else bool(switch)
+    return _switch(model, 'packed_prompt_perf', 'VALLE2_PACKED_PROMPT_PERF')
 
 
 def packed_prompt_perf_qualifies(kind, perf_mode, head_dim, forced, ragged, no_cache=False):
@@ -444,14 +447,9 @@ def packed_pass(model, texts, txs, pls, codes, into, dst_rows):
     x = torch.empty(rows.rows, d, device=dev, dtype=torch.float32)
     kernels.embed_nar_packed(tokens, codes.unsqueeze(-1), model.tokens_emb.weight.detach(), [model.audio_emb.weight.detach()], 1,
                              model.tokens_position_emb.pe, model.audio_position_emb.pe, rows, x)
-    if into.bf16:
-        stream_cache = KVCache(cfg.num_layers, 1, cfg.n_heads, rows.rows, dev, dtype=kernels.H16)
-        transformer_forward_packed_lm_bf16(model.transformer, x, stream_cache, rows,
-                                           scratch=ForwardScratch16(rows.rows, d, cfg.dim_feedforward, dev))
-    else:
-        stream_cache = KVCache(cfg.num_layers, 1, cfg.n_heads, rows.rows, dev)
-        transformer_forward_packed_lm(model.transformer, x, stream_cache, rows,
-                                      scratch=ForwardScratch(rows.rows, d, cfg.dim_feedforward, dev))
+    stream_cache = KVCache(cfg.num_layers, 1, cfg.n_heads, rows.rows, dev, dtype=kernels.H16 if into.bf16 else torch.float32)
+    packed_forward_for(stream_cache, lm=True)(model.transformer, x, stream_cache, rows,
+                                              scratch=(ForwardScratch16 if into.bf16 else ForwardScratch)(rows.rows, d, cfg.dim_feedforward, dev))
     stream_cache.unpack_into(into, rows.seg_start, rows.seg_len, rows.dst_row)
     return x.index_select(0, rows.last_rows)
 
@@ -471,20 +469,18 @@ def prompt_pass(model, plan, state, texts, first_codes, forced=False):
     rows = 1 if plan.kind == SHARED else plan.G
     text_ids = None
     state.prompt_rows = (False, rows * s0)
-    if packed_prompt_on(model) and packed_prompt_qualifies(plan.kind, plan.perf_mode, d // cfg.n_heads, forced, plan.ragged, plan.no_cache):
+    rule = (plan.kind, plan.perf_mode, d // cfg.n_heads, forced, plan.ragged, plan.no_cache)
+    fp32_rule = packed_prompt_on(model) and packed_prompt_qualifies(*rule)
+    perf_rule = not fp32_rule and packed_prompt_perf_on(model) and packed_prompt_perf_qualifies(*rule)
+    if fp32_rule or perf_rule:
         _write_prompts(codes, first_codes, n)
-        last = packed_pass(model, texts, plan.txs, plan.pls, codes[:plan.G * n:n], state.cache if state.prefix is None else state.prefix,
-                           range(plan.G))
+        # the fp32 rule: rows or grouped prefixes, an utterance's beams n code rows apart; the perf rule: independent rows
+        into = state.prefix if fp32_rule and state.prefix is not None else state.cache
+        last = packed_pass(model, texts, plan.txs, plan.pls, codes[:plan.G * n:n] if fp32_rule else codes[:plan.G], into, range(plan.G))
         state.prompt_rows = (True, sum(plan.ctx))
         if plan.kind == GROUPED:
             last = last.repeat_interleave(n, 0)       # every beam starts from its utterance's last hidden row
-        return last.contiguous(), {}, None
-    if packed_prompt_perf_on(model) and packed_prompt_perf_qualifies(plan.kind, plan.perf_mode, d // cfg.n_heads, forced, plan.ragged,
-                                                                     plan.no_cache):
-        _write_prompts(codes, first_codes, n)
-        last = packed_pass(model, texts, plan.txs, plan.pls, codes[:plan.G], state.cache, range(plan.G))
-        state.prompt_rows = (True, sum(plan.ctx))
-        if plan.kind == ROWS:
+        if perf_rule and plan.kind == ROWS:
             state.cache = state.cache.narrowed(plan.s_max)    # fp32 prompt K/V -> the bf16 cache of the decode steps
         return last.contiguous(), {}, None
     if not plan.ragged:

@@ -384,29 +384,39 @@ def attn_rows_packed(q, kcache, vcache, out, n_heads, rows):
     """Full-mask attention of every segment of `rows` (an engine.PackedRows) over its own rows of ONE K/V stream: q / out
     (M, ·) with heads at columns head*64, kcache / vcache (1, n_heads, S_max >= M, 64) — `attn_rows` of each utterance alone,
     in one launch and with no padding rows (vh_attn_rows_packed)."""
-    S_max = kcache.shape[2]
-    M = rows.rows
-    if tuple(kcache.shape) != (1, n_heads, S_max, HEAD_DIM) or kcache.shape != vcache.shape or M > S_max:
-        raise _lib.VhError(f'attn_rows_packed: cache {tuple(kcache.shape)} M={M}')
-    if q.shape[0] != M or out.shape[0] != M:
-        raise _lib.VhError('attn_rows_packed: q/out rows')
+    _, S_max = _packed_attn_args('attn_rows_packed', q, kcache, vcache, out, n_heads, rows)
     check(_lib.lib().vh_attn_rows_packed(
         _dev_f32(q, 'q'), q.stride(0), ptr(kcache), ptr(vcache), _dev_f32(out, 'out'), out.stride(0), n_heads, S_max,
         ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()), 'vh_attn_rows_packed')
     return out
 
 
-def _packed_train_args(what, q, kcache, vcache, out, lse2, n_heads, rows, mode):
+def needs_x_lens(what, rows):
+    """Refuse, under the caller's name `what`, segments without text lengths where the prefix-LM mask is asked for."""
+    if rows.seg_x_len is None:
+        raise _lib.VhError(f'{what}: the prefix mask needs PackedRows(lengths, device, x_lens)')
+
+
+def _packed_attn_args(what, q, kcache, vcache, out, n_heads, rows, prefix=False):
+    """What every packed attention refuses alike, under the caller's name `what`: a K/V stream that is not (1, n_heads,
+    S_max >= M, 64), q / out of other than M rows and, under the prefix mask, segments without text lengths.  Returns (M, S_max)."""
     S_max = kcache.shape[2]
     M = rows.rows
     if tuple(kcache.shape) != (1, n_heads, S_max, HEAD_DIM) or kcache.shape != vcache.shape or M > S_max:
         raise _lib.VhError(f'{what}: cache {tuple(kcache.shape)} M={M}')
     if q.shape[0] != M or out.shape[0] != M:
         raise _lib.VhError(f'{what}: q/out rows')
+    if prefix:
+        needs_x_lens(what, rows)
+    return M, S_max
+
+
+def _packed_train_args(what, q, kcache, vcache, out, lse2, n_heads, rows, mode):
+    M, S_max = _packed_attn_args(what, q, kcache, vcache, out, n_heads, rows)
     if tuple(lse2.shape) != (n_heads, M) or lse2.dtype != torch.float32 or not lse2.is_contiguous():
         raise _lib.VhError(f'{what}: lse2 must be contiguous float32 (n_heads, M)')
-    if mode == MASK_PREFIX and rows.seg_x_len is None:
-        raise _lib.VhError(f'{what}: the prefix mask needs PackedRows(lengths, device, x_lens)')
+    if mode == MASK_PREFIX:
+        needs_x_lens(what, rows)
     return M, S_max
 
 
@@ -888,12 +898,7 @@ def attn_rows_packed_bf16(q, kcache, vcache, out, n_heads, rows):
     engine.PackedRows) over its own rows of ONE 16-bit K/V stream.  q (pre-scaled by Q16_PRESCALE, as `linear_qkv_bf16` leaves
     it) / out (M, ·) H16 with heads at columns head*64, kcache / vcache (1, n_heads, S_max >= M, 64) H16 — `attn_rows_bf16` of
     each utterance alone, in one launch and with no padding rows (vh_attn_rows_packed_bf16)."""
-    S_max = kcache.shape[2]
-    M = rows.rows
-    if tuple(kcache.shape) != (1, n_heads, S_max, HEAD_DIM) or kcache.shape != vcache.shape or M > S_max:
-        raise _lib.VhError(f'attn_rows_packed_bf16: cache {tuple(kcache.shape)} M={M}')
-    if q.shape[0] != M or out.shape[0] != M:
-        raise _lib.VhError('attn_rows_packed_bf16: q/out rows')
+    _, S_max = _packed_attn_args('attn_rows_packed_bf16', q, kcache, vcache, out, n_heads, rows)
     check(_lib.lib().vh_attn_rows_packed_bf16(
         _bf16(q, 'q'), q.stride(0), _bf16(kcache, 'kcache'), _bf16(vcache, 'vcache'), _bf16(out, 'out'), out.stride(0), n_heads,
         S_max, ptr(rows.seg_start), ptr(rows.seg_len), rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()),
@@ -906,14 +911,7 @@ def attn_rows_packed_lm_bf16(q, kcache, vcache, out, n_heads, rows):
     engine.PromptRows) attends its own rows of ONE 16-bit K/V stream under the prefix mask of its own text length — per segment
     the bits of `attn_rows_bf16(B=1, Tq=Tk=len, MASK_PREFIX, x_len)` on it alone (vh_attn_rows_packed_lm_bf16).  Operands as for
     `attn_rows_packed_bf16`."""
-    S_max = kcache.shape[2]
-    M = rows.rows
-    if tuple(kcache.shape) != (1, n_heads, S_max, HEAD_DIM) or kcache.shape != vcache.shape or M > S_max:
-        raise _lib.VhError(f'attn_rows_packed_lm_bf16: cache {tuple(kcache.shape)} M={M}')
-    if q.shape[0] != M or out.shape[0] != M:
-        raise _lib.VhError('attn_rows_packed_lm_bf16: q/out rows')
-    if rows.seg_x_len is None:
-        raise _lib.VhError('attn_rows_packed_lm_bf16: the prefix mask needs PackedRows(lengths, device, x_lens)')
+    _, S_max = _packed_attn_args('attn_rows_packed_lm_bf16', q, kcache, vcache, out, n_heads, rows, prefix=True)
     check(_lib.lib().vh_attn_rows_packed_lm_bf16(
         _bf16(q, 'q'), q.stride(0), _bf16(kcache, 'kcache'), _bf16(vcache, 'vcache'), _bf16(out, 'out'), out.stride(0), n_heads,
         S_max, ptr(rows.seg_start), ptr(rows.seg_len), ptr(rows.seg_x_len), rows.n_seg, ptr(rows.blocks), rows.n_blocks, stream()),
