@@ -497,6 +497,40 @@ int vh_attn_rows_hd(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sr,
                     int B, int n_heads, int head_dim, int Tq, int Tk, float scale,
                     int mode, int x_len, const int32_t* x_len_dev, const int32_t* kv_len, void* stream);
 
+/* ---- training on flash attention at a head width other than 64 (pure additions of ABI 146: VH_VERSION stays) ----------
+ * vh_attn_rows_hd_lse: vh_attn_rows_hd — the same kernel body, checks and bits of `out` — that also stores, for every query
+ *   row, lse2[(b * n_heads + head) * Tq + i] = log2(sum_j exp2(s_ij)) over the visible keys, s = scale * log2(e) * q k^T:
+ *   vh_attn_rows_lse's units.  lse2 is (B, n_heads, Tq), contiguous, 16-byte aligned (null -> VH_EINVAL, misaligned ->
+ *   VH_EALIGN); a query without a visible key gets -inf.
+ * vh_attn_rows_hd_bwd: dq, dk, dv of that forward given dout, for Tq == Tk == T.  Two launches (queries as lanes: dQ and
+ *   D = rowsum(dO o O); keys as lanes: dK, dV), P recomputed tile by tile from lse2, no (B, h, T, T) map, no atomics: the same
+ *   call twice gives the same bits.  q / k / v / out / dout are strided views as above (batch, head, row strides in floats,
+ *   unit stride in the last dimension); dq, dk and dv are views of the same shape that SHARE one stride set (g_sb, g_sh,
+ *   g_sr): the column blocks of one (rows, 3 d) gradient buffer.  Every element of dq / dk / dv inside (B, h, T, head_dim)
+ *   is written exactly once, zeros included (keys at or beyond kv_len[b], keys no query sees; a row with kv_len[b] <= 0 gets
+ *   dq = dk = dv = 0 and no NaN): the caller may hand in uninitialised memory.  Nothing outside the views is written.
+ *   ws: device scratch of vh_attn_rows_hd_bwd_ws_bytes(B, n_heads, T) bytes (the D vector, B h T floats), 16-byte aligned.
+ *   Masks, head widths and the scale are vh_attn_rows_hd's.  All checks run before any launch: a null pointer (ws included),
+ *   an unknown mode, B / n_heads / T <= 0, a stride that is not a multiple of 4 floats, a workspace smaller than needed,
+ *   a grid that does not fit -> VH_EINVAL; VH_MASK_EXPLICIT, a head width outside the served set, a negative q / k / v /
+ *   dout row stride or one that puts row T - 1 more than 2^30 floats after row 0 (those rows are addressed by 32-bit
+ *   offsets) -> VH_EUNSUPPORTED; a pointer that is not 16-byte aligned -> VH_EALIGN. */
+int vh_attn_rows_hd_lse(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sr,
+                        const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sr,
+                        const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sr,
+                        float* out, int64_t o_sb, int64_t o_sh, int64_t o_sr,
+                        int B, int n_heads, int head_dim, int Tq, int Tk, float scale,
+                        int mode, int x_len, const int32_t* x_len_dev, const int32_t* kv_len, float* lse2, void* stream);
+size_t vh_attn_rows_hd_bwd_ws_bytes(int B, int n_heads, int T);
+int vh_attn_rows_hd_bwd(const float* q, int64_t q_sb, int64_t q_sh, int64_t q_sr,
+                        const float* k, int64_t k_sb, int64_t k_sh, int64_t k_sr,
+                        const float* v, int64_t v_sb, int64_t v_sh, int64_t v_sr,
+                        const float* out, int64_t o_sb, int64_t o_sh, int64_t o_sr,
+                        const float* dout, int64_t d_sb, int64_t d_sh, int64_t d_sr,
+                        const float* lse2, float* dq, float* dk, float* dv, int64_t g_sb, int64_t g_sh, int64_t g_sr,
+                        int B, int n_heads, int head_dim, int T, float scale, int mode, int x_len,
+                        const int32_t* x_len_dev, const int32_t* kv_len, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- perf mode of the decode step: bf16 K/V cache (opt-in; never the parity path) ---------------
  * SURVEY.md section 7's "perf mode": the K/V cache — 93 % of the bytes a decode step reads at configs[1] — stored
  * as bf16 (B, h, S_max, 64), everything else (weights, q, softmax, accumulators, residual stream) fp32 as in the parity

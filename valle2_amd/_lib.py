@@ -204,6 +204,17 @@ SIGNATURES = {
                                   c_f32p, C.c_int64, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int64,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, c_i32p, c_i32p,
                                   C.c_void_p]),
+    # training on flash attention at a head width other than 64 (additions under ABI 146)
+    'vh_attn_rows_hd_lse': (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int64,
+                                      c_f32p, C.c_int64, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int64,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, c_i32p, c_i32p,
+                                      c_f32p, C.c_void_p]),
+    'vh_attn_rows_hd_bwd_ws_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'vh_attn_rows_hd_bwd': (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int64,
+                                      c_f32p, C.c_int64, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int64,
+                                      c_f32p, C.c_int64, C.c_int64, C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p,
+                                      C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                      C.c_int, c_i32p, c_i32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'vh_greedy_step': (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_i64p, C.c_int64, c_i32p,
                                  c_i32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int,
                                  C.c_void_p]),

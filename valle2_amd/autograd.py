@@ -275,7 +275,11 @@ class QkvAttentionAnyHeadDimFn(torch.autograd.Function):
     on the general kernels with the probabilities materialised — qkv = x Wqkv^T, P = softmax(Q K^T / sqrt(hd) + mask),
     out = P V forward; dV = P^T dO, dP = dO V^T, dS, dQ = dS K, dK = dS^T Q backward — every operand a strided view of
     the (rows, 3 d) projection or its gradient, read and written in place.  Correct, not tuned (P is kept: O(T^2) memory
-    per (batch row, head))."""
+    per (batch row, head)).
+    Where `kernels.attn_hd_route` answers 'flash' (the switch kernels.ATTN_HD_FLASH / VALLE2_ATTN_HD_FLASH=1, default off;
+    a multiple of 4 from 16 to 128; analytic masks) the attention core is the flash pair instead — `kernels.attn_rows_hd`
+    with the rows' log-sum-exp forward, `kernels.attn_rows_hd_bwd` backward — over the same views: no P, no dP, nothing that
+    grows with T^2 is allocated or kept."""
 
     @staticmethod
     def forward(ctx, x, wqkv, B, T, n_heads, spec):
@@ -287,20 +291,35 @@ class QkvAttentionAnyHeadDimFn(torch.autograd.Function):
         qkv = kernels.linear(x, wqkv.detach(), out=torch.empty(B * T, 3 * d, device=x.device, dtype=torch.float32))
         q, k, v = (qkv.view(B, T, 3, n_heads, hd)[:, :, j].permute(0, 2, 1, 3) for j in range(3))
         out = torch.empty(B * T, d, device=x.device, dtype=torch.float32)
+        ctx.dims = (B, T, n_heads, hd)
+        ctx.flash = spec.get('rows') is None and kernels.attn_hd_route(hd, spec) == 'flash'
+        if ctx.flash:
+            lse2 = torch.empty(B, n_heads, T, device=x.device, dtype=torch.float32)
+            kernels.attn_rows_hd(q, k, v, out.view(B, T, n_heads, hd).permute(0, 2, 1, 3), hd ** -0.5, lse2=lse2, **spec)
+            ctx.save_for_backward(x, wqkv, qkv, out, lse2)
+            ctx.spec = spec
+            return out
         P = kernels.attn_generic(q, k, v, out.view(B, T, n_heads, hd).permute(0, 2, 1, 3), hd ** -0.5, **spec)
         ctx.save_for_backward(x, wqkv, qkv, P)
-        ctx.dims = (B, T, n_heads, hd)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, wqkv, qkv, P = ctx.saved_tensors
         B, T, h, hd = ctx.dims
         d = h * hd
+        if ctx.flash:
+            x, wqkv, qkv, out, lse2 = ctx.saved_tensors
+        else:
+            x, wqkv, qkv, P = ctx.saved_tensors
         q, k, v = (qkv.view(B, T, 3, h, hd)[:, :, j].permute(0, 2, 1, 3) for j in range(3))
         do = dout.contiguous().view(B, T, h, hd).permute(0, 2, 1, 3)
         dqkv = torch.empty(B * T, 3 * d, device=x.device, dtype=torch.float32)
         dq, dk, dv = (dqkv.view(B, T, 3, h, hd)[:, :, j].permute(0, 2, 1, 3) for j in range(3))
+        if ctx.flash:
+            kernels.attn_rows_hd_bwd(q, k, v, out.view(B, T, h, hd).permute(0, 2, 1, 3), do, lse2, dq, dk, dv, hd ** -0.5,
+                                     **ctx.spec)
+            return QkvAttentionAnyHeadDimFn._input_grads(ctx, dqkv, x, wqkv, d)
+        kernels.ATTN_HD_BWD_CALLS['materialized'] += 1
         tp = P.stride(2)
         dP = torch.empty(B, h, T, tp, device=x.device, dtype=torch.float32)[..., :T]
         _mm(P, do, dv, a_kmajor=True, b_kmajor=True)                      # dV = P^T dO
@@ -308,6 +327,10 @@ class QkvAttentionAnyHeadDimFn(torch.autograd.Function):
         check(_lib.lib().vh_softmax_bwd(P.data_ptr(), dP.data_ptr(), tp, B * h * T, T, hd ** -0.5, stream()), 'vh_softmax_bwd')
         _mm(dP, k, dq, b_kmajor=True)                                     # dQ = dS K
         _mm(dP, q, dk, a_kmajor=True, b_kmajor=True)                      # dK = dS^T Q
+        return QkvAttentionAnyHeadDimFn._input_grads(ctx, dqkv, x, wqkv, d)
+
+    @staticmethod
+    def _input_grads(ctx, dqkv, x, wqkv, d):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = _dx(dqkv, wqkv, 3 * d)

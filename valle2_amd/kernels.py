@@ -512,17 +512,21 @@ def attn_generic(q, k, v, out, scale, **spec):
     return P
 
 
-# The flash route of the many-row attention at head widths other than 64 (vh_attn_rows_hd).  None: the environment variable
-# VALLE2_ATTN_HD_FLASH=1 decides; True / False: this value does.  Default OFF.  attn_hd_route answers for callers that pick
-# a route per call (tools/ab_attn_hd.py); the stack (engine._transformer_forward_generic) does not ask it yet and always
-# takes attn_generic: the same kernels, launches and bits as before (DESIGN.md section 3.17 says why).
+# The flash route of the many-row attention at head widths other than 64 (vh_attn_rows_hd, vh_attn_rows_hd_lse,
+# vh_attn_rows_hd_bwd).  None: the environment variable VALLE2_ATTN_HD_FLASH=1 decides; True / False: this value does.  Default
+# OFF.  attn_hd_route answers for callers that pick a route per call: TRAINING asks it (autograd.QkvAttentionAnyHeadDimFn:
+# flash forward with lse + flash backward, no score map kept) and so does tools/ab_attn_hd.py; the inference stack
+# (engine._transformer_forward_generic) still does not and always takes attn_generic: the same kernels, launches and bits as
+# before (DESIGN.md section 3.17 says why).
 ATTN_HD_FLASH = None
 ATTN_HD_CALLS = {'flash': 0, 'materialized': 0}     # calls of attn_rows_hd / attn_generic since reset_attn_hd_calls()
+ATTN_HD_BWD_CALLS = {'flash': 0, 'materialized': 0}  # backward calls: attn_rows_hd_bwd / the node's five products
 
 
 def reset_attn_hd_calls():
-    for key in ATTN_HD_CALLS:
-        ATTN_HD_CALLS[key] = 0
+    for counts in (ATTN_HD_CALLS, ATTN_HD_BWD_CALLS):
+        for key in counts:
+            counts[key] = 0
 
 
 def attn_hd_route(hd, spec):
@@ -537,32 +541,76 @@ def attn_hd_route(hd, spec):
     return 'flash'
 
 
-def attn_rows_hd(q, k, v, out, scale, **spec):
+def _attn_hd_views(name, views, spec):
+    """The checks `attn_rows_hd` and `attn_rows_hd_bwd` share: (B, h, T, hd) float32 device views with unit stride in the last
+    dimension, int32 device length vectors."""
+    for t, nm in views:
+        _f32(t, nm)
+        if not t.is_cuda or t.stride(3) != 1:
+            raise _lib.VhError(f'{name}: {nm} must be a device view with unit stride in the last dimension')
+    B = views[0][0].shape[0]
+    for t_, nm in ((spec.get('x_len_dev'), 'x_len_dev'), (spec.get('kv_len'), 'kv_len')):
+        if t_ is not None and (t_.dtype != torch.int32 or t_.numel() < B or not t_.is_cuda or not t_.is_contiguous()):
+            raise _lib.VhError(f'{name}: {nm} must be a contiguous device int32 tensor of B entries')
+
+
+def _view_args(t):
+    return t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)
+
+
+def attn_rows_hd(q, k, v, out, scale, lse2=None, **spec):
     """`attn_generic` without the score map: one flash kernel (vh_attn_rows_hd) over the same views — q (B, h, Tq, hd),
     k / v (B, h, Tk, hd), out (B, h, Tq, hd) with unit stride in the last dimension, the per-head column blocks of a
     (rows, 3 d) projection read in place — for hd a multiple of 4 from 16 to 128 and the analytic masks of `spec` (mode,
-    x_len, x_len_dev, kv_len; a `mask` or `pad` is refused: those keep attn_generic).  Nothing is returned: no P exists."""
+    x_len, x_len_dev, kv_len; a `mask` or `pad` is refused: those keep attn_generic).  Nothing is returned: no P exists.
+    lse2: a contiguous (B, h, Tq) float32 tensor that receives every row's base-2 log-sum-exp (vh_attn_rows_hd_lse): what
+    `attn_rows_hd_bwd` recomputes P from."""
     if spec.get('mask') is not None or spec.get('pad') is not None:
         raise _lib.VhError('attn_rows_hd: caller-supplied masks take attn_generic')
     if q.dim() != 4 or out.shape != q.shape or k.shape != v.shape or k.dim() != 4 or k.shape[:2] != q.shape[:2] \
             or k.shape[3] != q.shape[3]:
         raise _lib.VhError(f'attn_rows_hd: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} out {tuple(out.shape)}')
-    for t, name in ((q, 'q'), (k, 'k'), (v, 'v'), (out, 'out')):
-        _f32(t, name)
-        if not t.is_cuda or t.stride(3) != 1:
-            raise _lib.VhError(f'attn_rows_hd: {name} must be a device view with unit stride in the last dimension')
+    _attn_hd_views('attn_rows_hd', ((q, 'q'), (k, 'k'), (v, 'v'), (out, 'out')), spec)
     B, h, Tq, hd = q.shape
     Tk = k.shape[2]
-    for t_, name in ((spec.get('x_len_dev'), 'x_len_dev'), (spec.get('kv_len'), 'kv_len')):
-        if t_ is not None and (t_.dtype != torch.int32 or t_.numel() < B or not t_.is_cuda or not t_.is_contiguous()):
-            raise _lib.VhError(f'attn_rows_hd: {name} must be a contiguous device int32 tensor of B entries')
+    args = (*_view_args(q), *_view_args(k), *_view_args(v), *_view_args(out), B, h, hd, Tq, Tk, float(scale),
+            spec.get('mode', MASK_FULL), int(spec.get('x_len', 0)), ptr(spec.get('x_len_dev')), ptr(spec.get('kv_len')))
+    if lse2 is not None and (lse2.dtype != torch.float32 or tuple(lse2.shape) != (B, h, Tq) or not lse2.is_cuda
+                             or not lse2.is_contiguous()):
+        raise _lib.VhError(f'attn_rows_hd: lse2 must be a contiguous device float32 tensor of shape {(B, h, Tq)}')
     ATTN_HD_CALLS['flash'] += 1
-    check(_lib.lib().vh_attn_rows_hd(
-        q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
-        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), out.data_ptr(), out.stride(0), out.stride(1), out.stride(2),
-        B, h, hd, Tq, Tk, float(scale), spec.get('mode', MASK_FULL), int(spec.get('x_len', 0)), ptr(spec.get('x_len_dev')),
-        ptr(spec.get('kv_len')), stream()), 'vh_attn_rows_hd')
+    if lse2 is None:
+        check(_lib.lib().vh_attn_rows_hd(*args, stream()), 'vh_attn_rows_hd')
+    else:
+        check(_lib.lib().vh_attn_rows_hd_lse(*args, lse2.data_ptr(), stream()), 'vh_attn_rows_hd_lse')
     return out
+
+
+def attn_rows_hd_bwd(q, k, v, out, dout, lse2, dq, dk, dv, scale, **spec):
+    """dq, dk, dv of `attn_rows_hd(q, k, v, out, scale, lse2=lse2, **spec)` given dout (vh_attn_rows_hd_bwd): two flash
+    launches, P recomputed tile by tile from lse2, no score map, no atomics (two runs give the same bits).  All nine are
+    (B, h, T, hd) views with unit stride in the last dimension (Tq == Tk == T); dq / dk / dv share one stride set — the column
+    blocks of one (rows, 3 d) gradient buffer — and every element of them is written once, so `torch.empty` memory will do."""
+    if spec.get('mask') is not None or spec.get('pad') is not None:
+        raise _lib.VhError('attn_rows_hd_bwd: caller-supplied masks take the materialised backward')
+    views = ((q, 'q'), (k, 'k'), (v, 'v'), (out, 'out'), (dout, 'dout'), (dq, 'dq'), (dk, 'dk'), (dv, 'dv'))
+    if q.dim() != 4 or any(t.shape != q.shape for t, _ in views):
+        raise _lib.VhError('attn_rows_hd_bwd: ' + ' '.join(f'{nm} {tuple(t.shape)}' for t, nm in views) + ' (one shape, Tq == Tk)')
+    _attn_hd_views('attn_rows_hd_bwd', views, spec)
+    if not (dq.stride() == dk.stride() == dv.stride()):
+        raise _lib.VhError('attn_rows_hd_bwd: dq/dk/dv must share one stride set')
+    B, h, T, hd = q.shape
+    if lse2.dtype != torch.float32 or tuple(lse2.shape) != (B, h, T) or not lse2.is_cuda or not lse2.is_contiguous():
+        raise _lib.VhError(f'attn_rows_hd_bwd: lse2 must be a contiguous device float32 tensor of shape {(B, h, T)}')
+    need = _lib.lib().vh_attn_rows_hd_bwd_ws_bytes(B, h, T)
+    ws = _stream_ws(_BWD_WS, q.device, need)
+    ATTN_HD_BWD_CALLS['flash'] += 1
+    check(_lib.lib().vh_attn_rows_hd_bwd(
+        *_view_args(q), *_view_args(k), *_view_args(v), *_view_args(out), *_view_args(dout), lse2.data_ptr(),
+        dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dq.stride(0), dq.stride(1), dq.stride(2), B, h, hd, T, float(scale),
+        spec.get('mode', MASK_FULL), int(spec.get('x_len', 0)), ptr(spec.get('x_len_dev')), ptr(spec.get('kv_len')),
+        ptr(ws), ws.numel() * 4, stream()), 'vh_attn_rows_hd_bwd')
+    return dq, dk, dv
 
 
 def attn_decode_ws(B, n_heads, n_split, device):
