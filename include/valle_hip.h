@@ -1250,6 +1250,42 @@ int vh_transformer_forward_packed_lm_bf16(const vh_forward16_desc* desc, const i
 int vh_kv_unpack_bf16(const uint16_t* src, uint16_t* dst, int n_streams, int n_heads, int S_src, int B_dst, int S_dst,
                       const int32_t* seg_start, const int32_t* seg_len, const int32_t* dst_row, int n_seg, void* stream);
 
+/* ---- the decoder of the 24 kHz EnCodec family: codes -> waveform (additions under ABI 146; csrc/codec.hip) -----------------
+ * Replaces the arithmetic behind EncodecPip.decode (valle/models/encodec_pip.py:59-72): the residual vector quantiser's
+ * decode and the causal SEANet decoder.  Activations are channels-last (B, T, C) fp32: a time step is a row.  Every shape,
+ * alignment and pointer fault is refused before any launch. */
+enum { VH_PAD_ZERO = 0, VH_PAD_REFLECT = 1 };
+/* out[b, t, :] = sum over q < Q of codebooks[q][codes[b, q, t]], added in codebook order 0 .. Q-1 starting from 0.0f (fp32
+ * torch adding in that order is bit-equal).  codes (B, Q, T) int64; codebooks (n_books, K, D), Q <= n_books; out (B, T, D);
+ * D % 4 == 0.  An id outside [0, K) is never read: it contributes nothing and ORs VH_DEVERR_EMBED_ID into *err_flag (device
+ * int32, may be NULL). */
+int vh_rvq_decode(const int64_t* codes, const float* codebooks, float* out, int B, int Q, int T, int n_books, int K, int D,
+                  int32_t* err_flag, void* stream);
+/* The causal windowed GEMM of every convolution of the decoder, on v_mfma_f32_32x32x2_f32:
+ *   out[b, t, co] = bias[co] + sum_k sum_ci act(xpad[b, t + k dilation, ci]) w[co, k, ci]  (+ residual[b, t, co])
+ * x (B, T, C_in); w (C_out, taps, C_in) — nn.Conv1d's (C_out, C_in, taps) with its last two dimensions swapped, so that the
+ * reduction runs along memory; bias (C_out) or NULL; residual (B, T, C_out) or NULL; out (B, T, C_out).  xpad is x with
+ * (taps - 1) dilation rows of LEFT padding per batch row (row b's window never reads row b - 1): zeros (VH_PAD_ZERO), or the
+ * reflection xpad[i] = x[pad - i] (VH_PAD_REFLECT), where an x row >= T reads as zero — the reference's small-input branch
+ * (zero-extend to pad + 1, reflect, cut the extension off) for T <= pad.  elu = 1 applies ELU (alpha 1, expm1 for x <= 0) to
+ * every x on load; act is the identity otherwise.  A ConvTranspose1d(C_in, C, 2 r, stride r) trimmed by r on the right is
+ * this entry with taps 2, VH_PAD_ZERO, C_out = r C and w[(p, co), 0, ci] = wt[ci, co, p + r], w[(p, co), 1, ci] =
+ * wt[ci, co, p]: its (B, T, r C) output IS the (B, T r, C) layout.  C_in % 4 == 0; C_out % 4 == 0 or C_out == 1 (the
+ * waveform); anything else is VH_EUNSUPPORTED by name.  An output element's sum order depends on (taps, C_in) alone: a row of
+ * a right-padded batch has the bits of the same row decoded alone — with lens (device int32 (B), or NULL: every batch row holds
+ * T rows): batch row b holds lens[b] len_scale valid rows (clamped to 0 .. T), and the reflection, which reads FORWARD at the
+ * start of a row, reads zero beyond them, exactly what the small-input branch gives that utterance alone.  Rows t >= the
+ * valid length are computed from whatever x holds there. */
+int vh_conv1d_causal(const float* x, const float* w, const float* bias, const float* residual, float* out, int B, int T,
+                     int C_in, int C_out, int taps, int dilation, int pad_mode, int elu, const int32_t* lens, int len_scale,
+                     void* stream);
+/* One nn.LSTM layer over T steps, zero initial state, gate order i, f, g, o: T launches, one per step (no workgroup waits
+ * for another inside a launch).  xproj (B, T, 4 H): W_ih x_t + b_ih + b_hh of every frame (one vh_conv1d_causal with taps 1);
+ * w_hh (4 H, H); h_seq (B, T, H) receives h_t; c (B, H) is scratch (the cell state; needs no initialisation); skip and y
+ * (B, T, H), both or neither: y = h_t + skip, the residual the decoder's LSTM block ends with.  H % 4 == 0, H <= 1024. */
+int vh_lstm_layer(const float* xproj, const float* w_hh, float* h_seq, float* c, const float* skip, float* y, int B, int T,
+                  int H, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -341,6 +341,11 @@ SIGNATURES = {
                                                         C.c_void_p]),
     'vh_kv_unpack_bf16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p,
                                     C.c_int, C.c_void_p]),
+    # the EnCodec decoder: codes -> waveform (additions under ABI 146)
+    'vh_rvq_decode': (C.c_int, [c_i64p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_void_p]),
+    'vh_conv1d_causal': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, c_i32p, C.c_int, C.c_void_p]),
+    'vh_lstm_layer': (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 _lib = None

@@ -1,10 +1,12 @@
 """The codec side of the path, WIRE FORMAT ONLY (reference: valle/models/encodec_pip.py:24-85,
 valle/collate.py:19-60, valle/models/valle_ar.py:95-97, valle/models/valle_nar.py:107-116).
 
-EnCodec's own arithmetic (SEANet encoder / decoder, residual vector quantiser) is NOT here: it is a third-party package
-(`encodec==0.1.1`, absent from this image) whose weights are downloaded, so there is neither an oracle nor a checkpoint to
-pin a kernel to — that part of the row stays "parity unpinned" (DESIGN.md section 7).  What IS here is everything between
-the codec's tensors and the models, so that a user of the reference finds the same objects:
+EnCodec's own arithmetic is not in THIS module.  Its DECODER half (residual vector quantiser decode + causal SEANet decoder,
+codes -> waveform) is built in valle2_amd/codec.py over csrc/codec.hip: an `EncodecDecoder` is a `codec=` object for the
+`synthesize*` functions below, which take any object with `decode` (pinned to a float64 mirror of
+`transformers`' EncodecModel on random weights, no trained checkpoint).  Its ENCODER half is not built: the `encodec` package
+(`encodec==0.1.1`) and its downloaded weights are absent, prompts come as codes.  What IS here is
+everything between the codec's tensors and the models, so that a user of the reference finds the same objects:
 
   layouts      codec  `(Q, T)` int64  (EncodecPip.encode, encodec_pip.py:24-41; `(B, Q, T)` batched, :43-57)
                collate item  {'codes': (Q, T), 'tokens': (n,)}  ->  ValleARCollate / ValleNARCollate (collate.py)

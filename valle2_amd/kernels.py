@@ -1331,3 +1331,67 @@ def gemm(a, b, out, a_kmajor=False, b_kmajor=False):
                                      int(b_kmajor), out.data_ptr(), ldc, scb, sch, M, N, K, nb, nh, splits,
                                      stream()), 'vh_gemm_batched')
     return out
+
+
+# ---- the EnCodec decoder's kernels (csrc/codec.hip): channels-last (B, T, C) fp32 activations ------------------------------
+PAD_ZERO, PAD_REFLECT = 0, 1
+
+
+def _codec_dense(t, name, shape=None):
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise _lib.VhError(f'{name}: a contiguous fp32 HIP device tensor is required, got {t.dtype} on {t.device}')
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise _lib.VhError(f'{name}: shape {tuple(t.shape)}, expected {tuple(shape)}')
+    return t.data_ptr()
+
+
+def rvq_decode(codes, codebooks, out=None):
+    """vh_rvq_decode: codes (B, Q, T) int64, codebooks (n_books, K, D) -> (B, T, D) = the sum of the Q embeddings in codebook
+    order.  An id outside [0, K) raises the device error flag (`_lib.raise_device_errors`) and is never read."""
+    if codes.dim() != 3 or codes.dtype != torch.int64 or not codes.is_cuda:
+        raise _lib.VhError(f'rvq_decode: codes must be a (B, Q, T) int64 HIP device tensor, got {tuple(codes.shape)} {codes.dtype}')
+    codes = codes.contiguous()
+    B, Q, T = codes.shape
+    n_books, K, D = codebooks.shape
+    if out is None:
+        out = torch.empty(B, T, D, device=codes.device, dtype=torch.float32)
+    check(_lib.lib().vh_rvq_decode(codes.data_ptr(), _codec_dense(codebooks, 'codebooks'), _codec_dense(out, 'out', (B, T, D)),
+                                   B, Q, T, n_books, K, D, ptr(_lib.err_flag(codes.device)), stream()), 'vh_rvq_decode')
+    return out
+
+
+def conv1d_causal(x, w, bias=None, residual=None, dilation=1, pad_mode=PAD_REFLECT, elu=False, out=None, lens=None, len_scale=1):
+    """vh_conv1d_causal: x (B, T, C_in), w (C_out, taps, C_in) -> (B, T, C_out) =
+    bias + sum_k sum_ci act(xpad[b, t + k dilation, ci]) w[co, k, ci] (+ residual), left-padded per batch row.
+    lens (B) device int32: batch row b holds lens[b] * len_scale valid rows, beyond which the reflect padding reads zero (a
+    right-padded ragged batch then gives every utterance the bits it has alone)."""
+    if lens is not None and (lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != x.shape[0] or not lens.is_contiguous()):
+        raise _lib.VhError('conv1d_causal: lens must be a contiguous device int32 tensor of B entries')
+    if x.dim() != 3 or w.dim() != 3 or w.shape[2] != x.shape[2]:
+        raise _lib.VhError(f'conv1d_causal: x {tuple(x.shape)} (B, T, C_in) against w {tuple(w.shape)} (C_out, taps, C_in)')
+    B, T, C_in = x.shape
+    C_out, taps, _ = w.shape
+    if out is None:
+        out = torch.empty(B, T, C_out, device=x.device, dtype=torch.float32)
+    check(_lib.lib().vh_conv1d_causal(
+        _codec_dense(x, 'x'), _codec_dense(w, 'w'), None if bias is None else _codec_dense(bias, 'bias', (C_out,)),
+        None if residual is None else _codec_dense(residual, 'residual', (B, T, C_out)), _codec_dense(out, 'out', (B, T, C_out)),
+        B, T, C_in, C_out, taps, int(dilation), int(pad_mode), int(bool(elu)), None if lens is None else lens.data_ptr(),
+        int(len_scale), stream()), 'vh_conv1d_causal')
+    return out
+
+
+def lstm_layer(xproj, w_hh, skip=None):
+    """vh_lstm_layer: xproj (B, T, 4 H) = W_ih x + b_ih + b_hh of every frame, w_hh (4 H, H) -> h (B, T, H), or h + skip when
+    `skip` (B, T, H) is given.  Zero initial state, gate order i, f, g, o; one launch per time step."""
+    if xproj.dim() != 3 or w_hh.dim() != 2 or xproj.shape[2] != w_hh.shape[0] or w_hh.shape[0] != 4 * w_hh.shape[1]:
+        raise _lib.VhError(f'lstm_layer: xproj {tuple(xproj.shape)} (B, T, 4 H) against w_hh {tuple(w_hh.shape)} (4 H, H)')
+    B, T, _ = xproj.shape
+    H = w_hh.shape[1]
+    h = torch.empty(B, T, H, device=xproj.device, dtype=torch.float32)
+    c = torch.empty(B, H, device=xproj.device, dtype=torch.float32)
+    y = None if skip is None else torch.empty_like(h)
+    check(_lib.lib().vh_lstm_layer(_codec_dense(xproj, 'xproj'), _codec_dense(w_hh, 'w_hh'), h.data_ptr(), c.data_ptr(),
+                                   None if skip is None else _codec_dense(skip, 'skip', (B, T, H)),
+                                   None if y is None else y.data_ptr(), B, T, H, stream()), 'vh_lstm_layer')
+    return h if skip is None else y
