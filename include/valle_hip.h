@@ -1286,6 +1286,42 @@ int vh_conv1d_causal(const float* x, const float* w, const float* bias, const fl
 int vh_lstm_layer(const float* xproj, const float* w_hh, float* h_seq, float* c, const float* skip, float* y, int B, int T,
                   int H, void* stream);
 
+/* ---- the encoder of the same family: waveform -> codes (additions under ABI 146: VH_VERSION stays; csrc/codec.hip) -------
+ * Replaces the arithmetic behind EncodecPip.encode (valle/models/encodec_pip.py): the causal SEANet encoder and the residual
+ * vector quantiser's encode.  The stride-1 convolutions, the residual blocks and the LSTM are vh_conv1d_causal and
+ * vh_lstm_layer; these three are what the encoder adds.  Every shape, alignment and pointer fault is refused before any
+ * launch. */
+/* The first convolution, C_in = 1: x (B, L) -> out (B, L, C_out), out[b, t, co] = bias[co] + sum_k xpad[b, t + k] w[co, k].
+ * w (C_out, taps); bias (C_out) or NULL; taps - 1 samples of LEFT reflection per batch row (xpad[i] = x[pad - i]); lens
+ * (device int32 (B)) or NULL: batch row b holds lens[b] valid samples (clamped to 0 .. L) and a FORWARD read beyond them
+ * reads zero, exactly as vh_conv1d_causal treats it (the reference's small-input branch for that utterance alone).  One lane
+ * computes 4 output channels: fma over the taps in order from 0, then + bias — the sum order depends on taps alone.
+ * C_out % 4 == 0; 1 <= taps <= 64. */
+int vh_conv1d_wave(const float* x, const float* w, const float* bias, float* out, int B, int L, int C_out, int taps,
+                   const int32_t* lens, void* stream);
+/* The strided, downsampling causal convolution (EncodecConv1d with stride > 1) on v_mfma_f32_32x32x2_f32:
+ *   out[b, t', co] = bias[co] + sum_k sum_ci act(xpad_b[t' stride + k, ci]) w[co, k, ci],  t' < T_out = ceil(T / stride)
+ * x (B, T, C_in); w (C_out, taps, C_in); bias (C_out) or NULL; out (B, T_out, C_out).  xpad_b is the reference's causal
+ * padding of batch row b over its own valid length len_b = lens ? clamp(lens[b], 0, T) : T:  taps - stride rows of left
+ * reflection (xpad[left - i] = x[i]), then the len_b rows, then ceil(len_b / stride) stride - len_b rows of right reflection
+ * (xpad[left + len_b + i] = x[len_b - 2 - i]); when len_b <= max(left, right) the reference's small-input rule holds: the
+ * row is zero-extended to max(left, right) + 1 rows, reflected, and the extension cut off the end.  elu = 1 applies ELU on
+ * load.  Output rows t' >= ceil(len_b / stride) of a batch row are written as zeros; no valid row of a later layer reads
+ * them.  The kernel is vh_conv1d_causal's (same tiles, same fragment order): an output's sum order depends on
+ * (taps, C_in) alone and a row of a padded batch has the bits of the same utterance alone.  C_in % 4 == 0, C_out % 4 == 0,
+ * 1 <= stride <= taps <= 64. */
+int vh_conv1d_down(const float* x, const float* w, const float* bias, float* out, int B, int T, int C_in, int C_out, int taps,
+                   int stride, int elu, const int32_t* lens, void* stream);
+/* The residual vector quantiser's encode, all Q stages in ONE launch: x (B, T, D) -> codes (B, Q, T) int64, the layout
+ * vh_rvq_decode reads.  Stage q picks id = argmax_k 2 r.E[q][k] - e_sq[q][k] (the nearest entry; the LOWEST index of equal
+ * scores; a row whose scores are not finite still gets an id inside [0, K)), then r -= E[q][id] in plain fp32 — the
+ * reference's residual - quantized.  codebooks (n_books, K, D), Q <= n_books; e_sq (n_books, K) = |E[q][k]|^2, precomputed
+ * by the caller.  A workgroup keeps the residual of 128 rows in registers across the stages, streams each codebook through
+ * LDS in chunks of 32 entries and forms the scores on v_mfma_f32_32x32x2_f32; a row's codes depend on that row alone.
+ * D % 4 == 0, D <= 128, K <= 16384; beyond them VH_EUNSUPPORTED. */
+int vh_rvq_encode(const float* x, const float* codebooks, const float* e_sq, int64_t* codes, int B, int T, int D, int Q,
+                  int n_books, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,11 +3,11 @@
 Python here is host plumbing over libvalle_hip.so (hand-written gfx950 kernels, C ABI in
 include/valle_hip.h).  There is no CPU compute path: ops raise `VhError` without a HIP device.
 """
-from .codec import EncodecDecoder  # noqa: F401
+from .codec import EncodecCodec, EncodecDecoder, EncodecEncoder  # noqa: F401
 from .config import ConfigValle  # noqa: F401
 from .sampling import Bounded, RepetitionAware, Sampling  # noqa: F401
 
-__all__ = ['Bounded', 'ConfigValle', 'EncodecDecoder', 'MODEL_DICT', 'RepetitionAware', 'Sampling', 'get_model_class']
+__all__ = ['Bounded', 'ConfigValle', 'EncodecCodec', 'EncodecDecoder', 'EncodecEncoder', 'MODEL_DICT', 'RepetitionAware', 'Sampling', 'get_model_class']
 
 
 def _models():

@@ -1,13 +1,18 @@
-"""The DECODER half of the 24 kHz EnCodec family on the device: codes `(Q, T)` -> waveform `(hop T,)`, fp32, in the kernels of
-csrc/codec.hip (vh_rvq_decode, vh_conv1d_causal, vh_lstm_layer).  `EncodecDecoder` drops into `codec_io.synthesize*` as the
-`codec=` object: the codes never leave the GPU and neither does the waveform.
+"""The 24 kHz EnCodec family on the device, fp32, in the kernels of csrc/codec.hip.  DECODER: codes `(Q, T)` -> waveform
+`(hop T,)` (vh_rvq_decode, vh_conv1d_causal, vh_lstm_layer); `EncodecDecoder` drops into `codec_io.synthesize*` as the `codec=`
+object: the codes never leave the GPU and neither does the waveform.  ENCODER: waveform `(L,)` -> codes `(Q, ceil(L / hop))`
+(vh_conv1d_wave, vh_conv1d_down, vh_rvq_encode over the decoder's stride-1 convolution and LSTM): `EncodecEncoder`, and
+`EncodecCodec`, both halves as one `codec=` object, so that a request can be (text, prompt waveform).
 
 What is here: the residual vector quantiser's decode and the causal SEANet decoder (first convolution, a 2-layer LSTM with its
 skip, per ratio a transposed convolution and residual blocks, the last convolution), weights taken from a state dict in the
-key layout of `transformers`' EncodecModel.  What is not: the encoder and RVQ encode (there is no `encode`: prompts come as
-codes), the non-causal 48 kHz model, 16-bit arithmetic, streaming, and the `encodec` package's own checkpoint names.  Parity
-is pinned against a float64 restatement on RANDOM weights (tests/codec_mirror.py, tests/golden/codec_small.npz); no trained
-checkpoint has been run through it.
+key layout of `transformers`' EncodecModel; and the mirror image, the causal SEANet encoder (first convolution over the raw
+waveform, per ratio residual blocks and a strided convolution with the reference's right-hand "extra" reflect padding, the
+LSTM, the last convolution) followed by the quantiser's encode (nearest entry per stage, all stages in one launch).  What is
+not: the non-causal 48 kHz model, `normalize=True`, chunking, 16-bit arithmetic, streaming, and the `encodec` package's own
+checkpoint names.  Parity is pinned against float64 restatements on RANDOM weights (tests/codec_mirror.py,
+tests/codec_enc_mirror.py, tests/golden/codec_small.npz, tests/golden/codec_enc_small.npz); no trained checkpoint has been run
+through either half.
 
 The decoder is causal — reflect padding on the left only, a one-directional LSTM, transposed convolutions trimmed on the right —
 so a ragged batch is right-padded, decoded once and trimmed (`decode_many`), bit for bit what each utterance gives alone.  One
@@ -31,38 +36,38 @@ _FAMILY = dict(use_causal_conv=True, norm_type='weight_norm', pad_mode='reflect'
                normalize=False, chunk_length_s=None, use_conv_shortcut=True)
 
 
-def _check_arch(arch: dict) -> dict:
+def _check_arch(arch: dict, who: str = 'EncodecDecoder') -> dict:
     unknown = sorted(set(arch) - set(ARCH_DEFAULTS))
     if unknown:
-        raise ValueError(f'EncodecDecoder: unknown architecture field(s) {unknown}')
+        raise ValueError(f'{who}: unknown architecture field(s) {unknown}')
     a = dict(ARCH_DEFAULTS, **arch)
     for name, want in _FAMILY.items():
         if a[name] != want:
-            raise ValueError(f'EncodecDecoder: {name}={a[name]!r} is outside the causal 24 kHz family served here ({name}={want!r})')
+            raise ValueError(f'{who}: {name}={a[name]!r} is outside the causal 24 kHz family served here ({name}={want!r})')
     a['upsampling_ratios'] = tuple(int(r) for r in a['upsampling_ratios'])
     ints = ('num_filters', 'hidden_size', 'num_residual_layers', 'kernel_size', 'last_kernel_size', 'residual_kernel_size',
             'dilation_growth_rate', 'num_lstm_layers', 'compress', 'codebook_size', 'sampling_rate')
     for name in ints:
         if not isinstance(a[name], int) or a[name] < (0 if name == 'num_residual_layers' else 1):
-            raise ValueError(f'EncodecDecoder: {name}={a[name]!r} must be a positive integer')
+            raise ValueError(f'{who}: {name}={a[name]!r} must be a positive integer')
     if not a['upsampling_ratios'] or any(r < 1 for r in a['upsampling_ratios']):
-        raise ValueError(f'EncodecDecoder: upsampling_ratios={a["upsampling_ratios"]!r} must be positive integers')
+        raise ValueError(f'{who}: upsampling_ratios={a["upsampling_ratios"]!r} must be positive integers')
     # every activation is a (rows, C) matrix whose rows stay on 16-byte boundaries
     if a['hidden_size'] % 4:
-        raise ValueError(f'EncodecDecoder: hidden_size={a["hidden_size"]} is not a multiple of 4 (channel counts must be)')
+        raise ValueError(f'{who}: hidden_size={a["hidden_size"]} is not a multiple of 4 (channel counts must be)')
     width = a['num_filters'] * 2 ** len(a['upsampling_ratios'])
     if width > 1024:
-        raise ValueError(f'EncodecDecoder: num_filters={a["num_filters"]} x 2^{len(a["upsampling_ratios"])} = {width} LSTM units; '
+        raise ValueError(f'{who}: num_filters={a["num_filters"]} x 2^{len(a["upsampling_ratios"])} = {width} LSTM units; '
                          'at most 1024 are served')
     for level in range(len(a['upsampling_ratios']) + 1):
         c = width >> level
         if c % 4:
-            raise ValueError(f'EncodecDecoder: num_filters={a["num_filters"]}: the channel count {c} after {level} upsampling '
+            raise ValueError(f'{who}: num_filters={a["num_filters"]}: the channel count {c} after {level} upsampling '
                              'stage(s) is not a multiple of 4')
     for level in range(len(a['upsampling_ratios']) + 1):
         c = width >> level
         if level and a['num_residual_layers'] and (c % a['compress'] or (c // a['compress']) % 4):
-            raise ValueError(f'EncodecDecoder: compress={a["compress"]}: the residual blocks\' hidden channel count '
+            raise ValueError(f'{who}: compress={a["compress"]}: the residual blocks\' hidden channel count '
                              f'{c}/{a["compress"]} is not a multiple of 4')
     return a
 
@@ -285,3 +290,267 @@ class EncodecDecoder:
                 y = K.conv1d_causal(y, *blk['conv2'], elu=True)
                 x = K.conv1d_causal(x, *blk['shortcut'], residual=y)
         return K.conv1d_causal(x, *w['last'], elu=True, lens=lens, len_scale=scale).view(B, self.hop * T)
+
+
+# ---- the encoder ----------------------------------------------------------------------------------------------------------------
+def encoder_state_dict_keys(arch: dict) -> dict:
+    """The encoder's key mapping, as `state_dict_keys` is the decoder's.  encoder.layers: 0 first convolution, then per ratio
+    in REVERSED upsampling_ratios [residual blocks ..., ELU, downsampling convolution], then [LSTM, ELU, last convolution]."""
+    p = 'encoder.layers.'
+    keys = {'first': p + '0.conv', 'stages': []}
+    idx = 1
+    for _ in arch['upsampling_ratios']:
+        stage = {'blocks': []}
+        for _ in range(arch['num_residual_layers']):
+            stage['blocks'].append({'conv1': f'{p}{idx}.block.1.conv', 'conv2': f'{p}{idx}.block.3.conv',
+                                    'shortcut': f'{p}{idx}.shortcut.conv'})
+            idx += 1
+        stage['down'] = f'{p}{idx + 1}.conv'
+        idx += 2
+        keys['stages'].append(stage)
+    keys['lstm'] = [{n: f'{p}{idx}.lstm.{n}_l{layer}' for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')}
+                    for layer in range(arch['num_lstm_layers'])]
+    keys['last'] = f'{p}{idx + 2}.conv'
+    return keys
+
+
+def _lstm_weights(sd, names, width):
+    w_ih, w_hh = _get(sd, names['weight_ih']).double(), _get(sd, names['weight_hh']).double()
+    bias = _get(sd, names['bias_ih']).double() + _get(sd, names['bias_hh']).double()
+    _expect(names['weight_ih'], w_ih, (4 * width, width))
+    _expect(names['weight_hh'], w_hh, (4 * width, width))
+    _expect(names['bias_ih'], bias, (4 * width,))
+    return w_ih[:, None, :].contiguous().float(), bias.float(), w_hh.contiguous().float()
+
+
+def _codebooks(sd, a):
+    books = []
+    while codebook_key(len(books)) in sd:
+        books.append(_get(sd, codebook_key(len(books))))
+    if not books:
+        raise KeyError(f'EncodecDecoder: the state dict has no {codebook_key(0)!r}')
+    for q, t in enumerate(books):
+        _expect(codebook_key(q), t, (a['codebook_size'], a['hidden_size']))
+    return torch.stack([t.float() for t in books]).contiguous()
+
+
+class EncodecEncoder:
+    """waveform -> codes for the causal 24 kHz EnCodec family, on the HIP device the waveform lives on: `transformers`'
+    EncodecModel.encoder followed by quantizer.encode, in the kernels of csrc/codec.hip."""
+    RVQ_MAX_D, RVQ_MAX_K = 128, 16384           # what vh_rvq_encode serves
+
+    def __init__(self, arch: dict, weights: dict):
+        self.arch = arch
+        self._host = weights            # fp32, on the host, in the kernels' layouts
+        self._dev = {}
+        self.ratios = tuple(reversed(arch['upsampling_ratios']))      # the order the encoder downsamples in
+        self.hop = 1
+        for r in self.ratios:
+            self.hop *= r
+
+    @classmethod
+    def from_state_dict(cls, sd, **arch) -> 'EncodecEncoder':
+        """Build from a state dict in `transformers`' EncodecModel key layout (`encoder_state_dict_keys`, `codebook_key`) and
+        the architecture numbers (`ARCH_DEFAULTS`), under the decoder's rules: no device work, an architecture outside the
+        family is a ValueError naming the field, a missing tensor a KeyError naming the key."""
+        a = _check_arch(arch, 'EncodecEncoder')
+        if a['hidden_size'] > cls.RVQ_MAX_D or a['codebook_size'] > cls.RVQ_MAX_K:
+            raise ValueError(f'EncodecEncoder: hidden_size={a["hidden_size"]} / codebook_size={a["codebook_size"]}: the quantiser '
+                             f'encodes up to hidden_size {cls.RVQ_MAX_D} and codebook_size {cls.RVQ_MAX_K}')
+        for r in a['upsampling_ratios']:
+            if 2 * r > 64:
+                raise ValueError(f'EncodecEncoder: upsampling_ratios={a["upsampling_ratios"]!r}: a downsampling convolution has '
+                                 f'2 x ratio taps, at most 64 are served')
+        keys = encoder_state_dict_keys(a)
+        c = a['num_filters']
+        w0, b0 = _conv(sd, keys['first'], 1, c, a['kernel_size'])
+        w = {'first': (w0.reshape(c, a['kernel_size']).contiguous(), b0), 'stages': [], 'lstm': []}
+        for ratio, stage in zip(reversed(a['upsampling_ratios']), keys['stages']):
+            blocks = []
+            for j, names in enumerate(stage['blocks']):
+                hid = c // a['compress']
+                blocks.append({'dilation': a['dilation_growth_rate'] ** j,
+                               'conv1': _conv(sd, names['conv1'], c, hid, a['residual_kernel_size']),
+                               'conv2': _conv(sd, names['conv2'], hid, c, 1),
+                               'shortcut': _conv(sd, names['shortcut'], c, c, 1)})
+            w['stages'].append({'blocks': blocks, 'down': _conv(sd, stage['down'], c, 2 * c, 2 * ratio)})
+            c *= 2
+        for names in keys['lstm']:
+            w['lstm'].append(_lstm_weights(sd, names, c))
+        w['last'] = _conv(sd, keys['last'], c, a['hidden_size'], a['last_kernel_size'])
+        w['codebooks'] = _codebooks(sd, a)
+        # |e|^2 of every entry in float64, stored as fp32: the quantiser's score is 2 r.e - |e|^2
+        w['e_sq'] = w['codebooks'].double().pow(2).sum(-1).float().contiguous()
+        return cls(a, w)
+
+    @property
+    def sampling_rate(self) -> int:
+        return self.arch['sampling_rate']
+
+    @property
+    def num_codebooks(self) -> int:
+        return int(self._host['codebooks'].shape[0])
+
+    def frames(self, n_samples: int) -> int:
+        """The frame count of n_samples: every downsampling stage takes the ceiling, which is ceil(n_samples / hop)."""
+        return -(-int(n_samples) // self.hop)
+
+    # ---- checks, all before any device work ---------------------------------------------------------------------------
+    def _check_wave(self, wave, name, rank):
+        if not isinstance(wave, Tensor) or not wave.is_floating_point():
+            raise ValueError(f'{name}: a floating-point waveform tensor is expected, got '
+                             f'{wave.dtype if isinstance(wave, Tensor) else type(wave)}')
+        if wave.dim() != rank:
+            raise ValueError(f'{name}: expected a {rank}-D waveform {"(B, L)" if rank == 2 else "(L,)"} (mono), got {tuple(wave.shape)}')
+        if wave.numel() == 0:
+            raise ValueError(f'{name}: an empty waveform {tuple(wave.shape)}')
+        return wave
+
+    def _check_q(self, num_codebooks):
+        if num_codebooks is None:
+            return self.num_codebooks
+        if not isinstance(num_codebooks, int) or isinstance(num_codebooks, bool) or not 1 <= num_codebooks <= self.num_codebooks:
+            raise ValueError(f'num_codebooks={num_codebooks!r}: the encoder holds {self.num_codebooks} codebooks (1 .. {self.num_codebooks})')
+        return num_codebooks
+
+    def _on_device(self, wave):
+        if not wave.is_cuda:
+            raise _lib.VhError(f'EncodecEncoder: the waveform is on {wave.device}; the encoder runs on a HIP device and there is '
+                               'no CPU fallback')
+        return wave.float().contiguous()
+
+    # ---- what EncodecPip offers on the encode side --------------------------------------------------------------------
+    @torch.inference_mode()
+    def embed(self, wave: Tensor) -> Tensor:
+        """waveform (L,) -> the encoder's output (T, hidden_size), T = ceil(L / hop): what the quantiser sees."""
+        return self._embed(self._on_device(self._check_wave(wave, 'wave', 1))[None])[0]
+
+    @torch.inference_mode()
+    def encode(self, wave: Tensor, num_codebooks=None) -> Tensor:
+        """waveform (L,) -> codes (Q, T) int64, T = ceil(L / hop); Q = num_codebooks, or every codebook held."""
+        self._check_wave(wave, 'wave', 1)
+        Q = self._check_q(num_codebooks)
+        return self._quantise(self._embed(self._on_device(wave)[None]), Q)[0]
+
+    @torch.inference_mode()
+    def batch_encode(self, waves: Tensor, num_codebooks=None) -> Tensor:
+        """waveforms (B, L) of one length -> codes (B, Q, T)."""
+        self._check_wave(waves, 'waves', 2)
+        Q = self._check_q(num_codebooks)
+        return self._quantise(self._embed(self._on_device(waves)), Q)
+
+    @torch.inference_mode()
+    def encode_many(self, waves, num_codebooks=None, return_embeddings=False):
+        """[waveform (L_b,)] -> [codes (Q, T_b)]: one right-padded batch; every level's valid lengths are computed on the host
+        and uploaded once, and each utterance's codes (and embeddings (T_b, hidden_size), with return_embeddings) are bit for
+        bit what `encode` / `embed` give for it alone."""
+        waves = list(waves)
+        Q = self._check_q(num_codebooks)
+        if not waves:
+            return ([], []) if return_embeddings else []
+        for i, wv in enumerate(waves):
+            self._check_wave(wv, f'waves[{i}]', 1)
+            if wv.device != waves[0].device:
+                raise ValueError(f'waves[{i}] is on {wv.device}, waves[0] on {waves[0].device}')
+        dev = waves[0].device
+        if dev.type != 'cuda':
+            self._on_device(waves[0])
+        lengths = [int(wv.shape[0]) for wv in waves]
+        L = max(lengths)
+        batch = torch.zeros(len(waves), L, device=dev, dtype=torch.float32)
+        for i, wv in enumerate(waves):
+            batch[i, :lengths[i]] = wv
+        lens = None
+        if any(n != L for n in lengths):
+            levels = [lengths]
+            for r in self.ratios:
+                levels.append([-(-n // r) for n in levels[-1]])
+            lens = _lib.to_device_async(torch.tensor(levels, dtype=torch.int32), dev)         # (levels, B), one upload
+        emb = self._embed(batch, lens)
+        codes = self._quantise(emb, Q)
+        frames = [self.frames(n) for n in lengths]
+        out = [codes[i, :, :t] for i, t in enumerate(frames)]
+        return (out, [emb[i, :t] for i, t in enumerate(frames)]) if return_embeddings else out
+
+    # ---- the device side ----------------------------------------------------------------------------------------------
+    _weights = EncodecDecoder._weights
+
+    def _embed(self, wave: Tensor, lens=None) -> Tensor:
+        """wave (B, L) fp32 on the device -> (B, T, hidden_size); lens (levels, B) int32 on the device, or None."""
+        from . import kernels as K
+        w = self._weights(wave.device)
+        level = 0
+        at = (lambda i: None) if lens is None else (lambda i: lens[i])
+        x = K.conv1d_wave(wave, *w['first'], lens=at(0))
+        for ratio, stage in zip(self.ratios, w['stages']):
+            for blk in stage['blocks']:
+                y = K.conv1d_causal(x, *blk['conv1'], dilation=blk['dilation'], elu=True, lens=at(level))
+                y = K.conv1d_causal(y, *blk['conv2'], elu=True)
+                x = K.conv1d_causal(x, *blk['shortcut'], residual=y)
+            x = K.conv1d_down(x, *stage['down'], stride=ratio, elu=True, lens=at(level))
+            level += 1
+        h = x
+        for layer, (w_ih, bias, w_hh) in enumerate(w['lstm']):
+            last = layer == len(w['lstm']) - 1
+            h = K.lstm_layer(K.conv1d_causal(h, w_ih, bias), w_hh, skip=x if last else None)
+        return K.conv1d_causal(h, *w['last'], elu=True, lens=at(level))
+
+    def _quantise(self, emb: Tensor, Q: int) -> Tensor:
+        from . import kernels as K
+        w = self._weights(emb.device)
+        return K.rvq_encode(emb, w['codebooks'], w['e_sq'], Q)
+
+
+class EncodecCodec:
+    """Both halves: the `codec=` object of `codec_io.synthesize*` for waveform prompts — `encode` on the prompt, `decode` on
+    the synthesised codes, nothing leaving the device."""
+
+    def __init__(self, encoder: EncodecEncoder, decoder: EncodecDecoder):
+        if encoder.hop != decoder.hop or encoder.num_codebooks != decoder.num_codebooks or \
+                encoder.arch['codebook_size'] != decoder.arch['codebook_size'] or encoder.sampling_rate != decoder.sampling_rate:
+            raise ValueError(f'EncodecCodec: the encoder (hop {encoder.hop}, {encoder.num_codebooks} codebooks of '
+                             f'{encoder.arch["codebook_size"]}) and the decoder (hop {decoder.hop}, {decoder.num_codebooks} of '
+                             f'{decoder.arch["codebook_size"]}) are not two halves of one codec')
+        self.encoder, self.decoder = encoder, decoder
+
+    @classmethod
+    def from_state_dict(cls, sd, **arch) -> 'EncodecCodec':
+        return cls(EncodecEncoder.from_state_dict(sd, **arch), EncodecDecoder.from_state_dict(sd, **arch))
+
+    @property
+    def sampling_rate(self) -> int:
+        return self.decoder.sampling_rate
+
+    @property
+    def num_codebooks(self) -> int:
+        return self.decoder.num_codebooks
+
+    @property
+    def hop(self) -> int:
+        return self.decoder.hop
+
+    def encode(self, wave, num_codebooks=None):
+        return self.encoder.encode(wave, num_codebooks)
+
+    def batch_encode(self, waves, num_codebooks=None):
+        return self.encoder.batch_encode(waves, num_codebooks)
+
+    def encode_many(self, waves, num_codebooks=None):
+        return self.encoder.encode_many(waves, num_codebooks)
+
+    def get_embedding(self, wave):
+        """waveform (L,) -> the encoder's output in the reference's layout (hidden_size, T)."""
+        return self.encoder.embed(wave).t()
+
+    def decode(self, codes):
+        return self.decoder.decode(codes)
+
+    def batch_decode(self, codes):
+        return self.decoder.batch_decode(codes)
+
+    def decode_many(self, codes_list):
+        return self.decoder.decode_many(codes_list)
+
+    def encode_decode(self, wave, num_codebooks=None):
+        """waveform (L,) -> its reconstruction (hop T,), T = ceil(L / hop)."""
+        return self.decoder.decode(self.encoder.encode(wave, num_codebooks))

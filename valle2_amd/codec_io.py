@@ -4,9 +4,10 @@ valle/collate.py:19-60, valle/models/valle_ar.py:95-97, valle/models/valle_nar.p
 EnCodec's own arithmetic is not in THIS module.  Its DECODER half (residual vector quantiser decode + causal SEANet decoder,
 codes -> waveform) is built in valle2_amd/codec.py over csrc/codec.hip: an `EncodecDecoder` is a `codec=` object for the
 `synthesize*` functions below, which take any object with `decode` (pinned to a float64 mirror of
-`transformers`' EncodecModel on random weights, no trained checkpoint).  Its ENCODER half is not built: the `encodec` package
-(`encodec==0.1.1`) and its downloaded weights are absent, prompts come as codes.  What IS here is
-everything between the codec's tensors and the models, so that a user of the reference finds the same objects:
+`transformers`' EncodecModel on random weights, no trained checkpoint).  Its ENCODER half (causal SEANet encoder + residual
+vector quantiser encode, waveform -> codes) is built there too: an `EncodecCodec` holds both halves, and a waveform prompt
+handed to `synthesize*` with it is encoded on the device.  The `encodec` package (`encodec==0.1.1`),
+its checkpoint names and its downloaded weights are absent.  What IS here is everything between the codec's tensors and the models, so that a user of the reference finds the same objects:
 
   layouts      codec  `(Q, T)` int64  (EncodecPip.encode, encodec_pip.py:24-41; `(B, Q, T)` batched, :43-57)
                collate item  {'codes': (Q, T), 'tokens': (n,)}  ->  ValleARCollate / ValleNARCollate (collate.py)
@@ -205,11 +206,16 @@ def synthesize_requests(ar, nar, items, codec=None, *, queued=False, slots=None)
 def _synthesize_list(ar, nar, items, codec, greedy_nar, ar_generate, nar_sampling=None):
     cfg = ar.config
     utts = []
-    for prompt_tokens, prompt, target_tokens, *sampling in items:
+    items = list(items)
+    waves = [i for i, item in enumerate(items) if item[1].dtype.is_floating_point]
+    if waves and codec is None:
+        raise ValueError('synthesize_many: a waveform prompt needs a codec to encode it')
+    encoded = {}
+    if len(waves) >= 2 and hasattr(codec, 'encode_many'):       # one ragged batch through the encoder, bit for bit `encode`
+        encoded = dict(zip(waves, codec.encode_many([items[i][1] for i in waves])))
+    for i, (prompt_tokens, prompt, target_tokens, *sampling) in enumerate(items):
         if prompt.dtype.is_floating_point:
-            if codec is None:
-                raise ValueError('synthesize_many: a waveform prompt needs a codec to encode it')
-            prompt = codec.encode(prompt)
+            prompt = encoded[i] if i in encoded else codec.encode(prompt)
         utts.append((prompt_tokens, to_prompt_codes(prompt, cfg), target_tokens, *sampling))     # codes (T, Q)
     firsts = ar_generate(utts)                                                          # per utterance (Ty,) first codebook
     for i, first in enumerate(firsts):

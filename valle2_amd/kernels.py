@@ -1395,3 +1395,60 @@ def lstm_layer(xproj, w_hh, skip=None):
                                    None if skip is None else _codec_dense(skip, 'skip', (B, T, H)),
                                    None if y is None else y.data_ptr(), B, T, H, stream()), 'vh_lstm_layer')
     return h if skip is None else y
+
+
+# ---- the EnCodec encoder's kernels (csrc/codec.hip) --------------------------------------------------------------------------
+def _codec_lens(lens, B, name):
+    if lens is None:
+        return None
+    if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
+        raise _lib.VhError(f'{name}: lens must be a contiguous device int32 tensor of B entries')
+    return lens.data_ptr()
+
+
+def conv1d_wave(x, w, bias=None, lens=None, out=None):
+    """vh_conv1d_wave: x (B, L) samples, w (C_out, taps) -> (B, L, C_out) = bias + sum_k xpad[b, t + k] w[co, k], taps - 1 samples
+    of left reflection per batch row; lens (B) device int32: a forward read beyond lens[b] samples reads zero."""
+    if x.dim() != 2 or w.dim() != 2:
+        raise _lib.VhError(f'conv1d_wave: x {tuple(x.shape)} (B, L) against w {tuple(w.shape)} (C_out, taps)')
+    B, L = x.shape
+    C_out, taps = w.shape
+    if out is None:
+        out = torch.empty(B, L, C_out, device=x.device, dtype=torch.float32)
+    check(_lib.lib().vh_conv1d_wave(_codec_dense(x, 'x'), _codec_dense(w, 'w'),
+                                    None if bias is None else _codec_dense(bias, 'bias', (C_out,)),
+                                    _codec_dense(out, 'out', (B, L, C_out)), B, L, C_out, taps, _codec_lens(lens, B, 'conv1d_wave'),
+                                    stream()), 'vh_conv1d_wave')
+    return out
+
+
+def conv1d_down(x, w, bias=None, stride=1, elu=False, lens=None, out=None):
+    """vh_conv1d_down: x (B, T, C_in), w (C_out, taps, C_in) -> (B, ceil(T / stride), C_out), the strided causal convolution
+    with the reference's left and right ("extra") reflect padding over every batch row's own lens[b] valid rows."""
+    if x.dim() != 3 or w.dim() != 3 or w.shape[2] != x.shape[2]:
+        raise _lib.VhError(f'conv1d_down: x {tuple(x.shape)} (B, T, C_in) against w {tuple(w.shape)} (C_out, taps, C_in)')
+    B, T, C_in = x.shape
+    C_out, taps, _ = w.shape
+    stride = int(stride)
+    T_out = -(-T // stride) if stride >= 1 else T
+    if out is None:
+        out = torch.empty(B, T_out, C_out, device=x.device, dtype=torch.float32)
+    check(_lib.lib().vh_conv1d_down(_codec_dense(x, 'x'), _codec_dense(w, 'w'),
+                                    None if bias is None else _codec_dense(bias, 'bias', (C_out,)),
+                                    _codec_dense(out, 'out', (B, T_out, C_out)), B, T, C_in, C_out, taps, stride, int(bool(elu)),
+                                    _codec_lens(lens, B, 'conv1d_down'), stream()), 'vh_conv1d_down')
+    return out
+
+
+def rvq_encode(x, codebooks, e_sq, num_codebooks=None):
+    """vh_rvq_encode: x (B, T, D), codebooks (n_books, K, D), e_sq (n_books, K) = |entry|^2 -> codes (B, Q, T) int64, every
+    stage in one launch (nearest entry, the lowest index of a tie; then the entry is subtracted in fp32)."""
+    if x.dim() != 3 or codebooks.dim() != 3 or codebooks.shape[2] != x.shape[2]:
+        raise _lib.VhError(f'rvq_encode: x {tuple(x.shape)} (B, T, D) against codebooks {tuple(codebooks.shape)} (n_books, K, D)')
+    B, T, D = x.shape
+    n_books, K, _ = codebooks.shape
+    Q = n_books if num_codebooks is None else int(num_codebooks)
+    codes = torch.empty(B, max(Q, 0), T, device=x.device, dtype=torch.int64)
+    check(_lib.lib().vh_rvq_encode(_codec_dense(x, 'x'), _codec_dense(codebooks, 'codebooks'), _codec_dense(e_sq, 'e_sq', (n_books, K)),
+                                   codes.data_ptr(), B, T, D, Q, n_books, K, stream()), 'vh_rvq_encode')
+    return codes
