@@ -22,46 +22,11 @@ import torch
 
 from tests import codec_enc_mirror as E
 from tests import codec_mirror as M
+from tests.codec_rules import DEV, codec_state_dict, codes_rule, g, within
 from tests.golden.gen_codec_golden import SMALL
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
-FACTOR = 8
-CODE_FACTOR = 16
 GOLDEN = M.__file__.rsplit('/', 1)[0] + '/golden/codec_enc_small.npz'
-
-
-def g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def within(name, got, ref64, ref32):
-    """max |got - ref64| <= FACTOR * e_ref, e_ref = max |ref32 - ref64|; prints the figures first."""
-    e_ref = (ref32.double() - ref64).abs().max().item()
-    err = (got.double().cpu() - ref64).abs().max().item()
-    print(f'{name}: e_ref={e_ref:.3e} gpu_err={err:.3e} ratio={err / e_ref if e_ref else float("inf"):.2f} max|ref|={ref64.abs().max().item():.3f}')
-    assert torch.isfinite(got).all(), name
-    assert err <= FACTOR * e_ref, f'{name}: |gpu - mirror64| = {err:.3e} > {FACTOR} x e_ref = {FACTOR * e_ref:.3e}'
-    return e_ref, err
-
-
-def codes_rule(name, got, books64, x64, x32):
-    """got (Q, rows) int64 on the CPU against the float64 mirror of x64 (rows, D); x32 is the fp32 reference's input."""
-    Q = got.shape[0]
-    K = books64.shape[1]
-    codes64, margin, e_score = E.rvq_scores(books64, x64, x32, Q)
-    decided = margin > CODE_FACTOR * e_score
-    assert got.dtype == torch.int64 and tuple(got.shape) == tuple(codes64.shape)
-    assert int(got.min()) >= 0 and int(got.max()) < K
-    gaps = E.chosen_gaps(books64, x64, got)
-    differ = (got != codes64).any(0)
-    print(f'{name}: rows={x64.shape[0]} e_score={e_score:.3e} undecided={int((~decided).sum())} differing rows={int(differ.sum())} '
-          f'(decided among them {int((differ & decided).sum())}) min margin={margin.min().item():.3e} '
-          f'worst gap / e_score={gaps.max().item() / e_score:.2f}')
-    assert (~decided).double().mean().item() <= 0.05, f'{name}: {int((~decided).sum())} of {len(decided)} rows undecided'
-    assert torch.equal(got[:, decided], codes64[:, decided]), f'{name}: codes differ on decided rows'
-    assert gaps.max().item() <= CODE_FACTOR * e_score, f'{name}: a chosen entry is {gaps.max().item():.3e} below the best score'
-    return e_score, gaps.max().item()
 
 
 # ---- vh_conv1d_wave --------------------------------------------------------------------------------------------------------
@@ -251,13 +216,6 @@ def small():
     z = np.load(GOLDEN)
     sd = {k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith('sd/')}
     return sd, {k: torch.from_numpy(z[k]) for k in z.files if not k.startswith('sd/')}
-
-
-def codec_state_dict(seed, **over):
-    """Both halves with the mirror's gains: the decoder's seeded state dict (and its codebooks) plus the encoder's."""
-    sd = dict(M.random_state_dict(seed=seed, **over))
-    sd.update({k: v for k, v in E.random_encoder_state_dict(seed=seed + 1, **over).items() if k.startswith('encoder.')})
-    return sd
 
 
 @pytest.fixture(scope='module')

@@ -15,26 +15,11 @@ import torch
 import torch.nn.functional as F
 
 from tests import codec_mirror as M
+from tests.codec_rules import DEV, g, within
 from tests.golden.gen_codec_golden import SMALL
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
-FACTOR = 8
 GOLDEN = M.__file__.rsplit('/', 1)[0] + '/golden/codec_small.npz'
-
-
-def g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def within(name, got, ref64, ref32):
-    """max |got - ref64| <= FACTOR * e_ref, e_ref = max |ref32 - ref64|; prints the figures first."""
-    e_ref = (ref32.double() - ref64).abs().max().item()
-    err = (got.double().cpu() - ref64).abs().max().item()
-    print(f'{name}: e_ref={e_ref:.3e} gpu_err={err:.3e} ratio={err / e_ref if e_ref else float("inf"):.2f} max|ref|={ref64.abs().max().item():.3f}')
-    assert torch.isfinite(got).all(), name
-    assert err <= FACTOR * e_ref, f'{name}: |gpu - mirror64| = {err:.3e} > {FACTOR} x e_ref = {FACTOR * e_ref:.3e}'
-    return e_ref, err
 
 
 # ---- vh_rvq_decode ---------------------------------------------------------------------------------------------------------
