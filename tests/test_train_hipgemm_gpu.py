@@ -1,7 +1,8 @@
 """The training backward's matrix products are hand-written kernels only (no library GEMM, no engine
 switch): `vh_gemm_tn` (dW = dY^T X, token-major operands read in place, deterministic split-K),
 `vh_linear_ex` (dX = dY W on the NT LDS-DMA tile kernel with W^T from `vh_transpose`; GELU forward with the
-pre-activation kept; GELU backward fused into the product) — checked against torch fp32 on the CPU — and
+pre-activation kept; GELU backward fused into the product) — checked against float64 on the CPU (every path of these
+kernels, at shapes built for it: tests/test_train_gemm_paths_gpu.py) — and
 the second, materialised derivation of the attention backward (vh_gemm_batched) against the same gradient
 tests as the flash kernels."""
 import pytest
@@ -92,40 +93,41 @@ def test_linear_ex_training_epilogues(M):
     pre = torch.empty(M, dff, device=DEV)
     hid = K.linear_ex(x.to(DEV), w1.to(DEV), bias=b1.to(DEV), pre_out=pre, act=K.ACT_GELU,
                       out=torch.empty(M, dff, device=DEV))
-    ref_pre = F.linear(x, w1, b1)
-    torch.testing.assert_close(pre.cpu(), ref_pre, atol=2e-5, rtol=1e-5)
-    torch.testing.assert_close(hid.cpu(), F.gelu(ref_pre), atol=2e-5, rtol=1e-5)
+    f64 = lambda t: t.cpu().double()                                  # every reference below: float64 on the CPU
+    ref_pre = F.linear(x.double(), w1.double(), b1.double())
+    torch.testing.assert_close(f64(pre), ref_pre, atol=2e-5, rtol=1e-5)
+    torch.testing.assert_close(f64(hid), F.gelu(ref_pre), atol=2e-5, rtol=1e-5)
     # backward through the activation fused into dX = dY . W2:  (dy @ w2) * gelu'(pre)
     w2 = 0.1 * torch.randn(d, dff, generator=g)
     dy = torch.randn(M, d, generator=g)
     wt = K.transpose(w2.to(DEV))                                     # (dff, 128)
     dpre = K.linear_ex(dy.to(DEV), wt, residual=pre, act=K.ACT_GELU_BWD, out=torch.empty(M, dff, device=DEV))
     p = ref_pre.clone().requires_grad_()
-    F.gelu(p).backward(dy @ w2)
-    torch.testing.assert_close(dpre.cpu(), p.grad, atol=3e-5, rtol=1e-5)
+    F.gelu(p).backward(dy.double() @ w2.double())
+    torch.testing.assert_close(f64(dpre), p.grad, atol=3e-5, rtol=1e-5)
     # the pair the training step uses: the forward keeps gelu'(pre) instead of pre, the backward multiplies by it
     dact = torch.empty(M, dff, device=DEV)
     hid2 = K.linear_ex(x.to(DEV), w1.to(DEV), bias=b1.to(DEV), pre_out=dact, act=K.ACT_GELU_D,
                        out=torch.empty(M, dff, device=DEV))
-    torch.testing.assert_close(hid2.cpu(), F.gelu(ref_pre), atol=2e-5, rtol=1e-5)
+    torch.testing.assert_close(f64(hid2), F.gelu(ref_pre), atol=2e-5, rtol=1e-5)
     pp = ref_pre.clone().requires_grad_()
     F.gelu(pp).backward(torch.ones_like(pp))
-    torch.testing.assert_close(dact.cpu(), pp.grad, atol=2e-5, rtol=1e-5)
+    torch.testing.assert_close(f64(dact), pp.grad, atol=2e-5, rtol=1e-5)
     dpre2 = K.linear_ex(dy.to(DEV), wt, residual=dact, act=K.ACT_MUL, out=torch.empty(M, dff, device=DEV))
-    torch.testing.assert_close(dpre2.cpu(), p.grad, atol=3e-5, rtol=1e-5)
+    torch.testing.assert_close(f64(dpre2), p.grad, atol=3e-5, rtol=1e-5)
     # ragged head: K = 1025 zero-padded to 1056 on both operands
     wp = 0.05 * torch.randn(1025, d, generator=g)
     dl = torch.zeros(M, 1056)
     dl[:, :1025] = torch.randn(M, 1025, generator=g)
     dx = K.linear_ex(dl.to(DEV)[:, :1025], K.transpose(wp.to(DEV)), K=1056, out=torch.empty(M, d, device=DEV))
-    torch.testing.assert_close(dx.cpu(), dl[:, :1025] @ wp, atol=5e-5, rtol=1e-5)
+    torch.testing.assert_close(f64(dx), dl[:, :1025].double() @ wp.double(), atol=5e-5, rtol=1e-5)
 
 
 @pytest.mark.parametrize('M,N,Kd', [(10240, 512, 512), (10240 - 37, 512, 1536), (2300, 2048, 512), (8192 + 5, 512, 256)])
 def test_linear_ex_tail_split(M, N, Kd):
     """vh_linear_ex with a workspace: the tiles beyond the last multiple of 256 run as K slices + the fix-up launch
     (320 / 320 / 288 / 260 tiles here; the last shape splits 2 ways only: K / split >= 128).  Every epilogue of the
-    fix-up against torch, and against the unsplit kernel (knob 10 = 1) on the same inputs."""
+    fix-up against float64 on the CPU, and against the unsplit kernel (knob 10 = 1) on the same inputs."""
     from valle2_amd import _lib, kernels as K
     assert _lib.lib().vh_linear_ex_ws_bytes(M, N, Kd) > 0
     g = torch.Generator().manual_seed(M + N)
@@ -133,7 +135,10 @@ def test_linear_ex_tail_split(M, N, Kd):
     w = (0.05 * torch.randn(N, Kd, generator=g)).to(DEV)
     b = torch.randn(N, generator=g).to(DEV)
     res = torch.randn(M, N, generator=g).to(DEV)
-    ref_pre = torch.addmm(b, a, w.t())
+    f64 = lambda t: t.cpu().double()                                  # every reference below: float64 on the CPU
+    prod = f64(a) @ f64(w).T
+    ref_pre = prod + f64(b)
+    saved = ref_pre.float().to(DEV)                                   # the pre-activation GELU_BWD is handed, in fp32
     outs = {}
     for knob in (0, 1):
         _lib.lib().vh_set_tuning(10, knob)
@@ -141,7 +146,7 @@ def test_linear_ex_tail_split(M, N, Kd):
             pre, cs = torch.empty(M, N, device=DEV), torch.zeros(N, device=DEV)
             plain = K.linear_ex(a, w, bias=b, residual=res, out=torch.empty(M, N, device=DEV), colsum=cs)
             act = K.linear_ex(a, w, bias=b, pre_out=pre, act=K.ACT_GELU, out=torch.empty(M, N, device=DEV))
-            bwd = K.linear_ex(a, w, residual=ref_pre, act=K.ACT_GELU_BWD, out=torch.empty(M, N, device=DEV))
+            bwd = K.linear_ex(a, w, residual=saved, act=K.ACT_GELU_BWD, out=torch.empty(M, N, device=DEV))
             dact = torch.empty(M, N, device=DEV)
             act_d = K.linear_ex(a, w, bias=b, pre_out=dact, act=K.ACT_GELU_D, out=torch.empty(M, N, device=DEV))
             mul = K.linear_ex(a, w, residual=res, act=K.ACT_MUL, out=torch.empty(M, N, device=DEV))
@@ -150,18 +155,18 @@ def test_linear_ex_tail_split(M, N, Kd):
         outs[knob] = (plain, cs, pre, act, bwd, act_d, dact, mul)
     plain, cs, pre, act, bwd, act_d, dact, mul = outs[0]
     tol = dict(atol=5e-5, rtol=2e-5)
-    torch.testing.assert_close(plain, ref_pre + res, **tol)
-    torch.testing.assert_close(cs, (ref_pre + res).sum(0), atol=2e-2, rtol=1e-4)
-    torch.testing.assert_close(pre, ref_pre, **tol)
-    torch.testing.assert_close(act, F.gelu(ref_pre), **tol)
-    p = ref_pre.clone().requires_grad_()
-    F.gelu(p).backward(a @ w.t())
-    torch.testing.assert_close(bwd, p.grad, **tol)
-    torch.testing.assert_close(act_d, F.gelu(ref_pre), **tol)
+    torch.testing.assert_close(f64(plain), ref_pre + f64(res), **tol)
+    torch.testing.assert_close(f64(cs), (ref_pre + f64(res)).sum(0), atol=2e-2, rtol=1e-4)
+    torch.testing.assert_close(f64(pre), ref_pre, **tol)
+    torch.testing.assert_close(f64(act), F.gelu(ref_pre), **tol)
+    p = f64(saved).requires_grad_()
+    F.gelu(p).backward(prod)
+    torch.testing.assert_close(f64(bwd), p.grad, **tol)
+    torch.testing.assert_close(f64(act_d), F.gelu(ref_pre), **tol)
     pg = ref_pre.clone().requires_grad_()
     F.gelu(pg).backward(torch.ones_like(pg))
-    torch.testing.assert_close(dact, pg.grad, **tol)
-    torch.testing.assert_close(mul, (a @ w.t()) * res, atol=2e-4, rtol=2e-5)
+    torch.testing.assert_close(f64(dact), pg.grad, **tol)
+    torch.testing.assert_close(f64(mul), prod * f64(res), atol=2e-4, rtol=2e-5)
     n_whole = ((M + 127) // 128 * (N // 128)) // 256 * 256          # whole tiles: the same kernel path, bit for bit
     rows_whole = n_whole // (N // 128) * 128
     for x, y in zip(outs[0], outs[1]):
